@@ -14,9 +14,16 @@ Multi-GPU: windows are independent scenes (social pooling never crosses a window
 across ranks with NO data-path collective; weak scaling (fixed windows per GPU).  Timing: barrier +
 torch.cuda.synchronize() on both sides of exactly K steps, max over ranks, rank 0 prints one JSON
 line LAST on stdout, kept under 4 KB (benchlib/emit.py: the complete record with every extra leg goes to
-bench_full.json and to an earlier stdout line prefixed `#full `).  The line also carries `roofline` (dominant kernel k_ioc vs the fp32 MFMA peak, duration from
-hipEvents on the launch stream over the timed steps) and `cpu_baseline` (the numpy oracle timed on
-this host on a bounded sample: 8 windows = 5120 samples).  Default: 512 windows per step per GPU.
+bench_full.json and to an earlier stdout line prefixed `#full `).  Default: 512 windows per step per GPU.
+
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs DIR` if given and prints the line.  Everything else is
+measured only with `--full`: the per-kernel hipEvent tables, `roofline` (dominant kernel k_ioc vs the fp32 MFMA peak, duration from
+hipEvents on the launch stream over the timed steps), `cpu_baseline` (the numpy oracle timed on this host on a bounded sample:
+8 windows = 5120 samples) with the `accuracy` gate, and the extra legs (alt / sdd / comm / multi-rank).
+
+`--dump-outputs DIR`: what the timed path returned in its LAST step (Y [R, T_pred, 2] and score [R]; with --train also the flat
+gradient) as DIR/<name>.npy, float32, at most 64 MB in all: an array larger than its share is a fixed, seeded sample of its rows,
+the row indices beside it as DIR/<name>_rows.npy (float64).  Inputs are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -61,6 +68,31 @@ def self_spawn(n_gpus):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
+DUMP_BUDGET = 64 << 20              # bytes over all the .npy files of one --dump-outputs
+DUMP_SEED = 20240917                # the row sample of an array too large for its share: the same rows in every run
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET):
+    """Write each (name, array) as out_dir/<name>.npy in float32 (float64 stays float64).  Each array gets an equal share of `budget`; one that
+    does not fit is replaced by the rows (axis 0) of a fixed seeded sample, sorted, with their indices as <name>_rows.npy (float64).
+    Returns {name: number of rows written}."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays)) - 4096               # room for the .npy headers
+    written = {}
+    for name, x in arrays:
+        x = np.ascontiguousarray(x, dtype=np.float64 if x.dtype == np.float64 else np.float32)
+        if x.nbytes > share:
+            row_bytes = x.nbytes // x.shape[0] + 8             # + the float64 row index
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(x.shape[0], share // row_bytes, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            x = x[rows]
+        elif os.path.exists(os.path.join(out_dir, name + "_rows.npy")):
+            os.remove(os.path.join(out_dir, name + "_rows.npy"))
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        written[name] = x.shape[0]
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -68,10 +100,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--windows", type=int, default=None, help="loader windows (scenes) per step per GPU (128 = the size the per-kernel tables "
                                                              "in profiles/README.md were taken at; throughput saturates around 512)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel hipEvent tables, roofline, cpu_baseline + accuracy, and the extra legs (alt / sdd / "
+                         "comm / multi-rank).  Off: set up, warm up, time the steps, --dump-outputs, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32, <= 64 MB in all; see the module docstring)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed region of the headline: no alt / sdd / cpu_baseline / accuracy legs.  This is the command the "
-                         "rocprofv3 sets under profiles/ are collected from, so that every kernel symbol appears at ONE launch size")
+                    help="with --full: only the timed region of the headline and its per-kernel / roofline figures, no alt / sdd / cpu_baseline / "
+                         "accuracy legs.  `--full --headline-only` is the command the rocprofv3 sets under profiles/ are collected from, so that "
+                         "every kernel symbol appears at ONE launch size")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--bf16", action="store_true",
                     help="bf16 matrix operands in the IOC kernel (BASELINE configs[2] arithmetic; NOT the headline fp32 line)")
@@ -106,13 +144,15 @@ def main():
                          "phase=train on a batch of one object (dims.bn_mode = 1: per-sample moments, model/model.py:453-462,471-481)")
     ap.add_argument("--data", choices=["both", "synthetic", "sdd"], default="both",
                     help="'both' (default): the headline on dense synthetic windows (every slot present, every social bin populated) "
-                         "plus an `sdd` object measured, outside the timed region, on real SDD bookstore windows; 'synthetic' skips it; "
+                         "plus, with --full, an `sdd` object measured, outside the timed region, on real SDD bookstore windows; 'synthetic' skips it; "
                          "'sdd': the TIMED region itself runs on the real SDD windows (9 of 32 slots present, 32-px neighbourhood) -- with "
                          "--flags 4 / 12 the compacted paths -- for profiling them (profiles/collect_r05.sh); not the headline workload")
     ap.add_argument("--train", action="store_true",
                     help="time a TRAINING step instead (forward + backward + gradient all-reduce + clip + Adam + device repack); "
                          "not the BASELINE metric -- the default run is")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_spawn(a.gpus)
     if (a.split or a.x6) and (a.bf16 or a.compact or a.shard == "agents" or (a.split and a.x6) or (a.x6 and a.train)):
@@ -227,7 +267,7 @@ def main():
     for _ in range(a.warmup):
         step()
     fence()
-    if not a.graph:                                  # per-kernel hipEvents are host-side records: not part of a replayed graph
+    if a.full and not a.graph:                       # per-kernel hipEvents are host-side records: not part of a replayed graph
         h.set_profiling(True)
         if a.shard == "agents":
             halves[0]["h"].set_profiling(True)
@@ -243,11 +283,13 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps))
-    h.set_profiling(False)
-    prof = h.get_profile()
-    if a.shard == "agents":
-        halves[0]["h"].set_profiling(False)
-        prof = halves[0]["h"].get_profile()
+    prof = []
+    if a.full:
+        h.set_profiling(False)
+        prof = h.get_profile()
+        if a.shard == "agents":
+            halves[0]["h"].set_profiling(False)
+            prof = halves[0]["h"].get_profile()
     ranks_seen = 1
     if use_dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -263,11 +305,18 @@ def main():
     if a.shard == "agents":
         Y = torch.cat([x["Y"] for x in halves]); score = torch.cat([x["score"] for x in halves])
     assert bool(torch.isfinite(Y).all()) and bool(torch.isfinite(score).all())
+    if a.dump_outputs and rank == 0:                 # before any extra leg reuses Y / score
+        outs = [("Y", Y.cpu().numpy()), ("score", score.cpu().numpy())]
+        if a.train:
+            outs.append(("grad", gflat.cpu().numpy()))
+        dump_outputs(a.dump_outputs, outs)
     comm = None
-    if a.shard == "agents":
+    if a.full and a.shard == "agents":
         comm = agent_sharded_comm(sharded, halves, fence, max(2, a.steps // 2), world, d.T_pred)
     # outside the timed region: the same steps through the opt-in row-compacted pooling, reported next to the headline
     alt = None
+    if not a.full:                                   # a plain run: the headline figure alone
+        a.headline_only = True
     if a.headline_only:
         a.no_cpu_baseline = True
         if a.data == "both":
@@ -307,13 +356,18 @@ def main():
 
     peak = BF16_MFMA_PEAK_TFLOPS if a.bf16 else FP32_MFMA_PEAK_TFLOPS
     algorithmic_bytes = d.R * (2 * d.T_pred * 2 * 4 + 4) + d.A * d.H * 4
-    traffic = committed_traffic(d, a.bf16) if a.mno == 32 and a.grid == 4 and a.data != "sdd" and not (a.compact or a.split or a.x6) else None
+    traffic = committed_traffic(d, a.bf16) if a.full and a.mno == 32 and a.grid == 4 and a.data != "sdd" and not (a.compact or a.split or a.x6) else None
     assert traffic is None or traffic >= algorithmic_bytes, (traffic, algorithmic_bytes)
+
+    def lean(rec):
+        """a plain run's record: the per-kernel tables and the figures derived from them are --full's"""
+        return rec if a.full else {k: v for k, v in rec.items() if k not in ("roofline", "kernel_ms", "forward_ms", "backward_ms",
+                                                                              "whole_step_tflops_3x_forward_credit")}
     if rank == 0 and a.train:
         samples = d.R * world * a.steps
         fwd = sum(v for k, v in kern_ms.items() if not k.startswith("bwd_"))
         bwd = sum(v for k, v in kern_ms.items() if k.startswith("bwd_"))
-        emit({
+        emit(lean({
             "metric": "TRAINING agent-trajectory-samples/sec (K=20, T_pred=40; fwd+bwd+allreduce+clip+Adam+repack)",
             "value": samples / dt, "unit": "samples/s", "n_gpus": ranks_seen, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -322,7 +376,7 @@ def main():
                                    "; dims.bf16 = 2: k_ioc_x3 forward (fp32 saves), k_ioc_bwd_x3, k_gemm_tn2_xp, k_conv_gather_x3, six-product sample generation; the remaining backward kernels fp32" if a.split else ""),
                        "windows_per_gpu": a.windows, "rows_per_gpu": d.R, "parallelism": "scene-sharded x%d, flat-gradient all-reduce" % world},
             "forward_ms": fwd, "backward_ms": bwd, "kernel_ms": kern_ms,
-            "whole_step_tflops_3x_forward_credit": 3 * whole_tflops})
+            "whole_step_tflops_3x_forward_credit": 3 * whole_tflops}))
     elif rank == 0:
         samples = d.R * world * a.steps
         out = {
@@ -422,11 +476,11 @@ def main():
     # N > 1, default partitioning: the agent-sharded form (north_star's "RCCL all-gather only for the social-pooling neighbour exchange", over
     # collectives and over peer buffers) and BASELINE configs[3] / configs[4] at their named multi-GPU shapes are measured as well, OUTSIDE the timed
     # region, into the same line (benchlib/legs_dist.py: multi_rank_legs; one watchdog bounds them all)
-    if world > 1 and a.shard == "scenes" and not (a.train or a.graph):
+    if a.full and world > 1 and a.shard == "scenes" and not (a.train or a.graph):
         multi_rank_legs(out if rank == 0 else None, a, d, w, grids_t, rank, world, dev, stream, fence,
                         lambda: emit(out))
     if rank == 0 and not a.train:
-        emit(out)
+        emit(lean(out))
     if use_dist:
         try:
             dist.destroy_process_group()

@@ -1,7 +1,7 @@
 #!/bin/bash
 # One compact line per launch class: same-box A/B of whole-path and IOC-kernel times (run it on two builds, compare).
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-line() { tag=$1; shift; python bench.py "$@" --headline-only 2>/dev/null | python -c "
+line() { tag=$1; shift; python bench.py --full "$@" --headline-only 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d.get('kernel_ms',{})
 print('$tag', 'ms/step %.3f' % d['ms_per_step'], 'min %.3f' % d.get('step_ms_min', 0), 'ioc %.3f' % k.get('ioc', 0), ' '.join('%s %.2f' % (n, k[n]) for n in ('ioc_bwd','decoder','deconv2','deconv34') if n in k))"; }

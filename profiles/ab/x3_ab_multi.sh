@@ -1,7 +1,7 @@
 #!/bin/bash
 # same-box A/B of several kernels_x3.hip build variants on the split-operand headline shape
 cd ${GRAFT_REPO_ROOT:-/root/repo}
-run2() { for i in 1 2; do python bench.py --split --steps 8 --warmup 3 --headline-only 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('   ioc %.3f  step %.3f' % (d['kernel_ms']['ioc'], d['ms_per_step']))"; done; }
+run2() { for i in 1 2; do python bench.py --full --split --steps 8 --warmup 3 --headline-only 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('   ioc %.3f  step %.3f' % (d['kernel_ms']['ioc'], d['ms_per_step']))"; done; }
 echo "default"; run2
 for v in "$@"; do
   export DESIRE_FILE_FLAGS="kernels_x3.hip=-mllvm,-sink-insts-to-avoid-spills,$v"

@@ -11,9 +11,9 @@ want() { [ -z "$SECTIONS" ] || echo " $SECTIONS " | grep -q " $1 "; }
 SECTIONS="$*"
 stats() {   # tag, bench args...
   tag=$1; shift
-  python $R/bench.py "$@" --headline-only > $O/${tag}_bench.json 2>/dev/null
+  python $R/bench.py --full "$@" --headline-only > $O/${tag}_bench.json 2>/dev/null
   rm -rf /tmp/st_$tag
-  rocprofv3 --kernel-trace -d /tmp/st_$tag -o tr -- python $R/bench.py "$@" --headline-only > /dev/null 2>&1
+  rocprofv3 --kernel-trace -d /tmp/st_$tag -o tr -- python $R/bench.py --full "$@" --headline-only > /dev/null 2>&1
   python $R/profiles/summarise_db.py $(find /tmp/st_$tag -name "*.db" | head -1) > $O/${tag}_kernel_stats.csv
 }
 pmc() {     # tag, bench args...
@@ -22,7 +22,7 @@ pmc() {     # tag, bench args...
   rm -rf /tmp/pmc_${tag}_*
   for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY" "SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS" "TA_BUSY_avr GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_${tag}_$i -o p$i -- python $R/bench.py "$@" --steps 2 --warmup 1 --headline-only > /dev/null 2>&1
+    rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_${tag}_$i -o p$i -- python $R/bench.py --full "$@" --steps 2 --warmup 1 --headline-only > /dev/null 2>&1
   done
   python $R/profiles/summarise_pmc.py $O/${tag}_pmc_per_kernel.json $(find /tmp/pmc_${tag}_* -name "*.db")
 }
@@ -33,7 +33,7 @@ if want headline; then
   pmc   bench_w128 --windows 128
 fi
 if want full; then
-  python $R/bench.py --steps 20 --warmup 5 > $O/bench_default_full.json 2>/dev/null      # the driver's line: headline + alt legs + sdd leg + cpu baseline
+  python $R/bench.py --full --steps 20 --warmup 5 > $O/bench_default_full.json 2>/dev/null      # the driver's line: headline + alt legs + sdd leg + cpu baseline
 fi
 if want x6; then
   stats bench_w512_x6 --x6 --steps 5 --warmup 2

@@ -11,9 +11,9 @@ want() { [ -z "$SECTIONS" ] || echo " $SECTIONS " | grep -q " $1 "; }
 SECTIONS="$*"
 stats() {   # tag, bench args...
   tag=$1; shift
-  python $R/bench.py "$@" --headline-only 2>/dev/null | tail -n 1 > $O/${tag}_bench.json
+  python $R/bench.py --full "$@" --headline-only 2>/dev/null | tail -n 1 > $O/${tag}_bench.json
   rm -rf /tmp/st_$tag
-  rocprofv3 --kernel-trace -d /tmp/st_$tag -o tr -- python $R/bench.py "$@" --headline-only > /dev/null 2>&1
+  rocprofv3 --kernel-trace -d /tmp/st_$tag -o tr -- python $R/bench.py --full "$@" --headline-only > /dev/null 2>&1
   python $R/profiles/summarise_db.py $(find /tmp/st_$tag -name "*.db" | head -1) > $O/${tag}_kernel_stats.csv
 }
 pmc() {     # tag, bench args...
@@ -22,7 +22,7 @@ pmc() {     # tag, bench args...
   rm -rf /tmp/pmc_${tag}_*
   for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY" "SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS" "TA_BUSY_avr GRBM_GUI_ACTIVE"; do
     i=$((i+1))
-    rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_${tag}_$i -o p$i -- python $R/bench.py "$@" --steps 2 --warmup 1 --headline-only > /dev/null 2>&1
+    rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_${tag}_$i -o p$i -- python $R/bench.py --full "$@" --steps 2 --warmup 1 --headline-only > /dev/null 2>&1
   done
   python $R/profiles/summarise_pmc.py $O/${tag}_pmc_per_kernel.json $(find /tmp/pmc_${tag}_* -name "*.db")
 }
@@ -33,7 +33,7 @@ if want headline; then
   pmc   bench_w128 --windows 128
 fi
 if want full; then      # the driver's command: `#full` record + the compact line; both kept
-  ( cd $R && python bench.py --steps 20 --warmup 5 > $O/bench_default_stdout.txt 2>/dev/null; tail -n 1 $O/bench_default_stdout.txt > $O/bench_default_line.json; cp bench_full.json $O/bench_default_full.json )
+  ( cd $R && python bench.py --full --steps 20 --warmup 5 > $O/bench_default_stdout.txt 2>/dev/null; tail -n 1 $O/bench_default_stdout.txt > $O/bench_default_line.json; cp bench_full.json $O/bench_default_full.json )
 fi
 if want sdd; then       # the timed region on REAL SDD windows with both compaction bits: device-side counts (the default) and the read-back A/B is in the full record
   stats bench_sdd_compact --data sdd --flags 12 --steps 5 --warmup 2

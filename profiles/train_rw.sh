@@ -6,7 +6,7 @@ rm -rf /tmp/pmc_rw_*
 i=0
 for c in FETCH_SIZE WRITE_SIZE; do
   i=$((i+1))
-  rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_rw_$i -o p$i -- python $R/bench.py --train "$@" --steps 2 --warmup 1 --headline-only > /dev/null 2>&1
+  rocprofv3 --pmc $c --kernel-trace -d /tmp/pmc_rw_$i -o p$i -- python $R/bench.py --full --train "$@" --steps 2 --warmup 1 --headline-only > /dev/null 2>&1
 done
 python $R/profiles/summarise_pmc.py /tmp/pmc_rw.json $(find /tmp/pmc_rw_* -name "*.db") > /dev/null 2>&1
 python - <<'PY'

@@ -96,3 +96,38 @@ def test_the_drivers_line_stays_small():
         assert json.loads(lines[0][6:])["alt"] == rec["alt"]
         with open(os.path.join(tmp, "full.json")) as f:
             assert json.load(f)["sdd"] == rec["sdd"]
+
+
+def test_plain_and_full_runs_are_both_on_the_command_line():
+    """A plain run is the headline alone; everything else it used to measure is behind --full.  --steps must be a real step count."""
+    p = subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout, p.stdout[-2000:]
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps" in (p.stdout + p.stderr)
+
+
+def test_dump_outputs_writes_float32_within_budget_and_samples_the_same_rows_every_time(tmp_path):
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    Y = rng.standard_normal((5000, 40, 2)).astype(np.float32)            # 1.6 MB: larger than its share of the budget below
+    score = rng.standard_normal(5000).astype(np.float32)                  # 20 KB: fits whole
+    budget = 1 << 20
+    runs = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        written = bench.dump_outputs(str(out), [("Y", Y), ("score", score.astype(np.float64))], budget=budget)
+        assert written["score"] == 5000 and 0 < written["Y"] < 5000, written
+        assert sum(f.stat().st_size for f in out.iterdir()) <= budget
+        y, rows, s = np.load(out / "Y.npy"), np.load(out / "Y_rows.npy"), np.load(out / "score.npy")
+        assert y.dtype == np.float32 and rows.dtype == np.float64 and s.dtype == np.float64
+        assert y.shape == (written["Y"], 40, 2) and np.all(np.diff(rows) > 0)
+        np.testing.assert_array_equal(y, Y[rows.astype(np.int64)])
+        np.testing.assert_array_equal(s, score)
+        assert not (out / "score_rows.npy").exists()
+        runs.append(rows)
+    np.testing.assert_array_equal(runs[0], runs[1])
+    # an array that fits is written whole, and a row index left by an earlier sampled dump into the same folder is removed
+    bench.dump_outputs(str(tmp_path / "a"), [("Y", Y[:100])], budget=budget)
+    assert np.load(tmp_path / "a" / "Y.npy").shape == (100, 40, 2) and not (tmp_path / "a" / "Y_rows.npy").exists()

@@ -49,7 +49,7 @@ def test_default_contract_fields():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--windows", "16"], cwd=ROOT,
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--windows", "16", "--full"], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = _line(p.stdout)
@@ -130,13 +130,50 @@ def test_default_contract_fields():
     assert c2["accuracy"]["ioc_max_abs_err_vs_rounding_oracle"] < 7e-3 * c2["accuracy"]["refinement_scale"]
 
 
+def test_plain_run_is_the_headline_alone_and_dumps_what_its_last_step_returned(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the contract keys and nothing measured besides the K timed steps; --dump-outputs writes
+    the last step's Y and score (float32), identical for two runs with the same arguments; --train adds the flat gradient."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    dumps = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        p = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--windows", "16", "--dump-outputs", str(out)], cwd=ROOT,
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        o = _last_json(p.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in o, k
+        for k in ("roofline", "kernel_ms", "cpu_baseline", "accuracy", "alt", "sdd", "comm"):
+            assert k not in o, k
+        assert o["steps"] == 3 and o["dtype"] == "f32" and o["metric"] == "agent-trajectory-samples/sec (K=20, T_pred=40)"
+        assert abs(o["value"] - o["config"]["rows_per_gpu"] * 3 / (o["ms_per_step"] * 3e-3)) < 1e-6 * o["value"]
+        R = 16 * 32 * 20
+        Y, score = np.load(out / "Y.npy"), np.load(out / "score.npy")
+        assert Y.dtype == np.float32 and Y.shape == (R, 40, 2) and score.dtype == np.float32 and score.shape == (R,)
+        assert np.isfinite(Y).all() and np.isfinite(score).all() and np.abs(Y).max() > 0
+        dumps.append((Y, score))
+    np.testing.assert_allclose(dumps[0][0], dumps[1][0], rtol=0, atol=1e-5)
+    np.testing.assert_allclose(dumps[0][1], dumps[1][1], rtol=0, atol=1e-5)
+    out = tmp_path / "train"
+    p = subprocess.run([sys.executable, "bench.py", "--train", "--steps", "2", "--warmup", "1", "--windows", "4", "--dump-outputs", str(out)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    o = _last_json(p.stdout)
+    assert o["metric"].startswith("TRAINING") and o["steps"] == 2 and "kernel_ms" not in o
+    g = np.load(out / "grad.npy")
+    assert g.dtype == np.float32 and g.ndim == 1 and np.isfinite(g).all() and np.abs(g).max() > 0
+    assert np.load(out / "Y.npy").shape == (4 * 32 * 20, 40, 2)
+
+
 def test_headline_only_is_the_profiled_command_and_its_traffic_is_a_real_launch():
-    """`bench.py --headline-only` (what profiles/collect_r04.sh runs under rocprofv3): the timed region and nothing else, so every kernel
+    """`bench.py --full --headline-only` (what profiles/collect_r04.sh runs under rocprofv3): the timed region and nothing else, so every kernel
     symbol is launched at one size; at a profiled size the line's traffic comes from that launch class and is >= the algorithmic bytes."""
     import torch
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--windows", "128", "--headline-only"], cwd=ROOT,
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--windows", "128", "--full", "--headline-only"], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     o = _last_json(p.stdout)
@@ -193,7 +230,7 @@ def test_eight_ranks_on_one_gpu_carry_every_leg():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["DESIRE_BENCH_ONE_GPU"] = "1"
     env["DESIRE_BENCH_LEG_TIMEOUT"] = "600"
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--windows", "8"], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "2", "--warmup", "1", "--windows", "8", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     o = _last_json(p.stdout)
@@ -211,7 +248,7 @@ def test_a_rank_dying_in_an_extra_leg_does_not_cost_the_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["DESIRE_BENCH_ONE_GPU"] = "1"
     env["DESIRE_BENCH_FAULT_AT"] = "config3"
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "8"], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "8", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     o = _last_json(p.stdout)
     assert o["n_gpus"] == 2 and o["value"] > 0
@@ -228,7 +265,7 @@ def test_gpus_flag_starts_its_own_ranks():
         pytest.skip("needs an MI355X")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["DESIRE_BENCH_ONE_GPU"] = "1"
-    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "8"], cwd=ROOT, env=env,
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--windows", "8", "--full"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     o = _last_json(p.stdout)
@@ -248,7 +285,7 @@ def test_compact_flag_is_labelled():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--windows", "16", "--compact", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--windows", "16", "--compact", "--no-cpu-baseline", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     o = _last_json(p.stdout)
@@ -259,7 +296,7 @@ def test_split_flag_is_labelled_and_gated():
     import torch
     if not torch.cuda.is_available():
         pytest.skip("needs an MI355X")
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--windows", "16", "--split"],
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--windows", "16", "--split", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     o = _last_json(p.stdout)
