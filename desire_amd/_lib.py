@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("DESIRE_HIP_LIB") or os.path.join(os.path.dirname(os.p
 
 EXPORTS = [
     "desire_last_error", "desire_version", "desire_dims_size", "desire_build_hash", "desire_create", "desire_destroy", "desire_set_weight",
-    "desire_finalize_weights", "desire_set_scene_grids", "desire_encode", "desire_sample",
+    "desire_finalize_weights", "desire_set_scene_grids", "desire_set_scene_images", "desire_encode", "desire_sample",
     "desire_ioc_refine", "desire_forward", "desire_read_buffer", "desire_neighbor_bins",
     "desire_scene_cells", "desire_set_profiling", "desire_get_profile", "desire_scene_cnn", "desire_losses",
     "desire_temporal_conv", "desire_feature_pooling", "desire_build_windows", "desire_gaussian_sample", "desire_ade_fde",
@@ -75,6 +75,7 @@ def load() -> C.CDLL:
     lib.desire_set_weight.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_size_t]
     lib.desire_finalize_weights.argtypes = [vp]
     lib.desire_set_scene_grids.argtypes = [vp, f32p, C.POINTER(C.c_int32)]
+    lib.desire_set_scene_images.argtypes = [vp, f32p, i32, i32, C.POINTER(C.c_int32)]
     lib.desire_encode.argtypes = [vp, f32p, f32p, vp]
     lib.desire_sample.argtypes = [vp, f32p, f32p, vp]
     lib.desire_ioc_refine.argtypes = [vp, f32p, f32p, vp]
@@ -156,7 +157,8 @@ class Handle:
             pass
 
     def set_option(self, name: str, value: int) -> None:
-        """One of the behavioural switches of desire_dims ("ioc_form", "ioc_split", "train_fp32_mask", "flags") on the live handle."""
+        """One of the behavioural switches of desire_dims ("ioc_form", "ioc_split", "train_fp32_mask", "flags") or a handle option
+        ("compact_min_rows", "compact_host_counts", "scene_grad") on the live handle."""
         _chk(self.lib.desire_set_option(self._h, name.encode(), int(value)))
         if hasattr(self.dims, name):                      # ("compact_min_rows" is a handle option, not a desire_dims field)
             self.dims = self.dims.replace(**{name: int(value)})
@@ -172,6 +174,13 @@ class Handle:
         if g.size != self.dims.n_scenes:
             raise DesireError("grid_of_scene must have n_scenes entries")
         _chk(self.lib.desire_set_scene_grids(self._h, dev_grids_ptr, g.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def set_scene_images(self, dev_images_ptr: int, Hi: int, Wi: int, grid_of_scene) -> None:
+        """Scene images [n_grids, Hi = 4 Gh, Wi = 4 Gw, 3] on the device: the handle runs (and in training, trains) the scene CNN itself."""
+        g = np.ascontiguousarray(grid_of_scene, dtype=np.int32)
+        if g.size != self.dims.n_scenes:
+            raise DesireError("grid_of_scene must have n_scenes entries")
+        _chk(self.lib.desire_set_scene_images(self._h, dev_images_ptr, int(Hi), int(Wi), g.ctypes.data_as(C.POINTER(C.c_int32))))
 
     def encode(self, past_ptr: int, fut_ptr: int, stream: int = 0) -> None:
         _chk(self.lib.desire_encode(self._h, past_ptr, fut_ptr or None, stream or None))
@@ -266,6 +275,12 @@ class Handle:
         class _Dev:
             __cuda_array_interface__ = {"shape": (cnt,), "typestr": dtype, "data": (int(p.value), False), "version": 2}
         return torch.as_tensor(_Dev(), device="cuda")
+
+    def scene_grid_grad(self):
+        """d(loss)/d(grids) [n_grids, Gh, Gw, C] of the last backward as a zero-copy device tensor (training mode with
+        set_option("scene_grad", 1); refused otherwise).  A caller that computes the grids with its own encoder backprops this into it."""
+        d = self.dims
+        return self.device_tensor("scene_grid_grad")[: d.n_grids * d.Gh * d.Gw * d.C].view(d.n_grids, d.Gh, d.Gw, d.C)
 
     def ioc_step(self, t: int, rank: int, nranks: int, Yall_ptr: int, plast_all_ptr: int, valid_all_ptr: int, Hall_ptr: int,
                  h_state_ptr: int, score_state_ptr: int, stream: int = 0) -> None:

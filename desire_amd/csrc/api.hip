@@ -228,12 +228,17 @@ extern "C" int desire_set_option(desire_handle* h, const char* name, int32_t val
         h->cp_pending = false; h->cp_enc = false;
         return DESIRE_OK;
     }
+    else if (nm == "scene_grad") {             // desire_backward also writes d loss / d grids into the workspace tensor "scene_grid_grad"
+        if (value != 0 && value != 1) return fail(DESIRE_ERR_ARG, "scene_grad must be 0 or 1");
+        h->scene_grad = value != 0;
+        return scene_grad_on(h) && h->training ? scene_grad_setup(h) : DESIRE_OK;
+    }
     else if (nm == "compact_min_rows") {       // DESIRE_FLAG_COMPACT_IOC: a slot class with fewer rows than this is folded into the next larger one (default 8192)
         if (value < 0) return fail(DESIRE_ERR_ARG, "compact_min_rows must be >= 0");
         h->ci_min_rows = value;
         return DESIRE_OK;
     }
-    else return fail(DESIRE_ERR_ARG, "unknown option: " + nm + " (ioc_form, ioc_split, train_fp32_mask, flags, compact_min_rows, compact_host_counts)");
+    else return fail(DESIRE_ERR_ARG, "unknown option: " + nm + " (ioc_form, ioc_split, train_fp32_mask, flags, compact_min_rows, compact_host_counts, scene_grad)");
     if (int rc = check_options(d)) return rc;
     if ((d.flags ^ h->d.flags) & (DESIRE_FLAG_COMPACT_ROWS | DESIRE_FLAG_COMPACT_IOC)) {
         h->cp_pending = false; h->cp_enc = false;       // the maps of the last desire_encode were built for the other setting: a new desire_encode comes first
@@ -336,6 +341,7 @@ extern "C" int desire_set_weight(desire_handle* h, const char* name, const float
                                         " values, got " + std::to_string(n));
     h->host_w[name] = desire_embed(h, name, host_data);
     h->finalized = false;
+    h->img_stale = true;
     h->training = false;            // the optimiser's master copy is rebuilt by the next desire_set_training(h, 1)
     return DESIRE_OK;
 }
@@ -346,6 +352,7 @@ extern "C" int desire_finalize_weights(desire_handle* h) {
         if (!h->host_w.count(kv.first)) return fail(DESIRE_ERR_STATE, "weight not set: " + kv.first);
     if (int rc = desire_pack_all(h)) return rc;
     h->finalized = true;
+    h->img_stale = true;
     return DESIRE_OK;
 }
 
@@ -357,6 +364,22 @@ extern "C" int desire_set_scene_grids(desire_handle* h, const float* dev_grids, 
     HIPCHK(hipMemcpy(h->ws["grid_of_scene"].p, host_grid_of_scene, h->d.n_scenes * sizeof(int32_t), hipMemcpyHostToDevice));
     h->grids = dev_grids;
     h->grids_set = true;
+    h->img_set = false; h->img = nullptr;          // the last of desire_set_scene_grids / desire_set_scene_images wins
+    return DESIRE_OK;
+}
+
+extern "C" int desire_set_scene_images(desire_handle* h, const float* dev_images, int32_t Hi, int32_t Wi, const int32_t* host_grid_of_scene) {
+    if (!h || !dev_images || !host_grid_of_scene) return fail(DESIRE_ERR_ARG, "null argument");
+    const desire_dims& d = h->d;
+    if (Hi != 4 * d.Gh || Wi != 4 * d.Gw) return fail(DESIRE_ERR_ARG, "scene image must be [n_grids, 4*Gh, 4*Gw, 3]");
+    const size_t n1 = (size_t)d.n_grids * (Hi / 2) * (Wi / 2) * 16, n2 = (size_t)d.n_grids * d.Gh * d.Gw * 32;
+    if (!h->ws.count("scnn1") && (h->ws["scnn1"].alloc(n1 * sizeof(float)) || h->ws["scnn2"].alloc(n2 * sizeof(float))))
+        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the scene CNN workspace");
+    if (!h->ws.count("scene_img_grid") && h->ws["scene_img_grid"].alloc((size_t)d.n_grids * d.Gh * d.Gw * d.C * sizeof(float)))
+        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the scene grid buffer");
+    if (int rc = desire_set_scene_grids(h, W(h, "scene_img_grid"), host_grid_of_scene)) return rc;
+    h->img = dev_images; h->img_set = true; h->img_stale = true;
+    if (h->training) return scene_grad_setup(h);
     return DESIRE_OK;
 }
 
@@ -439,6 +462,8 @@ extern "C" int desire_graph_launch(desire_handle* h, int32_t graph_id, void* str
 
 extern "C" int desire_device_buffer(desire_handle* h, const char* name, void** dev_ptr, size_t* bytes) {
     if (!h || !name || !dev_ptr || !bytes) return fail(DESIRE_ERR_ARG, "null argument");
+    if (!std::strcmp(name, "scene_grid_grad") && !(scene_grad_on(h) && h->training))
+        return fail(DESIRE_ERR_STATE, "scene_grid_grad needs training mode and desire_set_option(h, \"scene_grad\", 1)");
     auto it = h->ws.find(name);
     if (it == h->ws.end()) return fail(DESIRE_ERR_ARG, std::string("unknown buffer: ") + name);
     *dev_ptr = it->second.p; *bytes = it->second.bytes;

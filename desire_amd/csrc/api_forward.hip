@@ -508,6 +508,9 @@ extern "C" int desire_ioc_refine(desire_handle* h, float* dev_Yhat, float* dev_s
     if (!dev_Yhat || !dev_score) return fail(DESIRE_ERR_ARG, "null argument");
     if (h->d.ref_compat) return fail(DESIRE_ERR_STATE, "ref_compat: the reference graph has no ranking/refinement module (model/model.py:312-313)");
     if (!h->grids_set) return fail(DESIRE_ERR_STATE, "scene grids not set (desire_set_scene_grids)");
+    if (h->img_set && (h->training || h->img_stale)) {          // images attached: training runs the CNN every step (its saves feed the backward),
+        if (int rc = scene_images_run(h, static_cast<hipStream_t>(stream))) return rc;       // inference when weights or images changed
+    }
     const desire_dims& d = h->d;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // step-wise form (one launch of the agent-sharded kernel per step, a single rank): scenes of 160 .. 256 agents (beyond the cluster

@@ -44,6 +44,13 @@ extern "C" int desire_scene_cnn(desire_handle* h, const float* dev_image, int32_
     return DESIRE_OK;
 }
 
+// the scene CNN of desire_set_scene_images: the same three launches as desire_scene_cnn (bit-identical grid), post-ReLU scnn1 / scnn2 kept
+int scene_images_run(desire_ctx* h, hipStream_t s) {
+    if (int rc = desire_scene_cnn(h, h->img, 4 * h->d.Gh, 4 * h->d.Gw, W(h, "scene_img_grid"), s)) return rc;
+    h->img_stale = false;
+    return DESIRE_OK;
+}
+
 extern "C" int desire_losses(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float* dev_kld,
                              float* dev_recon, float* dev_cost, void* stream) {
     if (int rc = desire_ready(h)) return rc;

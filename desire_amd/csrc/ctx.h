@@ -88,18 +88,23 @@ struct desire_ctx {
     int adam_t = 0;                                          // Adam step counter
     int n_seg = 0;                                           // repack segments (train.hip)
     int n_seg16 = 0;                                         // split [hi | lo] bf16 packs among them (dims.bf16 = 2)
+    bool scene_grad = false;                                 // desire_set_option(h, "scene_grad", 1): desire_backward also writes "scene_grid_grad"
+    // desire_set_scene_images: the handle runs the scene CNN itself into its own grid buffer "scene_img_grid" (scnn1 / scnn2 kept for the backward)
+    const float* img = nullptr; bool img_set = false;        // (desire_set_scene_grids detaches them: the last setter called wins)
+    bool img_stale = true;                                   // the grid does not reflect the current weights / images (inference reruns the CNN)
 };
 
 struct Timer {
-    desire_ctx* h; hipStream_t s; bool on;
+    desire_ctx* h; hipStream_t s; bool on; size_t idx = 0;        // idx: its own entry (a Timer may run inside another one)
     Timer(desire_ctx* h_, hipStream_t s_, const char* name) : h(h_), s(s_), on(h_->profiling) {
         if (!on) return;
         Prof p; p.name = name;
         (void)hipEventCreate(&p.e0); (void)hipEventCreate(&p.e1);
         (void)hipEventRecord(p.e0, s);
+        idx = h->prof.size();
         h->prof.push_back(p);
     }
-    ~Timer() { if (on) (void)hipEventRecord(h->prof.back().e1, s); }
+    ~Timer() { if (on) (void)hipEventRecord(h->prof[idx].e1, s); }
 };
 
 // which parts of the training step use split operands under dims.bf16 = 2 (1: weight-gradient reductions, 2: data-gradient
@@ -137,3 +142,6 @@ bool compact_padded_ok(const desire_ctx* h);                   // the padded-til
 int compact_classes(const desire_ctx* h, int* m4);             // its slot classes (ascending, the handle's mno last): returns how many
 int compact_setup(desire_ctx* h);                              // its buffers, event and mapped count word (idempotent)
 int desire_pack_all(desire_ctx* h);                            // (re)builds every packed / folded device tensor from host_w
+int scene_grad_setup(desire_ctx* h);                           // buffers of the scene-grid gradient (train.hip; idempotent, training mode only)
+inline bool scene_grad_on(const desire_ctx* h) { return h->scene_grad || h->img_set; }      // images attached imply the grid gradient
+int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)

@@ -329,3 +329,23 @@ void launch_valid_from_frames(const float* past, int n_scenes, int T, int mno, u
 void launch_gather_frames(const float* frames, float* out, const int32_t* amap, int P, int T, int mno, hipStream_t s, const int32_t* dynP = nullptr);
 void launch_scatter_agents(const float* in, float* out, const int32_t* amap, int P, int ld, hipStream_t s, const int32_t* dynP = nullptr);
 void launch_gather_add_agents(const float* in, int ldi, float* out, int ldo, const int32_t* amap, int P, int n, hipStream_t s);
+
+// ---- scene-grid gradient (kernels_scene.hip; desire_set_option(h, "scene_grad", 1)) ----
+// one (view, refinement pass) of the IOC backward: rows (r, t) of R x T, their gate gradients, the positions the pass looked its cells up at
+struct SceneDsArgs {
+    const float* dag; const float* dac; const float* Y; const int32_t* gos; const float* wcat;
+    int R, T, H, K, mno, gpt, ngrp, Gh, Gw, n_keys, key_bits;
+    float* ds; uint32_t* keys; int32_t* idx;
+};
+struct SceneSortBufs { void* tmp; size_t tmp_bytes; uint32_t* keys_sorted; int32_t* idx_sorted; int32_t* beg; int32_t* end; float* part; };
+int scene_key_bits(long n_keys);                                             // radix bits of the keys 0 .. n_keys (n_keys = the padding sentinel)
+size_t scene_grad_sort_bytes(long n, int key_bits);                          // scratch of the stable sort of n rows
+void launch_scene_wcat(const float* Wg, const float* Wc, int H, int Ev, float* wcat, hipStream_t s);
+// dG [n_keys, 32] = (accumulate ? dG : 0) + the rows' ds summed per key in a fixed order (no float atomics: bitwise reproducible)
+int launch_scene_grid_grad(const SceneDsArgs& a, const SceneSortBufs& b, float* dG, int accumulate, hipStream_t s);
+// scene CNN backward (5x5 kernels, TF SAME padding pad = top / left): im2col rows out[(n, oy, ox)][(ky*5 + kx)*Ci + ci] (ld >= 25 Ci; columns past 25 Ci
+// are zero) of in [n, Hi, Wi, Ci]; and the data gradient dX [n, Hi, Wi, Ci] = (X > 0) * sum_{ky, kx, co} dY[n, oy, ox, co] W[ky, kx, ci, co] with X the
+// saved post-ReLU input of the layer
+void launch_im2col5(const float* in, float* out, int n, int Hi, int Wi, int Ci, int Ho, int Wo, int stride, int pad, int ld, hipStream_t s);
+void launch_conv5_dgrad_relu(const float* dY, const float* w, const float* X, float* dX, int n, int Hi, int Wi, int Ci, int Ho, int Wo, int Co,
+                             int stride, int pad, hipStream_t s);

@@ -369,6 +369,7 @@ int build_repack_maps(desire_ctx* h) {
 }
 
 int repack(desire_ctx* h, hipStream_t s) {
+    h->img_stale = true;                                   // scene_cnn/* may have moved: an inference forward reruns the scene CNN
     hipLaunchKernelGGL(k_repack, dim3(64, h->n_seg), dim3(256), 0, s, static_cast<const Seg*>(h->ws["repack_segs"].p),
                        static_cast<const uint32_t*>(h->ws["repack_idx"].p), W(h, "Wflat"));
     if (h->n_seg16)
@@ -387,6 +388,25 @@ int repack(desire_ctx* h, hipStream_t s) {
 }
 
 }  // namespace
+
+// scene-grid gradient (kernels_scene.hip): per-row ds, sort keys / indices and their sorted copies, chunk partials for up to RS * T rows of one
+// (view, pass); per-key ranges; the [3H, 32] operand; the result [n_grids, Gh, Gw, C].  Allocated here, never inside desire_backward.
+int scene_grad_setup(desire_ctx* h) {
+    const desire_dims& d = h->d;
+    const size_t n = ((size_t)h->R + 128) * d.T_pred, nk = (size_t)d.n_grids * d.Gh * d.Gw, f = sizeof(float);
+    const int bits = scene_key_bits((long)nk);
+    const struct { const char* n; size_t bytes; } bufs[] = {
+        {"sg_ds", n * 32 * f}, {"sg_part", n * 32 * f}, {"sg_keys", n * 4}, {"sg_keys_sorted", n * 4}, {"sg_idx", n * 4}, {"sg_idx_sorted", n * 4},
+        {"sg_beg", nk * 4}, {"sg_end", nk * 4}, {"sg_wcat", (size_t)3 * d.H * 32 * f}, {"sg_tmp", scene_grad_sort_bytes((long)n, bits)},
+        {"scene_grid_grad", nk * d.C * f},
+        {"sg_col", nk * 800 * f}, {"sg_d2", nk * 32 * f}, {"sg_d1", nk * 4 * 16 * f}};        // scene CNN backward (im2col rows, data gradients)
+    for (const auto& b : bufs) {
+        const bool fresh = !h->ws.count(b.n) || h->ws[b.n].bytes < b.bytes;
+        if (ensure(h, b.n, b.bytes)) return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for scene-gradient buffer ") + b.n);
+        if (fresh && !std::strcmp(b.n, "scene_grid_grad")) HIPCHK(hipMemset(h->ws[b.n].p, 0, b.bytes));
+    }
+    return DESIRE_OK;
+}
 
 extern "C" int desire_set_training(desire_handle* h, int enable) {
     if (int rc = desire_ready(h)) return rc;
@@ -463,6 +483,7 @@ extern "C" int desire_set_training(desire_handle* h, int enable) {
         return fail(DESIRE_ERR_HIP, "hipMalloc failed for the loss / bias-gradient buffers");
     HIPCHK(hipMemset(h->ws["loss_out"].p, 0, 8 * f));
     if (int rc = build_repack_maps(h)) return rc;
+    if (scene_grad_on(h)) { if (int rc = scene_grad_setup(h)) return rc; }
     h->adam_t = 0;
     h->training = true;
     return DESIRE_OK;
@@ -545,6 +566,8 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
     };
     // (under per-object statistics a conv bias cancels against the mean: its gradient is exactly zero, so the column sums of the
     //  post-norm gradients -- pure rounding noise -- are NOT fed to Adam; the Gflat slots of vae_*/b stay at the fill value 0)
+    const bool sg_on = scene_grad_on(h);                    // d loss / d grids wanted (the option, or scene images attached)
+    if (sg_on && !h->ws.count("sg_wcat")) return fail(DESIRE_ERR_STATE, "scene-gradient buffers missing");
     // ---- ranking / refinement module (trajectories detached: its only path into the rest is dHx) ----
     {
         Timer t(h, s, "bwd_ioc");
@@ -557,7 +580,7 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
         // DESIRE_FLAG_COMPACT_IOC: the forward ran one launch sequence per slot class (api.hip: IocView) and left each class's saves at its row
         // offset; the BPTT and every weight-gradient reduction below run per class on the same views, accumulating.  Otherwise: one view, the
         // handle's own shape.
-        struct BView { long R; int mno, n_scenes; const float* Hx; const float* p_last; const uint8_t* valid; size_t row_off; const int32_t* cmap; int gpt, ngrp; };
+        struct BView { long R; int mno, n_scenes; const float* Hx; const float* p_last; const uint8_t* valid; size_t row_off; const int32_t* cmap; int gpt, ngrp; const int32_t* gos; };
         std::vector<BView> views;
         if (h->ci_last) {
             if (ensure(h, "ci_dYr", (size_t)(R + 128) * T * 2 * sizeof(float)) || ensure(h, "ci_dscore", (size_t)(R + 128) * sizeof(float)) || ensure(h, "ci_dscoreT", (size_t)(R + 128) * T * sizeof(float)) ||
@@ -566,19 +589,28 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
             launch_fill_f32(W(h, "dHxHy_ioc"), (size_t)h->A * H, 0.f, s);
             int m4[4];
             compact_classes(h, m4);
-            size_t aoff = 0, roff = 0;
+            size_t aoff = 0, roff = 0, woff = 0;
             for (int i = 0; i < h->ci_n; ++i) {
                 const int c = h->ci_cls[i], n_c = h->ci_cnt[i], m_c = m4[c];
                 const int gpt = (m_c <= 32 && 32 % m_c) ? 32 / m_c : 0, ngrp = n_c * d.K;          // padded tiles: as desire_ioc_refine seated the class
                 const long R_c = gpt ? (long)((ngrp + gpt - 1) / gpt) * 32 : (long)n_c * d.K * m_c;
                 views.push_back(BView{R_c, m_c, n_c, W(h, "ci_Hx") + aoff * 2 * H, W(h, "ci_pl") + aoff * 2,
-                                      static_cast<const uint8_t*>(h->ws["ci_valid"].p) + aoff, roff, static_cast<const int32_t*>(h->ws["ci_map"].p) + (size_t)c * h->A, gpt, ngrp});
-                aoff += (size_t)n_c * m_c; roff += (size_t)R_c;
+                                      static_cast<const uint8_t*>(h->ws["ci_valid"].p) + aoff, roff, static_cast<const int32_t*>(h->ws["ci_map"].p) + (size_t)c * h->A, gpt, ngrp,
+                                      static_cast<const int32_t*>(h->ws["ci_gos"].p) + woff});
+                aoff += (size_t)n_c * m_c; roff += (size_t)R_c; woff += (size_t)n_c;
             }
         } else
-            views.push_back(BView{R, d.mno, d.n_scenes, W(h, "HxHy"), W(h, "p_last"), static_cast<const uint8_t*>(h->ws["valid"].p), 0, nullptr, 0, 0});
+            views.push_back(BView{R, d.mno, d.n_scenes, W(h, "HxHy"), W(h, "p_last"), static_cast<const uint8_t*>(h->ws["valid"].p), 0, nullptr, 0, 0,
+                                  static_cast<const int32_t*>(h->ws["grid_of_scene"].p)});
         const long RTf = (R + 128) * T;                    // stride of a refinement pass's saves (desire_set_training: rows + slack)
         launch_fill_f32(W(h, "dscore0"), (size_t)R, 0.f, s);
+        if (sg_on) {
+            if (!h->ws.count("sg_wcat")) return fail(DESIRE_ERR_STATE, "scene_grad buffers missing (desire_set_option after desire_set_training failed?)");
+            Timer ts(h, s, "bwd_scene_grad");
+            launch_scene_wcat(W(h, "Wflat") + h->slots.at("ioc/gates/kernel").off, W(h, "Wflat") + h->slots.at("ioc/candidate/kernel").off, H, d.E_v,
+                              W(h, "sg_wcat"), s);
+        }
+        bool scene_first = true;                    // the first (view, pass) writes d loss / d grids, the others accumulate
         bool first = true;                          // the first launch sequence writes the weight gradients, the others accumulate
         for (size_t vi = 0; vi < views.size(); ++vi) {
         const BView& v = views[vi];
@@ -643,6 +675,20 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
 #endif
             } else
             launch_ioc_bwd(q, s);
+            if (sg_on) {                // d loss / d grids from this pass's gate gradients (dag / dac are overwritten by the next pass)
+                Timer ts(h, s, "bwd_scene_grad");
+                SceneDsArgs sa{};
+                sa.dag = W(h, "ioc_dag"); sa.dac = W(h, "ioc_dac"); sa.Y = q.Y0; sa.gos = v.gos; sa.wcat = W(h, "sg_wcat");
+                sa.R = (int)Rv; sa.T = T; sa.H = H; sa.K = d.K; sa.mno = v.mno; sa.gpt = v.gpt; sa.ngrp = v.ngrp; sa.Gh = d.Gh; sa.Gw = d.Gw;
+                sa.n_keys = d.n_grids * d.Gh * d.Gw; sa.key_bits = scene_key_bits(sa.n_keys);
+                sa.ds = W(h, "sg_ds"); sa.keys = static_cast<uint32_t*>(h->ws["sg_keys"].p); sa.idx = static_cast<int32_t*>(h->ws["sg_idx"].p);
+                SceneSortBufs sb{h->ws["sg_tmp"].p, h->ws["sg_tmp"].bytes, static_cast<uint32_t*>(h->ws["sg_keys_sorted"].p),
+                                 static_cast<int32_t*>(h->ws["sg_idx_sorted"].p), static_cast<int32_t*>(h->ws["sg_beg"].p),
+                                 static_cast<int32_t*>(h->ws["sg_end"].p), W(h, "sg_part")};
+                if (launch_scene_grid_grad(sa, sb, W(h, "scene_grid_grad"), scene_first ? 0 : 1, s))
+                    return fail(DESIRE_ERR_HIP, "scene-grid gradient: launch failed");
+                scene_first = false;
+            }
             tn(h, sv_h + (size_t)(T - 1) * H, T * H, dYr_v, 2 * T, Rv, H, 2 * T, G(h, "ioc/reg/w"), 2 * T, acc, s);
             colsum(h, dYr_v, 2 * T, Rv, 2 * T, G(h, "ioc/reg/b"), acc, s);
             if (last_pass) {
@@ -681,6 +727,28 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
             launch_cls_scatter_add_agents(W(h, "ci_dHx"), H, W(h, "dHxHy_ioc"), H, v.cmap, v.n_scenes * v.mno, H, s);
         }
         }       // views
+        if (sg_on && scene_first) launch_fill_f32(W(h, "scene_grid_grad"), (size_t)d.n_grids * d.Gh * d.Gw * d.C, 0.f, s);     // no IOC row ran
+    }
+    // ---- scene CNN (desire_set_scene_images): from d loss / d grids back through conv3 (5x5 s1, linear), ReLU, conv2 (5x5 s2), ReLU, conv1 (5x5 s2)
+    // into the Gflat slots scene_cnn/*.  Weight gradients: im2col rows [pixels, 25 Ci] contracted with the output gradient on the MFMA reduction tn()
+    // (fixed slices, fixed order: bitwise reproducible); bias gradients: column sums; data gradients: one gather per input element (no atomics).
+    if (h->img_set) {
+        Timer t(h, s, "bwd_scene_cnn");
+        const int n = d.n_grids, G1h = 2 * d.Gh, G1w = 2 * d.Gw, Ih = 4 * d.Gh, Iw = 4 * d.Gw;
+        const long P3 = (long)n * d.Gh * d.Gw, P1 = (long)n * G1h * G1w;
+        float* col = W(h, "sg_col");
+        const float* dG = W(h, "scene_grid_grad");
+        launch_im2col5(W(h, "scnn2"), col, n, d.Gh, d.Gw, 32, d.Gh, d.Gw, 1, 2, 800, s);
+        tn(h, col, 800, dG, d.C, P3, 800, d.C, G(h, "scene_cnn/conv3/w"), d.C, 0, s);
+        colsum(h, dG, d.C, P3, d.C, G(h, "scene_cnn/conv3/b"), 0, s);
+        launch_conv5_dgrad_relu(dG, D(h, "scene_cnn/conv3/w"), W(h, "scnn2"), W(h, "sg_d2"), n, d.Gh, d.Gw, 32, d.Gh, d.Gw, d.C, 1, 2, s);
+        launch_im2col5(W(h, "scnn1"), col, n, G1h, G1w, 16, d.Gh, d.Gw, 2, 1, 400, s);
+        tn(h, col, 400, W(h, "sg_d2"), 32, P3, 400, 32, G(h, "scene_cnn/conv2/w"), 32, 0, s);
+        colsum(h, W(h, "sg_d2"), 32, P3, 32, G(h, "scene_cnn/conv2/b"), 0, s);
+        launch_conv5_dgrad_relu(W(h, "sg_d2"), D(h, "scene_cnn/conv2/w"), W(h, "scnn1"), W(h, "sg_d1"), n, G1h, G1w, 16, d.Gh, d.Gw, 32, 2, 1, s);
+        launch_im2col5(h->img, col, n, Ih, Iw, 3, G1h, G1w, 2, 1, 76, s);               // 75 columns, rows padded to 76 floats
+        tn(h, col, 76, W(h, "sg_d1"), 16, P1, 75, 16, G(h, "scene_cnn/conv1/w"), 16, 0, s);
+        colsum(h, W(h, "sg_d1"), 16, P1, 16, G(h, "scene_cnn/conv1/b"), 0, s);
     }
     // ---- mask fc ----
     if (Rs > 0) {

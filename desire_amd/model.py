@@ -129,6 +129,7 @@ class DESIREModel(object):
         self._weights_ver = 0                # version self._weights (host copy) corresponds to
         self._grids = None
         self._grid_of_scene = None
+        self._images = None                  # set_scene_images: the library runs (and trains) the scene CNN
         # reference attribute names (model/model.py:62-75)
         self.input_data = None
         self.target_data = None
@@ -178,9 +179,48 @@ class DESIREModel(object):
         return h
 
     def set_scene_grids(self, grids: np.ndarray, grid_of_scene: Sequence[int]) -> None:
-        """grids [n_grids, Gh, Gw, C] scene features rho(I); grid_of_scene[i] = grid index of window i."""
+        """grids [n_grids, Gh, Gw, C] scene features rho(I); grid_of_scene[i] = grid index of window i.  Detaches scene images."""
         self._grids = self.torch.as_tensor(np.ascontiguousarray(grids, np.float32), device=self.device)
         self._grid_of_scene = np.asarray(grid_of_scene, np.int32)
+        self._images = None
+
+    def set_scene_images(self, images, grid_of_scene: Sequence[int]) -> None:
+        """images [n_grids, 4 Gh, 4 Gw, 3] (host array or device tensor): the library runs the scene CNN rho(I) on every forward that needs it,
+        and train_step trains its weights scene_cnn/* through the IOC backward.  grid_of_scene[i] = image index of window i (replaced per batch by
+        the grid_of_scene= argument of forward / train_step).  Detaches scene grids."""
+        torch = self.torch
+        img = images if torch.is_tensor(images) else torch.as_tensor(np.ascontiguousarray(images, np.float32))
+        img = img.to(device=self.device, dtype=torch.float32).contiguous()
+        if img.dim() != 4 or img.shape[-1] != 3:
+            raise ValueError("scene images must be [n_grids, 4*Gh, 4*Gw, 3], got %s" % (tuple(img.shape),))
+        self._images = img
+        self._grids = None
+        self._grid_of_scene = np.asarray(grid_of_scene, np.int32)
+
+    def _attach_scene(self, h, n: int, grid_of_scene=None) -> None:
+        """Gives handle h this batch's scene input -- the images (the handle runs the CNN) or the grids -- with the batch's grid_of_scene when
+        given, else the stored mapping resized to n windows."""
+        d = h.dims
+        if grid_of_scene is not None:
+            gos = np.ascontiguousarray(grid_of_scene, np.int32).reshape(-1)
+            if gos.size != n:
+                raise ValueError("grid_of_scene has %d entries for %d windows" % (gos.size, n))
+        elif self._grid_of_scene is not None:
+            gos = self._grid_of_scene if len(self._grid_of_scene) == n else np.resize(self._grid_of_scene, n)
+        else:
+            gos = np.zeros(n, np.int32)
+        if getattr(self, "_images", None) is not None:
+            img = self._images
+            src = (img.data_ptr(), tuple(img.shape), gos.tobytes())
+            if getattr(h, "_scene_src", None) != src:          # same images and mapping: the handle keeps its grid (no needless CNN rerun)
+                h.set_scene_images(img.data_ptr(), int(img.shape[1]), int(img.shape[2]), gos)
+                h._scene_src = src
+            return
+        if self._grids is None:
+            self._grids = self.torch.zeros((d.n_grids, d.Gh, d.Gw, d.C), device=self.device)
+            self._grid_of_scene = np.zeros(n, np.int32)
+        h.set_scene_grids(self._grids.data_ptr(), gos)
+        h._scene_src = None
 
     def _pad_windows(self, batch: Sequence[np.ndarray], mno: int):
         x = np.stack([np.asarray(b) for b in batch]).astype(np.float32)      # [n, T, MNO, 3]
@@ -194,7 +234,7 @@ class DESIREModel(object):
 
     # ---- the hot path ---------------------------------------------------------------------------
     def forward(self, x_batch: Sequence[np.ndarray], y_batch: Optional[Sequence[np.ndarray]] = None,
-                eps: Optional[np.ndarray] = None, seed: int = 0):
+                eps: Optional[np.ndarray] = None, seed: int = 0, grid_of_scene=None):
         """x_batch: loader windows [T_obs, MNO, 3] (DataLoader.next_batch x); y_batch: future windows
         [T_pred, MNO, 3] or None (prior sampling).  Returns (Yhat [n, K, mno, T_pred, 2] normalised,
         score [n, K, mno]) as torch tensors on the GPU."""
@@ -202,11 +242,11 @@ class DESIREModel(object):
         d = self._handle(len(x_batch), posterior).dims
         past = self._pad_windows(x_batch, d.mno)
         fut = self._pad_windows(y_batch, d.mno) if posterior else None
-        out = self.forward_device(past, fut, eps, seed)
+        out = self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene)
         self.input_data, self.target_data = x_batch, y_batch
         return out
 
-    def forward_device(self, past, fut=None, eps=None, seed: int = 0):
+    def forward_device(self, past, fut=None, eps=None, seed: int = 0, grid_of_scene=None):
         """forward() on windows that are already in HBM: past [n, T_obs, mno, 3], fut [n, T_pred, mno, 3] or None -- float32 device
         tensors in the loader's layout with the slot axis padded to the model's mno (what desire_amd.prefetch's feeders and
         forward_from_video produce).  Nothing here touches the host except the launches themselves."""
@@ -224,11 +264,7 @@ class DESIREModel(object):
             eps_t = eps.reshape(d.R, d.L)
         else:
             eps_t = torch.as_tensor(np.ascontiguousarray(eps, np.float32), device=self.device).reshape(d.R, d.L)
-        if self._grids is None:
-            self._grids = torch.zeros((d.n_grids, d.Gh, d.Gw, d.C), device=self.device)
-            self._grid_of_scene = np.zeros(n, np.int32)
-        gos = self._grid_of_scene if len(self._grid_of_scene) == n else np.resize(self._grid_of_scene, n)
-        h.set_scene_grids(self._grids.data_ptr(), gos)
+        self._attach_scene(h, n, grid_of_scene)
         Y = torch.empty((n, d.K, d.mno, d.T_pred, 2), device=self.device, dtype=torch.float32)
         score = torch.empty((n, d.K, d.mno), device=self.device, dtype=torch.float32)
         stream = torch.cuda.current_stream().cuda_stream
@@ -280,18 +316,19 @@ class DESIREModel(object):
 
     # ---- training (train.py:140-181 runs only `cost`; the Adam op of model/model.py:386-403 is never applied) ----
     def train_step(self, x_batch: Sequence[np.ndarray], y_batch: Sequence[np.ndarray], eps: Optional[np.ndarray] = None,
-                   seed: int = 0, group=None, sync: bool = True):
+                   seed: int = 0, group=None, sync: bool = True, grid_of_scene=None):
         """One optimiser step on a batch of loader windows: forward (posterior path), backward, gradient mean over
         the data-parallel ranks (RCCL all-reduce of ONE flat buffer when torch.distributed is initialised),
         clip_by_global_norm(args.grad_clip), Adam(args.learning_rate).  Returns the loss terms of DESIGN.md section 8
         evaluated BEFORE the update (what `sess.run([cost, train_op])` would have returned); with sync=False a PendingLoss
         whose .get() returns them later (see train_step_device)."""
         d = self._handle(len(x_batch), True).dims
-        out = self.train_step_device(self._pad_windows(x_batch, d.mno), self._pad_windows(y_batch, d.mno), eps, seed, group, sync)
+        out = self.train_step_device(self._pad_windows(x_batch, d.mno), self._pad_windows(y_batch, d.mno), eps, seed, group, sync,
+                                     grid_of_scene=grid_of_scene)
         self.input_data, self.target_data = x_batch, y_batch
         return out
 
-    def train_step_device(self, past, fut, eps=None, seed: int = 0, group=None, sync: bool = True):
+    def train_step_device(self, past, fut, eps=None, seed: int = 0, group=None, sync: bool = True, grid_of_scene=None):
         """train_step on windows already in HBM (forward_device's layout).  sync=False: nothing waits for the GPU -- the loss terms
         go to a device buffer (desire_train_loss_async), a pinned copy is enqueued, and the returned PendingLoss reads them when asked,
         normally one step later (desire_amd/train.py): the host runs ahead of the device and the loader thread is never starved by a
@@ -311,7 +348,7 @@ class DESIREModel(object):
             if pending is not None:                   # resumed run: Adam moments and step counter of the checkpoint
                 h.set_opt_state(pending)
             self._configure_head_loss(h)
-        self.forward_device(past, fut, eps, seed)
+        self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene)
         past, fut, eps_t = self._keep
         stream = torch.cuda.current_stream().cuda_stream
         h.backward(past.data_ptr(), fut.data_ptr(), eps_t.data_ptr(), stream)
@@ -369,11 +406,7 @@ class DESIREModel(object):
             eps_t = torch.randn((d.R, d.L), generator=g, device=self.device, dtype=torch.float32)
         else:
             eps_t = torch.as_tensor(np.ascontiguousarray(eps, np.float32), device=self.device).reshape(d.R, d.L)
-        if self._grids is None:
-            self._grids = torch.zeros((d.n_grids, d.Gh, d.Gw, d.C), device=self.device)
-            self._grid_of_scene = np.zeros(n, np.int32)
-        gos = self._grid_of_scene if len(self._grid_of_scene) == n else np.resize(self._grid_of_scene, n)
-        h.set_scene_grids(self._grids.data_ptr(), gos)
+        self._attach_scene(h, n)
         Y = torch.empty((n, d.K, d.mno, d.T_pred, 2), device=self.device, dtype=torch.float32)
         score = torch.empty((n, d.K, d.mno), device=self.device, dtype=torch.float32)
         h.forward(past.data_ptr(), fut.data_ptr() if posterior else 0, eps_t.data_ptr(), Y.data_ptr(), score.data_ptr(), stream)

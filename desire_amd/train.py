@@ -81,9 +81,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--prefetch", type=int, default=2,
                    help="batches the loader thread keeps in flight (pinned staging -> copy stream -> device; desire_amd/prefetch.py); 0 = the "
                         "reference's serial loop: next_batch, copy, step, read the loss, every step (train.py:131-183)")
+    p.add_argument("--scene_images", type=str, default=None,
+                   help=".npz with one [4*scene_grid, 4*scene_grid, 3] float image per video, keyed by the video directory relative to --data_dir "
+                        "(e.g. bookstore/video6): the scene CNN runs on them and trains with the model (n_grids = the file's entries)")
     p.add_argument("--report_ade", action="store_true",
                    help="after every epoch: ADE / FDE (mean-of-K and best-of-K, normalised units) of PRIOR samples on the epoch's last batch")
     return p
+
+
+def _gos(grid_of_video, dval):
+    """grid_of_scene of a batch: the scene image of each window's video index (None without --scene_images)."""
+    return None if grid_of_video is None else grid_of_video[np.asarray(dval, np.int64)]
 
 
 def lr_at_epoch(args, epoch: int) -> float:
@@ -102,6 +110,29 @@ def split_windows(xval: Sequence[np.ndarray], t_obs: int) -> Tuple[List[np.ndarr
     past = [np.asarray(x)[:t_obs] for x in xval]
     fut = [np.asarray(x)[t_obs:] for x in xval]
     return past, fut
+
+
+def scene_image_keys(data_loader, data_dir: str) -> List[str]:
+    """The key of every video the loader reads, in its video index order d: the video directory relative to data_dir."""
+    paths = data_loader._csv_paths()[: data_loader.leave_dataset]
+    return [os.path.relpath(os.path.dirname(p), data_dir).replace(os.sep, "/") for p in paths]
+
+
+def load_scene_images(path: str, video_keys: Sequence[str], Gh: int, Gw: int) -> Tuple[np.ndarray, np.ndarray]:
+    """--scene_images: (images [n_grids, 4 Gh, 4 Gw, 3] float32, grid of every video index).  n_grids = the entries of the file (sorted by key);
+    a video without an entry, or an entry of another shape, raises ValueError naming them."""
+    with np.load(path) as z:
+        keys = sorted(z.files)
+        arrays = {k: np.asarray(z[k]) for k in keys}
+    missing = [k for k in video_keys if k not in arrays]
+    if missing:
+        raise ValueError("--scene_images %s has no image for the video(s) %s (keys: %s)" % (path, ", ".join(missing), ", ".join(keys)))
+    want = (4 * Gh, 4 * Gw, 3)
+    bad = ["%s %s" % (k, tuple(a.shape)) for k, a in arrays.items() if tuple(a.shape) != want]
+    if bad:
+        raise ValueError("--scene_images %s: every image must be %s, got %s" % (path, want, ", ".join(bad)))
+    images = np.stack([arrays[k].astype(np.float32) for k in keys])
+    return images, np.array([keys.index(k) for k in video_keys], np.int32)
 
 
 def train(args, data_loader=None, model=None, log: Callable[[str], None] = print) -> List[float]:
@@ -130,8 +161,16 @@ def train(args, data_loader=None, model=None, log: Callable[[str], None] = print
         os.makedirs(args.save_dir, exist_ok=True)
         with open(os.path.join(args.save_dir, "config.pkl"), "wb") as fh:
             pickle.dump(args, fh)
+    grid_of_video = None
+    if getattr(args, "scene_images", None):
+        G = int(getattr(args, "scene_grid", 64))
+        images, grid_of_video = load_scene_images(args.scene_images, scene_image_keys(data_loader, args.data_dir), G, G)
+        args.n_grids = int(images.shape[0])
     if model is None:
         model = DESIREModel(args, seed=args.seed)
+    if grid_of_video is not None:
+        model.set_scene_images(images, np.zeros(1, np.int32))
+        model._grid_of_video = grid_of_video
     losses: List[float] = []
     # the overlapped schedule needs the fast loader's next_batch_into; a reference-shaped loader (utils/data_loader.py's API: next_batch only) gets
     # the reference's serial loop instead of an AttributeError from the feeder thread
@@ -143,9 +182,9 @@ def train(args, data_loader=None, model=None, log: Callable[[str], None] = print
         data_loader.reset_batch_pointer()
         for batch in range(data_loader.num_batches):
             start = time.time()
-            xval, _, _ = data_loader.next_batch()
+            xval, _, dval = data_loader.next_batch()
             past, fut = split_windows(shard_batch(xval, rank, world), t_obs)
-            terms = model.train_step(past, fut, seed=args.seed + steps * world + rank)
+            terms = model.train_step(past, fut, seed=args.seed + steps * world + rank, grid_of_scene=_gos(grid_of_video, shard_batch(dval, rank, world)))
             losses.append(terms["loss"])
             steps += 1
             if rank == 0:
@@ -215,7 +254,8 @@ def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred,
             if last is not None and bt.epoch != last[2] and getattr(args, "report_ade", False):
                 _report_ade(args, model, last[0], last[1], last[2], rank, log)
             bt.wait()
-            pl = model.train_step_device(bt.past, bt.fut, seed=args.seed + steps * world + rank, sync=False)
+            pl = model.train_step_device(bt.past, bt.fut, seed=args.seed + steps * world + rank, sync=False,
+                                         grid_of_scene=_gos(getattr(model, "_grid_of_video", None), bt.d))
             if getattr(args, "report_ade", False):        # the epoch's last batch is evaluated after the feeder has moved on: keep a copy
                 last = (bt.past.clone(), bt.fut.clone(), bt.epoch)
             bt.release()

@@ -151,6 +151,9 @@ const char* desire_build_hash(void);
  * "flags"; takes effect at the next call (a flag that changes what desire_encode prepares -- DESIRE_FLAG_COMPACT_* -- at the next
  * desire_encode).  "compact_min_rows" (not a desire_dims field): the fold threshold of DESIRE_FLAG_COMPACT_IOC.  "compact_host_counts" (not a
  * desire_dims field): 1 = inference reads the compaction counts back like training does (see DESIRE_FLAG_COMPACT_ROWS), 0 = device-side counts (default).
+ * "scene_grad" (not a desire_dims field): 1 = desire_backward also writes d loss / d grids [n_grids, Gh, Gw, C] of the grids desire_set_scene_grids
+ * gave into the workspace tensor "scene_grid_grad" (desire_device_buffer; bitwise reproducible, no weight gradient changes); 0 = off (default), and
+ * the tensor is then refused (DESIRE_ERR_STATE), as it is outside training mode.
  * Unknown name or value out of range: DESIRE_ERR_ARG. */
 int desire_set_option(desire_handle* h, const char* name, int32_t value);
 
@@ -170,6 +173,12 @@ int desire_finalize_weights(desire_handle* h);
  * argument of sample(), :613).  dev_grids [n_grids, Gh, Gw, C]; host_grid_of_scene [n_scenes].
  * The device buffer is referenced, not copied: keep it alive while the handle uses it. */
 int desire_set_scene_grids(desire_handle* h, const float* dev_grids, const int32_t* host_grid_of_scene);
+/* Scene IMAGES instead of precomputed grids: dev_images [n_grids, Hi = 4*Gh, Wi = 4*Gw, 3] (referenced, not copied: keep it alive), host_grid_of_scene
+ * [n_scenes] validated as above.  The handle then owns its grid buffer and runs the scene CNN of desire_scene_cnn itself (bit-identical grid): a
+ * training-mode desire_forward every step, keeping the post-ReLU activations; an inference-mode forward only when the grid is stale (desire_set_weight,
+ * desire_finalize_weights, desire_adam_step, or the images set again).  In training, desire_backward then also fills the gradients of the six scene_cnn weights
+ * (and "scene_grid_grad", as desire_set_option(h, "scene_grad", 1) does).  The last of desire_set_scene_grids / desire_set_scene_images called wins. */
+int desire_set_scene_images(desire_handle* h, const float* dev_images, int32_t Hi, int32_t Wi, const int32_t* host_grid_of_scene);
 
 /* Encoders + CVAE encoder (model/model.py:233-259,471-492).
  * dev_past [n_scenes, T_obs, mno, 3] and dev_fut [n_scenes, T_pred, mno, 3] are stacks of the
