@@ -240,9 +240,11 @@ extern "C" int desire_set_option(desire_handle* h, const char* name, int32_t val
     }
     else return fail(DESIRE_ERR_ARG, "unknown option: " + nm + " (ioc_form, ioc_split, train_fp32_mask, flags, compact_min_rows, compact_host_counts, scene_grad)");
     if (int rc = check_options(d)) return rc;
-    if ((d.flags ^ h->d.flags) & (DESIRE_FLAG_COMPACT_ROWS | DESIRE_FLAG_COMPACT_IOC)) {
-        h->cp_pending = false; h->cp_enc = false;       // the maps of the last desire_encode were built for the other setting: a new desire_encode comes first
-    }
+    // the maps of the last desire_encode were built for the other setting, or for the other slot-class set (ioc_form and train_fp32_mask decide
+    // whether class 10 exists): a new desire_encode comes first
+    if (((d.flags ^ h->d.flags) & (DESIRE_FLAG_COMPACT_ROWS | DESIRE_FLAG_COMPACT_IOC)) ||
+        ((d.flags & DESIRE_FLAG_COMPACT_IOC) && (d.ioc_form != h->d.ioc_form || d.train_fp32_mask != h->d.train_fp32_mask)))
+        h->cp_pending = h->cp_enc = false;
     h->d = d;
     return DESIRE_OK;
 }

@@ -11,54 +11,53 @@
 bool compact_rows(const desire_ctx* h) { return (h->d.flags & DESIRE_FLAG_COMPACT_ROWS) != 0; }
 // DESIRE_FLAG_COMPACT_IOC: windows re-seated in the smallest slot class that holds their present agents (kernels_compact.hip).  Shapes served by the
 // step-wise IOC (more than 128 slots, or split operands at H = 256) keep their own layout.
-bool compact_ioc(const desire_ctx* h) {
+bool compact_ioc(const desire_ctx* h) { return (h->d.flags & DESIRE_FLAG_COMPACT_IOC) && ioc_plan(h).fwd != IocFwd::STEPWISE; }
+ClassLayout class_layout(const desire_ctx* h, bool pad, const int* counts) {
     const desire_dims& d = h->d;
-    if (!(d.flags & DESIRE_FLAG_COMPACT_IOC) || d.mno > 128) return false;
-    const int B_ = d.grid_size * d.grid_size;
-    const bool split_mode = (d.bf16 == 2 || d.bf16 == 3) && !h->training;
-    const bool split_served = ioc_x3_supported(d.mno, d.H, B_) || (d.mno == 64 && ioc_x6r2_supported(d.mno, d.H, B_));
-    return !(split_mode && !split_served && d.H == 256 && d.ioc_form == DESIRE_IOC_AUTO);
-}
-// slot classes that do not divide 32 (padded tiles: k_ioc<TM = 32> and k_ioc_x3 have that form, inference, groups of <= 32 slots, H <= 128)
-bool compact_padded_ok(const desire_ctx* h) {
-    const desire_dims& d = h->d;
-    if (h->training && !((d.bf16 == 0 || (d.bf16 == 2 && (train_x3_mask(h) & 4))) && d.ioc_form == DESIRE_IOC_AUTO)) return false;      // (BPTT: k_ioc_bwd / k_ioc_bwd_x3)
-    return (d.bf16 == 0 || d.bf16 == 2) && d.H <= 128 && (d.ioc_form == DESIRE_IOC_AUTO);
-}
-int compact_classes(const desire_ctx* h, int* m4) {         // slot classes: the three largest candidates below the handle's own mno, then mno itself
-    // candidates: 8, 16, 32, 64, 96; where the padded-tile kernels serve the handle also 10 (three groups of <= 10 slots per 32-row tile: a window with
-    // 9 present agents -- the typical SDD bookstore window -- runs in 10 rows per sample instead of 16)
+    ClassLayout L;
+    // the three largest candidates below the handle's own mno, then mno itself.  Candidates: 8, 16, 32, 64, 96; with padded tiles also 10 (three
+    // groups of <= 10 slots per 32-row tile: a window with 9 present agents -- the typical SDD bookstore window -- runs in 10 rows per sample, not 16)
     int cand[6], nc = 0;
-    const bool pad = compact_padded_ok(h);
-    for (int m : {8, 10, 16, 32, 64, 96}) if (m < h->d.mno && (m != 10 || pad)) cand[nc++] = m;
-    int n = 0;
-    for (int i = nc > 3 ? nc - 3 : 0; i < nc; ++i) m4[n++] = cand[i];
-    m4[n++] = h->d.mno;
-    for (int i = n; i < 4; ++i) m4[i] = h->d.mno;
-    return n;
+    for (int m : {8, 10, 16, 32, 64, 96}) if (m < d.mno && (m != 10 || pad)) cand[nc++] = m;
+    for (int i = nc > 3 ? nc - 3 : 0; i < nc; ++i) L.m[L.n++] = cand[i];
+    L.m[L.n++] = d.mno;
+    for (int i = L.n; i < 4; ++i) L.m[i] = d.mno;
+    for (int c = 0; c < L.n; ++c) {
+        IocView& v = L.c[c];
+        v.cls = c; v.mno = L.m[c]; v.n_scenes = counts ? counts[c] : d.n_scenes;
+        v.gpt = (v.mno <= 32 && 32 % v.mno) ? 32 / v.mno : 0; v.ngrp = v.n_scenes * d.K;          // padded tiles for a class that does not divide 32
+        v.R = v.gpt ? (long)((v.ngrp + v.gpt - 1) / v.gpt) * 32 : (long)v.ngrp * v.mno;
+        v.agent_off = L.agents; v.row_off = L.rows; v.win_off = L.wins;
+        L.agents += (size_t)v.n_scenes * v.mno; L.rows += (size_t)v.R; L.wins += (size_t)v.n_scenes;
+    }
+    return L;
+}
+IocView ioc_view(desire_ctx* h, const IocView* cls) {
+    if (!cls)
+        return IocView{-1, h->d.mno, h->d.n_scenes, 0, 0, h->R, 0, 0, 0, W(h, "HxHy"), W(h, "p_last"), static_cast<uint8_t*>(h->ws["valid"].p),
+                       static_cast<int32_t*>(h->ws["grid_of_scene"].p)};
+    IocView v = *cls;
+    v.Hx = W(h, "ci_Hx") + v.agent_off * 2 * h->d.H; v.p_last = W(h, "ci_pl") + v.agent_off * 2;
+    v.valid = static_cast<uint8_t*>(h->ws["ci_valid"].p) + v.agent_off; v.gos = static_cast<int32_t*>(h->ws["ci_gos"].p) + v.win_off;
+    v.cmap = static_cast<const int32_t*>(h->ws["ci_map"].p) + (size_t)v.cls * h->A; v.win = static_cast<const int32_t*>(h->ws["ci_win"].p) + (size_t)v.cls * h->d.n_scenes;
+    v.Y = W(h, "ci_Y") + v.row_off * h->d.T_pred * 2; v.score = W(h, "ci_score") + v.row_off;
+    return v;
 }
 // DEVICE-SIDE COUNTS (round 6): in inference with frozen batch-norm the host never learns how many agents are present -- every compacted launch is
 // sized for the worst case and reads its count from the scans' device words (kernels.h: DynCount), so a compacted call has no host wait and can be
 // captured in a hipGraph.  Training keeps the read-back (its backward sizes two dozen reductions from P), and so do per-sample batch statistics
 // (bn_mode 1: the normalisation kernels are not count-aware) and desire_set_option("compact_host_counts", 1) -- the A/B switch.
 bool compact_dyn(const desire_ctx* h) { return !h->training && h->d.bn_mode == 0 && !h->cp_host_counts; }
-// worst case of one slot class: every window of the batch seated in it
-static size_t class_rows_worst(const desire_ctx* h, int m_c) {
-    const int gpt = (m_c <= 32 && 32 % m_c) ? 32 / m_c : 0;
-    const size_t ngrp = (size_t)h->d.n_scenes * h->d.K;
-    return gpt ? ((ngrp + gpt - 1) / gpt) * 32 : ngrp * m_c;
-}
 int compact_setup(desire_ctx* h) {
     const desire_dims& d = h->d;
     const size_t A = h->A, R = h->R, f = sizeof(float);
-    // slot-class buffers: with device-side counts a class's region starts at a STATIC offset (the sum of the worst cases of the classes before it)
+    // slot-class buffers: with device-side counts a class's region starts at a STATIC offset (the sum of the worst cases of the classes before it).
+    // Sized for both class sets the handle can take -- with and without class 10, which ioc_form, train_fp32_mask and the training mode switch on a
+    // live handle -- so they never grow and pointers captured in a hipGraph stay valid.
     size_t Ac = A, Rc = R + 128, Wc = (size_t)d.n_scenes;
     if (d.flags & DESIRE_FLAG_COMPACT_IOC) {
-        int m4[4];
-        const int n_cls = compact_classes(h, m4);
-        Ac = 0; Rc = 0; Wc = 0;
-        for (int c = 0; c < n_cls; ++c) { Ac += (size_t)d.n_scenes * m4[c]; Rc += class_rows_worst(h, m4[c]); Wc += (size_t)d.n_scenes; }
-        Ac = std::max(Ac, A); Rc = std::max(Rc, R + 128);
+        const ClassLayout a = class_layout(h, false, nullptr), b = class_layout(h, true, nullptr);
+        Ac = std::max({a.agents, b.agents, A}); Rc = std::max({a.rows, b.rows, R + 128}); Wc = std::max(a.wins, b.wins);
     }
     struct WS { const char* n; size_t bytes; };
     const WS list[] = {{"cp_amap", A * sizeof(int32_t)}, {"cp_inv", A * sizeof(int32_t)}, {"cp_count", 8 * sizeof(int32_t)}, {"cp_HxHy", A * 2 * d.H * f},
@@ -87,9 +86,8 @@ static int compact_scans(desire_ctx* h, hipStream_t s) {
     launch_present_scan(static_cast<const uint8_t*>(h->ws["valid"].p), h->A, static_cast<int32_t*>(h->ws["cp_amap"].p), static_cast<int32_t*>(h->ws["cp_inv"].p),
                         static_cast<int32_t*>(h->ws["cp_count"].p), h->cp_host, s);
     if (compact_ioc(h)) {
-        int m4[4];
-        const int n_cls = compact_classes(h, m4);
-        launch_class_scan(static_cast<const uint8_t*>(h->ws["valid"].p), d.n_scenes, d.mno, n_cls, m4, d.K, h->ci_min_rows, static_cast<int32_t*>(h->ws["ci_win"].p),
+        const ClassLayout L = class_layout(h, ioc_plan(h).padded, nullptr);
+        launch_class_scan(static_cast<const uint8_t*>(h->ws["valid"].p), d.n_scenes, d.mno, L.n, L.m, d.K, h->ci_min_rows, static_cast<int32_t*>(h->ws["ci_win"].p),
                           static_cast<int32_t*>(h->ws["ci_map"].p), static_cast<int32_t*>(h->ws["cp_count"].p) + 4, h->cp_host + 4, s);
     }
     if (!compact_dyn(h)) HIPCHK(hipEventRecord(h->cp_ev, s));             // (device-side counts: nobody waits, and the call stays capturable)
@@ -360,147 +358,114 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
     return DESIRE_OK;
 }
 
-// One IOC launch sequence over a VIEW of the handle's rows: the handle's own shape (row_off 0), or one slot class of DESIRE_FLAG_COMPACT_IOC --
-// n_scenes windows of mno slots each with their own agent-level inputs; training-mode saves go to the view's row offset in the shared buffers.
-struct IocView {
-    int R, mno, n_scenes; float* Y; float* score; const float* Hx; int ldhx; const float* p_last; const uint8_t* valid; const int32_t* gos; size_t row_off;
-    const int32_t* dynN = nullptr;   // the view's window count on the device (a slot class under device-side counts): R / n_scenes / ngrp above are the worst case
-    int gpt = 0, ngrp = 0;       // padded tiles (slot classes that do not divide 32; kernels.h: IocArgs.gpt): groups per 32-row tile, real groups; R = tiles * 32
-};
+int ioc_cluster_exchange(desire_ctx* h, size_t n_groups, bool reset_err, hipStream_t s) {
+    if (!h->ws.count("hex") && (h->ws["hex"].alloc((size_t)2 * h->R * h->d.H * sizeof(float)) || h->ws["grp_cnt"].alloc(((size_t)h->R / 32 + 1) * sizeof(int)) ||
+                                h->ws["ioc_err"].alloc(sizeof(int))))
+        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the cluster exchange buffers");
+    HIPCHK(hipMemsetAsync(h->ws["grp_cnt"].p, 0, n_groups * sizeof(int), s));
+    if (reset_err) HIPCHK(hipMemsetAsync(h->ws["ioc_err"].p, 0, sizeof(int), s));
+    return DESIRE_OK;
+}
+int ioc_cluster_check(desire_ctx* h, hipStream_t s, const char* what) {
+    int err = 0;
+    HIPCHK(hipMemcpyAsync(&err, h->ws["ioc_err"].p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return err ? fail(DESIRE_ERR_HIP, std::string(what) + " hand-off timed out (workgroups of a group were not co-resident)") : DESIRE_OK;
+}
+#ifdef DESIRE_IOC_TIMING
+void ioc_timing_report(const long long* dbg, const char* const* names, int n, hipStream_t s) {
+    long long host[16];
+    (void)hipStreamSynchronize(s); (void)hipMemcpy(host, dbg, n * sizeof(long long), hipMemcpyDeviceToHost);
+    long long tot = 0; for (int k = 0; k < n; ++k) tot += host[k];
+    for (int k = 0; k < n; ++k) fprintf(stderr, "[ioc timing] %-45s %12lld cyc  %5.1f%%\n", names[k], host[k], 100.0 * host[k] / (double)tot);
+}
+#endif
+
+// One IOC launch sequence over a view of the handle's rows (the handle's own layout, or one slot class); training-mode saves go to the view's
+// row offset in the shared buffers.
 static int ioc_core(desire_handle* h, const IocView& v, hipStream_t s) {
     const desire_dims& d = h->d;
+    if (h->training && d.bf16 == 1) return fail(DESIRE_ERR_STATE, "bf16 operands are inference-only");
     IocArgs a{};
-    a.Y = v.Y; a.score = v.score; a.Hx = v.Hx; a.ldhx = v.ldhx; a.p_last = v.p_last;
-    a.valid = v.valid;
-    a.R = v.R; a.K = d.K; a.mno = v.mno; a.H = d.H; a.T = d.T_pred; a.iters = d.iters;
+    a.Y = v.Y; a.score = v.score; a.Hx = v.Hx; a.ldhx = 2 * d.H; a.p_last = v.p_last; a.valid = v.valid;
+    a.R = (int)v.R; a.K = d.K; a.mno = v.mno; a.H = d.H; a.T = d.T_pred; a.iters = d.iters;
     a.C = d.C; a.Gh = d.Gh; a.Gw = d.Gw; a.E_v = d.E_v; a.G = d.grid_size; a.nb_w = d.nb_w; a.nb_h = d.nb_h;
-    a.grids = h->grids; a.grid_of_scene = v.gos;
-    a.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
+    a.grids = h->grids; a.grid_of_scene = v.gos; a.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
     a.w_vel = D(h, "ioc/vel_w"); a.b_vel = D(h, "ioc/vel_b");
     a.Wsoc = D4(h, "ioc/Wsoc"); a.b_soc = D(h, "ioc/soc_b"); a.Wsoc_c = D4(h, "ioc/Wsoc_c");
     a.Wg = D4(h, "ioc/Wg"); a.Wc = D4(h, "ioc/Wc"); a.b_g = D(h, "ioc/gb"); a.b_c = D(h, "ioc/cb");
     a.w_score = D(h, "ioc/score_w"); a.b_score = D(h, "ioc/score_b");
     a.Wreg = D4(h, "ioc/Wreg"); a.b_reg = D(h, "ioc/reg_b"); a.NTreg = (2 * d.T_pred + 31) / 32;
-    a.variant = d.ioc_form;
-    a.gpt = v.gpt; a.ngrp = v.ngrp;
-    a.dyn = DynCount{v.dynN, 1, 0};
-    // bf16: one workgroup holds groups of up to 64 agents; 96 / 128 (and 64 when variant 4 / 6 asks for it) run the cluster form
-    // split forms: groups of up to 32 agents on 32-row tiles (also the training-mode forward); inference on groups of 64 agents runs the
-    // 64-row tile of kernels_x6r2.hip (one group per tile) in either piece count
-    const bool wide64 = v.mno == 64 && !h->training && ioc_x6r2_supported(v.mno, d.H, d.grid_size * d.grid_size);
-    const bool x3 = d.bf16 == 2 && (ioc_x3_supported(v.mno, d.H, d.grid_size * d.grid_size) || wide64 || (v.gpt > 0 && ioc_x3_supported(32, d.H, d.grid_size * d.grid_size)));
-    const bool x6 = d.bf16 == 3 && (ioc_x3_supported(v.mno, d.H, d.grid_size * d.grid_size) || wide64);     // six-product form: inference only
-    const bool cluster = d.bf16 == 1 ? (v.mno > 64 || (v.mno == 64 && (a.variant == 4 || a.variant == 6)))
-                                : (!(x3 || x6) || h->training) && ioc_uses_cluster(v.mno, d.H, d.grid_size * d.grid_size, a.variant);
-    if (cluster) {
-        const size_t n_groups = (size_t)v.R / v.mno;
-        if (!h->ws.count("hex")) {          // (sized for the handle's own shape: every view of it -- DESIRE_FLAG_COMPACT_IOC classes -- is smaller)
-            if (h->ws["hex"].alloc((size_t)2 * h->R * d.H * sizeof(float)) || h->ws["grp_cnt"].alloc(((size_t)h->R / 32 + 1) * sizeof(int)) ||
-                h->ws["ioc_err"].alloc(sizeof(int)))
-                return fail(DESIRE_ERR_HIP, "hipMalloc failed for the cluster exchange buffers");
-        }
-        HIPCHK(hipMemsetAsync(h->ws["grp_cnt"].p, 0, n_groups * sizeof(int), s));
-        HIPCHK(hipMemsetAsync(h->ws["ioc_err"].p, 0, sizeof(int), s));
+    a.variant = d.ioc_form; a.gpt = v.gpt; a.ngrp = v.ngrp; a.dyn = DynCount{v.dynN, 1, 0};
+    const IocPlan p = ioc_plan(d, h->training, v.mno, v.gpt, v.R, [&](int n) { return ioc_bin_split_capacity(a, n); });
+    if (!p.fp32_weights()) { a.Wsoc = D4(h, "ioc/Wsoc16"); a.Wg = D4(h, "ioc/Wg16"); a.Wc = D4(h, "ioc/Wc16"); a.Wreg = D4(h, "ioc/Wreg16"); }
+    if (p.cluster()) {
+        if (int rc = ioc_cluster_exchange(h, (size_t)v.R / v.mno, true, s)) return rc;
         a.hex = W(h, "hex"); a.grp_cnt = static_cast<int*>(h->ws["grp_cnt"].p); a.err = static_cast<int*>(h->ws["ioc_err"].p);
     }
-    // a handful of windows, fp32 inference: the bins of every tile split over several workgroups (k_ioc NSPL; dims.ioc_split = 1: off).
-    // The members of a tile wait for each other, so the split is taken only when the whole launch is co-resident on THIS device
-    // (occupancy x compute units, not a constant: a partition with fewer CUs falls back to the plain form).
-    if (!cluster && d.bf16 == 0 && !h->training && d.ioc_split != 1 && a.variant == 0 && v.gpt == 0) {
-        int nspl = ioc_bin_split(v.R, v.mno, d.H, d.grid_size * d.grid_size, d.iters);
-        if (nspl > 1 && d.ioc_split > 1) nspl = std::min(nspl, d.ioc_split);
+    if (p.nspl > 1) {
         const size_t tiles = ((size_t)v.R + 31) / 32, tiles_max = ((size_t)h->R + 31) / 32;
-        while (nspl > 1 && (size_t)ioc_bin_split_capacity(a, nspl) < tiles * nspl) --nspl;
-        if (nspl > 1) {
-            if (!h->ws.count("hex_s") || !h->ws["hex_s"].p || !h->ws["cnt_s"].p) {
-                if (h->ws["hex_s"].alloc(tiles_max * 2 * 4 * 32 * d.H * sizeof(float)) || h->ws["cnt_s"].alloc(tiles_max * sizeof(int)))
-                    return fail(DESIRE_ERR_HIP, "hipMalloc failed for the bin-split exchange buffers");
-            }
-            // the error word is mapped host memory: no read-back (and no stream synchronisation) per call; a timed-out hand-off is
-            // reported by the NEXT call on this handle.  Allocated and checked on its own (a failure here must not leave a later call
-            // with exchange buffers and a null word); the kernels write it with system-scope atomics.
-            if (!h->host_err) {
-                if (hipHostMalloc(reinterpret_cast<void**>(&h->host_err), sizeof(int), hipHostMallocMapped) != hipSuccess || !h->host_err) {
-                    h->host_err = nullptr;
-                    return fail(DESIRE_ERR_HIP, "hipHostMalloc failed for the bin-split error word");
-                }
-                *h->host_err = 0;
-            }
-            if (*static_cast<volatile int*>(h->host_err)) {
-                *h->host_err = 0;
-                return fail(DESIRE_ERR_HIP, "bin-split IOC hand-off timed out in an earlier call (workgroups of a tile were not co-resident)");
-            }
-            // (a fill KERNEL, not hipMemsetAsync: memset nodes of a captured graph were seen to run out of order on replay -- section 6a --
-            //  and a counter that still holds the previous pass's arrivals lets every member read its peers' slots before they are written)
-            launch_fill_f32(W(h, "cnt_s"), tiles, 0.f, s);
-            a.hex = W(h, "hex_s"); a.grp_cnt = static_cast<int*>(h->ws["cnt_s"].p); a.err = h->host_err;
-            a.nspl = nspl;
+        if ((!h->ws.count("hex_s") || !h->ws["hex_s"].p || !h->ws["cnt_s"].p) &&
+            (h->ws["hex_s"].alloc(tiles_max * 2 * 4 * 32 * d.H * sizeof(float)) || h->ws["cnt_s"].alloc(tiles_max * sizeof(int))))
+            return fail(DESIRE_ERR_HIP, "hipMalloc failed for the bin-split exchange buffers");
+        // the error word is mapped host memory: no read-back (and no stream synchronisation) per call; a timed-out hand-off is
+        // reported by the NEXT call on this handle.  Allocated and checked on its own (a failure here must not leave a later call
+        // with exchange buffers and a null word); the kernels write it with system-scope atomics.
+        if (!h->host_err) {
+            if (hipHostMalloc(reinterpret_cast<void**>(&h->host_err), sizeof(int), hipHostMallocMapped) != hipSuccess || !h->host_err)
+                { h->host_err = nullptr; return fail(DESIRE_ERR_HIP, "hipHostMalloc failed for the bin-split error word"); }
+            *h->host_err = 0;
         }
+        if (*static_cast<volatile int*>(h->host_err)) {
+            *h->host_err = 0;
+            return fail(DESIRE_ERR_HIP, "bin-split IOC hand-off timed out in an earlier call (workgroups of a tile were not co-resident)");
+        }
+        // (a fill KERNEL, not hipMemsetAsync: memset nodes of a captured graph were seen to run out of order on replay -- section 6a --
+        //  and a counter that still holds the previous pass's arrivals lets every member read its peers' slots before they are written)
+        launch_fill_f32(W(h, "cnt_s"), tiles, 0.f, s);
+        a.hex = W(h, "hex_s"); a.grp_cnt = static_cast<int*>(h->ws["cnt_s"].p); a.err = h->host_err;
+        a.nspl = p.nspl;
     }
 #ifdef DESIRE_IOC_TIMING
     if (!h->ws.count("dbg")) { h->ws["dbg"].alloc(10 * sizeof(long long)); }
     a.dbg = static_cast<long long*>(h->ws["dbg"].p);
 #endif
-    if (h->training && d.bf16 != 1) {
-        // training-mode forward: one launch per refinement pass, each keeping its own activations and the positions it ran on
-        // (the pass's input is DETACHED where it enters the features -- cells, bins, velocity embedding -- and Y_p = Y_{p-1} + dY_p
-        // carries the gradient: DESIGN.md section 8)
-        const size_t RT = (size_t)v.R * d.T_pred, RTf = (size_t)(h->R + 128) * d.T_pred, ro = v.row_off * d.T_pred;     // a view's saves sit at its row offset
-        a.iters = 1;
-        for (int p = 0; p < d.iters; ++p) {
-            const size_t po = (size_t)p * RTf + ro;
-            launch_copy_f32(W(h, "ioc_Yin") + po * 2, v.Y, RT * 2, s);
-            a.sv_x = W(h, "ioc_sv_x") + po * h->E; a.sv_r = W(h, "ioc_sv_r") + po * d.H;
-            a.sv_u = W(h, "ioc_sv_u") + po * d.H; a.sv_c = W(h, "ioc_sv_c") + po * d.H;
-            a.sv_h = W(h, "ioc_sv_h") + po * d.H;
-            if (cluster && p > 0) HIPCHK(hipMemsetAsync(h->ws["grp_cnt"].p, 0, ((size_t)v.R / v.mno) * sizeof(int), s));
-            if (x3) {       // split-bf16 operands; the saves are fp32 and the backward pass is the fp32 one
-                a.Wsoc = D4(h, "ioc/Wsoc16"); a.Wg = D4(h, "ioc/Wg16"); a.Wc = D4(h, "ioc/Wc16"); a.Wreg = D4(h, "ioc/Wreg16");
-                Timer t(h, s, "ioc"); launch_ioc_x3(a, s);
-            } else
-            { Timer t(h, s, "ioc"); launch_ioc(a, s); }
+    // training-mode forward: one launch per refinement pass, each keeping its own activations and the positions it ran on (the pass's input is
+    // DETACHED where it enters the features -- cells, bins, velocity embedding -- and Y_p = Y_{p-1} + dY_p carries the gradient: DESIGN.md section 8)
+    const int passes = h->training ? d.iters : 1;
+    if (h->training) a.iters = 1;
+    for (int it = 0; it < passes; ++it) {
+        if (h->training) {
+            const size_t po = ((size_t)it * (h->R + 128) + v.row_off) * d.T_pred;         // a pass's saves (rows + slack), a view's at its row offset
+            launch_copy_f32(W(h, "ioc_Yin") + po * 2, v.Y, (size_t)v.R * d.T_pred * 2, s);
+            a.sv_x = W(h, "ioc_sv_x") + po * h->E; a.sv_r = W(h, "ioc_sv_r") + po * d.H; a.sv_u = W(h, "ioc_sv_u") + po * d.H;
+            a.sv_c = W(h, "ioc_sv_c") + po * d.H; a.sv_h = W(h, "ioc_sv_h") + po * d.H;
+            if (p.cluster() && it > 0) { if (int rc = ioc_cluster_exchange(h, (size_t)v.R / v.mno, false, s)) return rc; }
         }
-    } else
-    if (x3 || x6) {   // split-bf16 operands: fp32-equivalent results on the bf16 matrix pipe (shapes without that form run the fp32 kernels)
-        a.Wsoc = D4(h, "ioc/Wsoc16"); a.Wg = D4(h, "ioc/Wg16"); a.Wc = D4(h, "ioc/Wc16"); a.Wreg = D4(h, "ioc/Wreg16");
         Timer t(h, s, "ioc");
-        if (x6) launch_ioc_x6(a, s); else launch_ioc_x3(a, s);
-    } else
-    if (d.bf16 == 1) {
-        if (h->training) return fail(DESIRE_ERR_STATE, "bf16 operands are inference-only");
-        a.Wsoc = D4(h, "ioc/Wsoc16"); a.Wg = D4(h, "ioc/Wg16"); a.Wc = D4(h, "ioc/Wc16"); a.Wreg = D4(h, "ioc/Wreg16");
-        Timer t(h, s, "ioc");
-        if (cluster) { if (launch_ioc_bf16_cluster(a, s)) return fail(DESIRE_ERR_HIP, "bf16 cluster IOC: no resident grid for this shape"); }
-        else launch_ioc_bf16(a, s);
-    } else
-    { Timer t(h, s, "ioc"); launch_ioc(a, s); }
-#ifdef DESIRE_IOC_TIMING
-    {
-        long long host[10];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(host, a.dbg, sizeof(host), hipMemcpyDeviceToHost);
-        const char* n32[10] = {"P0 pos+clear", "P1 ev/es/masks", "build0+bar", "build(b+1)", "mma bin", "bin barrier",
-                               "P3 e_r+bar", "P4 gates(2 mma)+ep+2bar", "P5 cand+ep+2bar", ""};
-        const char* n16[10] = {"loop top", "P1 ev/es/masks", "barrier 1", "P2 pooling chain + e_r", "barrier 2", "P4 gates + r*h",
-                               "barrier 3", "P5 cand + publish", "barrier 4", ""};
-        const char* nx3[10] = {"step top (bar 4 wait)", "P1 ev/es/masks", "barrier 1", "P2 pooling chain", "exchange + e_r", "barrier 2",
-                               "P4 gates + r*h", "barrier 3", "P5 cand + publish", "barrier 4"};
-        const char* ncl[10] = {"step top: positions + clear + bar", "P1 ev/es/masks", "wait for the peers", "copy peers' Ht + bar", "P2 pooling chains",
-                               "exchange + e_r", "barrier 2", "P4 gates + r*h + cand frags", "bar 3 + P5 cand + publish stores", "drain + arrive + bar"};
-        const char** names = (x3 || x6) ? nx3 : d.bf16 == 1 ? (cluster ? ncl : n16) : n32;
-        const int nk = (x3 || x6 || (d.bf16 == 1 && cluster)) ? 10 : 9;
-        long long tot = 0; for (int k = 0; k < nk; ++k) tot += host[k];
-        for (int k = 0; k < nk; ++k) fprintf(stderr, "[ioc timing] %-26s %12lld cyc  %5.1f%%\n", names[k], host[k], 100.0 * host[k] / (double)tot);
+        switch (p.fwd) {
+            case IocFwd::FP32: case IocFwd::FP32_WIDE: launch_ioc(a, p.fwd == IocFwd::FP32_WIDE, s); break;
+            case IocFwd::FP32_CLUSTER: launch_ioc_cluster(a, s); break;
+            case IocFwd::BF16: case IocFwd::BF16_WIDE: launch_ioc_bf16(a, p.fwd == IocFwd::BF16_WIDE, s); break;
+            case IocFwd::BF16_CLUSTER: if (launch_ioc_bf16_cluster(a, s)) return fail(DESIRE_ERR_HIP, "bf16 cluster IOC: no resident grid for this shape"); break;
+            case IocFwd::X3: launch_ioc_x3(a, s); break;
+            case IocFwd::X3R2: launch_ioc_x3r2(a, s); break;
+            case IocFwd::X6: launch_ioc_x6(a, s); break;
+            case IocFwd::X6R2: launch_ioc_x6r2(a, s); break;
+            case IocFwd::STEPWISE: return fail(DESIRE_ERR_STATE, "the step-wise IOC has no view form");
+        }
     }
+#ifdef DESIRE_IOC_TIMING
+    const char* n32[9] = {"P0 pos+clear", "P1 ev/es/masks", "build0+bar", "build(b+1)", "mma bin", "bin barrier", "P3 e_r+bar", "P4 gates(2 mma)+ep+2bar", "P5 cand+ep+2bar"};
+    const char* n16[9] = {"loop top", "P1 ev/es/masks", "barrier 1", "P2 pooling chain + e_r", "barrier 2", "P4 gates + r*h", "barrier 3", "P5 cand + publish", "barrier 4"};
+    const char* nx3[10] = {"step top (bar 4 wait)", "P1 ev/es/masks", "barrier 1", "P2 pooling chain", "exchange + e_r", "barrier 2", "P4 gates + r*h", "barrier 3", "P5 cand + publish", "barrier 4"};
+    const char* ncl[10] = {"step top: positions + clear + bar", "P1 ev/es/masks", "wait for the peers", "copy peers' Ht + bar", "P2 pooling chains",
+                           "exchange + e_r", "barrier 2", "P4 gates + r*h + cand frags", "bar 3 + P5 cand + publish stores", "drain + arrive + bar"};
+    const bool split = !p.fp32_weights() && d.bf16 != 1, cl16 = p.fwd == IocFwd::BF16_CLUSTER;
+    ioc_timing_report(a.dbg, split ? nx3 : cl16 ? ncl : d.bf16 == 1 ? n16 : n32, split || cl16 ? 10 : 9, s);
 #endif
     HIPCHK(hipGetLastError());
-    if (cluster) {
-        int err = 0;
-        HIPCHK(hipMemcpyAsync(&err, h->ws["ioc_err"].p, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (err) return fail(DESIRE_ERR_HIP, "IOC cluster hand-off timed out (workgroups of a group were not co-resident)");
-    }
-    return DESIRE_OK;
+    return p.cluster() ? ioc_cluster_check(h, s, "IOC cluster") : DESIRE_OK;
 }
 
 extern "C" int desire_ioc_refine(desire_handle* h, float* dev_Yhat, float* dev_score, void* stream) {
@@ -513,16 +478,7 @@ extern "C" int desire_ioc_refine(desire_handle* h, float* dev_Yhat, float* dev_s
     }
     const desire_dims& d = h->d;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    // step-wise form (one launch of the agent-sharded kernel per step, a single rank): scenes of 160 .. 256 agents (beyond the cluster
-    // form's 128-bit neighbour masks) on any operands but plain bf16, and -- dims.bf16 = 2 / 3, inference -- H = 256 (BASELINE configs[3]:
-    // no persistent split kernel: the bin-split accumulators do not fit eight waves' registers) with split operands instead of the fp32
-    // fallback: 16.1 -> 9.1 ms (three products) / 12.7 ms (six) at configs[3]'s per-GPU shape.  (Groups of 96 / 128 agents at H <= 128
-    // were measured too: 34.4 vs 34.9 ms with three products, SLOWER with six -- they keep the fp32 cluster kernel.)
-    const int B_ = d.grid_size * d.grid_size;
-    const bool split_mode = (d.bf16 == 2 || d.bf16 == 3) && !h->training;
-    const bool split_served = ioc_x3_supported(d.mno, d.H, B_) || (d.mno == 64 && ioc_x6r2_supported(d.mno, d.H, B_));
-    const bool stepwise = d.mno > 128 || (split_mode && !split_served && d.H == 256 && d.ioc_form == DESIRE_IOC_AUTO);
-    if (stepwise) {
+    if (ioc_plan(h).fwd == IocFwd::STEPWISE) {        // one launch of the agent-sharded kernel per step, a single rank (ioc_plan.h)
         if (h->training) return fail(DESIRE_ERR_STATE, "training supports up to 128 agents per scene");
         const size_t RH = (size_t)h->R * d.H;
         if ((!h->ws.count("stw_h") || !h->ws["stw_h"].p || !h->ws["stw_sc"].p) &&
@@ -543,10 +499,10 @@ extern "C" int desire_ioc_refine(desire_handle* h, float* dev_Yhat, float* dev_s
                 q.w_vel = D(h, "ioc/vel_w"); q.b_vel = D(h, "ioc/vel_b"); q.Wsoc = D4(h, "ioc/Wsoc"); q.b_soc = D(h, "ioc/soc_b");
                 q.Wg = D4(h, "ioc/Wg"); q.Wc = D4(h, "ioc/Wc"); q.b_g = D(h, "ioc/gb"); q.b_c = D(h, "ioc/cb"); q.w_score = D(h, "ioc/score_w");
                 q.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
-                if (split_mode) {
+                if (d.bf16 == 2 || d.bf16 == 3) {
                     q.np = d.bf16 == 3 ? 3 : 2;
                     q.Wsoc = D4(h, "ioc/Wsoc16l"); q.Wg = D4(h, "ioc/Wg16"); q.Wc = D4(h, "ioc/Wc16");
-                    q.plo_soc = (size_t)B_ * NTs * (d.H / 16) * 64; q.plo_g = (size_t)2 * NTs * (KXs / 16) * 64; q.plo_c = (size_t)NTs * (KXs / 16) * 64;
+                    q.plo_soc = (size_t)d.grid_size * d.grid_size * NTs * (d.H / 16) * 64; q.plo_g = (size_t)2 * NTs * (KXs / 16) * 64; q.plo_c = (size_t)NTs * (KXs / 16) * 64;
                 }
                 launch_ioc_step(q, s);
             }
@@ -559,59 +515,45 @@ extern "C" int desire_ioc_refine(desire_handle* h, float* dev_Yhat, float* dev_s
         // DESIRE_FLAG_COMPACT_IOC: one launch sequence per slot class over the windows seated in it; windows without a present agent are not run
         // (their rows keep the Y they came with and score 0)
         if (int rc = compact_wait(h, s)) return rc;
-        const bool dyn = compact_dyn(h);
-        const int32_t* cnt_dev = static_cast<const int32_t*>(h->ws["cp_count"].p) + 4;
-        int m4[4];
-        const int n_cls = compact_classes(h, m4);
-        const int32_t* cnt = h->cp_host + 4;
-        size_t aoff = 0, roff = 0, woff = 0;
-        const size_t T2 = (size_t)d.T_pred * 2;
+        // device-side counts: every class is launched for the worst case (all windows in it) at a static offset; an empty class's grids exit
+        const bool pad = ioc_plan(h).padded, dyn = compact_dyn(h);
+        int cnt[4] = {0, 0, 0, 0};
+        for (int c = 0, n = class_layout(h, pad, nullptr).n; c < n; ++c) {
+            cnt[c] = dyn ? d.n_scenes : static_cast<volatile const int32_t*>(h->cp_host + 4)[c];
+            if (cnt[c] < 0 || cnt[c] > d.n_scenes) return fail(DESIRE_ERR_HIP, "slot-class scan returned a count out of range");
+        }
+        const ClassLayout L = class_layout(h, pad, cnt);
+        const int T2 = d.T_pred * 2;
         launch_fill_f32(dev_score, (size_t)h->R, 0.f, s);
-        h->ci_n = 0;
-        for (int c = 0; c < n_cls; ++c) {
-            // device-side counts: every class is launched for the worst case (all windows in it) at a static offset; an empty class's grids exit
-            const int n_c = dyn ? d.n_scenes : static_cast<volatile const int32_t*>(cnt)[c], m_c = m4[c];
-            const int32_t* dynN = dyn ? cnt_dev + c : nullptr;
-            if (n_c < 0 || n_c > d.n_scenes) return fail(DESIRE_ERR_HIP, "slot-class scan returned a count out of range");
-            if (n_c == 0) continue;
-            const int32_t* cmap = static_cast<const int32_t*>(h->ws["ci_map"].p) + (size_t)c * h->A;
-            const int32_t* win = static_cast<const int32_t*>(h->ws["ci_win"].p) + (size_t)c * d.n_scenes;
-            const int gpt = (m_c <= 32 && 32 % m_c) ? 32 / m_c : 0, ngrp = n_c * d.K;              // padded tiles for a class that does not divide 32
-            const int R_c = gpt ? ((ngrp + gpt - 1) / gpt) * 32 : n_c * d.K * m_c;
-            IocView v{R_c, m_c, n_c, W(h, "ci_Y") + roff * T2, W(h, "ci_score") + roff, W(h, "ci_Hx") + aoff * 2 * d.H, 2 * d.H, W(h, "ci_pl") + aoff * 2,
-                      static_cast<const uint8_t*>(h->ws["ci_valid"].p) + aoff, static_cast<const int32_t*>(h->ws["ci_gos"].p) + woff, roff};
-            v.gpt = gpt; v.ngrp = ngrp; v.dynN = dynN;
+        for (int c = 0; c < 4; ++c) h->ci_cnt[c] = c < L.n ? L.c[c].n_scenes : 0;
+        for (int c = 0; c < L.n; ++c) {
+            if (L.c[c].n_scenes == 0) continue;
+            IocView v = ioc_view(h, &L.c[c]);
+            if (dyn) v.dynN = static_cast<const int32_t*>(h->ws["cp_count"].p) + 4 + c;
             {
                 Timer t(h, s, "ioc_repack");
-                launch_cls_gather_agents(W(h, "HxHy"), 2 * d.H, W(h, "p_last"), static_cast<const int32_t*>(h->ws["grid_of_scene"].p), cmap, win, n_c, m_c,
-                                         const_cast<float*>(v.Hx), const_cast<float*>(v.p_last), const_cast<uint8_t*>(v.valid), const_cast<int32_t*>(v.gos), s, dynN);
-                launch_cls_rows(dev_Yhat, v.Y, cmap, n_c, m_c, d.K, d.mno, (int)T2, 0, s, gpt, dynN);
+                launch_cls_gather_agents(W(h, "HxHy"), 2 * d.H, W(h, "p_last"), static_cast<const int32_t*>(h->ws["grid_of_scene"].p), v.cmap, v.win, v.n_scenes, v.mno,
+                                         v.Hx, v.p_last, v.valid, v.gos, s, v.dynN);
+                launch_cls_rows(dev_Yhat, v.Y, v.cmap, v.n_scenes, v.mno, d.K, d.mno, T2, 0, s, v.gpt, v.dynN);
             }
             if (int rc = ioc_core(h, v, s)) return rc;
             {
                 Timer t(h, s, "ioc_repack");
-                launch_cls_rows(dev_Yhat, v.Y, cmap, n_c, m_c, d.K, d.mno, (int)T2, 1, s, gpt, dynN);
-                launch_cls_rows(dev_score, v.score, cmap, n_c, m_c, d.K, d.mno, 1, 1, s, gpt, dynN);
+                launch_cls_rows(dev_Yhat, v.Y, v.cmap, v.n_scenes, v.mno, d.K, d.mno, T2, 1, s, v.gpt, v.dynN);
+                launch_cls_rows(dev_score, v.score, v.cmap, v.n_scenes, v.mno, d.K, d.mno, 1, 1, s, v.gpt, v.dynN);
             }
-            h->ci_cls[h->ci_n] = c; h->ci_cnt[h->ci_n] = n_c; ++h->ci_n;
-            aoff += (size_t)n_c * m_c; roff += (size_t)R_c; woff += (size_t)n_c;
         }
         h->ci_last = true;
-        if (h->training && d.bf16 != 1) {
-            launch_copy_f32(W(h, "Y_ref"), dev_Yhat, (size_t)h->R * d.T_pred * 2, s);
-            launch_copy_f32(W(h, "score_sv"), dev_score, (size_t)h->R, s);
-        }
-        HIPCHK(hipGetLastError());
-        return DESIRE_OK;
+    } else {
+        h->ci_last = false;
+        IocView full = ioc_view(h); full.Y = dev_Yhat; full.score = dev_score;
+        if (int rc = ioc_core(h, full, s)) return rc;
     }
-    h->ci_last = false;
-    IocView full{h->R, d.mno, d.n_scenes, dev_Yhat, dev_score, W(h, "HxHy"), 2 * d.H, W(h, "p_last"), static_cast<const uint8_t*>(h->ws["valid"].p),
-                 static_cast<const int32_t*>(h->ws["grid_of_scene"].p), 0};
-    if (int rc = ioc_core(h, full, s)) return rc;
     if (h->training && d.bf16 != 1) {
         launch_copy_f32(W(h, "Y_ref"), dev_Yhat, (size_t)h->R * d.T_pred * 2, s);
         launch_copy_f32(W(h, "score_sv"), dev_score, (size_t)h->R, s);
     }
+    HIPCHK(hipGetLastError());
     return DESIRE_OK;
 }
 

@@ -2,6 +2,7 @@
 // train.hip (training ABI).  Host code only.
 #pragma once
 #include "../../include/desire_hip.h"
+#include "ioc_plan.h"
 #include "kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -69,7 +70,7 @@ struct desire_ctx {
     // present-row compaction (DESIRE_FLAG_COMPACT_ROWS, kernels_compact.hip): mapped host word the scan kernel reports the present-agent count
     // into, the event behind it, the count of the last desire_sample (-1: none yet)
     int32_t* cp_host = nullptr; hipEvent_t cp_ev = nullptr; bool cp_pending = false; int cp_P = -1;
-    int ci_n = 0, ci_cls[4] = {0, 0, 0, 0}, ci_cnt[4] = {0, 0, 0, 0}; bool ci_last = false; int ci_min_rows = 8192;     // DESIRE_FLAG_COMPACT_IOC: the classes the last IOC stage ran (class index, windows)
+    int ci_cnt[4] = {0, 0, 0, 0}; bool ci_last = false; int ci_min_rows = 8192;     // DESIRE_FLAG_COMPACT_IOC: windows per slot class of the last IOC stage
     bool cp_enc = false;                                     // the last desire_encode ran its stack on the present agents only (saves in compact agent order)
     bool cp_host_counts = false;                             // desire_set_option("compact_host_counts", 1): inference reads the counts back like training does (A/B)
     bool cp_last = false;                                    // the last desire_sample ran compacted (desire_backward follows it, not the flag)
@@ -138,9 +139,28 @@ int desire_ready(desire_handle* h);
 bool compact_rows(const desire_ctx* h);                        // DESIRE_FLAG_COMPACT_ROWS set
 bool compact_ioc(const desire_ctx* h);                         // DESIRE_FLAG_COMPACT_IOC set and the shape is served
 bool compact_dyn(const desire_ctx* h);                         // compacted launches take their counts from device words (inference, frozen batch-norm): no host wait
-bool compact_padded_ok(const desire_ctx* h);                   // the padded-tile IOC kernels serve this handle (slot class 10)
-int compact_classes(const desire_ctx* h, int* m4);             // its slot classes (ascending, the handle's mno last): returns how many
 int compact_setup(desire_ctx* h);                              // its buffers, event and mapped count word (idempotent)
+inline IocPlan ioc_plan(const desire_ctx* h) { return ioc_plan(h->d, h->training, h->d.mno, 0, h->R); }     // of the handle's own shape (ioc_plan.h)
+// A view of the handle's rows that one IOC launch sequence -- the forward or its BPTT -- runs on: the handle's own layout (cls = -1), or one
+// slot class of DESIRE_FLAG_COMPACT_IOC, n_scenes windows of mno slots seated in the class buffers at the class's offsets
+struct IocView {
+    int cls = -1, mno = 0, n_scenes = 0, gpt = 0, ngrp = 0;  // gpt, ngrp: padded tiles (kernels.h: IocArgs.gpt); R = tiles * 32
+    long R = 0;
+    size_t agent_off = 0, row_off = 0, win_off = 0;          // in ci_Hx / ci_pl / ci_valid, in ci_Y / ci_score and the training saves, in ci_gos
+    float* Hx = nullptr; float* p_last = nullptr; uint8_t* valid = nullptr; int32_t* gos = nullptr;     // agent-level inputs (Hx: ld 2H)
+    const int32_t* cmap = nullptr; const int32_t* win = nullptr;                                        // a slot class's agent map and windows
+    float* Y = nullptr; float* score = nullptr; const int32_t* dynN = nullptr;     // forward: its rows; device-side counts: the class's window count
+};
+// The slot classes (ascending, the handle's mno last; class 10 only when `pad`) with their geometry and offsets for per-class window counts
+// (nullptr: the worst case, every window in every class -- device-side counts and buffer sizing)
+struct ClassLayout { int n = 0; int m[4] = {0, 0, 0, 0}; IocView c[4]; size_t agents = 0, rows = 0, wins = 0; };
+ClassLayout class_layout(const desire_ctx* h, bool pad, const int* counts);
+IocView ioc_view(desire_ctx* h, const IocView* cls = nullptr);     // a class of class_layout with its pointers bound; nullptr: the handle's own layout
+// The cluster form's exchange, sized for the handle's own shape (every view is smaller): allocated on first use, the counters of n_groups groups
+// zeroed (and the error word when reset_err); ioc_cluster_check reads the error word back (a stream synchronisation)
+int ioc_cluster_exchange(desire_ctx* h, size_t n_groups, bool reset_err, hipStream_t s);
+int ioc_cluster_check(desire_ctx* h, hipStream_t s, const char* what);
+void ioc_timing_report(const long long* dbg, const char* const* names, int n, hipStream_t s);      // DESIRE_IOC_TIMING: per-phase cycle counters -> stderr
 int desire_pack_all(desire_ctx* h);                            // (re)builds every packed / folded device tensor from host_w
 int scene_grad_setup(desire_ctx* h);                           // buffers of the scene-grid gradient (train.hip; idempotent, training mode only)
 inline bool scene_grad_on(const desire_ctx* h) { return h->scene_grad || h->img_set; }      // images attached imply the grid gradient

@@ -137,38 +137,17 @@ struct IocArgs {
     // ngrp = n_c * K, R = gpt ? ceil(ngrp / gpt) * 32 : ngrp * mno (ioc_dyn_rows, common.h); the arguments hold the worst case (every window in this class)
     DynCount dyn;
 };
-void launch_ioc(const IocArgs& a, hipStream_t s);
-// Which IOC form serves (mno, H, bins): the cluster form (32-row tiles exchanging hidden states through global memory) takes every
-// group that does not fit ONE workgroup's LDS tile -- more than 64 agents, 64 agents at H = 256, or 64 agents with so many
-// social bins (> 25 at H = 128) that the 64-row tile's neighbour masks push it past 160 KB.
-inline bool ioc_uses_cluster(int mno, int H, int bins, int variant) {
-    if (mno > 64 || (mno == 64 && H == 256) || (variant == 4 && mno >= 64)) return true;
-    if (mno == 64) {
-        const size_t tile = ((size_t)65 * (2 * H + 52) + 2 * 64 * (H + 4) + 64 * 4 + 48 + (H / 32) * 64) * 4 + (size_t)64 * bins * 8 + 128;
-        return tile > 160 * 1024;
-    }
-    return false;
-}
-// Few tiles (a handful of windows): how many workgroups share one 32-row tile's social bins (k_ioc NSPL), so that the launch covers
-// up to 256 CUs instead of one per (scene, k) group.  1 = the plain form.
-inline int ioc_bin_split(int R, int mno, int H, int bins, int iters) {
-    if (mno > 32 || H > 128 || iters != 1) return 1;
-    const int tiles = (R + 31) / 32;
-    for (int n = 4; n >= 2; --n)          // (8 per tile measured no faster than 4: what is left of a step is the part every member repeats)
-        if (tiles * n <= 256 && bins >= n) return n;
-    return 1;
-}
+void launch_ioc(const IocArgs& a, bool wide, hipStream_t s);    // k_ioc on 32-row tiles, or 64-row tiles when `wide` (H = 256: always 32)
+void launch_ioc_cluster(const IocArgs& a, hipStream_t s);       // k_ioc_cl: groups of 64 / 96 / 128 agents over mno/32 workgroups
 int ioc_bin_split_capacity(const IocArgs& a, int n);           // resident workgroups of the n-member bin-split kernel on this device (kernels_rnn.hip)
-void launch_ioc_bf16(const IocArgs& a, hipStream_t s);
+void launch_ioc_bf16(const IocArgs& a, bool wide, hipStream_t s);       // wide: two row blocks per workgroup
 // bf16 cluster form (kernels_bf16_cl.hip): groups of 64 / 96 / 128 agents over mno/32 workgroups; returns != 0 when the
 // persistent grid cannot be made resident
 int launch_ioc_bf16_cluster(const IocArgs& a, hipStream_t s);
 // split-bf16 form (kernels_x3.hip): fp32-equivalent results from three bf16 MFMAs per product; weight pointers = [hi | lo] packs
-bool ioc_x3_supported(int mno, int H, int bins);
 void launch_ioc_x3(const IocArgs& a, hipStream_t s);
 void launch_ioc_x6(const IocArgs& a, hipStream_t s);
-bool ioc_x6r2_supported(int mno, int H, int bins);             // ... on 64-row tiles, two row blocks per wave (kernels_x6r2.hip)
-void launch_ioc_x6r2(const IocArgs& a, hipStream_t s);
+void launch_ioc_x6r2(const IocArgs& a, hipStream_t s);             // ... on 64-row tiles, two row blocks per wave (kernels_x6r2.hip)
 void launch_ioc_x3r2(const IocArgs& a, hipStream_t s);             // ... with two-piece operands (dims.bf16 = 2)
 // sample generation with three-piece operands (kernels_x6.hip, dims.bf16 = 3)
 bool decoder_x6_supported(int H);
@@ -305,7 +284,6 @@ struct IocBwdArgs {
     int gpt; int ngrp;                                     // padded tiles (see IocArgs.gpt): 32-row forms of k_ioc_bwd / k_ioc_bwd_x3
 };
 void launch_ioc_bwd(const IocBwdArgs& a, hipStream_t s);
-bool ioc_bwd_x3_supported(int mno, int H);                       // kernels_bwd_x3.hip: groups of up to 32 agents, H = 64 / 128
 void launch_ioc_bwd_x3(const IocBwdArgs& a, hipStream_t s);      // a.WcT_h / a.WgT_h / a.WsT = the [hi | lo] packs "ioc/W?T16"
 // cluster form (kernels_bwd_cl.hip): groups of 64 / 96 / 128 agents, H <= 128, <= 16 bins; grp_cnt zeroed per launch; != 0: shape not served
 int launch_ioc_bwd_cluster(const IocBwdArgs& a, int* grp_cnt, int* err, hipStream_t s);

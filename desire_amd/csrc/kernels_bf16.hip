@@ -444,12 +444,11 @@ static void launch16(const IocArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((k_ioc_bf16<H, 16, 32, WM>), grid, block, ioc16_lds(a, WM), s, a);
     }
 }
-// mno must divide 32 (32-row tiles, two workgroups per CU at H <= 128) or be 64 (64-row tiles, twice the waves);
-// a.variant == 2 forces 64-row tiles (A/B)
-void launch_ioc_bf16(const IocArgs& a, hipStream_t s) {
+// mno divides 32 (32-row tiles, two workgroups per CU at H <= 128) or, with `two`, is 64 (64-row tiles, twice the waves; ioc_plan.h also
+// takes them for ioc_form 2, A/B)
+void launch_ioc_bf16(const IocArgs& a, bool two, hipStream_t s) {
     // (64-row tiles with two row blocks per wave -- half the weight bytes per row, one workgroup per CU -- were bit-identical and SLOWER,
     //  3.67 vs 3.20 ms per 81 920 rows: one wave per SIMD leaves the position-only phase, the exchange and the epilogues uncovered; removed)
-    const bool two = a.mno > 32 || a.variant == 2;
     if (a.H == 128) { if (two) launch16<128, 2>(a, s); else launch16<128, 1>(a, s); }
     else if (a.H == 64) { if (two) launch16<64, 2>(a, s); else launch16<64, 1>(a, s); }
     else { if (two) launch16<256, 2>(a, s); else launch16<256, 1>(a, s); }

@@ -875,7 +875,6 @@ void launch_ioc_bwd_x3_t(const IocBwdArgs& a, hipStream_t s) {
     hipLaunchKernelGGL((k_ioc_bwd_x3<H, 16, 32>), dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
 }
 }  // namespace
-bool ioc_bwd_x3_supported(int mno, int H) { return mno <= 32 && (H == 128 || H == 64); }
 // a.WcT_h / a.WgT_h / a.WsT = the [hi | lo] packs "ioc/WcT16" / "ioc/WgT16" / "ioc/WsT16"; a.WrT stays the fp32 pack (prologue)
 void launch_ioc_bwd_x3(const IocBwdArgs& a, hipStream_t s) {
     if (a.H == 128) launch_ioc_bwd_x3_t<128>(a, s); else launch_ioc_bwd_x3_t<64>(a, s);

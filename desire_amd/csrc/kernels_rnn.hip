@@ -931,15 +931,10 @@ int ioc_bin_split_capacity(const IocArgs& a, int n) {
     cache[key] = cap;
     return cap;
 }
-void launch_ioc_cluster(const IocArgs& a, hipStream_t s);
-void launch_ioc(const IocArgs& a, hipStream_t s) {
-    // groups larger than one workgroup tile (mno > 64, or mno = 64 at H = 256) or variant=4: cluster form
-    if (ioc_uses_cluster(a.mno, a.H, a.G * a.G, a.variant)) { launch_ioc_cluster(a, s); return; }
-    // 32-row tiles (two workgroups per CU at H <= 128) whenever whole (scene,k) groups fit; variant=2 forces 64 rows (A/B)
-    const bool small = (a.mno <= 32) && a.variant != 2;
+void launch_ioc(const IocArgs& a, bool wide, hipStream_t s) {
     if (a.H == 256) launch_ioc_t<256, 32>(a, s);                  // mno = 64 at H = 256 exceeds the 160 KB LDS tile
-    else if (a.H == 128) { if (small) launch_ioc_t<128, 32>(a, s); else launch_ioc_t<128, 64>(a, s); }
-    else { if (small) launch_ioc_t<64, 32>(a, s); else launch_ioc_t<64, 64>(a, s); }
+    else if (a.H == 128) { if (wide) launch_ioc_t<128, 64>(a, s); else launch_ioc_t<128, 32>(a, s); }
+    else { if (wide) launch_ioc_t<64, 64>(a, s); else launch_ioc_t<64, 32>(a, s); }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -493,7 +493,6 @@ static size_t iocx3_lds(const IocArgs& a, int np = 2) {
     b += (size_t)((TM * (B + 1) + 1) & ~1) * 4 + 16 * 8 + (size_t)TM * 4 * 4 + 3 * 16 * 4 + (size_t)NT * TM * 4 + TM + 16;
     return b;
 }
-bool ioc_x3_supported(int mno, int H, int bins) { return mno >= 1 && mno <= 32 && 32 % mno == 0 && (H == 64 || H == 128) && bins <= 64; }
 template <int H>
 static void launch_x3(const IocArgs& a, hipStream_t s) {
     const dim3 grid((a.R + 31) / 32), block((H / 32) * 64);
@@ -515,12 +514,9 @@ static void launch_x3(const IocArgs& a, hipStream_t s) {
         hipLaunchKernelGGL((k_ioc_x3<H, 16, 32, false>), grid, block, iocx3_lds(a), s, a);
     }
 }
+// (groups of 64 agents: launch_ioc_x3r2.  For <= 32 agents that form was measured slower -- with two pieces the 32-row tiles' second workgroup
+//  per CU is worth more than the halved weight stream)
 void launch_ioc_x3(const IocArgs& a, hipStream_t s) {
-    // groups of 64 agents: 64-row tiles with two row blocks per wave on fp32 LDS tiles split on the fly (kernels_x6r2.hip with two pieces:
-    // every weight fragment used twice).  For groups of <= 32 agents that form was measured slower (30.7 vs 29.1 ms at 512 windows -- with
-    // two pieces the 32-row tiles' second workgroup per CU is worth more than the halved weight stream), so it serves only the shape
-    // it alone can
-    if (!a.sv_h && a.mno > 32 && ioc_x6r2_supported(a.mno, a.H, a.G * a.G)) { launch_ioc_x3r2(a, s); return; }
     if (a.H == 128) launch_x3<128>(a, s); else launch_x3<64>(a, s);
 }
 // three pieces per operand, six products per fp32 product (dims.bf16 = 3): same shapes, inference only
@@ -530,11 +526,8 @@ static void launch_x6(const IocArgs& a, hipStream_t s) {
     allow_big_lds(k_ioc_x3<H, 16, 32, false, 3>);
     hipLaunchKernelGGL((k_ioc_x3<H, 16, 32, false, 3>), grid, block, iocx3_lds(a, 3), s, a);
 }
+// (launches of >= 256 64-row tiles run launch_ioc_x6r2, within 1-2 ulp; this 32-row / three-image form serves the shapes whose masks do not fit beside
+//  a 64-row tile and launches that would leave CUs idle: one window = 20 tiles of 32 rows on 20 CUs takes 1.29 ms, 10 tiles of 64 rows 2.39 ms)
 void launch_ioc_x6(const IocArgs& a, hipStream_t s) {
-    // default: 64-row tiles, two row blocks per wave, fp32 operand tiles split on the fly (kernels_x6r2.hip; results within 1-2 ulp);
-    // a.variant == 13 (DESIRE_IOC_X6_TILE32) keeps the 32-row / three-image form below (A/B), which also serves the shapes whose masks do not fit beside a
-    // 64-row tile -- and launches that would leave CUs idle with 64-row tiles (a few windows: one window = 20 tiles of 32 rows on 20 CUs
-    // takes 1.29 ms, 10 tiles of 64 rows 2.39 ms)
-    if ((a.mno > 32 || (a.variant != 13 && ((a.R + 63) / 64 >= 256 || a.variant == 14))) && ioc_x6r2_supported(a.mno, a.H, a.G * a.G)) { launch_ioc_x6r2(a, s); return; }    // (14: always, A/B and tests)
     if (a.H == 128) launch_x6<128>(a, s); else launch_x6<64>(a, s);
 }

@@ -439,12 +439,6 @@ static size_t iocx6r2_lds(const IocArgs& a) {
     b += (size_t)TM * (B + 1) * 8 + 16 * 8 + (size_t)TM * 4 * 4 + 3 * 16 * 4 + (size_t)NT * TM * 4 + TM + 64;
     return b;
 }
-bool ioc_x6r2_supported(int mno, int H, int bins) {
-    if (!((H == 64 || H == 128) && mno >= 1 && ((mno <= 32 && 32 % mno == 0) || mno == 64))) return false;
-    const int KX = 16 + 32 + 2 * H, NT = H / 32;
-    const size_t lds = ((size_t)64 * (KX + 4) + (size_t)64 * (H + 4) + (size_t)H * 68) * 4 + (size_t)64 * (bins + 1) * 8 + 128 + 1024 + 192 + (size_t)NT * 256 + 128;
-    return lds <= 160 * 1024;
-}
 template <int H, int NP>
 static void launch_x6r2(const IocArgs& a, hipStream_t s) {
     const dim3 grid((a.R + 63) / 64), block((H / 32) * 64);

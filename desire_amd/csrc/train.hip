@@ -426,7 +426,7 @@ extern "C" int desire_set_training(desire_handle* h, int enable) {
     if (d.bf16 == 1 || d.bf16 == 3) return fail(DESIRE_ERR_STATE, "training runs with dims.bf16 = 0 (fp32 operands) or 2 (split-bf16 operands where a kernel has that form, fp32 kernels elsewhere); 1 and 3 are inference-only");
     if (d.ref_compat) return fail(DESIRE_ERR_STATE, "ref_compat is forward-only: the reference never defines a runnable cost (model/model.py:342)");
     if (d.mno > 128) return fail(DESIRE_ERR_STATE, "training supports up to 128 agents per scene (160 .. 256 run the step-wise IOC: inference)");
-    if (ioc_uses_cluster(d.mno, d.H, d.grid_size * d.grid_size, 0) && (d.H > 128 || d.grid_size > 4))
+    if (ioc_plan(h).bwd == IocBwd::CLUSTER && (d.H > 128 || d.grid_size > 4))
         return fail(DESIRE_ERR_STATE, "training of groups larger than one workgroup tile (64 / 96 / 128 agents: cluster-form BPTT) needs H <= 128 and grid_size <= 4");
     if (d.iters > 4) return fail(DESIRE_ERR_STATE, "training keeps the activations of every IOC refinement pass: iters <= 4");
     if (d.T_pred > d.H) return fail(DESIRE_ERR_STATE, "training needs T_pred <= H");
@@ -577,31 +577,20 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
                           d.mno, d.K, T, d.sx, d.sy, s);
         // one BPTT per refinement pass, last pass first: Y_final = Y0 + sum_p dY_p, so every pass's regression head sees the same
         // dL/dY_final; only the last pass's scores enter the loss.  Weight gradients of the passes accumulate.
-        // DESIRE_FLAG_COMPACT_IOC: the forward ran one launch sequence per slot class (api.hip: IocView) and left each class's saves at its row
-        // offset; the BPTT and every weight-gradient reduction below run per class on the same views, accumulating.  Otherwise: one view, the
-        // handle's own shape.
-        struct BView { long R; int mno, n_scenes; const float* Hx; const float* p_last; const uint8_t* valid; size_t row_off; const int32_t* cmap; int gpt, ngrp; const int32_t* gos; };
-        std::vector<BView> views;
+        // DESIRE_FLAG_COMPACT_IOC: the forward ran one launch sequence per slot class (api_forward.hip: class_layout) and left each class's saves at
+        // its row offset; the BPTT and every weight-gradient reduction below run per class on the same views, accumulating.  Otherwise: one view,
+        // the handle's own shape.
+        std::vector<IocView> views;
         if (h->ci_last) {
             if (ensure(h, "ci_dYr", (size_t)(R + 128) * T * 2 * sizeof(float)) || ensure(h, "ci_dscore", (size_t)(R + 128) * sizeof(float)) || ensure(h, "ci_dscoreT", (size_t)(R + 128) * T * sizeof(float)) ||
                 ensure(h, "ci_dHx_rows", (size_t)(R + 128) * H * sizeof(float)) || ensure(h, "ci_dHx", (size_t)h->A * H * sizeof(float)) || ensure(h, "dHxHy_ioc", (size_t)h->A * H * sizeof(float)))
                 return fail(DESIRE_ERR_HIP, "hipMalloc failed for the slot-class gradient buffers");
             launch_fill_f32(W(h, "dHxHy_ioc"), (size_t)h->A * H, 0.f, s);
-            int m4[4];
-            compact_classes(h, m4);
-            size_t aoff = 0, roff = 0, woff = 0;
-            for (int i = 0; i < h->ci_n; ++i) {
-                const int c = h->ci_cls[i], n_c = h->ci_cnt[i], m_c = m4[c];
-                const int gpt = (m_c <= 32 && 32 % m_c) ? 32 / m_c : 0, ngrp = n_c * d.K;          // padded tiles: as desire_ioc_refine seated the class
-                const long R_c = gpt ? (long)((ngrp + gpt - 1) / gpt) * 32 : (long)n_c * d.K * m_c;
-                views.push_back(BView{R_c, m_c, n_c, W(h, "ci_Hx") + aoff * 2 * H, W(h, "ci_pl") + aoff * 2,
-                                      static_cast<const uint8_t*>(h->ws["ci_valid"].p) + aoff, roff, static_cast<const int32_t*>(h->ws["ci_map"].p) + (size_t)c * h->A, gpt, ngrp,
-                                      static_cast<const int32_t*>(h->ws["ci_gos"].p) + woff});
-                aoff += (size_t)n_c * m_c; roff += (size_t)R_c; woff += (size_t)n_c;
-            }
+            const ClassLayout L = class_layout(h, ioc_plan(h).padded, h->ci_cnt);
+            for (int c = 0; c < L.n; ++c)
+                if (L.c[c].n_scenes > 0) views.push_back(ioc_view(h, &L.c[c]));
         } else
-            views.push_back(BView{R, d.mno, d.n_scenes, W(h, "HxHy"), W(h, "p_last"), static_cast<const uint8_t*>(h->ws["valid"].p), 0, nullptr, 0, 0,
-                                  static_cast<const int32_t*>(h->ws["grid_of_scene"].p)});
+            views.push_back(ioc_view(h));
         const long RTf = (R + 128) * T;                    // stride of a refinement pass's saves (desire_set_training: rows + slack)
         launch_fill_f32(W(h, "dscore0"), (size_t)R, 0.f, s);
         if (sg_on) {
@@ -613,7 +602,7 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
         bool scene_first = true;                    // the first (view, pass) writes d loss / d grids, the others accumulate
         bool first = true;                          // the first launch sequence writes the weight gradients, the others accumulate
         for (size_t vi = 0; vi < views.size(); ++vi) {
-        const BView& v = views[vi];
+        const IocView& v = views[vi];
         const long Rv = v.R, RT = Rv * T;
         const int n_tiles32v = (int)((Rv + 31) / 32);
         float* dYr_v = W(h, "dYr"); float* dscore_v = W(h, "dscore"); float* dscoreT_v = W(h, "dscoreT"); float* dHx_v = W(h, "dHx_rows");
@@ -646,15 +635,13 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
             q.pool_flags = static_cast<unsigned long long*>(h->ws["ioc_pool_flags"].p);
             q.dHx_rows = dHx_v;
             q.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
-            const bool cl_bwd = ioc_uses_cluster(v.mno, d.H, d.grid_size * d.grid_size, 0);
+            const IocBwd bwd = ioc_plan(d, true, v.mno, v.gpt, Rv).bwd; const bool cl_bwd = bwd == IocBwd::CLUSTER;
             q.bias_part = cl_bwd ? nullptr : W(h, "bias_part");           // (the cluster form keeps the separate column-sum passes)
             if (cl_bwd) {
-                const size_t n_groups = (size_t)Rv / v.mno;
-                HIPCHK(hipMemsetAsync(h->ws["grp_cnt"].p, 0, n_groups * sizeof(int), s));
-                if (vi == 0 && last_pass) HIPCHK(hipMemsetAsync(h->ws["ioc_err"].p, 0, sizeof(int), s));
+                if (int rc = ioc_cluster_exchange(h, (size_t)Rv / v.mno, vi == 0 && last_pass, s)) return rc;
                 if (launch_ioc_bwd_cluster(q, static_cast<int*>(h->ws["grp_cnt"].p), static_cast<int*>(h->ws["ioc_err"].p), s))
                     return fail(DESIRE_ERR_STATE, "cluster-form IOC backward does not serve this shape");
-            } else if (d.bf16 == 2 && (train_x3_mask(h) & 4) && ioc_bwd_x3_supported(v.mno, H)) {      // split-bf16 operands in the data-gradient contractions
+            } else if (bwd == IocBwd::X3) {      // split-bf16 operands in the data-gradient contractions
                 q.WcT_h = D4(h, "ioc/WcT16"); q.WgT_h = D4(h, "ioc/WgT16"); q.WsT = D4(h, "ioc/WsT16");
 #ifdef DESIRE_IOC_TIMING
                 if (!h->ws.count("dbgb")) { h->ws["dbgb"].alloc(12 * sizeof(long long)); }
@@ -662,16 +649,9 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
 #endif
                 launch_ioc_bwd_x3(q, s);
 #ifdef DESIRE_IOC_TIMING
-                {
-                    long long host[12];
-                    (void)hipStreamSynchronize(s);
-                    (void)hipMemcpy(host, q.dbg, sizeof(host), hipMemcpyDeviceToHost);
-                    const char* nm[12] = {"loop tail (dh)", "bar top", "P0 pos/clear/load h", "bar P0", "P1 masks + part 1 (loads, stores, images)", "barriers after parts",
-                                          "t2 mma + dar", "gates mma + dpr", "pooled rebuild + store", "dpool mma + tile write", "bin barrier", "gather / NB"};
-                    long long tot = 0; for (int k = 0; k < 12; ++k) tot += host[k];
-                    fprintf(stderr, "k_ioc_bwd_x3 block 7 wave 0: total %lld cycles\n", tot);
-                    for (int k = 0; k < 12; ++k) fprintf(stderr, "  %-45s %12lld  %5.1f %%\n", nm[k], host[k], 100.0 * host[k] / (double)tot);
-                }
+                const char* nm[12] = {"loop tail (dh)", "bar top", "P0 pos/clear/load h", "bar P0", "P1 masks + part 1 (loads, stores, images)", "barriers after parts",
+                                      "t2 mma + dar", "gates mma + dpr", "pooled rebuild + store", "dpool mma + tile write", "bin barrier", "gather / NB"};
+                ioc_timing_report(q.dbg, nm, 12, s);       // (k_ioc_bwd_x3, block 7, wave 0)
 #endif
             } else
             launch_ioc_bwd(q, s);
@@ -917,13 +897,7 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
     { Timer t(h, s, "bwd_encoder_x"); enc_bwd("enc_x", "ex", d.T_obs, 0); }
     }       // Ae > 0
     HIPCHK(hipGetLastError());
-    if (ioc_uses_cluster(d.mno, d.H, d.grid_size * d.grid_size, 0)) {
-        int e = 0;
-        HIPCHK(hipMemcpyAsync(&e, h->ws["ioc_err"].p, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (e) return fail(DESIRE_ERR_HIP, "IOC cluster backward: hand-off timed out (workgroups of a group were not co-resident)");
-    }
-    return DESIRE_OK;
+    return ioc_plan(h).bwd == IocBwd::CLUSTER ? ioc_cluster_check(h, s, "IOC cluster backward:") : DESIRE_OK;
 }
 
 extern "C" int desire_set_head_loss(desire_handle* h, float weight) {

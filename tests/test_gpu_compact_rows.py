@@ -519,3 +519,52 @@ def test_a_compacted_forward_replays_from_a_hipgraph(torch_cuda):
     except _lib.DesireError:
         pass
     h.close()
+
+
+def test_slot_class_buffers_follow_option_and_mode_switches(torch_cuda):
+    """The slot-class set of a handle depends on ioc_form, train_fp32_mask and the training mode (whether class 10 exists), all of which change on a
+    live handle.  Its class buffers are sized once, for both class sets, and desire_set_option drops the maps of the last desire_encode when the set
+    may change.  Windows with 9, 14 and 30 present agents use classes 10, 16 and 32; after every switch Y and score are bit-identical to a fresh
+    handle created with the current settings and the same weights."""
+    torch = torch_cuda
+    from desire_amd import _lib
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+
+    def step(h, d, ins):
+        p_t, f_t, e_t = ins
+        Y = torch.full((d.R, d.T_pred, 2), 7.0, device="cuda"); sc = torch.full((d.R,), 3.0, device="cuda")
+        h.forward(p_t.data_ptr(), f_t.data_ptr(), e_t.data_ptr(), Y.data_ptr(), sc.data_ptr())
+        torch.cuda.synchronize()
+        return Y.cpu().numpy(), sc.cpu().numpy()
+
+    def fresh(d, w, g_t, gos, ins, training=False):
+        h = _lib.Handle(d); h.set_weights(w); h.set_option("compact_min_rows", 0)
+        if training:
+            h.set_training(True)
+        h.set_scene_grids(g_t.data_ptr(), gos)
+        out = step(h, d, ins)
+        h.close()
+        return out
+
+    base = small_dims(n_scenes=3, mno=32, K=2, T_obs=6, T_pred=7, n_grids=1).replace(flags=FLAG_COMPACT_ROWS | FLAG_COMPACT_IOC)
+    # (1) inference: ioc_form 2 (classes 8 / 16 / 32), then 0 (8 / 10 / 16 / 32)
+    # (2) dims.bf16 = 2 with the fp32 BPTT (train_fp32_mask 4): a training-mode forward (no class 10), then an inference forward (class 10)
+    for d0, switch in ((base.replace(ioc_form=2), "ioc_form"), (base.replace(bf16=2, train_fp32_mask=4), "training")):
+        w = init_weights(d0, 17)
+        past, fut, eps, grids, gos, keep = ragged_counts(d0, seed=31, counts=[9, 14, 30])
+        g_t = t(grids)
+        ins = (t(past), t(fut), t(eps))
+        h = _lib.Handle(d0); h.set_weights(w); h.set_option("compact_min_rows", 0)
+        h.set_scene_grids(g_t.data_ptr(), gos)
+        if switch == "ioc_form":
+            runs = [(d0, False, lambda: None), (d0.replace(ioc_form=0), False, lambda: h.set_option("ioc_form", 0))]
+        else:
+            runs = [(d0, True, lambda: h.set_training(True)), (d0, False, lambda: h.set_training(False))]
+        for d, training, apply in runs:
+            apply()
+            Y, sc = step(h, d, ins)
+            Yf, scf = fresh(d, w, g_t, gos, ins, training)
+            assert np.isfinite(Y).all() and np.isfinite(sc).all(), (switch, training)
+            np.testing.assert_array_equal(Y, Yf, err_msg="%s, training=%s" % (switch, training))
+            np.testing.assert_array_equal(sc, scf, err_msg="%s, training=%s" % (switch, training))
+        h.close()
