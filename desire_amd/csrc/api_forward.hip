@@ -54,10 +54,10 @@ int compact_setup(desire_ctx* h) {
     // slot-class buffers: with device-side counts a class's region starts at a STATIC offset (the sum of the worst cases of the classes before it).
     // Sized for both class sets the handle can take -- with and without class 10, which ioc_form, train_fp32_mask and the training mode switch on a
     // live handle -- so they never grow and pointers captured in a hipGraph stay valid.
-    size_t Ac = A, Rc = R + 128, Wc = (size_t)d.n_scenes;
+    size_t Ac = A, Rc = ioc_save_rows(h), Wc = (size_t)d.n_scenes;
     if (d.flags & DESIRE_FLAG_COMPACT_IOC) {
         const ClassLayout a = class_layout(h, false, nullptr), b = class_layout(h, true, nullptr);
-        Ac = std::max({a.agents, b.agents, A}); Rc = std::max({a.rows, b.rows, R + 128}); Wc = std::max(a.wins, b.wins);
+        Ac = std::max({a.agents, b.agents, A}); Rc = std::max({a.rows, b.rows, ioc_save_rows(h)}); Wc = std::max(a.wins, b.wins);
     }
     struct WS { const char* n; size_t bytes; };
     const WS list[] = {{"cp_amap", A * sizeof(int32_t)}, {"cp_inv", A * sizeof(int32_t)}, {"cp_count", 8 * sizeof(int32_t)}, {"cp_HxHy", A * 2 * d.H * f},
@@ -436,7 +436,7 @@ static int ioc_core(desire_handle* h, const IocView& v, hipStream_t s) {
     if (h->training) a.iters = 1;
     for (int it = 0; it < passes; ++it) {
         if (h->training) {
-            const size_t po = ((size_t)it * (h->R + 128) + v.row_off) * d.T_pred;         // a pass's saves (rows + slack), a view's at its row offset
+            const size_t po = ioc_save_off(h, it, v);         // a pass's saves (rows + slack), a view's at its row offset
             launch_copy_f32(W(h, "ioc_Yin") + po * 2, v.Y, (size_t)v.R * d.T_pred * 2, s);
             a.sv_x = W(h, "ioc_sv_x") + po * h->E; a.sv_r = W(h, "ioc_sv_r") + po * d.H; a.sv_u = W(h, "ioc_sv_u") + po * d.H;
             a.sv_c = W(h, "ioc_sv_c") + po * d.H; a.sv_h = W(h, "ioc_sv_h") + po * d.H;

@@ -1,5 +1,5 @@
-// ctx.h -- the handle behind desire_handle* and the small host helpers shared by api.hip (inference ABI) and
-// train.hip (training ABI).  Host code only.
+// ctx.h -- the handle behind desire_handle* and the small host helpers shared by api.hip (inference ABI),
+// train.hip and backward.hip (training ABI).  Host code only.
 #pragma once
 #include "../../include/desire_hip.h"
 #include "ioc_plan.h"
@@ -111,6 +111,8 @@ struct Timer {
 // which parts of the training step use split operands under dims.bf16 = 2 (1: weight-gradient reductions, 2: data-gradient
 // convolutions, 4: IOC BPTT, 8: six-product sample generation in the forward pass): everything dims.train_fp32_mask does not hold back
 inline int train_x3_mask(const desire_ctx* h) { return 15 & ~h->d.train_fp32_mask; }
+inline int wgrad_pieces(const desire_ctx* h) { return (h->d.bf16 == 2 && (train_x3_mask(h) & 1)) ? 2 : 0; }     // bf16 pieces per operand of the weight-gradient reductions (0: fp32)
+inline bool dgrad_split(const desire_ctx* h) { return h->d.bf16 == 2 && (train_x3_mask(h) & 2); }               // split-bf16 operands in the two large data-gradient convolutions
 
 inline const float* D(desire_ctx* h, const char* name) { return h->dev.at(name).f(); }
 inline const float4* D4(desire_ctx* h, const char* name) { return reinterpret_cast<const float4*>(h->dev.at(name).f()); }
@@ -156,12 +158,18 @@ struct IocView {
 struct ClassLayout { int n = 0; int m[4] = {0, 0, 0, 0}; IocView c[4]; size_t agents = 0, rows = 0, wins = 0; };
 ClassLayout class_layout(const desire_ctx* h, bool pad, const int* counts);
 IocView ioc_view(desire_ctx* h, const IocView* cls = nullptr);     // a class of class_layout with its pointers bound; nullptr: the handle's own layout
+// Rows of the IOC buffers: the handle's rows + slack for the partial padded tiles of the slot classes (DESIRE_FLAG_COMPACT_IOC).  The training-mode
+// forward (ioc_core) writes each refinement pass's saves and the backward reads them at ioc_save_off, in (row, t) units: a pass's stride is
+// ioc_save_rows * T_pred, a view's saves start at its row offset.
+inline size_t ioc_save_rows(const desire_ctx* h) { return (size_t)h->R + 128; }
+inline size_t ioc_save_off(const desire_ctx* h, int pass, const IocView& v) { return ((size_t)pass * ioc_save_rows(h) + v.row_off) * h->d.T_pred; }
 // The cluster form's exchange, sized for the handle's own shape (every view is smaller): allocated on first use, the counters of n_groups groups
 // zeroed (and the error word when reset_err); ioc_cluster_check reads the error word back (a stream synchronisation)
 int ioc_cluster_exchange(desire_ctx* h, size_t n_groups, bool reset_err, hipStream_t s);
 int ioc_cluster_check(desire_ctx* h, hipStream_t s, const char* what);
 void ioc_timing_report(const long long* dbg, const char* const* names, int n, hipStream_t s);      // DESIRE_IOC_TIMING: per-phase cycle counters -> stderr
 int desire_pack_all(desire_ctx* h);                            // (re)builds every packed / folded device tensor from host_w
+__attribute__((visibility("hidden"))) int ensure(desire_ctx* h, const char* name, size_t bytes);     // workspace buffer `name` of at least `bytes` (train.hip; non-zero: hipMalloc failed; not an exported symbol)
 int scene_grad_setup(desire_ctx* h);                           // buffers of the scene-grid gradient (train.hip; idempotent, training mode only)
 inline bool scene_grad_on(const desire_ctx* h) { return h->scene_grad || h->img_set; }      // images attached imply the grid gradient
 int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)
