@@ -23,6 +23,7 @@ def main():
                   posterior=int(rng.integers(0, 2)), iters=int(rng.choice([1, 1, 2])), L=int(rng.choice([64, 128])),
                   nb_w=float(rng.choice([0.05, 0.2, 0.5])), nb_h=float(rng.choice([0.05, 0.25, 0.5])))
         kw["n_grids"] = int(rng.integers(1, kw["n_scenes"] + 1))
+        kw["Gh"], kw["Gw"] = int(rng.choice([8, 12, 20, 44, 64])), int(rng.choice([8, 12, 20, 44, 64]))      # scene grid rows / columns, independently
         if kw["grid_size"] > 4 and H > 128:
             kw["grid_size"] = 4
         if rng.random() < 0.25:

@@ -31,9 +31,16 @@ def main():
         d = small_dims(mno=64, n_scenes=1, K=2, n_grids=1, nb_w=0.04, nb_h=0.04)
     else:
         d = small_dims(mno=32, n_scenes=3, K=3, T_pred=9, n_grids=1, iters=2 if case == "two_passes" else 1)
+    rect = None
+    if case == "rect":         # a rectangular scene grid "GhxGw" (sys.argv[2]), two grids mapped crosswise: the inputs of tests/test_gpu_scene_rect.py,
+        from tests.test_gpu_scene_rect import W32, _inputs, _oracle_pass       # refined from the ORACLE's Y0 and also compared with the oracle
+        Gh, Gw = (int(v) for v in sys.argv[2].split("x"))
+        rect = _inputs({**W32, "Gh": Gh, "Gw": Gw}, 3)
+        d, w, past, fut, eps, grids, gos = (rect[k] for k in ("d", "w", "past", "fut", "eps", "grids", "gos"))
+    else:
+        w = init_weights(d, 21)
+        past, fut, eps, grids, gos = make_case(d, seed=22, n_absent=3)
     m_loc = d.mno // world
-    w = init_weights(d, 21)
-    past, fut, eps, grids, gos = make_case(d, seed=22, n_absent=3)
     sl = slice(rank * m_loc, (rank + 1) * m_loc)
     d_loc = d.replace(mno=m_loc)
     epsr = eps.reshape(d.n_scenes, d.K, d.mno, d.L)[:, :, sl].reshape(-1, d.L)
@@ -46,6 +53,9 @@ def main():
     Y0 = torch.zeros((d_loc.R, d.T_pred, 2), device="cuda")
     h.sample(keep["eps"].data_ptr(), Y0.data_ptr())
     torch.cuda.synchronize()
+    if rect is not None:
+        cut = lambda a: np.ascontiguousarray(a.reshape((d.n_scenes, d.K, d.mno) + a.shape[1:])[:, :, sl]).reshape((d_loc.R,) + a.shape[1:])
+        Y0 = t(cut(rect["ref"]["Y0"].astype(np.float32)))
     Ya, sa = Y0.clone(), torch.zeros(d_loc.R, device="cuda")
     ShardedIoc(h, rank, world).run(Ya, sa)                                # T_pred all-gathers per pass, issued from Python
     torch.cuda.synchronize()
@@ -64,6 +74,11 @@ def main():
     ok = all(torch.equal(Yb, Ya) and torch.equal(sb, sa) for Yb, sb in outs) and bool(torch.isfinite(Ya).all()) and float((Ya - Y0).abs().max()) > 0
     peer.close()
     print("rank %d peer == gathered: %s (max |dY| %.3e)" % (rank, ok, float((Ya - Y0).abs().max())), flush=True)
+    if rect is not None:       # the gates of tests/test_gpu_parity.py: 1e-3 on trajectories, 5e-3 on scores
+        rY, rs = _oracle_pass(rect)
+        eY, es = float(np.abs(Ya.cpu().numpy() - cut(rY)).max()), float(np.abs(sa.cpu().numpy() - cut(rs)).max())
+        print("rank %d within the oracle's gate: %s (Y %.2e, score %.2e)" % (rank, eY < 1e-3 and es < 5e-3, eY, es), flush=True)
+        ok = ok and eY < 1e-3 and es < 5e-3
     dist.destroy_process_group()
     sys.exit(0 if ok else 1)
 

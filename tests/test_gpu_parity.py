@@ -148,6 +148,24 @@ def test_neighbor_bins_and_scene_cells_bit_exact(torch_cuda):
     torch.cuda.synchronize()
     cy, cx = O.scene_cell(p, d.Gh, d.Gw)
     np.testing.assert_array_equal(cells_t.cpu().numpy(), np.stack([cy, cx], -1))
+    # a rectangular grid whose sides are no powers of two (y * Gh rounds in fp32): every cell edge k / G as fp32 and its two fp32 neighbours, on
+    # both axes and against both sides (a kernel that scales x with Gh, or contracts the multiply, departs here), out of range, +-0.0
+    dr = small_dims(mno=32, Gh=44, Gw=56)
+    hr = _lib.Handle(dr)
+    f = np.float32
+    edges = np.concatenate([np.arange(G + 1, dtype=f) / f(G) for G in (dr.Gh, dr.Gw)])
+    vals = np.concatenate([edges, np.nextafter(edges, f(-1)), np.nextafter(edges, f(2)),
+                           f([0.0, -0.0, -1e-30, -0.5, -7.0, 1.0, 1.5, 9.0, 0.999999, 1e30, -1e30])]).astype(f)
+    other = rng.uniform(-0.2, 1.2, vals.size).astype(f)
+    q = np.concatenate([np.stack([vals, other], -1), np.stack([other, vals], -1), np.stack([vals, vals[::-1]], -1),
+                        rng.uniform(-0.2, 1.2, (5000, 2)).astype(f)]).astype(f)
+    q_t = torch.as_tensor(q, device=dev)
+    cq_t = torch.full((len(q), 2), -7, dtype=torch.int32, device=dev)
+    hr.scene_cells(q_t.data_ptr(), cq_t.data_ptr(), len(q))
+    torch.cuda.synchronize()
+    cy, cx = O.scene_cell(q, dr.Gh, dr.Gw)
+    np.testing.assert_array_equal(cq_t.cpu().numpy(), np.stack([cy, cx], -1))
+    assert set(cy) == set(range(dr.Gh)) and set(cx) == set(range(dr.Gw))      # every row and column is hit
 
 
 def test_config1_shape_properties(torch_cuda):

@@ -35,7 +35,9 @@ def _case(kw=None, seed=42, n_absent=4):
     return d, w, past, fut, eps, images, gos
 
 
-def _autograd(monkeypatch, d, w, past, fut, eps, images, gos):
+def _autograd(monkeypatch, d, w, past, fut, eps, images, gos, Y0_gpu=None):
+    """Y0_gpu given (the rectangular cases): the reference's stop-gradient quantities are pinned to the kernel's trajectories, as
+    tests/test_gpu_scene_grad.py::pinned_to_kernel does and for its reason -- a present position of these cases lies within 1e-6 of a cell edge."""
     import torch
     import torch.nn.functional as F
     from oracle import desire_torch as OT
@@ -46,7 +48,14 @@ def _autograd(monkeypatch, d, w, past, fut, eps, images, gos):
     x = F.relu(OT.conv2d_tf(x, wl["scene_cnn/conv1/w"], 2, "SAME") + wl["scene_cnn/conv1/b"])
     x = F.relu(OT.conv2d_tf(x, wl["scene_cnn/conv2/w"], 2, "SAME") + wl["scene_cnn/conv2/b"])
     g = OT.conv2d_tf(x, wl["scene_cnn/conv3/w"], 1, "SAME") + wl["scene_cnn/conv3/b"]
-    out = OT.forward_loss(to_oracle_layout(past), to_oracle_layout(fut), eps, g, gos, wl, d)
+    assert tuple(g.shape) == (d.n_grids, d.Gh, d.Gw, d.C)
+    fixed = None
+    if Y0_gpu is not None:
+        with torch.no_grad():
+            o1 = OT.forward_loss(to_oracle_layout(past), to_oracle_layout(fut), eps, g, gos, wl, d)
+        present = np.repeat((past[:, d.T_obs - 1, :, 0] != 0)[:, None, :], d.K, 1).reshape(d.R)
+        fixed = {"Yd": np.where(present[:, None, None], Y0_gpu.astype(np.float64), o1["Yd"].numpy()), "dmax": o1["dmax"].numpy()}
+    out = OT.forward_loss(to_oracle_layout(past), to_oracle_layout(fut), eps, g, gos, wl, d, fixed=fixed)
     out["loss"].backward()
     return {k: v.grad.numpy() for k, v in wl.items() if v.grad is not None}
 
@@ -77,7 +86,10 @@ class Run:
 
     def fwd(self):
         import torch
-        self.h.forward(self.past.data_ptr(), self.fut.data_ptr(), self.eps.data_ptr(), self.Y.data_ptr(), self.score.data_ptr())
+        self.h.encode(self.past.data_ptr(), self.fut.data_ptr())               # desire_forward, with the decoded Y0 kept in the caller's row layout
+        self.h.sample(self.eps.data_ptr(), self.Y.data_ptr())
+        self.Y0 = self.Y.cpu().numpy().copy()
+        self.h.ioc_refine(self.Y.data_ptr(), self.score.data_ptr())
         torch.cuda.synchronize()
         return self.Y.cpu().numpy().copy(), self.score.cpu().numpy().copy()
 
@@ -95,16 +107,20 @@ class Run:
 
 
 CFG = [("fp32", dict(), 4), ("compact12", dict(flags=12), 22), ("iters2", dict(iters=2), 4), ("split_bf16", dict(bf16=2), 4),
-       ("cluster_bwd_mno96", dict(mno=96, n_scenes=1, K=2, H=128), 7)]
+       ("cluster_bwd_mno96", dict(mno=96, n_scenes=1, K=2, H=128), 7),
+       # rectangular grids: images 48 x 80 and 80 x 48
+       ("fp32_12x20", dict(Gh=12, Gw=20), 4), ("fp32_20x12", dict(Gh=20, Gw=12), 4),
+       ("compact12_12x20", dict(flags=12, Gh=12, Gw=20), 22), ("compact12_20x12", dict(flags=12, Gh=20, Gw=12), 22),
+       ("split_bf16_12x20", dict(bf16=2, Gh=12, Gw=20), 4), ("split_bf16_20x12", dict(bf16=2, Gh=20, Gw=12), 4)]
 
 
 @pytest.mark.parametrize("name,kw,n_absent", CFG, ids=[c[0] for c in CFG])
 def test_scene_cnn_gradients_match_autograd_and_nothing_else_moves(monkeypatch, name, kw, n_absent):
     d, w, past, fut, eps, images, gos = _case(kw, seed=45 if name == "iters2" else 42, n_absent=n_absent)
-    ref = _autograd(monkeypatch, d, w, past, fut, eps, images, gos)
     a = Run(d, w, past, fut, eps, images, gos, "images")
     b = Run(d, w, past, fut, eps, images, gos, "grid")
     ya, yb = a.fwd(), b.fwd()
+    ref = _autograd(monkeypatch, d, w, past, fut, eps, images, gos, Y0_gpu=a.Y0 if d.Gh != d.Gw else None)
     assert np.array_equal(ya[0], yb[0]) and np.array_equal(ya[1], yb[1])         # training-mode forward: the same grid, bit for bit
     assert np.array_equal(a.img_grid(), b.grid.cpu().numpy())
     a.bwd(); b.bwd()

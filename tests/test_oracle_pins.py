@@ -107,6 +107,50 @@ def test_neighbor_bins_known_answers():
     assert list(cy) == [0, 32, 0, 2] and list(cx) == [0, 63, 63, 1]
 
 
+def test_scene_cell_on_a_rectangular_grid_by_hand():
+    """Gh = 3 rows scale y, Gw = 5 columns scale x; positions (x, y).  Every answer below is written out by hand, one position per side
+    outside the frame included; none of them survives Gh and Gw being swapped, or a clamp with the other side."""
+    pts = np.float32([[0.0, 0.0],          # the origin                                   -> (0, 0)
+                      [0.5, 0.5],          # y * 3 = 1.5, x * 5 = 2.5                      -> (1, 2)
+                      [0.99, 0.99],        # 2.97, 4.95: the last row and column           -> (2, 4)
+                      [0.7, 0.2],          # 0.6, 3.5                                      -> (0, 3)
+                      [0.3, 0.9],          # 2.7, 1.5                                      -> (2, 1)
+                      [0.9, 0.5],          # 1.5, 4.5 (swapped dims would say (2, 2))      -> (1, 4)
+                      [-0.3, 0.4],         # left of the frame: x clamps to column 0       -> (1, 0)
+                      [1.2, 0.4],          # right of it: 6.0 clamps to column Gw - 1 = 4  -> (1, 4)
+                      [0.5, -0.1],         # above: y clamps to row 0                      -> (0, 2)
+                      [0.5, 1.7]])         # below: 5.1 clamps to row Gh - 1 = 2           -> (2, 2)
+    cy, cx = O.scene_cell(pts, 3, 5)
+    assert cy.tolist() == [0, 1, 2, 0, 2, 1, 1, 1, 0, 2]
+    assert cx.tolist() == [0, 2, 4, 3, 1, 4, 0, 4, 2, 2]
+    assert cy.dtype == np.int32 and cx.dtype == np.int32
+
+
+def test_ioc_pass_reads_the_grid_at_grid_row_column(monkeypatch):
+    """ioc_pass looks the scene feature up as grids[grid_of_scene[scene], cy, cx]: a 3 x 5 grid whose value encodes 100 g + 10 cy + cx, two grids
+    mapped to the two scenes crosswise, positions from the hand-written table above.  The feature is read where it enters the GRU cell
+    (columns E_v .. E_v + C of its input)."""
+    d = Dims(n_scenes=2, mno=2, K=1, T_obs=2, T_pred=2, n_grids=2, Gh=3, Gw=5, nb_w=0.5, nb_h=0.5)
+    w = init_weights(d, 0)
+    g, cy, cx = np.meshgrid(np.arange(2), np.arange(3), np.arange(5), indexing="ij")
+    grids = np.repeat((100 * g + 10 * cy + cx)[..., None], d.C, -1).astype(np.float32)
+    Y = np.float32([[[0.5, 0.5], [0.9, 0.5]],        # row 0, scene 0 -> grid 1: cells (1, 2), (1, 4)
+                    [[0.7, 0.2], [-0.3, 0.4]],       # row 1, scene 0 -> grid 1: (0, 3), (1, 0)
+                    [[0.3, 0.9], [1.2, 0.4]],        # row 2, scene 1 -> grid 0: (2, 1), (1, 4)
+                    [[0.5, -0.1], [0.5, 1.7]]])      # row 3, scene 1 -> grid 0: (0, 2), (2, 2)
+    want = np.float32([[112, 114], [103, 110], [21, 14], [2, 22]])
+    seen = []
+    cell = O.gru_cell
+    monkeypatch.setattr(O, "gru_cell", lambda x, *a, **k: (seen.append(np.array(x)), cell(x, *a, **k))[1])
+    rng = np.random.default_rng(0)
+    score, dY = O.ioc_pass(Y, rng.standard_normal((d.R, d.H)).astype(np.float32), np.full((d.R, 2), 0.5, np.float32), np.ones(d.R, bool),
+                           grids, [1, 0], w, d)
+    assert len(seen) == d.T_pred and np.isfinite(dY).all() and np.isfinite(score).all()
+    for t in range(d.T_pred):
+        e_s = seen[t][:, d.E_v:d.E_v + d.C]
+        np.testing.assert_array_equal(e_s, np.repeat(want[:, t:t + 1], d.C, 1))
+
+
 def test_temporal_conv_channel_order_and_quirk():
     """O1 (model/model.py:116-133): depthwise, output channel c*100+q, input channels are (id, x)."""
     rng = np.random.default_rng(3)

@@ -50,6 +50,43 @@ def test_autograd_matches_finite_differences(case):
         assert abs(fd - grads[name][idx]) < 1e-6 + 1e-4 * abs(fd), (name, idx, fd, grads[name][idx])
 
 
+def test_grid_gradient_matches_finite_differences_on_a_rectangular_grid(monkeypatch):
+    """d loss / d grids on a 3 x 5 grid (two grids, scenes mapped to them crosswise): autograd of the torch oracle fed a grid tensor that requires
+    grad against central differences, the method and the step of the check above.  Cells no position reaches carry an exact zero."""
+    import torch
+    d = small_dims(n_scenes=2, mno=8, K=3, T_obs=4, T_pred=5, n_grids=2, Gh=3, Gw=5, nb_w=0.5, nb_h=0.5)
+    w = init_weights(d, 5)
+    past, fut, eps, grids, _ = make_case(d, seed=6, n_absent=2)
+    past, fut, gos = to_oracle_layout(past), to_oracle_layout(fut), np.int32([1, 0])
+    assert grids.shape == (2, 3, 5, d.C)
+    orig = OT._t
+    monkeypatch.setattr(OT, "_t", lambda x: x if torch.is_tensor(x) else orig(x))
+    G = torch.as_tensor(grids, dtype=torch.float64).clone().requires_grad_(True)
+    out = OT.forward_loss(past, fut, eps, G, gos, OT.leaf_weights(w), d)
+    out["loss"].backward()
+    grad = G.grad.numpy()
+    fixed = {"Yd": out["Yd"].detach().numpy(), "dmax": out["dmax"].detach().numpy()}
+    wt = {k: OT._t(v) for k, v in w.items()}
+    loss_of = lambda g: float(OT.forward_loss(past, fut, eps, g, gos, wt, d, fixed=fixed)["loss"])
+    # the reference's own lookup says which cells are reached, per grid
+    cy, cx = O.scene_cell(fixed["Yd"].astype(np.float32), d.Gh, d.Gw)
+    gidx = gos[np.repeat(np.arange(d.n_scenes), d.K * d.mno)]
+    present = np.repeat((past[d.T_obs - 1, :, 0] != 0).reshape(d.n_scenes, 1, d.mno), d.K, 1).reshape(d.R)
+    reached = np.zeros((2, 3, 5), bool)
+    reached[gidx[present][:, None], cy[present], cx[present]] = True
+    assert reached[0].any() and reached[1].any() and not reached.all()
+    assert not np.any(grad[~reached]) and (np.abs(grad[reached]).max(-1) > 0).all()
+    rng = np.random.default_rng(0)
+    cells = [tuple(c) for c in np.argwhere(reached)] + [tuple(np.argwhere(~reached)[0])]
+    for g, y, x in cells:
+        c = int(rng.integers(0, d.C))
+        h = 1e-5
+        gp, gm = grids.astype(np.float64).copy(), grids.astype(np.float64).copy()
+        gp[g, y, x, c] += h; gm[g, y, x, c] -= h
+        fd = (loss_of(gp) - loss_of(gm)) / (2 * h)
+        assert abs(fd - grad[g, y, x, c]) < 1e-6 + 1e-4 * abs(fd), ((g, y, x, c), fd, grad[g, y, x, c])
+
+
 def test_adam_step_tf_formula():
     w, g = np.array([1.0, -2.0]), np.array([0.5, -0.25])
     m = v = np.zeros(2)
