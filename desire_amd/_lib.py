@@ -25,6 +25,7 @@ EXPORTS = [
     "desire_graph_begin", "desire_graph_end", "desire_graph_launch", "desire_rollout", "desire_build_windows_la", "desire_adam_state",
     "desire_set_option", "desire_train_loss_async", "desire_set_head_loss",
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
+    "desire_rank_samples", "desire_ranked_errors",
 ]
 
 
@@ -91,6 +92,8 @@ def load() -> C.CDLL:
     lib.desire_build_windows_la.argtypes = [vp, f32p, i32, i32, C.POINTER(C.c_int32), i32, i32, f32p, f32p, vp]
     lib.desire_gaussian_sample.argtypes = [vp, f32p, f32p, f32p, i32, vp]
     lib.desire_ade_fde.argtypes = [vp, f32p, f32p, f32p, vp]
+    lib.desire_rank_samples.argtypes = [vp, f32p, f32p, i32, vp, f32p, f32p, vp]
+    lib.desire_ranked_errors.argtypes = [vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
     lib.desire_backward.argtypes = [vp, f32p, f32p, f32p, vp]
@@ -232,6 +235,21 @@ class Handle:
 
     def ade_fde(self, yhat_ptr: int, fut_ptr: int, out_ptr: int, stream: int = 0) -> None:
         _chk(self.lib.desire_ade_fde(self._h, yhat_ptr, fut_ptr, out_ptr, stream or None))
+
+    def rank_samples(self, score_ptr: int, yhat_ptr: int, n_top: int, order_ptr: int, top_y_ptr: int = 0, top_score_ptr: int = 0,
+                     stream: int = 0) -> None:
+        """order [A, K] int32 = every agent's samples by descending score (ties to the lower k, NaN last); optionally the n_top best rows of
+        Y -> top_y [A, n_top, T_pred, 2] and their scores -> top_score [A, n_top]."""
+        _chk(self.lib.desire_rank_samples(self._h, score_ptr, yhat_ptr or None, int(n_top), order_ptr, top_y_ptr or None, top_score_ptr or None,
+                                          stream or None))
+
+    def ranked_errors(self, yhat_ptr: int, fut_ptr: int, order_ptr: int, n_top: int, horizons, unit_x: float, unit_y: float, out_ptr: int,
+                      stream: int = 0) -> None:
+        """out [A, len(horizons), 4] = (ADE_h, FDE_h of the best-scored sample, best ADE_h, FDE_h among the n_top best-scored); errors are
+        scaled by (unit_x, unit_y) per axis: (1, 1) normalised units, (1/sx, 1/sy) pixels."""
+        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+        _chk(self.lib.desire_ranked_errors(self._h, yhat_ptr, fut_ptr, order_ptr, int(n_top), hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size,
+                                           C.c_float(unit_x), C.c_float(unit_y), out_ptr, stream or None))
 
     def set_training(self, on: bool) -> None:
         _chk(self.lib.desire_set_training(self._h, int(on)))

@@ -288,6 +288,9 @@ extern "C" int desire_create(const desire_dims* dims, desire_handle** out) {
         // the same handle (desire_amd/prefetch.py: DeviceWindowFeeder) -- the builder then touches these two buffers (through h->bw_starts / h->bw_err,
         // never through the map: other calls insert into it) and nothing else of the handle
         {"bw_starts", (size_t)d.n_scenes * sizeof(int32_t)}, {"bw_err", sizeof(int32_t)},
+        // desire_ranked_errors: (ADE_h, FDE_h) of every sample for the 8 horizons a call accepts, counted frames of every agent -- here, so that
+        // no call allocates and a captured call never has to
+        {"rank_tab", d.ref_compat ? 0 : R * 16 * f}, {"rank_cnt", d.ref_compat ? 0 : A * 8 * sizeof(int32_t)},
     };
     for (const WS& w : list) {
         if (h->ws[w.n].alloc(w.bytes)) { desire_destroy(h); return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for ") + w.n); }

@@ -157,3 +157,46 @@ extern "C" int desire_ade_fde(desire_handle* h, const float* dev_Yhat, const flo
     return DESIRE_OK;
 }
 
+// ---- ranking by IOC score (kernels_rank.hip): the order of every agent's K samples, the n_top best rows, the errors of the paper's protocol ----
+extern "C" int desire_rank_samples(desire_handle* h, const float* dev_score, const float* dev_Yhat, int32_t n_top, int32_t* dev_order,
+                                   float* dev_top_Y, float* dev_top_score, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_score) return fail(DESIRE_ERR_ARG, "dev_score is NULL");
+    if (!dev_order) return fail(DESIRE_ERR_ARG, "dev_order is NULL");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no IOC score to rank by");
+    if (n_top < 1 || n_top > d.K) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
+    if (dev_top_Y && !dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL (dev_top_Y is gathered from it)");
+    if (d.K > RANK_MAX_K) return fail(DESIRE_ERR_ARG, "K above " + std::to_string(RANK_MAX_K) + " is not ranked on the device");
+    launch_rank_select(dev_score, dev_Yhat, dev_order, dev_top_Y, dev_top_score, d.n_scenes, d.mno, d.K, d.T_pred, n_top,
+                       static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
+extern "C" int desire_ranked_errors(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const int32_t* dev_order, int32_t n_top,
+                                    const int32_t* host_horizons, int32_t n_h, float unit_x, float unit_y, float* dev_out, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_fut) return fail(DESIRE_ERR_ARG, "dev_fut is NULL");
+    if (!dev_order) return fail(DESIRE_ERR_ARG, "dev_order is NULL");
+    if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (!dev_out) return fail(DESIRE_ERR_ARG, "dev_out is NULL");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no IOC score to rank by");
+    if (n_top < 1 || n_top > d.K) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
+    if (n_h < 1 || n_h > 8) return fail(DESIRE_ERR_ARG, "n_h must be 1..8");
+    RankHz hz{};
+    hz.n = n_h;
+    for (int i = 0; i < n_h; ++i) {
+        hz.h[i] = host_horizons[i];
+        if (hz.h[i] < 1 || hz.h[i] > d.T_pred) return fail(DESIRE_ERR_ARG, "host_horizons[" + std::to_string(i) + "] must be 1..T_pred");
+        if (i && hz.h[i] <= hz.h[i - 1]) return fail(DESIRE_ERR_ARG, "host_horizons must be strictly increasing");
+    }
+    int sc = 0, kc = 0;
+    if (!sample_errors_geometry(d.mno, d.K, d.T_pred, &sc, &kc)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the error kernel's LDS");
+    launch_ranked_errors(dev_Yhat, dev_fut, dev_order, W(h, "rank_tab"), static_cast<int32_t*>(h->ws.at("rank_cnt").p), dev_out, d.n_scenes,
+                         d.mno, d.K, d.T_pred, n_top, hz, d.sx, d.sy, unit_x, unit_y, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}

@@ -221,6 +221,16 @@ void launch_gaussian_sample(const float* p, const float* nrm, float* out, int n,
 void launch_ade_fde(const float* Y, const float* fut, float* out, int n_scenes, int mno, int K, int T, float sx, float sy,
                     hipStream_t s);
 
+// ---- ranking by IOC score (kernels_rank.hip) ----
+struct RankHz { int n; int h[8]; };                        // horizons in frames, strictly increasing, by value in the kernel arguments
+constexpr int RANK_MAX_K = 4096;                           // k_rank_select keeps an agent's K scores and its order in LDS
+void launch_rank_select(const float* score, const float* Y, int32_t* order, float* top_Y, float* top_score, int n_scenes, int mno, int K,
+                        int T, int n_top, hipStream_t s);
+bool sample_errors_geometry(int mno, int K, int T, int* SC, int* KC);      // false: one row of T_pred errors does not fit the LDS
+// tab [R, hz.n, 2] and cnt [A, hz.n] are scratch of the call (the handle's "rank_tab" / "rank_cnt")
+void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order, float* tab, int32_t* cnt, float* out, int n_scenes, int mno,
+                          int K, int T, int n_top, const RankHz& hz, float sx, float sy, float ux, float uy, hipStream_t s);
+
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);
 void launch_loss_grad_y(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, const float* nvalid, float* dY,

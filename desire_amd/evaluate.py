@@ -1,0 +1,121 @@
+"""Evaluation of a checkpoint in the paper's protocol: prior samples of every window of a data set, ranked by IOC score on the
+device, errors per horizon of the best-scored sample (top-1), of the best among the top N by score and of the best of all K.
+
+    python -m desire_amd.evaluate --checkpoint save/social_model-400.npz --data_dir data/ --max_num_obj 32 --d_dim 128 \\
+        --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json]
+
+The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
+steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
+float64 on the host over the agents the loss counts (present at the last observed frame and in at least one target frame); a horizon's
+mean runs over those of them with a target frame before it, so every horizon carries its own agent count.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from typing import Iterator, List, Optional, Tuple
+
+import numpy as np
+
+from .train import build_parser as _train_parser, parse_horizons, split_windows
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = _train_parser()
+    p.description = "DESIRE evaluation on MI355X: ranked ADE / FDE per horizon of a checkpoint (model flags of desire_amd.train)"
+    p.add_argument("--checkpoint", type=str, required=True, help="weights archive written by desire_amd.train (social_model-N.npz)")
+    p.add_argument("--units", type=str, default="px",
+                   help="px (pixels), norm (normalised units) or a factor on pixels, e.g. 0.2 for the paper's 1/5 resolution")
+    p.add_argument("--max_windows", type=int, default=0, help="stop after this many windows (0 = all)")
+    p.add_argument("--out", type=str, default=None, help="write the result JSON here (default: standard output only)")
+    return p
+
+
+def iter_batches(data_loader, batch_size: int, max_windows: int = 0) -> Iterator[Tuple[List[np.ndarray], List[int]]]:
+    """Every window of every video of the loader once, in order, in batches of batch_size (the last one may be shorter): video v from frame
+    0 in steps of seq_length while a window plus the loader's look-ahead frame fits (utils/data_loader.py:190-205 without the random jump).
+    Yields (windows [seq_length, max_num_obj, 3], video index of each)."""
+    from .data_loader import window_to_slots
+    T, xs, ds, n = data_loader.seq_length, [], [], 0
+    for v, video in enumerate(data_loader.data):
+        idx = 0
+        while idx + T < video.shape[0] and not (max_windows and n >= max_windows):
+            xs.append(window_to_slots(video[idx:idx + T + 1], T, data_loader.max_num_obj)[0])
+            ds.append(v)
+            idx += T
+            n += 1
+            if len(xs) == batch_size:
+                yield xs, ds
+                xs, ds = [], []
+    if xs:
+        yield xs, ds
+
+
+def evaluate(args, data_loader=None, model=None) -> dict:
+    """Runs the walk; returns the result dict main() prints.  `data_loader` / `model` may be injected (tests)."""
+    from .data_loader import DataLoader
+    from .model import DESIREModel, default_top
+    if args.pred_length is None:
+        args.pred_length = args.seq_length
+    t_obs, t_pred = int(args.seq_length), int(args.pred_length)
+    if data_loader is None:
+        data_loader = DataLoader(args.batch_size, t_obs + t_pred, args.max_num_obj, args.leave_dataset, preprocess=False,
+                                 data_dir=args.data_dir, traj_bin=args.traj_bin, fix_id0=args.fix_id0)
+    if model is None:
+        model = DESIREModel.restore(args, args.checkpoint)
+    K = int(args.num_samples)
+    top = int(args.eval_top or default_top(K))
+    hz = parse_horizons(args.eval_horizons, t_pred)
+    units = args.units if args.units in ("px", "norm") else float(args.units)
+    names = ("top1", "best_of_top", "best_of_K")
+    sums = {k: np.zeros((len(hz), 2), np.float64) for k in names}
+    agents = np.zeros(len(hz), np.int64)
+    mean_k, n_all, n_windows = np.zeros(2, np.float64), 0, 0
+    for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
+        past, fut = split_windows(xs, t_obs)
+        model.predict(past, top=top, seed=args.seed)
+        Y, score = model.final_output, model.final_states
+        ranked = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units=units).astype(np.float64)
+        best = model.evaluate_ranked(Y, score, fut, top=K, horizons=hz, units=units).astype(np.float64)
+        ev = model.evaluate(Y, fut).astype(np.float64)
+        pw, fw = np.stack(past), np.stack(fut)
+        mno = ranked.shape[0] // pw.shape[0]
+        valid = np.zeros((pw.shape[0], mno), bool)
+        valid[:, :pw.shape[2]] = pw[:, -1, :, 0] != 0
+        seen = np.zeros((pw.shape[0], t_pred, mno), bool)
+        seen[:, :, :pw.shape[2]] = fw[:, :, :, 0] != 0
+        for i, h in enumerate(hz):
+            c = (valid & seen[:, :h].any(1)).reshape(-1)
+            agents[i] += int(c.sum())
+            sums["top1"][i] += ranked[c, i, 0:2].sum(0)
+            sums["best_of_top"][i] += ranked[c, i, 2:4].sum(0)
+            sums["best_of_K"][i] += best[c, i, 2:4].sum(0)
+        c = (valid & seen.any(1)).reshape(-1)
+        mean_k += ev[c, 0:2].sum(0)
+        n_all += int(c.sum())
+        n_windows += len(xs)
+    res = {"checkpoint": args.checkpoint, "units": args.units, "seed": int(args.seed), "K": K, "top": top, "horizons": hz,
+           "windows": n_windows, "agents": [int(a) for a in agents]}
+    for k in names:
+        m = sums[k] / np.maximum(agents, 1)[:, None]
+        res[k] = {"ade": [float(v) for v in m[:, 0]], "fde": [float(v) for v in m[:, 1]]}
+    # mean-of-K comes from the ADE / FDE harness: normalised units, the whole prediction
+    res["mean_of_K"] = {"ade": float(mean_k[0] / max(n_all, 1)), "fde": float(mean_k[1] / max(n_all, 1)), "units": "norm", "horizon": t_pred,
+                        "agents": n_all}
+    return res
+
+
+def main(argv: Optional[List[str]] = None) -> None:
+    args = build_parser().parse_args(argv)
+    res = evaluate(args)
+    text = json.dumps(res, indent=1)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
+    print(text)
+    sys.stdout.flush()
+
+
+if __name__ == "__main__":
+    main()

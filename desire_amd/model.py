@@ -26,6 +26,16 @@ from . import _lib
 from .spec import Dims, init_weights, weight_shapes
 
 
+def default_top(K: int) -> int:
+    """How many of an agent's K samples "the top 10 % by score" are (the paper's protocol): max(1, K // 10)."""
+    return max(1, int(K) // 10)
+
+
+def default_horizons(T_pred: int):
+    """The paper's 1 / 2 / 3 / 4 s of a 4 s prediction in frames of this model: ceil(T_pred * q / 4) for q = 1..4, duplicates collapsed."""
+    return sorted({(int(T_pred) * q + 3) // 4 for q in (1, 2, 3, 4)})
+
+
 def _next_divisor_of_64(n: int) -> int:
     """Pad max_num_obj up to a slot count the IOC tiling accepts: a divisor of 32, or a multiple of 32 up to 256 (above 128 the IOC pass
     runs step-wise and training is refused)."""
@@ -424,6 +434,61 @@ class DESIREModel(object):
         fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
         out = torch.empty((d.A, 4), device=self.device)
         h.ade_fde(Y.data_ptr(), fut.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return out.cpu().numpy()
+
+    # ---- ranking by IOC score (desire_rank_samples / desire_ranked_errors) ---------------------------------
+    def predict(self, x_batch: Sequence[np.ndarray], top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None):
+        """The `top` most plausible futures of every agent of a batch of observed loader windows [T_obs, MNO, 3], ranked by IOC score
+        (prior sampling: no future given).  See predict_device for the result."""
+        d = self._handle(len(x_batch), False).dims
+        out = self.predict_device(self._pad_windows(x_batch, d.mno), top, eps, seed, grid_of_scene=grid_of_scene)
+        self.input_data, self.target_data = x_batch, None
+        return out
+
+    def predict_device(self, past, top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None):
+        """predict() on windows already in HBM (forward_device's layout).  Returns a dict of device tensors: "traj" [n, mno, top, T_pred, 2]
+        IN PIXELS, best-scored first; "score" [n, mno, top]; "order" [n, mno, K] int32 (sample indices by descending score, ties to the
+        lower index); "present" [n, mno] bool (id != 0 at the last observed frame -- the rows of absent agents are whatever the forward
+        left, zeros under the default padding-skipping flags, and their order is the identity).  top=None: default_top(K).  All K samples
+        and scores stay available as self.final_output / self.final_states."""
+        torch = self.torch
+        Y, score = self.forward_device(past, None, eps, seed, grid_of_scene=grid_of_scene)
+        n = int(past.shape[0])
+        h = self._handle(n, False)
+        d = h.dims
+        top = default_top(d.K) if top is None else int(top)
+        if not 1 <= top <= d.K:
+            raise ValueError("top must be 1..num_samples (%d), got %d" % (d.K, top))
+        order = torch.empty((n, d.mno, d.K), device=self.device, dtype=torch.int32)
+        traj = torch.empty((n, d.mno, top, d.T_pred, 2), device=self.device, dtype=torch.float32)
+        sc = torch.empty((n, d.mno, top), device=self.device, dtype=torch.float32)
+        h.rank_samples(score.data_ptr(), Y.data_ptr(), top, order.data_ptr(), traj.data_ptr(), sc.data_ptr(),
+                       torch.cuda.current_stream().cuda_stream)
+        traj /= torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)
+        return {"traj": traj, "score": sc, "order": order, "present": past[:, -1, :, 0] != 0}
+
+    def evaluate_ranked(self, Y, score, fut_windows, top: Optional[int] = None, horizons=None, units="px") -> np.ndarray:
+        """[A, n_h, 4] = per horizon (ADE, FDE of the best-scored sample, best ADE, best FDE among the `top` best-scored samples) over the
+        target frames before the horizon the object is present in; zeros where there is none.  horizons in frames (default
+        default_horizons(T_pred)), top default default_top(K); units "px" (pixels), "norm" (normalised units, evaluate()'s) or a float f
+        = f x pixels (0.2: the paper's 1/5 resolution).  `fut_windows` as in evaluate()."""
+        torch = self.torch
+        n = int(Y.shape[0])
+        h = self._handles.get((n, 0, 0)) or self._handle(n, True)
+        d = h.dims
+        top = default_top(d.K) if top is None else int(top)
+        hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
+        if units == "norm":
+            ux, uy = 1.0, 1.0
+        else:
+            f = 1.0 if units == "px" else float(units)
+            ux, uy = f / d.sx, f / d.sy
+        fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
+        stream = torch.cuda.current_stream().cuda_stream
+        order = torch.empty((d.A, d.K), device=self.device, dtype=torch.int32)
+        out = torch.empty((d.A, len(hz), 4), device=self.device, dtype=torch.float32)
+        h.rank_samples(score.data_ptr(), 0, top, order.data_ptr(), 0, 0, stream)
+        h.ranked_errors(Y.data_ptr(), fut.data_ptr(), order.data_ptr(), top, hz, ux, uy, out.data_ptr(), stream)
         return out.cpu().numpy()
 
     # ---- checkpoints (train.py:114,197-206 saves TF checkpoints; here: a named fp32 archive) -----------------

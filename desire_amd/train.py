@@ -86,7 +86,24 @@ def build_parser() -> argparse.ArgumentParser:
                         "(e.g. bookstore/video6): the scene CNN runs on them and trains with the model (n_grids = the file's entries)")
     p.add_argument("--report_ade", action="store_true",
                    help="after every epoch: ADE / FDE (mean-of-K and best-of-K, normalised units) of PRIOR samples on the epoch's last batch")
+    p.add_argument("--report_ranked", action="store_true",
+                   help="after every epoch, on the same batch: errors of the paper's protocol in pixels -- ADE / FDE per horizon of the sample the IOC "
+                        "scores best (top-1) and of the best among the --eval_top best-scored samples")
+    p.add_argument("--eval_top", type=int, default=None, help="samples per agent the ranked report keeps (default: 10 %% of --num_samples, at least 1)")
+    p.add_argument("--eval_horizons", type=str, default=None,
+                   help="horizons of the ranked report in frames, comma separated and increasing, e.g. 3,6,9,12 (default: quarters of --pred_length)")
     return p
+
+
+def parse_horizons(text, t_pred: int) -> List[int]:
+    """--eval_horizons: "3,6,9,12" -> [3, 6, 9, 12]; None -> the quarters of the prediction (model.default_horizons)."""
+    from .model import default_horizons
+    if not text:
+        return default_horizons(t_pred)
+    hz = [int(x) for x in str(text).split(",") if x.strip()]
+    if not hz or len(hz) > 8 or any(b <= a for a, b in zip(hz, hz[1:])) or hz[0] < 1 or hz[-1] > t_pred:
+        raise ValueError("--eval_horizons: 1 to 8 strictly increasing frame counts in 1..pred_length (%d), got %r" % (t_pred, text))
+    return hz
 
 
 def _gos(grid_of_video, dval):
@@ -198,8 +215,8 @@ def train(args, data_loader=None, model=None, log: Callable[[str], None] = print
                 log("model saved to {}".format(path))
             if args.max_steps and steps >= args.max_steps:
                 return losses
-        if getattr(args, "report_ade", False) and data_loader.num_batches > 0:
-            _report_ade(args, model, past, fut, epoch, rank, log)
+        if data_loader.num_batches > 0:
+            _report(args, model, past, fut, epoch, rank, log)
     return losses
 
 
@@ -222,6 +239,38 @@ def _report_ade(args, model, past, fut, epoch, rank, log) -> None:
         e = ev[there].mean(0)
         log("epoch {} rank {}: ADE/FDE mean-of-K = {:.5f} / {:.5f}, best-of-K = {:.5f} / {:.5f} ({} agents)".format(
             epoch, rank, e[0], e[1], e[2], e[3], int(there.sum())))
+
+
+def _report_ranked(args, model, past, fut, epoch, rank, log) -> None:
+    """--report_ranked: what the ranking module is for.  The batch, the prior samples (same seed) and the agents of _report_ade; the K samples
+    of every agent are ranked by IOC score on the device and the errors are those of the paper's protocol, in pixels, per horizon: of the
+    best-scored sample and of the best among the top N by score."""
+    import torch
+    from .model import default_top
+    if torch.is_tensor(past):
+        Y, score = model.forward_device(past, None, seed=args.seed)
+        pw, fw = past.cpu().numpy(), fut.cpu().numpy()
+    else:
+        Y, score = model.forward(past, None, seed=args.seed)
+        pw, fw = np.stack([np.asarray(p) for p in past]), np.stack([np.asarray(f) for f in fut])
+    top = int(getattr(args, "eval_top", None) or default_top(int(Y.shape[1])))
+    hz = parse_horizons(getattr(args, "eval_horizons", None), int(Y.shape[3]))
+    ev = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units="px")
+    there = np.zeros(ev.shape[0], bool)
+    m = pw.shape[2]
+    there.reshape(pw.shape[0], -1)[:, :m] = (pw[:, -1, :, 0] != 0) & (fw[:, :, :, 0] != 0).all(1)
+    if there.any():
+        e = ev[there].astype(np.float64).mean(0)                       # [n_h, 4]
+        fmt = lambda col: "[" + ", ".join("%.3f" % v for v in e[:, col]) + "]"
+        log("epoch {} rank {}: ranked px @h={}: top-1 ADE/FDE = {} / {}, best-of-top-{} = {} / {} ({} agents)".format(
+            epoch, rank, "[" + ", ".join(str(h) for h in hz) + "]", fmt(0), fmt(1), top, fmt(2), fmt(3), int(there.sum())))
+
+
+def _report(args, model, past, fut, epoch, rank, log) -> None:
+    if getattr(args, "report_ade", False):
+        _report_ade(args, model, past, fut, epoch, rank, log)
+    if getattr(args, "report_ranked", False):
+        _report_ranked(args, model, past, fut, epoch, rank, log)
 
 
 def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred, losses) -> List[float]:
@@ -247,16 +296,17 @@ def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred,
 
     steps = 0
     last = None
+    reporting = getattr(args, "report_ade", False) or getattr(args, "report_ranked", False)
     try:
         for bt in feeder:
             start = time.time()
             model.learning_rate = lr_at_epoch(args, bt.epoch)
-            if last is not None and bt.epoch != last[2] and getattr(args, "report_ade", False):
-                _report_ade(args, model, last[0], last[1], last[2], rank, log)
+            if last is not None and bt.epoch != last[2]:
+                _report(args, model, last[0], last[1], last[2], rank, log)
             bt.wait()
             pl = model.train_step_device(bt.past, bt.fut, seed=args.seed + steps * world + rank, sync=False,
                                          grid_of_scene=_gos(getattr(model, "_grid_of_video", None), bt.d))
-            if getattr(args, "report_ade", False):        # the epoch's last batch is evaluated after the feeder has moved on: keep a copy
+            if reporting:                                 # the epoch's last batch is evaluated after the feeder has moved on: keep a copy
                 last = (bt.past.clone(), bt.fut.clone(), bt.epoch)
             bt.release()
             if pending is not None:
@@ -271,8 +321,8 @@ def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred,
         feeder.close()
     if pending is not None:
         settle(pending)
-    if last is not None and getattr(args, "report_ade", False):
-        _report_ade(args, model, last[0], last[1], last[2], rank, log)
+    if last is not None:
+        _report(args, model, last[0], last[1], last[2], rank, log)
     return losses
 
 

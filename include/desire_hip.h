@@ -271,6 +271,26 @@ int desire_rollout(desire_handle* h, const float* dev_past, const float* dev_nor
  * the object is present in (FDE: the last such frame); zeros for an object absent from every target frame. */
 int desire_ade_fde(desire_handle* h, const float* dev_Yhat, const float* dev_fut, float* dev_out, void* stream);
 
+/* ---- ranking by IOC score: the consumer of dev_score.  Agent a = scene * mno + slot, row r = (scene * K + k) * mno + slot.
+ * dev_order [A, K] int32: dev_order[a, j] = the sample index k with the j-th highest score of agent a.  IEEE > on the fp32 scores; ties go to
+ * the lower k (so -0.0 and 0.0 tie); NaN scores come last, among themselves by lower k; +inf first, -inf before the NaNs.  An agent whose K
+ * scores are all equal -- every absent slot under DESIRE_FLAG_COMPACT_IOC -- gets the identity order, so the call needs no validity input and
+ * no state of the last desire_encode.  An integer path: bit-exact.
+ * Errors: frame t of agent a counts when dev_fut[scene, t, slot, 0] != 0 (desire_ade_fde's rule); e = sqrt((unit_x * dx)^2 + (unit_y * dy)^2)
+ * with dx, dy as in desire_ade_fde: (unit_x, unit_y) = (1, 1) gives normalised units, (1/sx, 1/sy) pixels, (0.2/sx, 0.2/sy) the paper's 1/5
+ * resolution.  For a horizon h (frames): ADE_h = mean of e over the counted frames t < h, summed in increasing t; FDE_h = e at the last counted
+ * frame < h.  dev_out [A, n_h, 4] = (ADE_h, FDE_h of the sample dev_order[a, 0]; min over j < n_top of ADE_h, of FDE_h of the samples
+ * dev_order[a, j]); four zeros where the agent has no counted frame before h.  With n_top = K and h = T_pred columns 2, 3 are desire_ade_fde's.
+ * Neither call uses float atomics: results are bitwise reproducible and do not depend on the rest of the batch. */
+/* order [A,K] int32 out (see above).  dev_top_Y [A, n_top, T_pred, 2] and dev_top_score [A, n_top] (each may be NULL): the n_top
+ * best-scored samples of every agent, best first, copied from dev_Yhat / dev_score.  1 <= n_top <= K.  Stream-ordered, capturable. */
+int desire_rank_samples(desire_handle* h, const float* dev_score, const float* dev_Yhat, int32_t n_top,
+                        int32_t* dev_order, float* dev_top_Y, float* dev_top_score, void* stream);
+/* dev_out [A, n_h, 4] (see above).  dev_order from desire_rank_samples.  host_horizons[n_h] in frames, strictly increasing,
+ * 1 .. T_pred, n_h <= 8; read on the host at call time and passed by value.  Stream-ordered, capturable. */
+int desire_ranked_errors(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const int32_t* dev_order, int32_t n_top,
+                         const int32_t* host_horizons, int32_t n_h, float unit_x, float unit_y, float* dev_out, void* stream);
+
 /* ---- hipGraph capture: desire_graph_begin(h, stream); any stream-ordered desire_* calls on that stream (desire_forward,
  * desire_backward, desire_clip_grads, desire_ioc_step ...) ; desire_graph_end -> graph id; desire_graph_launch replays them with
  * the SAME device pointers.  For launch-bound shapes (small batches, the training step, the agent-sharded IOC loop).  Calls
