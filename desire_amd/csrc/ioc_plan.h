@@ -2,6 +2,7 @@
 // (tests/test_ioc_plan.py compiles it with g++); the launchers launch the family they are asked for and pick only template instances.
 #pragma once
 #include "../../include/desire_hip.h"
+#include "ioc_lds.h"
 
 #include <functional>
 
@@ -10,11 +11,7 @@
 // social bins (> 25 at H = 128) that the 64-row tile's neighbour masks push it past 160 KB.
 inline bool ioc_uses_cluster(int mno, int H, int bins, int variant) {
     if (mno > 64 || (mno == 64 && H == 256) || (variant == 4 && mno >= 64)) return true;
-    if (mno == 64) {
-        const size_t tile = ((size_t)65 * (2 * H + 52) + 2 * 64 * (H + 4) + 64 * 4 + 48 + (H / 32) * 64) * 4 + (size_t)64 * bins * 8 + 128;
-        return tile > 160 * 1024;
-    }
-    return false;
+    return mno == 64 && IocLds::tile(H, 16, 32, 64, bins).bytes() > 160 * 1024;
 }
 // Few tiles (a handful of windows): how many workgroups share one 32-row tile's social bins (k_ioc NSPL), so that the launch covers
 // up to 256 CUs instead of one per (scene, k) group.  1 = the plain form.
@@ -30,9 +27,7 @@ inline bool ioc_x3_supported(int mno, int H, int bins) { return mno >= 1 && mno 
 // ... on 64-row tiles, two row blocks per wave (kernels_x6r2.hip): its LDS tile must fit 160 KB
 inline bool ioc_x6r2_supported(int mno, int H, int bins) {
     if (!((H == 64 || H == 128) && mno >= 1 && ((mno <= 32 && 32 % mno == 0) || mno == 64))) return false;
-    const int KX = 16 + 32 + 2 * H, NT = H / 32;
-    const size_t lds = ((size_t)64 * (KX + 4) + (size_t)64 * (H + 4) + (size_t)H * 68) * 4 + (size_t)64 * (bins + 1) * 8 + 128 + 1024 + 192 + (size_t)NT * 256 + 128;
-    return lds <= 160 * 1024;
+    return IocHtLds::x6r2(H, 16, 32, bins).bytes() <= 160 * 1024;
 }
 // split-bf16 BPTT (kernels_bwd_x3.hip): groups of up to 32 agents, H = 64 / 128
 inline bool ioc_bwd_x3_supported(int mno, int H) { return mno <= 32 && (H == 64 || H == 128); }

@@ -3,14 +3,20 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// dynamic LDS above 64 KiB must be opted into once per kernel
-template <class F>
-inline void allow_big_lds(F* f) {
-    static bool done = false;
-    if (!done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        done = true;
-    }
+#include "ioc_lds.h"
+
+// dynamic LDS above 64 KiB must be opted into once per kernel: the kernel K, opted in, as the pointer the runtime queries take
+template <auto K>
+inline const void* big_lds_kernel() {
+    static const hipError_t once = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)once;
+    return reinterpret_cast<const void*>(K);
+}
+// ... and its launch: every instantiation is named once per launch site
+template <auto K, class... Args>
+inline void launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
+    (void)big_lds_kernel<K>();
+    hipLaunchKernelGGL(K, grid, block, lds, s, args...);
 }
 
 // A launch whose row count is known on the DEVICE only (DESIRE_FLAG_COMPACT_*, inference: the present agents of a batch / the windows seated in a

@@ -19,17 +19,13 @@
 #include "kernels.h"
 
 #include "bf16.h"
+#include "ioc_tile.h"
 
 // ------------------------------------------------------------------------------------------------------------------
 // IOC scoring / refinement, bf16 operands.  Tile = 32*WM rows = whole (scene,k) groups (mno divides 32 with WM = 1, or
 // mno = 64 with WM = 2); workgroup = WM * H/32 waves, wave (mt, cb) owns rows [32mt, 32mt+32) x hidden columns
 // [32cb, 32cb+32).  Weight pointers of IocArgs (Wg, Wc, Wsoc, Wreg) point at the bf16 packs ("ioc/*16" in api.hip).
 // ------------------------------------------------------------------------------------------------------------------
-#ifdef DESIRE_IOC_TIMING
-#define TICK16(k) { const long long now_ = clock64(); tacc[k] += now_ - tprev; tprev = now_; }
-#else
-#define TICK16(k)
-#endif
 template <int H, int EV, int C, int WM, bool WIDE = (WM > 1)>      // WIDE: one 64-agent group spans both row blocks (compile-time: branch-free chains)
 __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OCC : 1) void k_ioc_bf16(IocArgs a) {
 #ifdef DESIRE_IOC_TIMING
@@ -57,6 +53,12 @@ __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OC
     constexpr bool SPLIT = IOC16_SPLIT && NT <= 4;                          // pooling split over BINS between the waves of a row block
     float* EX = reinterpret_cast<float*>(smem_raw + ((reinterpret_cast<unsigned char*>(occ + 2) - smem_raw + 15) & ~15));   // [WM][NT][1024]
     float* EXB = EX + WM * NT * 1024;                                       // [WM * NT / 2][1024] second set's upper half (B <= 32)
+    constexpr IocHtLds P0 = IocHtLds::bf16(H, EV, C, WM, 0, SPLIT), P1 = IocHtLds::bf16(H, EV, C, WM, 1, SPLIT);     // (ioc_lds.h: what the launcher sizes the LDS by)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == (TM * LDXB + TM * LDRB + H * LDT) * 2);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == TM * 8 && P1.sz[P1.MASKS] == 2 * TM * 8);
+    IOC_LDS_TIED(P0.off(P0.OCC) - P0.off(P0.LUT) == 16 * 8 + (TM * 2 * 2 + 3 * EV + NT * TM) * 4 + TM);
+    IOC_LDS_TIED(!SPLIT || (P0.off(P0.OCC) % 16 == 0 && P0.off(P0.EX) == P0.off(P0.OCC) + 16)       /* EX: occ + 8 rounded up to 16 (without SPLIT it is not used) */);
+    IOC_LDS_TIED(!SPLIT || (P0.sz[P0.EX] == WM * NT * 4096 && P0.sz[P0.EXB] == WM * NT * 2048));
 
     const int lane = lane_id(), w = wave_id(), tid = threadIdx.x;
     const int cb = w % NT, mt = w / NT;
@@ -74,12 +76,8 @@ __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OC
     constexpr int JG = wide ? JGM : 2;                                // 16-wide neighbour chunks of this wave's rows
     const int jbase = wide ? 0 : mt * 32;                             // first local row its neighbours can have
 
-    for (int i = tid; i < 3 * EV; i += NTHR) wv[i] = (i < 2 * EV) ? a.w_vel[i] : a.b_vel[i - 2 * EV];
-    if (tid < 16) {
-        const unsigned lo = ((tid & 1) ? 0x3F80u : 0u) | ((tid & 2) ? 0x3F800000u : 0u);
-        const unsigned hi2 = ((tid & 4) ? 0x3F80u : 0u) | ((tid & 8) ? 0x3F800000u : 0u);
-        lut[tid] = make_uint2(lo, hi2);
-    }
+    ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);
+    ioc_stage_lut(lut, tid);
     if (tid < TM) vld[tid] = a.valid[agent_of_row(min(row0 + tid, a.R - 1), a.K, a.mno)];
     const float bgr = a.b_g[col], bgu = a.b_g[H + col], bcc = a.b_c[col], bso = a.b_soc[col], wsc = a.w_score[col];
     const float* grid = a.grids + (size_t)a.grid_of_scene[my_scene] * a.Gh * a.Gw * C;
@@ -127,7 +125,7 @@ __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OC
         __syncthreads();
 
         for (int t = 0; t < a.T; ++t) {
-            TICK16(0)
+            IOC_TICK(0)
             if (tid < TM && t + 1 < a.T)
                 ynext = *reinterpret_cast<const float2*>(a.Y + ((size_t)min(row0 + tid, a.R - 1) * a.T + t + 1) * 2);
             // ---- P1: e_v, e_s, neighbour bits (row threads) ----
@@ -152,12 +150,11 @@ __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OC
                                                           [&](int j, int b) { atomicOr(&masks[r8 * LDM + b], 1ull << (grp_base + j)); });
                 nb_publish_occ(oc, occ, B);
             }
-            TICK16(1)
+            IOC_TICK(1)
             __syncthreads();
-            TICK16(2)
+            IOC_TICK(2)
             // ---- P2: social pooling chain -> e_r ----
-            unsigned long long om_all = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-            om_all |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+            unsigned long long om_all = ioc_occ64(occ);
             if constexpr (SPLIT) {
                 // The occupied bins are dealt round-robin to the NT waves of a row block.  A wave runs the whole chain of ITS
                 // bins -- link 1 once per hidden block (no longer repeated by every wave), link 2 into all NT column blocks --
@@ -310,9 +307,9 @@ __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OC
                 for (int i = 0; i < 16; ++i)
                     Xb[(arow + (i & 3) + 8 * (i >> 2)) * LDXB + EV + C + col] = bf16_of(fmaxf(soc[i] + bso, 0.f));
             }
-            TICK16(3)
+            IOC_TICK(3)
             __syncthreads();
-            TICK16(4)
+            IOC_TICK(4)
             // ---- P4: gates over [x | h], and the candidate's x part (same A fragments: three n-tiles per LDS read) ----
             // B fragments run through a ring of RD k-groups requested that many groups before their use; their addresses are formed per
             // step from wave-uniform bases (the opaque zero keeps ~60 of them from being hoisted out of the time loop into spilled
@@ -361,9 +358,9 @@ __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OC
 #pragma unroll
                 for (int g = 0; g < GH16; ++g) ch[g] = (wch + g * 64)[ul];
             }
-            TICK16(5)
+            IOC_TICK(5)
             __syncthreads();
-            TICK16(6)
+            IOC_TICK(6)
             // ---- P5: candidate += (r*h) part, blend, score; publish h_t ----
             {
 #pragma unroll
@@ -382,15 +379,15 @@ __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OC
             }
             for (int i = tid; i < TM * LDM; i += NTHR) masks[i] = 0ull;
             if (tid < 2) occ[tid] = 0;
-            TICK16(7)
+            IOC_TICK(7)
             __syncthreads();
-            TICK16(8)
+            IOC_TICK(8)
         }
         // ---- score ----
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             float v = sp[i];
-            v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8); v += __shfl_xor(v, 16);
+            v = ioc_sum32(v);
             if (c31 == 0) red[cb * TM + arow + (i & 3) + 8 * (i >> 2)] = v;
         }
         __syncthreads();
@@ -425,23 +422,15 @@ __global__ __launch_bounds__((H / 32) * WM * 64, ((H / 32) * WM <= 4) ? IOC16_OC
 #endif
 }
 
-static size_t ioc16_lds(const IocArgs& a, int WM) {
-    const int H = a.H, TM = 32 * WM, E = 16 + 32 + H, KX = E + H, B = a.G * a.G, NT = H / 32;
-    size_t b = (size_t)TM * (KX + 8) * 2 + (size_t)TM * (H + 8) * 2 + (size_t)H * (TM + 8) * 2;
-    b += (size_t)TM * (B + 1) * 8 + 16 * 8 + (size_t)TM * 4 * 4 + 3 * 16 * 4 + (size_t)NT * TM * 4 + TM + 64;
-    if (IOC16_SPLIT && NT <= 4) b += (size_t)WM * NT * 4096 + 16 + (B <= 32 ? (size_t)WM * NT * 2048 : 0);   // partial-tile exchange
-    return b;
-}
 template <int H, int WM>
 static void launch16(const IocArgs& a, hipStream_t s) {
     const int TM = 32 * WM;
     const dim3 grid((a.R + TM - 1) / TM), block((H / 32) * WM * 64);
+    const size_t lds = IocHtLds::bf16(H, 16, 32, WM, a.G * a.G, IOC16_SPLIT && H / 32 <= 4).bytes();
     if (WM > 1 && a.mno <= 32) {                              // (64-row tiles forced onto small groups: a.variant == 2)
-        allow_big_lds(k_ioc_bf16<H, 16, 32, WM, false>);
-        hipLaunchKernelGGL((k_ioc_bf16<H, 16, 32, WM, false>), grid, block, ioc16_lds(a, WM), s, a);
+        launch_big_lds<k_ioc_bf16<H, 16, 32, WM, false>>(grid, block, lds, s, a);
     } else {
-        allow_big_lds(k_ioc_bf16<H, 16, 32, WM>);
-        hipLaunchKernelGGL((k_ioc_bf16<H, 16, 32, WM>), grid, block, ioc16_lds(a, WM), s, a);
+        launch_big_lds<k_ioc_bf16<H, 16, 32, WM>>(grid, block, lds, s, a);
     }
 }
 // mno divides 32 (32-row tiles, two workgroups per CU at H <= 128) or, with `two`, is 64 (64-row tiles, twice the waves; ioc_plan.h also
@@ -539,8 +528,7 @@ __global__ __launch_bounds__(DS_WG) void k_deconv2_bf16(ConvArgs a) {
 // (Measured and dropped: two sample pairs per wave -- half the weight-fragment stream, 1.24 vs 0.95 ms: with two waves per workgroup nothing
 // covers the 16-deep LDS read-add-write scatter after every tap.)
 void launch_deconv2_bf16(const ConvArgs& a, hipStream_t s) {
-    allow_big_lds(k_deconv2_bf16);
-    hipLaunchKernelGGL(k_deconv2_bf16, dim3((a.n + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a);
+    launch_big_lds<k_deconv2_bf16>(dim3((a.n + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a);
 }
 
 // deconv3: [n,8,8,64] -> [n,16,16,32], 5x5 SAME stride 2, output-parity gather (see k_deconv3); one wave per sample,
@@ -727,8 +715,7 @@ __global__ __launch_bounds__((H / 32) * 64, (H / 32) <= 4 ? 2 : 1) void k_decode
 template <int H>
 static void launch_dec16(const DecArgs& a, hipStream_t s) {
     const size_t lds = (size_t)(32 * (H + 4) + 2 * H + 64) * sizeof(float) + (size_t)2 * 32 * (H + 8) * sizeof(u16);
-    allow_big_lds(k_decoder_bf16<H>);
-    hipLaunchKernelGGL((k_decoder_bf16<H>), dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
+    launch_big_lds<k_decoder_bf16<H>>(dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
 }
 void launch_decoder_bf16(const DecArgs& a, hipStream_t s) {
     if (a.H == 256) launch_dec16<256>(a, s);
@@ -983,8 +970,7 @@ __global__ __launch_bounds__(DS_WG) void k_mask_bf16(MaskArgs a) {
 }
 void launch_mask_bf16(const MaskArgs& a, hipStream_t s) {
     const size_t lds = (size_t)64 * LDA16 * sizeof(u16);               // 66.6 KB >= the [64][H+4] fp32 softmax tile
-    allow_big_lds(k_mask_bf16);
-    hipLaunchKernelGGL(k_mask_bf16, dim3((a.R + 63) / 64), dim3(DS_WG), lds, s, a);
+    launch_big_lds<k_mask_bf16>(dim3((a.R + 63) / 64), dim3(DS_WG), lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -20,15 +20,11 @@
 // epilogue addresses from per-pass opaque row bases: 1 spilled register where there were 190.  6.15 -> 4.73 ms at configs[2]'s shape.
 #include "bf16.h"
 #include "cluster.h"
+#include "ioc_tile.h"
 #include "kernels.h"
 
 #define CLMAXM 128
 
-#ifdef DESIRE_IOC_TIMING
-#define TICKC(k) { const long long now_ = clock64(); tacc[k] += now_ - tprev; tprev = now_; }
-#else
-#define TICKC(k)
-#endif
 // TPGT: tiles per group as a compile-time constant (2, 3, 4: the neighbour-chunk loops of the pooling chains are then branch-free), or 0 = read
 // it from the arguments
 #ifndef IOC16CL_OCC
@@ -61,6 +57,11 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
     unsigned char* vld = reinterpret_cast<unsigned char*>(red + NT * TM);   // [CLMAXM]
     unsigned* occ = reinterpret_cast<unsigned*>(vld + CLMAXM);              // [2] bins that hold a neighbour anywhere in the tile
     float2* pgv = reinterpret_cast<float2*>(occ + 2);                        // [CLMAXM] the same positions with NaN for absent agents (pair loop)
+    constexpr IocHtLds P0 = IocHtLds::bf16_cluster(H, EV, C, 0, CLMAXM), P1 = IocHtLds::bf16_cluster(H, EV, C, 1, CLMAXM);     // (ioc_lds.h)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == (TM * LDXB + TM * LDRB + H * LDT) * 2);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == TM * 2 * 8 && P1.sz[P1.MASKS] == 2 * TM * 2 * 8);
+    IOC_LDS_TIED(P0.off(P0.PGV) - P0.off(P0.LUT) == 16 * 8 + (CLMAXM * 2 + TM * 2 + 3 * EV + NT * TM) * 4 + CLMAXM + 8);
+    IOC_LDS_TIED(P0.sz[P0.PGV] == CLMAXM * 8);
     // partial-tile exchange of the bin-split pooling: two sets of NT 4 KB slots INSIDE the Ht tile.  Ht is dead between the end of the
     // pooling chains and the end of the step (my columns are rewritten by publish_h, the other members' by the next step's copy), so
     // the exchange costs no LDS of its own and two workgroups still share a CU
@@ -77,12 +78,8 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
     const agent_buf hexr = agent_buffer(hex16, 2u * (unsigned)n_tiles * (H * TM * 2));
     const int my_slot = tile_pos * TM + r8;                            // group-local slot of my VALU row
 
-    for (int i = tid; i < 3 * EV; i += NTHR) wv[i] = (i < 2 * EV) ? a.w_vel[i] : a.b_vel[i - 2 * EV];
-    if (tid < 16) {
-        const unsigned lo = ((tid & 1) ? 0x3F80u : 0u) | ((tid & 2) ? 0x3F800000u : 0u);
-        const unsigned hi2 = ((tid & 4) ? 0x3F80u : 0u) | ((tid & 8) ? 0x3F800000u : 0u);
-        lut[tid] = make_uint2(lo, hi2);
-    }
+    ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);
+    ioc_stage_lut(lut, tid);
     const float bgr = a.b_g[col], bgu = a.b_g[H + col], bcc = a.b_c[col], bso = a.b_soc[col], wsc = a.w_score[col];
     const uint4* Wg = reinterpret_cast<const uint4*>(a.Wg);
     const uint4* Wc = reinterpret_cast<const uint4*>(a.Wc);
@@ -160,7 +157,7 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
             __syncthreads();
             for (int t = 0; t < a.T; ++t) {
                 if (t + 1 < a.T && tid < a.mno) ynx = *reinterpret_cast<const float2*>(a.Y + ((size_t)(grow0 + tid) * a.T + t + 1) * 2);
-                TICKC(0)
+                IOC_TICK(0)
                 // 16-byte loads (sc1) of the peers' h_{t-1} tiles (published at the end of step t-1, parity (t-1)&1), all of a thread's
                 // chunks in flight: chunk i of a tile = column i >> 2, exchange positions 8 (i & 3) .. + 7 = lane half (i & 1), accumulator
                 // elements 8 (i >> 1 & 1) .. + 7 (publish_h).  (Requesting them BEFORE the position-only phase was measured twice -- rounds 2 and 5: 4.73 ->
@@ -240,11 +237,11 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
                         if (4 * (q8 + k * TPR) < C)
                             *reinterpret_cast<uint2*>(Xb + r8 * LDXB + EV + 4 * (q8 + k * TPR)) = make_uint2(pk_bf16(g4[k].x, g4[k].y), pk_bf16(g4[k].z, g4[k].w));
                 }
-                TICKC(1)
+                IOC_TICK(1)
                 // ---- neighbours' h_{t-1} into the group's Ht ----
                 if (t > 0) {
                     group_wait_wt(cnt, tpg * (it * (a.T + 1) + t), a.err);
-                    TICKC(2)
+                    IOC_TICK(2)
                     if constexpr (TPGT > 0) {
                         request_peers();
 #pragma unroll
@@ -272,15 +269,14 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
                     }
                 }
                 __syncthreads();
-                TICKC(3)
+                IOC_TICK(3)
                 // every reader of this step's positions is past the barrier: the next step's go in, my rows' current ones become "previous"
                 if (t + 1 < a.T && tid < a.mno) {
                     if ((tid >> 5) == tile_pos) { pp[(tid & 31) * 2] = pg[tid * 2]; pp[(tid & 31) * 2 + 1] = pg[tid * 2 + 1]; }
                     put_positions();
                 }
                 // ---- P2: social pooling chain -> e_r ----
-                unsigned long long om_all = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-                om_all |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+                unsigned long long om_all = ioc_occ64(occ);
                 auto frag_bits = [&](int b, uint4 (&mf)[JGM]) {           // neighbour bits of row c31 in bin b -> bf16 B fragments
                     const unsigned long long m0 = masks[(c31 * LDM + b) * 2], m1 = masks[(c31 * LDM + b) * 2 + 1];
 #pragma unroll
@@ -353,7 +349,7 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     __builtin_amdgcn_s_setprio(0);
-                    TICKC(4)
+                    IOC_TICK(4)
                     if (om) {                                          // (workgroup-uniform)
                         __syncthreads();                               // every wave is done reading Ht: it now carries the exchange slots
 #pragma unroll
@@ -407,9 +403,9 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
                     for (int i = 0; i < 16; ++i)
                         Xb[(arow + (i & 3) + 8 * (i >> 2)) * LDXB + EV + C + col] = bf16_of(fmaxf(soc[i] + bso, 0.f));
                 }
-                TICKC(5)
+                IOC_TICK(5)
                 __syncthreads();
-                TICKC(6)
+                IOC_TICK(6)
                 // the pooling chains are done with the neighbour masks and every wave has read the occupancy words: cleared for the next step
                 for (int i = tid; i < TM * LDM * 2; i += NTHR) masks[i] = 0ull;
                 if (tid < 2) occ[tid] = 0;
@@ -462,7 +458,7 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
 #pragma unroll
                     for (int g = 0; g < GH16; ++g) ch[g] = (wch + g * 64)[ul];
                 }
-                TICKC(7)
+                IOC_TICK(7)
                 __syncthreads();
                 // ---- P5: candidate += (r*h) part, blend, score; publish h_t ----
                 {
@@ -477,15 +473,15 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
                     __builtin_amdgcn_s_setprio(0);
                     publish_h(h, true, (unsigned)((t & 1) * n_tiles + tile) * (H * TM * 2));       // LDS images + exchange buffer, parity t & 1
                 }
-                TICKC(8)
+                IOC_TICK(8)
                 group_publish_wt(cnt);                       // includes the end-of-step __syncthreads
-                TICKC(9)
+                IOC_TICK(9)
             }
             // ---- score ----
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float v = sp[i];
-                v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8); v += __shfl_xor(v, 16);
+                v = ioc_sum32(v);
                 if (c31 == 0) red[cb * TM + arow + (i & 3) + 8 * (i >> 2)] = v;
             }
             __syncthreads();
@@ -524,18 +520,11 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4) ? IOC16CL_OCC : 1) v
 #endif
 }
 
-static size_t ioc16_cl_lds(const IocArgs& a, bool split) {
-    const int H = a.H, TM = 32, E = 16 + 32 + H, KX = E + H, B = a.G * a.G, NT = H / 32;
-    size_t b = (size_t)TM * (KX + 8) * 2 + (size_t)TM * (H + 8) * 2 + (size_t)H * (CLMAXM + 8) * 2;
-    b += (size_t)TM * (B + 1) * 16 + 16 * 8 + (size_t)CLMAXM * 2 * 4 + TM * 2 * 4 + 3 * 16 * 4 + (size_t)NT * TM * 4 + CLMAXM + 8 + CLMAXM * 8 + 64;
-    (void)split;                                           // the bin-split exchange lives inside the Ht tile
-    return b;
-}
 template <int H, bool SPLIT, int TPGT = 0>
 static int launch16_cl(const IocArgs& a, u16* hex16, hipStream_t s) {
     auto kern = k_ioc_bf16_cl<H, 16, 32, SPLIT, TPGT>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const size_t lds = ioc16_cl_lds(a, SPLIT);
+    const size_t lds = IocHtLds::bf16_cluster(H, 16, 32, a.G * a.G, CLMAXM).bytes();       // (the bin-split exchange lives inside the Ht tile)
     const int threads = (H / 32) * 64;
     int per_cu = 0, dev = 0;
     hipDeviceProp_t prop;

@@ -5,6 +5,7 @@
 // gradients written to HBM, and every weight gradient computed afterwards as one big A^T.G reduction over all
 // rows and steps (k_gemm_tn, slice partials + fixed-order reduce = deterministic).
 #include "common.h"
+#include "ioc_tile.h"
 #include "kernels.h"
 
 __device__ __forceinline__ f32x16 splat16b(float v) {
@@ -256,13 +257,13 @@ void launch_decoder_bwd(const DecBwdArgs& a, hipStream_t s) {
     const size_t lds = (2 * 32 * (H + 4) + 32 * (2 * H + 4) + 32 * 5 + 5 * H) * sizeof(float);
     const dim3 grid((a.R + 31) / 32);
     if (a.nw == 5) {                                      // the X encoder with the Gaussian head's per-step gradient (desire_set_head_loss)
-        if (H == 256) { allow_big_lds(k_decoder_bwd<256, 5>); hipLaunchKernelGGL((k_decoder_bwd<256, 5>), grid, dim3(512), lds, s, a); }
-        else if (H == 128) { allow_big_lds(k_decoder_bwd<128, 5>); hipLaunchKernelGGL((k_decoder_bwd<128, 5>), grid, dim3(256), lds, s, a); }
+        if (H == 256) { launch_big_lds<k_decoder_bwd<256, 5>>(grid, dim3(512), lds, s, a); }
+        else if (H == 128) { launch_big_lds<k_decoder_bwd<128, 5>>(grid, dim3(256), lds, s, a); }
         else hipLaunchKernelGGL((k_decoder_bwd<64, 5>), grid, dim3(128), lds, s, a);
         return;
     }
-    if (H == 256) { allow_big_lds(k_decoder_bwd<256>); hipLaunchKernelGGL(k_decoder_bwd<256>, grid, dim3(512), lds, s, a); }
-    else if (H == 128) { allow_big_lds(k_decoder_bwd<128>); hipLaunchKernelGGL(k_decoder_bwd<128>, grid, dim3(256), lds, s, a); }
+    if (H == 256) { launch_big_lds<k_decoder_bwd<256>>(grid, dim3(512), lds, s, a); }
+    else if (H == 128) { launch_big_lds<k_decoder_bwd<128>>(grid, dim3(256), lds, s, a); }
     else hipLaunchKernelGGL(k_decoder_bwd<64>, grid, dim3(128), lds, s, a);
 }
 
@@ -1191,6 +1192,11 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
     unsigned* occ = reinterpret_cast<unsigned*>(vld + TM);            // [2] bins that hold a neighbour anywhere in the tile
     unsigned* rowbits = occ + 2;                                      // CPB: [B] rows of the tile with a neighbour in bin b
     unsigned char* rowlist = reinterpret_cast<unsigned char*>(rowbits + 36);   // CPB: per wave 32 bytes, packed row -> tile row
+    constexpr IocBwdLds P0 = IocBwdLds::tile(H, TM, 0), P1 = IocBwdLds::tile(H, TM, 1);     // (ioc_lds.h: what the launcher sizes the LDS by)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == 4 * TM * LD1 * 4);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == 0 && P1.sz[P1.MASKS] == TM * (int)sizeof(mask_t) && P1.sz[P1.OBS] == P1.sz[P1.MASKS]);
+    IOC_LDS_TIED(P0.off(P0.ROWLIST) - P0.off(P0.PC) == (TM * 2 + TM + H) * 4 + TM + (2 + 36) * 4);
+    IOC_LDS_TIED(!(TM == 32 && H <= 128) || P0.sz[P0.ROWLIST] == NT * 32);
     // CPB (32-row tiles): dpool_b is only ever gathered from rows that HAVE a neighbour in bin b -- contract those rows only,
     // as 16-row v_mfma_f32_16x16x4_f32 tiles whose A rows are fetched through the row list (no packed copy needed)
     constexpr bool CPB = (TM == 32) && (H <= 128);
@@ -1422,8 +1428,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
 #pragma unroll
         for (int c = 0; c < NCH; ++c) nb[c] = make_float4(0.f, 0.f, 0.f, 0.f);
         // bins without a neighbour anywhere in the tile have dpool_b gathered by nobody: only their (zero) pooled rows are written
-        unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-        om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+        unsigned long long om = ioc_occ64(occ);
         int buf = 0;
         for (int b = 0; b < B; ++b) {
             const bool live = (om >> b) & 1ull;
@@ -1534,15 +1539,9 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
         }
     }
 }
-static size_t ioc_bwd_lds(const IocBwdArgs& a, int TM) {
-    const int H = a.H, LD1 = H + 4, B = a.G * a.G;
-    size_t f = (size_t)TM * LD1 * 4 + (size_t)TM * B * (TM == 32 ? 2 : 4) + TM * 2 + TM + H;
-    return f * sizeof(float) + TM + 64 + 512;               // + occupancy words, row bitmaps / row lists of the packed dpool
-}
 template <int H, int TM>
 static void launch_ioc_bwd_t(const IocBwdArgs& a, hipStream_t s) {
-    allow_big_lds(k_ioc_bwd<H, 16, 32, TM>);
-    hipLaunchKernelGGL((k_ioc_bwd<H, 16, 32, TM>), dim3((a.R + TM - 1) / TM), dim3((H / 32) * (TM / 32) * 64), ioc_bwd_lds(a, TM), s, a);
+    launch_big_lds<k_ioc_bwd<H, 16, 32, TM>>(dim3((a.R + TM - 1) / TM), dim3((H / 32) * (TM / 32) * 64), IocBwdLds::tile(H, TM, a.G * a.G).bytes(), s, a);
 }
 // groups of up to 32 agents: 32-row tiles; 64 agents per scene (H <= 128): one 64-row tile per group
 void launch_ioc_bwd(const IocBwdArgs& a, hipStream_t s) {
@@ -1551,8 +1550,8 @@ void launch_ioc_bwd(const IocBwdArgs& a, hipStream_t s) {
         return;
     }
     if (a.gpt > 0 && a.H <= 128) {                          // padded tiles (slot classes that do not divide 32)
-        if (a.H == 128) { allow_big_lds(k_ioc_bwd<128, 16, 32, 32, true>); hipLaunchKernelGGL((k_ioc_bwd<128, 16, 32, 32, true>), dim3((a.R + 31) / 32), dim3(256), ioc_bwd_lds(a, 32), s, a); }
-        else { allow_big_lds(k_ioc_bwd<64, 16, 32, 32, true>); hipLaunchKernelGGL((k_ioc_bwd<64, 16, 32, 32, true>), dim3((a.R + 31) / 32), dim3(128), ioc_bwd_lds(a, 32), s, a); }
+        if (a.H == 128) { launch_big_lds<k_ioc_bwd<128, 16, 32, 32, true>>(dim3((a.R + 31) / 32), dim3(256), IocBwdLds::tile(a.H, 32, a.G * a.G).bytes(), s, a); }
+        else { launch_big_lds<k_ioc_bwd<64, 16, 32, 32, true>>(dim3((a.R + 31) / 32), dim3(128), IocBwdLds::tile(a.H, 32, a.G * a.G).bytes(), s, a); }
         return;
     }
     if (a.H == 256) launch_ioc_bwd_t<256, 32>(a, s);

@@ -12,6 +12,7 @@
 // (k_ioc_bwd contracts first and gathers afterwards, which in a cluster would make every member contract every row).
 // Everything else (GRU cell backward, regression / score heads, streams for the weight-gradient GEMMs) is k_ioc_bwd's.
 #include "cluster.h"
+#include "ioc_tile.h"
 #include "kernels.h"
 
 #define BCLMAXM 128
@@ -40,6 +41,10 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_bwd_cl(IocBwdArgs a, i
     float* wsc = dsc + TM;                    // [H]
     unsigned char* vld = reinterpret_cast<unsigned char*>(wsc + H);   // [mno]
     unsigned* occ = reinterpret_cast<unsigned*>(vld + BCLMAXM);        // [2] bins in which one of my rows is observed
+    constexpr IocBwdLds P0 = IocBwdLds::cluster(H, 0, BCLMAXM), P1 = IocBwdLds::cluster(H, 1, BCLMAXM);     // (ioc_lds.h)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == (3 * TM * LD1 + BCLMAXM * LD1) * 4);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == 0 && P1.sz[P1.MASKS] == TM * 2 * 8 && P1.sz[P1.OBS] == TM * 2 * 8);
+    IOC_LDS_TIED(P0.off(P0.OCC) - P0.off(P0.PC) == (BCLMAXM * 2 + TM + H) * 4 + BCLMAXM);
     float* DR = A2;                           // [32][LDR] regression-head operand (prologue only)
 
     const int lane = lane_id(), cb = wave_id(), tid = threadIdx.x;
@@ -239,8 +244,7 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_bwd_cl(IocBwdArgs a, i
                 for (int c = 0; c < NCH; ++c) *reinterpret_cast<float4*>(ab + q8 * 4 + c * 4 * TPR) = s[c];
             };
             f32x16 nb = zero16();
-            unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-            om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+            unsigned long long om = ioc_occ64(occ);
             int buf = 0;
             if (om) build(__ffsll((long long)om) - 1, 0);
             __syncthreads();
@@ -260,16 +264,11 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_bwd_cl(IocBwdArgs a, i
     }
 }
 
-static size_t ioc_bwd_cl_lds(const IocBwdArgs& a) {
-    const int H = a.H, LD1 = H + 4, B = a.G * a.G, TM = 32;
-    size_t f = (size_t)TM * LD1 + 2 * TM * LD1 + (size_t)BCLMAXM * LD1 + BCLMAXM * 2 + TM + H;
-    return f * sizeof(float) + (size_t)4 * TM * B * 8 + BCLMAXM + 8 + 64;
-}
 template <int H>
 static int launch_t(const IocBwdArgs& a, int* grp_cnt, int* err, hipStream_t s) {
     auto kern = k_ioc_bwd_cl<H, 16, 32>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    const size_t lds = ioc_bwd_cl_lds(a);
+    const size_t lds = IocBwdLds::cluster(H, a.G * a.G, BCLMAXM).bytes();
     if (lds > 160 * 1024) return -1;
     const int tpg = a.mno / 32, n_tiles = a.R / 32;
     int grid = n_tiles < 256 ? n_tiles : 256;                // one workgroup per CU: all of them resident

@@ -14,6 +14,7 @@
 #include "common.h"
 #include "kernels.h"
 
+#include "ioc_tile.h"
 #include "split.h"
 #include <cstdio>
 
@@ -280,8 +281,7 @@ template <int WK, int WN, bool CONV, bool LISTS = false>
 void launch_t(const TnArgs& a, const ConvGather& cg, int nblocks, hipStream_t s) {
     constexpr int NP = 2;
     const size_t lds = (size_t)2 * NP * (WK + WN) * 64 * 32 * sizeof(u16);
-    allow_big_lds(k_gemm_tn2_xp<WK, WN, CONV, NP, LISTS>);
-    hipLaunchKernelGGL((k_gemm_tn2_xp<WK, WN, CONV, NP, LISTS>), dim3(nblocks, a.nslices), dim3(256), lds, s, a, cg);
+    launch_big_lds<k_gemm_tn2_xp<WK, WN, CONV, NP, LISTS>>(dim3(nblocks, a.nslices), dim3(256), lds, s, a, cg);
 #ifdef DESIRE_IOC_TIMING
     if (a.M > 1000000 && !CONV && !a.flags) {
         long long host[8];
@@ -416,8 +416,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_gather_x3(ConvArgs a) {
 template <int CI, int IW, int OW, int STRIDE, int PAD, int CO, int SPW>
 void launch_cg(const ConvArgs& a, hipStream_t s) {
     const size_t lds = (size_t)2 * (SPW * IW * IW + 1) * (CI + 8) * sizeof(u16);
-    allow_big_lds(k_conv_gather_x3<CI, IW, OW, STRIDE, PAD, CO, SPW>);
-    hipLaunchKernelGGL((k_conv_gather_x3<CI, IW, OW, STRIDE, PAD, CO, SPW>), dim3((a.n + SPW - 1) / SPW), dim3(256), lds, s, a);
+    launch_big_lds<k_conv_gather_x3<CI, IW, OW, STRIDE, PAD, CO, SPW>>(dim3((a.n + SPW - 1) / SPW), dim3(256), lds, s, a);
 }
 }  // namespace
 // a.Wp = the [hi | lo] pack ("vae_dec/deconv3/Wbwd16", "vae_dec/deconv2/Wbwd16")
@@ -450,11 +449,6 @@ __device__ __forceinline__ float f4e(const float4& v, int e) { return e == 0 ? v
 // gate / candidate contractions of the BPTT step: one k-group of pack fragments ahead (a deeper ring was measured in round 5 and was not faster:
 // docs/DESIGN_DETAIL.md section 13 item 3)
 #define BWDX3_MM(NB) mmax_groups<NB, 2, true>
-#ifdef DESIRE_IOC_TIMING
-#define TICKB(k) { const long long now_ = clock64(); tacc[k] += now_ - tprev; tprev = now_; }
-#else
-#define TICKB(k)
-#endif
 template <int H, int EV, int C, bool PAD = false>      // PAD: padded tiles (IocBwdArgs.gpt); a template parameter so that the packed form is unchanged
 __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
 #ifdef DESIRE_IOC_TIMING
@@ -483,6 +477,11 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
     unsigned char* vld = reinterpret_cast<unsigned char*>(wsc + H);   // [32]
     unsigned* occ = reinterpret_cast<unsigned*>(vld + TM);            // [2] bins that hold a neighbour anywhere in the tile
     uint2* lut = reinterpret_cast<uint2*>(occ + 2);                   // [16] nibble -> 4 bf16 (0.0 / 1.0): A fragments of the scatter MFMAs
+    constexpr IocBwdLds P0 = IocBwdLds::x3(H, 0), P1 = IocBwdLds::x3(H, 1);     // (ioc_lds.h: what the launcher sizes the LDS by)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == 3 * TM * LD1 * 4 + 2 * ILO1 * 2);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == 0 && P1.sz[P1.MASKS] == TM * 4 && P1.sz[P1.OBS] == TM * 4);
+    IOC_LDS_TIED(P0.off(P0.LUT) - P0.off(P0.PC) == (TM * 2 + TM + H) * 4 + TM + 8);
+    IOC_LDS_TIED(P0.sz[P0.LUT] == 16 * 8);
     float* DR = A2;                           // [32][LDR] regression-head operand (prologue only; 2T <= 2H assumed)
 
     const int lane = lane_id(), w = wave_id(), tid = threadIdx.x;
@@ -570,11 +569,7 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
     float* o_dac = a.dac + tb * H; float* o_rh = a.rh + tb * H; float* o_hp = a.hprev + tb * H; float* o_dag = a.dag + tb * 2 * H;
     float* o_dpr = a.dpre_r + tb * H; float* o_dpv = a.dpre_v + tb * EV;
 
-    if (tid < 16) {
-        const unsigned lo = ((tid & 1) ? 0x3F80u : 0u) | ((tid & 2) ? 0x3F800000u : 0u);
-        const unsigned hi2 = ((tid & 4) ? 0x3F80u : 0u) | ((tid & 8) ? 0x3F800000u : 0u);
-        lut[tid] = make_uint2(lo, hi2);
-    }
+    ioc_stage_lut(lut, tid);
     const int gb31 = (lr / a.mno) * a.mno;                 // first tile row of the group this lane's row belongs to (obs bits are slots of the group)
     for (int i = tid; i < H; i += NTHR) wsc[i] = a.w_score[i];
     if (tid < TM) {
@@ -613,9 +608,9 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
             const unsigned ix = rt * H + c0_s + 8 * q;
             pu[q] = *reinterpret_cast<const float4*>(svu + ix); pcx[q] = *reinterpret_cast<const float4*>(svc + ix); pr[q] = *reinterpret_cast<const float4*>(svr + ix);
         }
-        TICKB(0)
+        IOC_TICK(0)
         __syncthreads();
-        TICKB(1)
+        IOC_TICK(1)
         // ---- P0: positions, cleared masks, h_{t-1} tile ----
         if (tid < TM) {
             const int row = min(row0 + tid, a.R - 1);
@@ -641,9 +636,9 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
             }
         };
         load_hprev();                                    // read by part 1 and by the pooled rebuild of this step
-        TICKB(2)
+        IOC_TICK(2)
         __syncthreads();
-        TICKB(3)
+        IOC_TICK(3)
         // ---- P1: neighbour / observer masks ----
         {
             const float px = pc[r8 * 2], py = pc[r8 * 2 + 1];
@@ -693,9 +688,9 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
         flush32(I2, LDB2, ILO2, H, o_dag, 2 * H, H, t, nloc);
         flush32(I2, LDB2, ILO2, 0, o_rh, H, 0, t, nloc);
         cs_c += colsum16(sc_c); cs_u += colsum16(sc_u);
-        TICKB(4)
+        IOC_TICK(4)
         __syncthreads();
-        TICKB(5)
+        IOC_TICK(5)
         __builtin_amdgcn_s_setprio(3);          // (wave priority by phase, as in k_ioc: 3 / 2 / 1 for the candidate / gate / pooling contractions -- IOC backward 21.5 -> 21.2 ms)
         f32x16 dev = zero16(), der;
         {
@@ -728,9 +723,9 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
             cs_r += colsum16(sc_r);
         }
         __builtin_amdgcn_s_setprio(0);
-        TICKB(6)
+        IOC_TICK(6)
         __syncthreads();
-        TICKB(5)
+        IOC_TICK(5)
         // (h_{t-1} is still in its tile -- da_c went to the images, not over it as in the fp32 kernel -- so the pooled rebuild needs no reload);
         // da_c is consumed, its images take dpre_r
         __builtin_amdgcn_s_setprio(2);
@@ -769,9 +764,9 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
             cs_p += colsum16(sc_p);
         }
         __builtin_amdgcn_s_setprio(0);
-        TICKB(7)
+        IOC_TICK(7)
         __syncthreads();
-        TICKB(5)
+        IOC_TICK(5)
         // ---- social pooling backward ----
         // dh_j += sum_b sum_{i : j in bin b of i} dpool_b[i] = sum_b (M_b^T dpool_b)[j]: dpool_b comes out of its contraction UNtransposed (lane = hidden
         // column, registers = rows), which is the B-operand layout of a second MFMA whose A operand is the 0/1 observer matrix (exact in bf16, built from
@@ -779,8 +774,7 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
         // the bin loop runs barrier-free, every wave on its own column block.  (dpool_b enters as its two bf16 pieces, like every operand of this kernel.)
         f32x16 nbacc = zero16();
         // bins without a neighbour anywhere in the tile have dpool_b gathered by nobody: only their (zero) pooled rows are written
-        unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-        om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+        unsigned long long om = ioc_occ64(occ);
         for (int b = 0; b < B; ++b) {
             const bool live = (om >> b) & 1ull;
             {   // pooled_b[i] = sum_{j in bin b of i} h_{t-1}[j]  -> HBM (operand of the social-fc weight gradient)
@@ -804,13 +798,13 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
                     for (int c = 0; c < NCH; ++c) *reinterpret_cast<float4*>(dst + c * 4 * TPR) = s[c];
                 }
             }
-            TICKB(8)
+            IOC_TICK(8)
             if (!live) continue;
             __builtin_amdgcn_s_setprio(1);
             f32x16 dpl[1] = {zero16()};
             const unsigned ts[1] = {(unsigned)((b * NT + cb) * G16 * 64)};
             mmax_ring<1, 2, false, G16, G16>(dpl, a3_lane, ILO1, WsT, ts, (unsigned)PLS);
-            TICKB(9)
+            IOC_TICK(9)
             // accumulator elements 0..7 = rows 4 hi + {0..3, 8..11}, elements 8..15 = the same + 16: the k order of the two scatter MFMAs
             const FragP<2> p0 = split8<2>(dpl[0][0], dpl[0][1], dpl[0][2], dpl[0][3], dpl[0][4], dpl[0][5], dpl[0][6], dpl[0][7]);
             const FragP<2> p1 = split8<2>(dpl[0][8], dpl[0][9], dpl[0][10], dpl[0][11], dpl[0][12], dpl[0][13], dpl[0][14], dpl[0][15]);
@@ -819,17 +813,17 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
             const uint4 m0 = make_uint4(l0.x, l0.y, l1.x, l1.y), m1 = make_uint4(l2.x, l2.y, l3.x, l3.y);
             nbacc = mfma16(m0, p0.p[1], nbacc); nbacc = mfma16(m1, p1.p[1], nbacc);
             nbacc = mfma16(m0, p0.p[0], nbacc); nbacc = mfma16(m1, p1.p[0], nbacc);
-            TICKB(11)
+            IOC_TICK(11)
             __builtin_amdgcn_s_setprio(0);
         }
-        TICKB(10)
+        IOC_TICK(10)
         __syncthreads();                                   // every wave is done with h_{t-1} (pooled rebuilds): its tile takes the neighbour gradient
-        TICKB(5)
+        IOC_TICK(5)
 #pragma unroll
         for (int i = 0; i < 16; ++i) NB[(4 * hi_s + 8 * (i >> 2) + (i & 3)) * LD1 + cb * 32 + lr_s] = nbacc[i];
-        TICKB(11)
+        IOC_TICK(11)
         __syncthreads();
-        TICKB(5)
+        IOC_TICK(5)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float4 n4 = *reinterpret_cast<const float4*>(NB + lr_s * LD1 + c0_s + 8 * q);
@@ -863,16 +857,12 @@ __global__ __launch_bounds__((H / 32) * 64, 2) void k_ioc_bwd_x3(IocBwdArgs a) {
 
 template <int H>
 void launch_ioc_bwd_x3_t(const IocBwdArgs& a, hipStream_t s) {
-    const int B = a.G * a.G;
-    const size_t lds = (size_t)(32 * (H + 4) * 3) * sizeof(float) + (size_t)2 * 32 * (H + 8) * sizeof(u16) + (size_t)2 * 32 * B * sizeof(unsigned)
-                       + (size_t)(32 * 2 + 32 + H) * sizeof(float) + 32 + 64 + 16 * sizeof(uint2);
+    const size_t lds = IocBwdLds::x3(H, a.G * a.G).bytes();
     if (a.gpt > 0) {                                        // padded tiles
-        allow_big_lds(k_ioc_bwd_x3<H, 16, 32, true>);
-        hipLaunchKernelGGL((k_ioc_bwd_x3<H, 16, 32, true>), dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
+        launch_big_lds<k_ioc_bwd_x3<H, 16, 32, true>>(dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
         return;
     }
-    allow_big_lds(k_ioc_bwd_x3<H, 16, 32>);
-    hipLaunchKernelGGL((k_ioc_bwd_x3<H, 16, 32>), dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
+    launch_big_lds<k_ioc_bwd_x3<H, 16, 32>>(dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
 }
 }  // namespace
 // a.WcT_h / a.WgT_h / a.WsT = the [hi | lo] packs "ioc/WcT16" / "ioc/WgT16" / "ioc/WsT16"; a.WrT stays the fp32 pack (prologue)

@@ -133,8 +133,7 @@ void launch_conv2(const ConvArgs& a, hipStream_t s) {
 }
 void launch_conv3(const ConvArgs& a, hipStream_t s) {
     const size_t lds = (68 + 4 * 64 * 68) * sizeof(float);
-    allow_big_lds(k_conv_gather<64, 8, 4, 1, 0, 128>);
-    hipLaunchKernelGGL((k_conv_gather<64, 8, 4, 1, 0, 128>), dim3((a.n + 3) / 4), dim3(DS_WG), lds, s, a);
+    launch_big_lds<k_conv_gather<64, 8, 4, 1, 0, 128>>(dim3((a.n + 3) / 4), dim3(DS_WG), lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -243,10 +242,9 @@ __global__ __launch_bounds__(DS_WG) void k_deconv2(ConvArgs a) {
     }
 }
 void launch_deconv2(const ConvArgs& a, hipStream_t s) {
-    allow_big_lds(k_deconv2<true>); allow_big_lds(k_deconv2<false>);
     const int ng = dyn_units(a.n, a.dyn);                  // (device-side count: the grid follows the count hint, the kernel strides over what is left)
-    if (a.mode == 0) hipLaunchKernelGGL(k_deconv2<true>, dim3((ng + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a);
-    else hipLaunchKernelGGL(k_deconv2<false>, dim3((ng + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a);
+    if (a.mode == 0) launch_big_lds<k_deconv2<true>>(dim3((ng + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a);
+    else launch_big_lds<k_deconv2<false>>(dim3((ng + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -337,10 +335,9 @@ __global__ __launch_bounds__(NS * 64) void k_deconv3(ConvArgs a) {
 }
 void launch_deconv3(const ConvArgs& a, hipStream_t s) {
     const size_t lds = (128 + (size_t)4 * 64 * 68) * sizeof(float);
-    allow_big_lds(k_deconv3<true, 4>); allow_big_lds(k_deconv3<false, 4>);
     const int ng = dyn_units(a.n, a.dyn);
-    if (a.mode == 0) hipLaunchKernelGGL((k_deconv3<true, 4>), dim3((ng + 3) / 4), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((k_deconv3<false, 4>), dim3((ng + 3) / 4), dim3(256), lds, s, a);
+    if (a.mode == 0) launch_big_lds<k_deconv3<true, 4>>(dim3((ng + 3) / 4), dim3(256), lds, s, a);
+    else launch_big_lds<k_deconv3<false, 4>>(dim3((ng + 3) / 4), dim3(256), lds, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -76,15 +76,12 @@ static void launch_gemm_rows_n(const GemmArgs& a, int epi, hipStream_t s) {
     constexpr int TMR = 32 * MT;
     dim3 grid((a.M + TMR - 1) / TMR, (a.NT + 4 * NTW - 1) / (4 * NTW));
     const size_t lds = TMR * LDA_C * sizeof(float);
-    allow_big_lds(k_gemm_rows<EPI_BIAS, NTW, MT>); allow_big_lds(k_gemm_rows<EPI_BIAS_RELU, NTW, MT>);
-    allow_big_lds(k_gemm_rows<EPI_SCALE_SHIFT_ELU, NTW, MT>); allow_big_lds(k_gemm_rows<EPI_NONE, NTW, MT>);
-    allow_big_lds(k_gemm_rows<EPI_ELUGRAD, NTW, MT>); allow_big_lds(k_gemm_rows<EPI_SIGGRAD, NTW, MT>);
-    if (epi == EPI_NONE) hipLaunchKernelGGL((k_gemm_rows<EPI_NONE, NTW, MT>), grid, dim3(DS_WG), lds, s, a);
-    else if (epi == EPI_ELUGRAD) hipLaunchKernelGGL((k_gemm_rows<EPI_ELUGRAD, NTW, MT>), grid, dim3(DS_WG), lds, s, a);
-    else if (epi == EPI_SIGGRAD) hipLaunchKernelGGL((k_gemm_rows<EPI_SIGGRAD, NTW, MT>), grid, dim3(DS_WG), lds, s, a);
-    else if (epi == EPI_BIAS) hipLaunchKernelGGL((k_gemm_rows<EPI_BIAS, NTW, MT>), grid, dim3(DS_WG), lds, s, a);
-    else if (epi == EPI_BIAS_RELU) hipLaunchKernelGGL((k_gemm_rows<EPI_BIAS_RELU, NTW, MT>), grid, dim3(DS_WG), lds, s, a);
-    else hipLaunchKernelGGL((k_gemm_rows<EPI_SCALE_SHIFT_ELU, NTW, MT>), grid, dim3(DS_WG), lds, s, a);
+    if (epi == EPI_NONE) launch_big_lds<k_gemm_rows<EPI_NONE, NTW, MT>>(grid, dim3(DS_WG), lds, s, a);
+    else if (epi == EPI_ELUGRAD) launch_big_lds<k_gemm_rows<EPI_ELUGRAD, NTW, MT>>(grid, dim3(DS_WG), lds, s, a);
+    else if (epi == EPI_SIGGRAD) launch_big_lds<k_gemm_rows<EPI_SIGGRAD, NTW, MT>>(grid, dim3(DS_WG), lds, s, a);
+    else if (epi == EPI_BIAS) launch_big_lds<k_gemm_rows<EPI_BIAS, NTW, MT>>(grid, dim3(DS_WG), lds, s, a);
+    else if (epi == EPI_BIAS_RELU) launch_big_lds<k_gemm_rows<EPI_BIAS_RELU, NTW, MT>>(grid, dim3(DS_WG), lds, s, a);
+    else launch_big_lds<k_gemm_rows<EPI_SCALE_SHIFT_ELU, NTW, MT>>(grid, dim3(DS_WG), lds, s, a);
 }
 // A workgroup normally holds a 64-row A tile and each wave runs four column tiles over it.  With few row tiles (a handful of
 // windows per call) that leaves most CUs idle behind one long dependent MFMA chain, so small launches give every wave ONE
@@ -201,6 +198,5 @@ __global__ __launch_bounds__(DS_WG) void k_mask(MaskArgs a) {
 
 void launch_mask(const MaskArgs& a, hipStream_t s) {
     const size_t lds = DS_TM * LDA_C * sizeof(float);
-    allow_big_lds(k_mask);
-    hipLaunchKernelGGL(k_mask, dim3((a.R + DS_TM - 1) / DS_TM), dim3(DS_WG), lds, s, a);
+    launch_big_lds<k_mask>(dim3((a.R + DS_TM - 1) / DS_TM), dim3(DS_WG), lds, s, a);
 }

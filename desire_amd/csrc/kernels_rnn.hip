@@ -358,11 +358,9 @@ template <int H, int TM>
 static void launch_decoder_t(const DecArgs& a, hipStream_t s) {
     const size_t lds = (2 * TM * (H + 4) + 2 * H + TM * 2) * sizeof(float);
     if (a.sv_r || a.sv_c || a.hdump) {
-        allow_big_lds(k_decoder<H, TM, true>);
-        hipLaunchKernelGGL((k_decoder<H, TM, true>), dim3((a.R + TM - 1) / TM), dim3((H / 32) * (TM / 32) * 64), lds, s, a);
+        launch_big_lds<k_decoder<H, TM, true>>(dim3((a.R + TM - 1) / TM), dim3((H / 32) * (TM / 32) * 64), lds, s, a);
     } else {
-        allow_big_lds(k_decoder<H, TM, false>);
-        hipLaunchKernelGGL((k_decoder<H, TM, false>), dim3((a.R + TM - 1) / TM), dim3((H / 32) * (TM / 32) * 64), lds, s, a);
+        launch_big_lds<k_decoder<H, TM, false>>(dim3((a.R + TM - 1) / TM), dim3((H / 32) * (TM / 32) * 64), lds, s, a);
     }
 }
 void launch_decoder(const DecArgs& a, hipStream_t s) {
@@ -390,16 +388,12 @@ void launch_decoder(const DecArgs& a, hipStream_t s) {
 // neighbour bit-masks: 32 bits are enough when the tile holds 32 rows (mno <= 32), which keeps a 36-bin tile under half
 // the LDS of a CU (two workgroups per CU); 64-row tiles use 64 bits
 #include "cluster.h"
+#include "ioc_tile.h"
 #include "split.h"
 template <int TM> struct MaskT { typedef unsigned long long type; };
 template <> struct MaskT<32> { typedef unsigned type; };
 __device__ __forceinline__ int ffs_(unsigned m) { return __ffs((int)m); }
 __device__ __forceinline__ int ffs_(unsigned long long m) { return __ffsll((long long)m); }
-#ifdef DESIRE_IOC_TIMING
-#define TICK(k) { const long long now_ = clock64(); tacc[k] += now_ - tprev; tprev = now_; }
-#else
-#define TICK(k)
-#endif
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 // CP ("compact pooling", opt-in: DESIRE_IOC_VARIANT=8, TM = 32): only the rows that have a neighbour in bin b are built,
 // packed into the first rows of the operand tile, contracted as 16-row v_mfma_f32_16x16x4_f32 tiles and added into the rows
@@ -437,6 +431,11 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
     unsigned* occ = reinterpret_cast<unsigned*>(vld + TM);                 // [2] bins that hold a neighbour anywhere in the tile
     unsigned* rowbits = occ + 2;                                           // CP: [B] rows of the tile with a neighbour in bin b
     unsigned* rowlist = rowbits + 36;                                      // CP: [2][TM/4] packed u8: tile row of operand row s
+    constexpr IocLds P0 = IocLds::tile(H, EV, C, TM, 0), P1 = IocLds::tile(H, EV, C, TM, 1);     // (ioc_lds.h: what the launcher sizes the LDS by)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == ((TM + 1) * LDX + 2 * TM * LDB) * 4);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == 0 && P1.sz[P1.MASKS] == TM * (int)sizeof(mask_t));
+    IOC_LDS_TIED(P0.off(P0.ROWLIST) - P0.off(P0.PC) == (TM * 2 * 2 + 3 * EV + NT * TM) * 4 + TM + (2 + 36) * 4);
+    IOC_LDS_TIED(P0.sz[P0.ROWLIST] == 2 * (TM / 4) * 4);
 
     const int lane = lane_id(), w = wave_id(), tid = threadIdx.x;
     const int cb = w % NT, mt = w / NT;
@@ -458,7 +457,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
     const int my_slot = r8 - grp_base;
     const int n_nb = dead_row ? 0 : a.mno;              // slots my row looks for neighbours in
 
-    for (int i = tid; i < 3 * EV; i += NTHR) wv[i] = (i < 2 * EV) ? a.w_vel[i] : a.b_vel[i - 2 * EV];
+    ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);
     for (int i = tid; i < LDX; i += NTHR) XH[TM * LDX + i] = 0.f;
     if (tid < TM) { const int ag = ioc_agent_of_row(min(row0 + tid, a.R - 1), a.K, a.mno, gpt, a.ngrp); vld[tid] = ag >= 0 ? a.valid[ag] : 0; }
 
@@ -546,7 +545,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
         constexpr int GX = E >> 3;                                                        // x-part groups
 
         for (int t = 0; t < a.T; ++t) {
-            TICK(0)
+            IOC_TICK(0)
             // prefetch next step's positions (consumed at the end of this step)
             if (tid < TM && t + 1 < a.T)
                 ynext = *reinterpret_cast<const float2*>(a.Y + ((size_t)min(row0 + tid, a.R - 1) * a.T + t + 1) * 2);
@@ -584,11 +583,10 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
                 }
             }
             __syncthreads();
-            TICK(1)
+            IOC_TICK(1)
             // ---- P2/P3 (compact form) ----
             if constexpr (CP) {
-                unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-                om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+                unsigned long long om = ioc_occ64(occ);
                 constexpr int T16 = H / 16;                          // 16-column tiles per row / 16-k groups per contraction
                 // operand row s of bin b = the s-th tile row that has a neighbour there (ascending rows)
                 auto build_c = [&](int b, int buf) {
@@ -684,13 +682,12 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
             //      the same two barriers, so waves that finish building early start their MFMAs while others build
             {
                 f32x16 soc = zero16();          // biases join after the contraction (a splat start value would pin 16 registers)
-                unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-                om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+                unsigned long long om = ioc_occ64(occ);
                 if (NSPL > 1) om &= my_bins;
                 int buf = 0;
                 if (om) build(ffs_(om) - 1, 0);
                 __syncthreads();
-                TICK(2)
+                IOC_TICK(2)
                 // wave priority by phase (round 6): two workgroups per CU = two waves per SIMD; a wave inside its bin loop (3) or its gate / candidate
                 // contraction (2) wins the issue arbitration against one that builds operands or sits in the position phase (0).  Same-box ABAB on the
                 // headline: k_ioc 78.77 - 79.10 ms without, 78.55 - 78.65 with (the reverse order, 1 / 3: 79.1 - 79.25).  Where it pays properly is the
@@ -703,16 +700,16 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
                     MmaHead hd;
                     if (active) mma_begin(hd, wb, GH);             // this bin's first weight fragments travel while the next operand is built
                     if (om) build(ffs_(om) - 1, buf ^ 1);
-                    TICK(3)
+                    IOC_TICK(3)
                     if (active) {
                         f32x16 t1[1] = {soc};
                         const float* ap1[1] = {AB + buf * TM * LDB + (mt * 32 + (lane & 31)) * LDB + 4 * (lane >> 5)};
                         mma_run<1>(t1, ap1, wb, GH, hd);
                         soc = t1[0];
                     }
-                    TICK(4)
+                    IOC_TICK(4)
                     __syncthreads();
-                    TICK(5)
+                    IOC_TICK(5)
                     buf ^= 1;
                 }
                 __builtin_amdgcn_s_setprio(0);
@@ -748,7 +745,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
                 }
             }
             __syncthreads();
-            TICK(6)
+            IOC_TICK(6)
             if (TRAIN) {                                                 // keep x_t = [e_v | e_s | e_r] for the weight gradients
                 for (int i = tid; i < TM * (E >> 2); i += NTHR) {
                     const int r = i / (E >> 2), c4 = i - r * (E >> 2);
@@ -779,7 +776,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
                 }
             }
             __syncthreads();
-            TICK(7)
+            IOC_TICK(7)
             // ---- P5: candidate over [x | r*h], blend, score ----
             if (active) {
                 f32x16 ac = zero16();
@@ -806,14 +803,13 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
             if (tid < 2) occ[tid] = 0;
             if (CP && tid < B) rowbits[tid] = 0;
             __syncthreads();
-            TICK(8)
+            IOC_TICK(8)
         }
         // ---- score: sum the per-lane partials over the 32 columns of this wave, then over column blocks ----
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             float v = active ? sp[i] : 0.f;
-            v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 8); v += __shfl_xor(v, 16);
+            v = ioc_sum32(v);
             if ((lane & 31) == 0) red[cb * TM + mt * 32 + acc_row(i)] = v;
         }
         __syncthreads();
@@ -851,39 +847,31 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
         for (int k = 0; k < 10; ++k) a.dbg[k] = tacc[k];
 #endif
 }
-static size_t ioc_lds_bytes(const IocArgs& a, int TM) {
-    const int EV = 16, H = a.H, NT = H / 32, E = EV + 32 + H, LDX = E + H + 4, LDB = H + 4, B = a.G * a.G;
-    size_t f = (size_t)(TM + 1) * LDX + 2 * TM * LDB + (size_t)TM * B * (TM == 32 ? 1 : 2) + TM * 4 + 3 * EV + NT * TM;
-    return f * sizeof(float) + TM + 64 + 256;              // + occupancy words, CP row bitmaps / row lists
-}
 template <int H, int TM>
 static void launch_ioc_t(const IocArgs& a, hipStream_t s) {
     const dim3 grid((a.R + TM - 1) / TM), block((H / 32) * (TM / 32) * 64);
+    const size_t lds = IocLds::tile(H, 16, 32, TM, a.G * a.G).bytes();
     if (a.sv_h) {                                              // training-mode forward: keeps x_t, r, u, c, h per step
         if constexpr (TM == 32 && H <= 128) {
             if (a.gpt > 0) {                                   // padded tiles (slot classes that do not divide 32): the row-compacted pooling form
-                allow_big_lds(k_ioc<H, 16, 32, 32, true, true, 1, true>);
-                hipLaunchKernelGGL((k_ioc<H, 16, 32, 32, true, true, 1, true>), grid, block, ioc_lds_bytes(a, TM), s, a);
+                launch_big_lds<k_ioc<H, 16, 32, 32, true, true, 1, true>>(grid, block, lds, s, a);
                 return;
             }
         }
         if constexpr (TM == 32 && H <= 128) {                  // 32-row tiles: the row-compacted pooling (k_ioc CP) also while training
             if (a.variant != 9) {                              // (DESIRE_IOC_TRAIN_DENSE: dense pooling, A/B)
-                allow_big_lds(k_ioc<H, 16, 32, 32, true, true>);
-                hipLaunchKernelGGL((k_ioc<H, 16, 32, 32, true, true>), grid, block, ioc_lds_bytes(a, TM), s, a);
+                launch_big_lds<k_ioc<H, 16, 32, 32, true, true>>(grid, block, lds, s, a);
                 return;
             }
         }
         if constexpr (H <= 128 || TM == 32) {
-            allow_big_lds(k_ioc<H, 16, 32, TM, true>);
-            hipLaunchKernelGGL((k_ioc<H, 16, 32, TM, true>), grid, block, ioc_lds_bytes(a, TM), s, a);
+            launch_big_lds<k_ioc<H, 16, 32, TM, true>>(grid, block, lds, s, a);
         }
         return;
     }
     if constexpr (TM == 32 && H <= 128) {
         if (a.variant == 8) {                                  // opt-in (DESIRE_IOC_COMPACT): row-compacted pooling (see k_ioc)
-            allow_big_lds(k_ioc<H, 16, 32, 32, false, true>);
-            hipLaunchKernelGGL((k_ioc<H, 16, 32, 32, false, true>), grid, block, ioc_lds_bytes(a, TM), s, a);
+            launch_big_lds<k_ioc<H, 16, 32, 32, false, true>>(grid, block, lds, s, a);
             return;
         }
     }
@@ -891,21 +879,24 @@ static void launch_ioc_t(const IocArgs& a, hipStream_t s) {
         if (a.nspl > 1) {                                      // few tiles: the social bins of a tile split over nspl workgroups (see k_ioc)
             const dim3 gs(grid.x * a.nspl);
             switch (a.nspl) {
-                case 3: allow_big_lds(k_ioc<H, 16, 32, 32, false, false, 3>); hipLaunchKernelGGL((k_ioc<H, 16, 32, 32, false, false, 3>), gs, block, ioc_lds_bytes(a, TM), s, a); return;
-                case 4: allow_big_lds(k_ioc<H, 16, 32, 32, false, false, 4>); hipLaunchKernelGGL((k_ioc<H, 16, 32, 32, false, false, 4>), gs, block, ioc_lds_bytes(a, TM), s, a); return;
-                default: allow_big_lds(k_ioc<H, 16, 32, 32, false, false, 2>); hipLaunchKernelGGL((k_ioc<H, 16, 32, 32, false, false, 2>), gs, block, ioc_lds_bytes(a, TM), s, a); return;
+                case 3: launch_big_lds<k_ioc<H, 16, 32, 32, false, false, 3>>(gs, block, lds, s, a); return;
+                case 4: launch_big_lds<k_ioc<H, 16, 32, 32, false, false, 4>>(gs, block, lds, s, a); return;
+                default: launch_big_lds<k_ioc<H, 16, 32, 32, false, false, 2>>(gs, block, lds, s, a); return;
             }
         }
     }
     if constexpr (TM == 32 && H <= 128) {
         if (a.gpt > 0) {                                       // padded tiles (slot classes that do not divide 32)
-            allow_big_lds(k_ioc<H, 16, 32, 32, false, false, 1, true>);
-            hipLaunchKernelGGL((k_ioc<H, 16, 32, 32, false, false, 1, true>), grid, block, ioc_lds_bytes(a, TM), s, a);
+            launch_big_lds<k_ioc<H, 16, 32, 32, false, false, 1, true>>(grid, block, lds, s, a);
             return;
         }
     }
-    allow_big_lds(k_ioc<H, 16, 32, TM, false>);
-    hipLaunchKernelGGL((k_ioc<H, 16, 32, TM, false>), grid, block, ioc_lds_bytes(a, TM), s, a);
+    launch_big_lds<k_ioc<H, 16, 32, TM, false>>(grid, block, lds, s, a);
+}
+template <int H>
+static const void* bin_split_kernel(int n) {
+    return n == 2 ? big_lds_kernel<k_ioc<H, 16, 32, 32, false, false, 2>>() : n == 3 ? big_lds_kernel<k_ioc<H, 16, 32, 32, false, false, 3>>()
+                                                                                     : big_lds_kernel<k_ioc<H, 16, 32, 32, false, false, 4>>();
 }
 // Workgroups of the bin-split k_ioc<H, ..., NSPL = n> this device keeps resident at once (occupancy x compute units); 0 when the shape has
 // no such form or the query fails.  The members of a tile wait for each other inside the kernel, so a launch is only safe when ALL of
@@ -915,14 +906,11 @@ int ioc_bin_split_capacity(const IocArgs& a, int n) {
     static std::map<std::tuple<int, int, int, size_t>, int> cache;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
-    const size_t lds = ioc_lds_bytes(a, 32);
+    const size_t lds = IocLds::tile(a.H, 16, 32, 32, a.G * a.G).bytes();
     const auto key = std::make_tuple(dev, a.H, n, lds);
     auto it = cache.find(key);
     if (it != cache.end()) return it->second;
-    const void* kern = nullptr;
-    if (a.H == 128) kern = n == 2 ? (const void*)k_ioc<128, 16, 32, 32, false, false, 2> : n == 3 ? (const void*)k_ioc<128, 16, 32, 32, false, false, 3> : (const void*)k_ioc<128, 16, 32, 32, false, false, 4>;
-    else kern = n == 2 ? (const void*)k_ioc<64, 16, 32, 32, false, false, 2> : n == 3 ? (const void*)k_ioc<64, 16, 32, 32, false, false, 3> : (const void*)k_ioc<64, 16, 32, 32, false, false, 4>;
-    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    const void* kern = a.H == 128 ? bin_split_kernel<128>(n) : bin_split_kernel<64>(n);
     int per_cu = 0, cus = 0;
     int cap = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (a.H / 32) * 64, lds) == hipSuccess && per_cu > 0 &&
@@ -968,6 +956,10 @@ __global__ __launch_bounds__((H / 32) * 64, (H / 32) <= 4 ? 1 : 2) void k_ioc_cl
     float* red = wv + 3 * EV;                           // [NT][TM]
     unsigned char* vld = reinterpret_cast<unsigned char*>(red + NT * TM);  // [MAXM]
     unsigned* occ = reinterpret_cast<unsigned*>(vld + MAXM);               // [2] bins that hold a neighbour anywhere in the tile
+    constexpr IocLds P0 = IocLds::cluster(H, EV, C, 0, MAXM), P1 = IocLds::cluster(H, EV, C, 1, MAXM);     // (ioc_lds.h)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == (TM * LDX + 2 * TM * LDB) * 4);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == 0 && P1.sz[P1.MASKS] == TM * 2 * 8);
+    IOC_LDS_TIED(P0.off(P0.OCC) - P0.off(P0.PC) == (MAXM * 2 + TM * 2 + 3 * EV + NT * TM) * 4 + MAXM);
 
     const int lane = lane_id(), w = wave_id(), tid = threadIdx.x;
     const int cb = w;
@@ -977,7 +969,7 @@ __global__ __launch_bounds__((H / 32) * 64, (H / 32) <= 4 ? 1 : 2) void k_ioc_cl
     IOC_DYN(a)                                          // (a slot class counted on the device: kernels.h DynCount; the persistent grid is the worst case's)
     const int n_tiles = a.R / TM;
 
-    for (int i = tid; i < 3 * EV; i += NTHR) wv[i] = (i < 2 * EV) ? a.w_vel[i] : a.b_vel[i - 2 * EV];
+    ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);
     const float bgr = a.b_g[col], bgu = a.b_g[H + col], bcc = a.b_c[col], bso = a.b_soc[col], wsc = a.w_score[col];
     const float* x_lane = XH + (lane & 31) * LDX + 4 * (lane >> 5);
     float* my_x = XH + (4 * (lane >> 5)) * LDX + col;
@@ -1085,8 +1077,7 @@ __global__ __launch_bounds__((H / 32) * 64, (H / 32) <= 4 ? 1 : 2) void k_ioc_cl
                     for (int c = 0; c < NCH; ++c) *reinterpret_cast<float4*>(ab + q8 * 4 + c * 4 * TPR) = s[c];
                 };
                 f32x16 soc = zero16();          // biases join after the contraction (a splat start value would pin 16 registers)
-                unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-                om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+                unsigned long long om = ioc_occ64(occ);
                 int buf = 0;
                 if (om) build(ffs_(om) - 1, 0);
                 __syncthreads();
@@ -1161,8 +1152,7 @@ __global__ __launch_bounds__((H / 32) * 64, (H / 32) <= 4 ? 1 : 2) void k_ioc_cl
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float v = sp[i];
-                v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
-                v += __shfl_xor(v, 8); v += __shfl_xor(v, 16);
+                v = ioc_sum32(v);
                 if ((lane & 31) == 0) red[cb * TM + acc_row(i)] = v;
             }
             __syncthreads();
@@ -1194,19 +1184,14 @@ __global__ __launch_bounds__((H / 32) * 64, (H / 32) <= 4 ? 1 : 2) void k_ioc_cl
         (void)epoch;
     }
 }
-static size_t ioc_cl_lds_bytes(const IocArgs& a) {
-    const int EV = 16, H = a.H, NT = H / 32, E = EV + 32 + H, LDX = E + H + 4, LDB = H + 4, B = a.G * a.G, TM = 32;
-    size_t f = (size_t)TM * LDX + 2 * TM * LDB + (size_t)TM * B * 4 + 128 * 2 + TM * 2 + 3 * EV + NT * TM;
-    return f * sizeof(float) + 128 + 64;
-}
 template <int H>
 static void launch_ioc_cl_t(const IocArgs& a, hipStream_t s) {
-    allow_big_lds(k_ioc_cl<H, 16, 32>);
+    const size_t lds = IocLds::cluster(H, 16, 32, a.G * a.G).bytes();
     const int tpg = a.mno / 32, n_tiles = a.R / 32;
     int grid = n_tiles < 256 ? n_tiles : 256;            // one workgroup per CU: all of them resident
     grid -= grid % tpg;
-    if (a.sv_h) hipLaunchKernelGGL((k_ioc_cl<H, 16, 32, true>), dim3(grid), dim3((H / 32) * 64), ioc_cl_lds_bytes(a), s, a);
-    else hipLaunchKernelGGL((k_ioc_cl<H, 16, 32>), dim3(grid), dim3((H / 32) * 64), ioc_cl_lds_bytes(a), s, a);
+    if (a.sv_h) launch_big_lds<k_ioc_cl<H, 16, 32, true>>(dim3(grid), dim3((H / 32) * 64), lds, s, a);
+    else launch_big_lds<k_ioc_cl<H, 16, 32>>(dim3(grid), dim3((H / 32) * 64), lds, s, a);
 }
 void launch_ioc_cluster(const IocArgs& a, hipStream_t s) {
     if (a.H == 256) launch_ioc_cl_t<256>(a, s);
@@ -1259,13 +1244,17 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4 || NP != 0) ? 1 : 2) 
     float* wv = reinterpret_cast<float*>(masks + TM * B * MW);    // [3][EV]
     float* red = wv + 3 * EV;                           // [NT][TM]
     unsigned* occ = reinterpret_cast<unsigned*>(red + NT * TM);   // [2] bins that hold a neighbour anywhere in the tile
+    constexpr IocLds P0 = IocLds::step(H, EV, C, 0, 1), P1 = IocLds::step(H, EV, C, 1, 1), P2 = IocLds::step(H, EV, C, 1, 2);     // (ioc_lds.h)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == (TM * LDX + 2 * TM * LDB) * 4);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == 0 && P1.sz[P1.MASKS] == TM * 8 && P2.sz[P2.MASKS] == TM * 2 * 8);
+    IOC_LDS_TIED(P0.off(P0.OCC) - P0.off(P0.WV) == (3 * EV + NT * TM) * 4);
     const int lane = lane_id(), cb = wave_id(), tid = threadIdx.x;
     const int col = cb * 32 + (lane & 31);
     const int r8 = tid / TPR, q8 = tid % TPR;
     const int row0 = blockIdx.x * TM;
     const int mall = a.m_loc * a.nranks;
     const int n_groups = a.R / a.m_loc;
-    for (int i = tid; i < 3 * EV; i += NTHR) wv[i] = (i < 2 * EV) ? a.w_vel[i] : a.b_vel[i - 2 * EV];
+    ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);
     for (int i = tid; i < TM * B * MW; i += NTHR) masks[i] = 0ull;
     if (tid < 2) occ[tid] = 0;
     for (int i = tid; i < TM * (H >> 2); i += NTHR) {
@@ -1374,8 +1363,7 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4 || NP != 0) ? 1 : 2) 
         for (int c = 0; c < NCH; ++c) *reinterpret_cast<float4*>(ab + q8 * 4 + c * 4 * TPR) = s[c];
     };
     f32x16 soc = zero16();          // biases join after the contraction (a splat start value would pin 16 registers)
-    unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-    om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+    unsigned long long om = ioc_occ64(occ);
     int buf = 0;
     if (om) build(ffs_(om) - 1, 0);
     __syncthreads();
@@ -1441,7 +1429,7 @@ __global__ __launch_bounds__((H / 32) * 64, ((H / 32) <= 4 || NP != 0) ? 1 : 2) 
             if (a.st_h_copy) a.st_h_copy[(size_t)row * H + col] = h[i];      // peer form, last step: h_T for the regression head, in ordinary memory
         }
         float v = h[i] * wsc;
-        v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8); v += __shfl_xor(v, 16);
+        v = ioc_sum32(v);
         if ((lane & 31) == 0) red[cb * TM + acc_row(i)] = v;
     }
     __syncthreads();
@@ -1489,6 +1477,10 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_step_x2(IocStepArgs a)
     float* wv = reinterpret_cast<float*>(masks + TM * B * MW);          // [3][EV]
     float* red = wv + 3 * EV;                                           // [NT][TM]
     unsigned* occ = reinterpret_cast<unsigned*>(red + NT * TM);
+    constexpr IocLds P0 = IocLds::step_x2(H, EV, C, 0, 1), P1 = IocLds::step_x2(H, EV, C, 1, 1), P2 = IocLds::step_x2(H, EV, C, 1, 2);     // (ioc_lds.h)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == (NP * XLO + 2 * NP * BLO) * 2);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == 0 && P1.sz[P1.MASKS] == TM * 8 && P2.sz[P2.MASKS] == TM * 2 * 8);
+    IOC_LDS_TIED(P0.off(P0.OCC) - P0.off(P0.WV) == (3 * EV + NT * TM) * 4);
     const int lane = lane_id(), cb = wave_id(), tid = threadIdx.x;
     const int col = cb * 32 + (lane & 31);
     const int r8 = tid / TPR, q8 = tid % TPR;
@@ -1505,7 +1497,7 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_step_x2(IocStepArgs a)
         splitp<2>(v0, v1, pp);
         *reinterpret_cast<unsigned*>(img) = pp[0]; *reinterpret_cast<unsigned*>(img + plo) = pp[1];
     };
-    for (int i = tid; i < 3 * EV; i += NTHR) wv[i] = (i < 2 * EV) ? a.w_vel[i] : a.b_vel[i - 2 * EV];
+    ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);
     for (int i = tid; i < TM * B * MW; i += NTHR) masks[i] = 0ull;
     if (tid < 2) occ[tid] = 0;
     for (int i = tid; i < TM * (H >> 2); i += NTHR) {
@@ -1622,8 +1614,7 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_step_x2(IocStepArgs a)
         }
     };
     f32x16 soc = zero16();
-    unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-    om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+    unsigned long long om = ioc_occ64(occ);
     int buf = 0;
     if (om) build(ffs_(om) - 1, 0);
     __syncthreads();
@@ -1702,7 +1693,7 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_step_x2(IocStepArgs a)
             if (a.st_h_copy) a.st_h_copy[(size_t)row * H + col] = h[i];
         }
         float v = h[i] * wsc;
-        v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8); v += __shfl_xor(v, 16);
+        v = ioc_sum32(v);
         if ((lane & 31) == 0) red[cb * TM + acc_row(i)] = v;
     }
     }
@@ -1720,23 +1711,13 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_step_x2(IocStepArgs a)
         a.st_score[row0 + tid] = (a.t == 0 ? 0.f : a.st_score[row0 + tid]) + sc;
     }
 }
-static size_t ioc_step_x2_lds(const IocStepArgs& a) {
-    const int EV = 16, H = a.H, NT = H / 32, E = EV + 32 + H, KX = E + H, B = a.G * a.G, TM = 32;
-    const int MW = (a.m_loc * a.nranks + 63) >> 6;
-    return (size_t)2 * TM * (KX + 8) * 2 + (size_t)2 * 2 * TM * (H + 8) * 2 + (size_t)TM * B * MW * 8 + (3 * EV + NT * TM) * sizeof(float) + 64;
-}
-static size_t ioc_step_lds(const IocStepArgs& a) {
-    const int EV = 16, H = a.H, NT = H / 32, E = EV + 32 + H, LDX = E + H + 4, LDB = H + 4, B = a.G * a.G, TM = 32;
-    const int MW = (a.m_loc * a.nranks + 63) >> 6;
-    return ((size_t)TM * LDX + 2 * TM * LDB + (size_t)TM * B * MW * 2 + 3 * EV + NT * TM) * sizeof(float) + 64;
-}
 void launch_ioc_step(const IocStepArgs& a, hipStream_t s) {
     const dim3 grid((a.R + 31) / 32), block((a.H / 32) * 64);
-    const size_t lds = ioc_step_lds(a);
-#define STEP_LAUNCH(HH, NPP) { allow_big_lds(k_ioc_step<HH, 16, 32, NPP>); hipLaunchKernelGGL((k_ioc_step<HH, 16, 32, NPP>), grid, block, lds, s, a); }
+    const int B = a.G * a.G, MW = (a.m_loc * a.nranks + 63) >> 6;
+    const size_t lds = (a.np == 2 ? IocLds::step_x2(a.H, 16, 32, B, MW) : IocLds::step(a.H, 16, 32, B, MW)).bytes();
+#define STEP_LAUNCH(HH, NPP) launch_big_lds<k_ioc_step<HH, 16, 32, NPP>>(grid, block, lds, s, a);
     if (a.np == 2) {                 // two-piece operands: the piece-image form (the fp32-tile form of round 4, k_ioc_step<.., 2>, measured slower and is gone)
-        const size_t l2 = ioc_step_x2_lds(a);
-#define STEP2_LAUNCH(HH) { allow_big_lds(k_ioc_step_x2<HH, 16, 32>); hipLaunchKernelGGL((k_ioc_step_x2<HH, 16, 32>), grid, block, l2, s, a); }
+#define STEP2_LAUNCH(HH) launch_big_lds<k_ioc_step_x2<HH, 16, 32>>(grid, block, lds, s, a);
         if (a.H == 256) STEP2_LAUNCH(256) else if (a.H == 128) STEP2_LAUNCH(128) else STEP2_LAUNCH(64)
 #undef STEP2_LAUNCH
         return;

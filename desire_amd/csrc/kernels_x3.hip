@@ -15,17 +15,13 @@
 #include "kernels.h"
 
 #include "bf16.h"
+#include "ioc_tile.h"
 #include "split.h"
 
 // ------------------------------------------------------------------------------------------------------------------
 // IOC scoring / refinement with split operands.  Tile = 32 rows = whole (scene,k) groups (mno divides 32), H in {64, 128}.
 // Weight pointers of IocArgs point at the [hi | lo] bf16 packs.
 // ------------------------------------------------------------------------------------------------------------------
-#ifdef DESIRE_IOC_TIMING
-#define TICKX(k) { const long long now_ = clock64(); tacc[k] += now_ - tprev; tprev = now_; }
-#else
-#define TICKX(k)
-#endif
 // NP = bf16 pieces per fp32 operand: 2 (dims.bf16 = 2, three products per fp32 product, two workgroups per CU) or 3 (dims.bf16 = 3,
 // six products, fp32-class accuracy; three operand images = 120 KB of LDS, one workgroup per CU with the whole register file).
 // PAD: padded tiles (IocArgs.gpt: slot classes that do not divide 32), a template parameter so that the packed-row instantiations stay as they were
@@ -55,6 +51,10 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
     float* red = wv + 3 * EV;                                         // [NT][TM]
     unsigned char* vld = reinterpret_cast<unsigned char*>(red + NT * TM);   // [TM]
     unsigned* occ = reinterpret_cast<unsigned*>(vld + TM);                  // [2] bins that hold a neighbour anywhere in the tile
+    constexpr IocHtLds P0 = IocHtLds::x3(H, EV, C, NP, 0), P1 = IocHtLds::x3(H, EV, C, NP, 1);     // (ioc_lds.h: what the launcher sizes the LDS by)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == NP * (XLO + RLO + TLO) * 2);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == ((TM + 1) & ~1) * 4 && P1.sz[P1.MASKS] == ((TM * 2 + 1) & ~1) * 4);
+    IOC_LDS_TIED(P0.off(P0.OCC) - P0.off(P0.LUT) == 16 * 8 + (TM * 2 * 2 + 3 * EV + NT * TM) * 4 + TM);
     float* EX0 = reinterpret_cast<float*>(Ht);                              // exchange set 0: inside the h^T tile (dead after the pooling)
     float* EX1 = reinterpret_cast<float*>(RHb);                             // set 1: inside the r*h tile (idle until the gates)
 
@@ -74,12 +74,8 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
     const int my_slot = r8 - grp_base;
     const int n_nb = dead_row ? 0 : a.mno;
 
-    for (int i = tid; i < 3 * EV; i += NTHR) wv[i] = (i < 2 * EV) ? a.w_vel[i] : a.b_vel[i - 2 * EV];
-    if (tid < 16) {
-        const unsigned lo = ((tid & 1) ? 0x3F80u : 0u) | ((tid & 2) ? 0x3F800000u : 0u);
-        const unsigned hi2 = ((tid & 4) ? 0x3F80u : 0u) | ((tid & 8) ? 0x3F800000u : 0u);
-        lut[tid] = make_uint2(lo, hi2);
-    }
+    ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);
+    ioc_stage_lut(lut, tid);
     if (tid < TM) { const int ag = ioc_agent_of_row(min(row0 + tid, a.R - 1), a.K, a.mno, gpt, a.ngrp); vld[tid] = ag >= 0 ? a.valid[ag] : 0; }
     const float bgr = a.b_g[col], bgu = a.b_g[H + col], bcc = a.b_c[col], bso = a.b_soc[col], wsc = a.w_score[col];
     const float* grid = a.grids + (size_t)a.grid_of_scene[my_scene] * a.Gh * a.Gw * C;
@@ -145,7 +141,7 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
         __syncthreads();
 
         for (int t = 0; t < a.T; ++t) {
-            TICKX(0)
+            IOC_TICK(0)
             if (tid < TM && t + 1 < a.T)
                 ynext = *reinterpret_cast<const float2*>(a.Y + ((size_t)min(row0 + tid, a.R - 1) * a.T + t + 1) * 2);
             // ---- P1: e_v, e_s, neighbour bits (row threads) ----
@@ -178,12 +174,11 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
                                                           [&](int j, int b) { atomicOr(&masks[r8 * LDM + b], 1u << (grp_base + j)); });
                 nb_publish_occ(oc, occ, B);
             }
-            TICKX(1)
+            IOC_TICK(1)
             __syncthreads();
-            TICKX(2)
+            IOC_TICK(2)
             // ---- P2: social pooling chain -> e_r (occupied bins dealt round-robin to the waves) ----
-            unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-            om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+            unsigned long long om = ioc_occ64(occ);
             {
                 unsigned long long mine = 0ull;
                 {
@@ -316,7 +311,7 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
                 }
                 // fixed-order sum of the partial tiles: round s hands slot s to the wave s column blocks further on; rounds
                 // alternate between the two slot sets, one barrier per round
-                TICKX(3)
+                IOC_TICK(3)
                 if (om) {                                          // (workgroup-uniform)
                     __syncthreads();                               // every wave is done reading Ht: it now carries exchange set 0
 #pragma unroll
@@ -348,9 +343,9 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
                          fmaxf(soc[0][4 * q + 2] + bso, 0.f), fmaxf(soc[0][4 * q + 3] + bso, 0.f), pa, pb);
                 }
             }
-            TICKX(4)
+            IOC_TICK(4)
             __syncthreads();
-            TICKX(5)
+            IOC_TICK(5)
             // ---- P4: gates over [x | h], and the candidate's x part (same A fragments: three n-tiles per LDS read) ----
             // B fragments run through a ring of RD4 k-groups, requested RD4 groups (~ 850 matrix cycles) before their use
             f32x16 u, ac = zero16();
@@ -418,9 +413,9 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
 #pragma unroll
                     for (int i = 0; i < NP; ++i) chp[g][i] = (wch + i * WC_LO + g * 64)[ul];
             }
-            TICKX(6)
+            IOC_TICK(6)
             __syncthreads();
-            TICKX(7)
+            IOC_TICK(7)
             // ---- P5: candidate += (r*h) part, blend, score; publish h_t ----
             {
 #pragma unroll
@@ -445,15 +440,15 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
             }
             for (int i = tid; i < TM * LDM; i += NTHR) masks[i] = 0u;
             if (tid < 2) occ[tid] = 0;
-            TICKX(8)
+            IOC_TICK(8)
             __syncthreads();
-            TICKX(9)
+            IOC_TICK(9)
         }
         // ---- score ----
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             float v = sp[i];
-            v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8); v += __shfl_xor(v, 16);
+            v = ioc_sum32(v);
             if (c31 == 0) red[cb * TM + arow + (i & 3) + 8 * (i >> 2)] = v;
         }
         __syncthreads();
@@ -487,31 +482,22 @@ __global__ __launch_bounds__((H / 32) * 64, NP == 2 ? 2 : 1) void k_ioc_x3(IocAr
 #endif
 }
 
-static size_t iocx3_lds(const IocArgs& a, int np = 2) {
-    const int H = a.H, TM = 32, KX = 16 + 32 + 2 * H, B = a.G * a.G, NT = H / 32;
-    size_t b = np * ((size_t)TM * (KX + 8) * 2 + (size_t)TM * (H + 8) * 2 + (size_t)H * (TM + 8) * 2);
-    b += (size_t)((TM * (B + 1) + 1) & ~1) * 4 + 16 * 8 + (size_t)TM * 4 * 4 + 3 * 16 * 4 + (size_t)NT * TM * 4 + TM + 16;
-    return b;
-}
 template <int H>
 static void launch_x3(const IocArgs& a, hipStream_t s) {
     const dim3 grid((a.R + 31) / 32), block((H / 32) * 64);
+    const size_t lds = IocHtLds::x3(H, 16, 32, 2, a.G * a.G).bytes();
     if (a.sv_h) {                                              // training-mode forward
         if (a.gpt > 0) {                                       // padded tiles
-            allow_big_lds(k_ioc_x3<H, 16, 32, true, 2, true>);
-            hipLaunchKernelGGL((k_ioc_x3<H, 16, 32, true, 2, true>), grid, block, iocx3_lds(a), s, a);
+            launch_big_lds<k_ioc_x3<H, 16, 32, true, 2, true>>(grid, block, lds, s, a);
             return;
         }
-        allow_big_lds(k_ioc_x3<H, 16, 32, true>);
-        hipLaunchKernelGGL((k_ioc_x3<H, 16, 32, true>), grid, block, iocx3_lds(a), s, a);
+        launch_big_lds<k_ioc_x3<H, 16, 32, true>>(grid, block, lds, s, a);
     } else {
         if (a.gpt > 0) {                                      // padded tiles
-            allow_big_lds(k_ioc_x3<H, 16, 32, false, 2, true>);
-            hipLaunchKernelGGL((k_ioc_x3<H, 16, 32, false, 2, true>), grid, block, iocx3_lds(a), s, a);
+            launch_big_lds<k_ioc_x3<H, 16, 32, false, 2, true>>(grid, block, lds, s, a);
             return;
         }
-        allow_big_lds(k_ioc_x3<H, 16, 32, false>);
-        hipLaunchKernelGGL((k_ioc_x3<H, 16, 32, false>), grid, block, iocx3_lds(a), s, a);
+        launch_big_lds<k_ioc_x3<H, 16, 32, false>>(grid, block, lds, s, a);
     }
 }
 // (groups of 64 agents: launch_ioc_x3r2.  For <= 32 agents that form was measured slower -- with two pieces the 32-row tiles' second workgroup
@@ -523,8 +509,7 @@ void launch_ioc_x3(const IocArgs& a, hipStream_t s) {
 template <int H>
 static void launch_x6(const IocArgs& a, hipStream_t s) {
     const dim3 grid((a.R + 31) / 32), block((H / 32) * 64);
-    allow_big_lds(k_ioc_x3<H, 16, 32, false, 3>);
-    hipLaunchKernelGGL((k_ioc_x3<H, 16, 32, false, 3>), grid, block, iocx3_lds(a, 3), s, a);
+    launch_big_lds<k_ioc_x3<H, 16, 32, false, 3>>(grid, block, IocHtLds::x3(H, 16, 32, 3, a.G * a.G).bytes(), s, a);
 }
 // (launches of >= 256 64-row tiles run launch_ioc_x6r2, within 1-2 ulp; this 32-row / three-image form serves the shapes whose masks do not fit beside
 //  a 64-row tile and launches that would leave CUs idle: one window = 20 tiles of 32 rows on 20 CUs takes 1.29 ms, 10 tiles of 64 rows 2.39 ms)

@@ -159,17 +159,14 @@ static void launch_dec6(const DecArgs& a, hipStream_t s, int np) {
     const size_t lds = (size_t)(32 * (H + 4) + 2 * H + 64) * sizeof(float) + (size_t)6 * 32 * (H + 8) * sizeof(u16);
     if (a.sv_r && np == 2) {                                   // training-mode forward with two-piece operands (DESIRE_FLAG_TRAIN_FWD_3P)
         const size_t lds2 = (size_t)(32 * (H + 4) + 2 * H + 64) * sizeof(float) + (size_t)4 * 32 * (H + 8) * sizeof(u16);
-        allow_big_lds(k_decoder_x6<H, true, 2>);
-        hipLaunchKernelGGL((k_decoder_x6<H, true, 2>), dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds2, s, a);
+        launch_big_lds<k_decoder_x6<H, true, 2>>(dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds2, s, a);
         return;
     }
     if (a.sv_r) {                                              // training-mode forward (api.hip sets all four save streams together)
-        allow_big_lds(k_decoder_x6<H, true>);
-        hipLaunchKernelGGL((k_decoder_x6<H, true>), dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
+        launch_big_lds<k_decoder_x6<H, true>>(dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
         return;
     }
-    allow_big_lds(k_decoder_x6<H, false>);
-    hipLaunchKernelGGL((k_decoder_x6<H, false>), dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
+    launch_big_lds<k_decoder_x6<H, false>>(dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
 }
 bool decoder_x6_supported(int H) { return H == 64 || H == 128 || H == 256; }
 void launch_decoder_x6(const DecArgs& a, hipStream_t s, int np) {
@@ -267,12 +264,10 @@ __global__ __launch_bounds__(DS_WG, 2) void k_deconv2_x6(ConvArgs a, size_t plo)
 void launch_deconv2_x6(const ConvArgs& a, hipStream_t s, int np) {
     const size_t plo = (size_t)25 * 2 * 8 * 64;                        // uint4 per piece: 25 taps x 2 n-tiles x 8 k-groups x 64 lanes
     if (np == 2) {
-        allow_big_lds(k_deconv2_x6<2>);
-        hipLaunchKernelGGL(k_deconv2_x6<2>, dim3((dyn_units(a.n, a.dyn) + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a, plo);
+        launch_big_lds<k_deconv2_x6<2>>(dim3((dyn_units(a.n, a.dyn) + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a, plo);
         return;
     }
-    allow_big_lds(k_deconv2_x6<3>);
-    hipLaunchKernelGGL(k_deconv2_x6<3>, dim3((dyn_units(a.n, a.dyn) + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a, plo);
+    launch_big_lds<k_deconv2_x6<3>>(dim3((dyn_units(a.n, a.dyn) + 3) / 4), dim3(DS_WG), 4 * 4096 * sizeof(float), s, a, plo);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -397,13 +392,11 @@ void launch_deconv3_x6(const ConvArgs& a, hipStream_t s, int np) {
     const size_t plo = (size_t)25 * 1 * 4 * 64;                       // uint4 per piece: 25 taps x 1 n-tile x 4 k-groups x 64 lanes
     if (np == 2) {
         const size_t ldsi = (size_t)2 * (2 * 64 * 72 + 192) * sizeof(u16);
-        allow_big_lds(k_deconv3_x6i<2>);
-        hipLaunchKernelGGL(k_deconv3_x6i<2>, dim3((dyn_units(a.n, a.dyn) + 1) / 2), dim3(DS_WG), ldsi, s, a, plo);
+        launch_big_lds<k_deconv3_x6i<2>>(dim3((dyn_units(a.n, a.dyn) + 1) / 2), dim3(DS_WG), ldsi, s, a, plo);
         return;
     }
     const size_t ldsi = (size_t)3 * (2 * 64 * 72 + 192) * sizeof(u16);
-    allow_big_lds(k_deconv3_x6i<3>);
-    hipLaunchKernelGGL(k_deconv3_x6i<3>, dim3((dyn_units(a.n, a.dyn) + 1) / 2), dim3(DS_WG), ldsi, s, a, plo);
+    launch_big_lds<k_deconv3_x6i<3>>(dim3((dyn_units(a.n, a.dyn) + 1) / 2), dim3(DS_WG), ldsi, s, a, plo);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -540,12 +533,10 @@ bool rows_x6_supported(int K, int NT) { return (K % 16) == 0 && K <= 128 && NT %
 // a.Bp = the three-piece pack; a.K a multiple of 16; a.NT a multiple of 16 (deconv1: 64 n-tiles)
 void launch_deconv1_x6(const GemmArgs& a, hipStream_t s) {
     const size_t lds = (size_t)3 * ILO6 * sizeof(u16);
-    allow_big_lds(k_deconv1_x6<4>);
-    hipLaunchKernelGGL((k_deconv1_x6<4>), dim3((a.M + 63) / 64, a.NT / 16), dim3(DS_WG), lds, s, a);
+    launch_big_lds<k_deconv1_x6<4>>(dim3((a.M + 63) / 64, a.NT / 16), dim3(DS_WG), lds, s, a);
 }
 // a.Wp = the three-piece pack "mask/W6"; H = 64 or 128, V a multiple of 128
 void launch_mask_x6(const MaskArgs& a, hipStream_t s) {
     const size_t lds = (size_t)3 * ILO6 * sizeof(u16);
-    allow_big_lds(k_mask_x6);
-    hipLaunchKernelGGL(k_mask_x6, dim3((a.R + 63) / 64), dim3(DS_WG), lds, s, a);
+    launch_big_lds<k_mask_x6>(dim3((a.R + 63) / 64), dim3(DS_WG), lds, s, a);
 }

@@ -15,13 +15,9 @@
 #include "common.h"
 #include "kernels.h"
 
+#include "ioc_tile.h"
 #include "split.h"
 
-#ifdef DESIRE_IOC_TIMING
-#define TICK6(k) { const long long now_ = clock64(); tacc[k] += now_ - tprev; tprev = now_; }
-#else
-#define TICK6(k)
-#endif
 
 // NP = 3: six products (dims.bf16 = 3); NP = 2: the same tile with two-piece operands, three products (dims.bf16 = 2).
 template <int H, int EV, int C, bool WIDE, int NP = 3>          // WIDE: one 64-agent group spans both row blocks (compile-time: keeps the chains branch-free)
@@ -50,6 +46,10 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
     float* red = wv + 3 * EV;                                         // [NT][TM]
     unsigned char* vld = reinterpret_cast<unsigned char*>(red + NT * TM);   // [TM]
     unsigned* occ = reinterpret_cast<unsigned*>(vld + TM);                  // [2]
+    constexpr IocHtLds P0 = IocHtLds::x6r2(H, EV, C, 0), P1 = IocHtLds::x6r2(H, EV, C, 1);     // (ioc_lds.h: what the launcher sizes the LDS by)
+    IOC_LDS_TIED(P0.off(P0.MASKS) == (TM * LDX + TM * LDB + H * LDT) * 4);
+    IOC_LDS_TIED(P0.sz[P0.MASKS] == TM * 8 && P1.sz[P1.MASKS] == 2 * TM * 8);
+    IOC_LDS_TIED(P0.off(P0.OCC) - P0.off(P0.LUT) == 16 * 8 + (TM * 2 * 2 + 3 * EV + NT * TM) * 4 + TM);
     float* EX0 = HtT;                                                       // exchange sets: inside the h^T tile (dead between the pooling
     float* EX1 = HtT + NT * 1024;                                           // chains and the end of the step)
 
@@ -67,12 +67,8 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
     constexpr bool wide = WIDE;
     constexpr int JG = WIDE ? JGM : 2;
 
-    for (int i = tid; i < 3 * EV; i += NTHR) wv[i] = (i < 2 * EV) ? a.w_vel[i] : a.b_vel[i - 2 * EV];
-    if (tid < 16) {
-        const unsigned lo = ((tid & 1) ? 0x3F80u : 0u) | ((tid & 2) ? 0x3F800000u : 0u);
-        const unsigned hi2 = ((tid & 4) ? 0x3F80u : 0u) | ((tid & 8) ? 0x3F800000u : 0u);
-        lut[tid] = make_uint2(lo, hi2);
-    }
+    ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);
+    ioc_stage_lut(lut, tid);
     if (tid < TM) vld[tid] = a.valid[agent_of_row(min(row0 + tid, a.R - 1), a.K, a.mno)];
     const float bgr = a.b_g[col], bgu = a.b_g[H + col], bcc = a.b_c[col], bso = a.b_soc[col], wsc = a.w_score[col];
     const float* grid = a.grids + (size_t)a.grid_of_scene[my_scene] * a.Gh * a.Gw * C;
@@ -122,7 +118,7 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
         __syncthreads();
 
         for (int t = 0; t < a.T; ++t) {
-            TICK6(0)
+            IOC_TICK(0)
             if (tid < TM && t + 1 < a.T)
                 ynext = *reinterpret_cast<const float2*>(a.Y + ((size_t)min(row0 + tid, a.R - 1) * a.T + t + 1) * 2);
             // ---- P1: e_v, e_s, neighbour bits (row threads) ----
@@ -151,12 +147,11 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
                                                           [&](int j, int b) { atomicOr(&masks[r8 * LDM + b], 1ull << (grp_base + j)); });
                 nb_publish_occ(oc, occ, B);
             }
-            TICK6(1)
+            IOC_TICK(1)
             __syncthreads();
-            TICK6(2)
+            IOC_TICK(2)
             // ---- P2: social pooling chain -> e_r (occupied bins dealt round-robin to the waves; both row blocks per weight fragment) ----
-            unsigned long long om = (unsigned long long)__builtin_amdgcn_readfirstlane((int)occ[0]) & 0xffffffffull;
-            om |= (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)occ[1]) << 32;
+            unsigned long long om = ioc_occ64(occ);
             {
                 unsigned long long mine = 0ull;
                 {
@@ -248,7 +243,7 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-                TICK6(3)
+                IOC_TICK(3)
                 // fixed-order sum of the partial tiles: round (sft, m) hands slot sft of block m to the wave sft column blocks further on;
                 // rounds alternate between the two slot sets, one barrier per round
                 if (om) {                                          // (workgroup-uniform)
@@ -278,9 +273,9 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
                     for (int i = 0; i < 16; ++i)
                         XH[(32 * m + arow + (i & 3) + 8 * (i >> 2)) * LDX + EV + C + col] = fmaxf(soc[m][0][i] + bso, 0.f);
             }
-            TICK6(4)
+            IOC_TICK(4)
             __syncthreads();
-            TICK6(5)
+            IOC_TICK(5)
             // ---- P4: gates over [x | h], and the candidate's x part (three n-tiles and both row blocks per weight fragment) ----
             f32x16 u[RB], ac[RB];
             {
@@ -353,9 +348,9 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
 #pragma unroll
                     for (int i = 0; i < NP; ++i) chp[g][i] = (wch + i * WC_LO + g * 64)[ul];
             }
-            TICK6(6)
+            IOC_TICK(6)
             __syncthreads();
-            TICK6(7)
+            IOC_TICK(7)
             // ---- P5: candidate += (r*h) part, blend, score; publish h_t ----
             {
                 const float* rp0 = RH + c31 * LDB + 8 * hi;
@@ -386,9 +381,9 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
             }
             for (int i = tid; i < TM * LDM; i += NTHR) masks[i] = 0ull;
             if (tid < 2) occ[tid] = 0;
-            TICK6(8)
+            IOC_TICK(8)
             __syncthreads();
-            TICK6(9)
+            IOC_TICK(9)
         }
         // ---- score ----
 #pragma unroll
@@ -396,7 +391,7 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 float v = sp[m][i];
-                v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8); v += __shfl_xor(v, 16);
+                v = ioc_sum32(v);
                 if (c31 == 0) red[cb * TM + 32 * m + arow + (i & 3) + 8 * (i >> 2)] = v;
             }
         __syncthreads();
@@ -433,21 +428,14 @@ __global__ __launch_bounds__((H / 32) * 64, 1) void k_ioc_x6r2(IocArgs a) {
 #endif
 }
 
-static size_t iocx6r2_lds(const IocArgs& a) {
-    const int H = a.H, TM = 64, KX = 16 + 32 + 2 * H, B = a.G * a.G, NT = H / 32;
-    size_t b = ((size_t)TM * (KX + 4) + (size_t)TM * (H + 4) + (size_t)H * (TM + 4)) * 4;
-    b += (size_t)TM * (B + 1) * 8 + 16 * 8 + (size_t)TM * 4 * 4 + 3 * 16 * 4 + (size_t)NT * TM * 4 + TM + 64;
-    return b;
-}
 template <int H, int NP>
 static void launch_x6r2(const IocArgs& a, hipStream_t s) {
     const dim3 grid((a.R + 63) / 64), block((H / 32) * 64);
+    const size_t lds = IocHtLds::x6r2(H, 16, 32, a.G * a.G).bytes();
     if (a.mno > 32) {
-        allow_big_lds(k_ioc_x6r2<H, 16, 32, true, NP>);
-        hipLaunchKernelGGL((k_ioc_x6r2<H, 16, 32, true, NP>), grid, block, iocx6r2_lds(a), s, a);
+        launch_big_lds<k_ioc_x6r2<H, 16, 32, true, NP>>(grid, block, lds, s, a);
     } else {
-        allow_big_lds(k_ioc_x6r2<H, 16, 32, false, NP>);
-        hipLaunchKernelGGL((k_ioc_x6r2<H, 16, 32, false, NP>), grid, block, iocx6r2_lds(a), s, a);
+        launch_big_lds<k_ioc_x6r2<H, 16, 32, false, NP>>(grid, block, lds, s, a);
     }
 }
 void launch_ioc_x6r2(const IocArgs& a, hipStream_t s) {
