@@ -61,12 +61,13 @@ std::vector<float> pack_b16(int K, int N, const std::function<int(int, int, int)
 
 int desire_upload(desire_ctx* h, const std::string& name, const std::vector<float>& v) {
     if (h->pack_mode == 1) { h->captured[name] = v; return 0; }
-    DevBuf& b = h->dev[name];
-    if (b.p && b.bytes == v.size() * sizeof(float))          // same shape: refresh in place (pointers stay valid)
-        return hipMemcpy(b.p, v.data(), b.bytes, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-    b.release();
-    if (b.alloc(v.size() * sizeof(float))) return -1;
-    return hipMemcpy(b.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+    const size_t bytes = v.size() * sizeof(float);
+    const DevBuf* b = h->dev.find(name.c_str());
+    if (!b || b->bytes != bytes) {                           // same shape: refresh in place (pointers stay valid); otherwise exactly the new size
+        h->dev.release(name.c_str());
+        if (h->dev.ensure(name.c_str(), bytes)) return -1;
+    }
+    return hipMemcpy(h->dev.get(name.c_str()), v.data(), bytes, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
 }
 
 static void embed_walk(const Embed& em, const std::function<void(size_t, size_t)>& f) {
@@ -275,8 +276,7 @@ extern "C" int desire_create(const desire_dims* dims, desire_handle** out) {
     if (h->Hl != h->d.H) embeddings(h);
     const desire_dims& d = h->d;
     const size_t A = h->A, R = h->R, f = sizeof(float);
-    struct WS { const char* n; size_t bytes; };
-    const WS list[] = {
+    const WsItem list[] = {
         {"HxHy", A * 2 * d.H * f}, {"p_last", A * 2 * f}, {"valid", A}, {"lmask", A}, {"nfut", A * f}, {"vae_in", A * h->V * f},
         {"c1", A * 8192 * f}, {"c2", A * 4096 * f}, {"c3", A * 2048 * f}, {"params", A * 2 * d.L * f},
         {"z", R * d.L * f}, {"d1", R * 2048 * f}, {"d2", R * 4096 * f}, {"d3", R * 8192 * f},
@@ -286,17 +286,15 @@ extern "C" int desire_create(const desire_dims* dims, desire_handle** out) {
         {"grid_of_scene", (size_t)d.n_scenes * sizeof(int32_t)},
         // desire_build_windows*: allocated here, not lazily, because a feeder thread may call the builder while the owner thread runs a forward on
         // the same handle (desire_amd/prefetch.py: DeviceWindowFeeder) -- the builder then touches these two buffers (through h->bw_starts / h->bw_err,
-        // never through the map: other calls insert into it) and nothing else of the handle
+        // never through the map: allocating calls insert into it) and nothing else of the handle
         {"bw_starts", (size_t)d.n_scenes * sizeof(int32_t)}, {"bw_err", sizeof(int32_t)},
         // desire_ranked_errors: (ADE_h, FDE_h) of every sample for the 8 horizons a call accepts, counted frames of every agent -- here, so that
         // no call allocates and a captured call never has to
         {"rank_tab", d.ref_compat ? 0 : R * 16 * f}, {"rank_cnt", d.ref_compat ? 0 : A * 8 * sizeof(int32_t)},
     };
-    for (const WS& w : list) {
-        if (h->ws[w.n].alloc(w.bytes)) { desire_destroy(h); return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for ") + w.n); }
-        (void)hipMemset(h->ws[w.n].p, 0, w.bytes);
-    }
-    h->bw_starts = static_cast<int32_t*>(h->ws.at("bw_starts").p); h->bw_err = static_cast<int32_t*>(h->ws.at("bw_err").p);
+    if (int rc = ws_ensure(h, list)) { desire_destroy(h); return rc; }
+    for (const WsItem& w : list) (void)hipMemset(W(h, w.n), 0, w.bytes);
+    h->bw_starts = Wt<int32_t>(h, "bw_starts"); h->bw_err = Wt<int32_t>(h, "bw_err");
     if (d.bin_mode == 1) {
         // log-polar social bins: G rings with geometric radii between r_min = nb_h and r_max = nb_w, G equal sectors
         std::vector<float> tab(20, 0.f);
@@ -308,8 +306,8 @@ extern "C" int desire_create(const desire_dims* dims, desire_handle** out) {
             tab[9 + 2 * k] = (float)std::sin(2.0 * M_PI * k / G);
         }
         h->bin_tab_host = tab;
-        if (h->ws["bin_tab"].alloc(20 * f)) { desire_destroy(h); return fail(DESIRE_ERR_HIP, "hipMalloc failed for bin_tab"); }
-        if (hipMemcpy(h->ws["bin_tab"].p, tab.data(), 20 * f, hipMemcpyHostToDevice) != hipSuccess) { desire_destroy(h); return fail(DESIRE_ERR_HIP, "bin table upload failed"); }
+        if (int rc = ws_ensure(h, {{"bin_tab", 20 * f}})) { desire_destroy(h); return rc; }
+        if (hipMemcpy(W(h, "bin_tab"), tab.data(), 20 * f, hipMemcpyHostToDevice) != hipSuccess) { desire_destroy(h); return fail(DESIRE_ERR_HIP, "bin table upload failed"); }
     }
     *out = h;
     return DESIRE_OK;
@@ -329,8 +327,8 @@ extern "C" int desire_destroy(desire_handle* h) {
     if (h->cp_host) { (void)hipHostFree(h->cp_host); h->cp_host = nullptr; }
     if (h->cp_ev) { (void)hipEventDestroy(h->cp_ev); h->cp_ev = nullptr; }
     (void)desire_peer_close(h);
-    for (auto& kv : h->dev) kv.second.release();
-    for (auto& kv : h->ws) kv.second.release();
+    h->dev.release_all();
+    h->ws.release_all();
     for (auto& p : h->prof) { (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1); }
     for (void* g : h->graphs) if (g) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(g));
     delete h;
@@ -366,7 +364,7 @@ extern "C" int desire_set_scene_grids(desire_handle* h, const float* dev_grids, 
     for (int i = 0; i < h->d.n_scenes; ++i)
         if (host_grid_of_scene[i] < 0 || host_grid_of_scene[i] >= h->d.n_grids)
             return fail(DESIRE_ERR_ARG, "grid_of_scene entry out of range");
-    HIPCHK(hipMemcpy(h->ws["grid_of_scene"].p, host_grid_of_scene, h->d.n_scenes * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(W(h, "grid_of_scene"), host_grid_of_scene, h->d.n_scenes * sizeof(int32_t), hipMemcpyHostToDevice));
     h->grids = dev_grids;
     h->grids_set = true;
     h->img_set = false; h->img = nullptr;          // the last of desire_set_scene_grids / desire_set_scene_images wins
@@ -378,10 +376,8 @@ extern "C" int desire_set_scene_images(desire_handle* h, const float* dev_images
     const desire_dims& d = h->d;
     if (Hi != 4 * d.Gh || Wi != 4 * d.Gw) return fail(DESIRE_ERR_ARG, "scene image must be [n_grids, 4*Gh, 4*Gw, 3]");
     const size_t n1 = (size_t)d.n_grids * (Hi / 2) * (Wi / 2) * 16, n2 = (size_t)d.n_grids * d.Gh * d.Gw * 32;
-    if (!h->ws.count("scnn1") && (h->ws["scnn1"].alloc(n1 * sizeof(float)) || h->ws["scnn2"].alloc(n2 * sizeof(float))))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the scene CNN workspace");
-    if (!h->ws.count("scene_img_grid") && h->ws["scene_img_grid"].alloc((size_t)d.n_grids * d.Gh * d.Gw * d.C * sizeof(float)))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the scene grid buffer");
+    if (int rc = ws_ensure(h, {{"scnn1", n1 * sizeof(float)}, {"scnn2", n2 * sizeof(float)},
+                               {"scene_img_grid", (size_t)d.n_grids * d.Gh * d.Gw * d.C * sizeof(float)}})) return rc;
     if (int rc = desire_set_scene_grids(h, W(h, "scene_img_grid"), host_grid_of_scene)) return rc;
     h->img = dev_images; h->img_set = true; h->img_stale = true;
     if (h->training) return scene_grad_setup(h);
@@ -422,10 +418,9 @@ extern "C" int desire_read_buffer(desire_handle* h, const char* name, float* hos
             return DESIRE_OK;
         }
     {   // any other workspace buffer by its internal name (training-mode saves and gradient streams; the caller knows the layout)
-        auto it = h->ws.find(nm);
-        if (it != h->ws.end() && it->second.p) {
-            if (n * f > it->second.bytes) return fail(DESIRE_ERR_ARG, nm + ": holds " + std::to_string(it->second.bytes / f) + " values");
-            HIPCHK(hipMemcpy(host_out, it->second.p, n * f, hipMemcpyDeviceToHost));
+        if (const DevBuf* b = h->ws.find(name)) {
+            if (n * f > b->bytes) return fail(DESIRE_ERR_ARG, nm + ": holds " + std::to_string(b->bytes / f) + " values");
+            HIPCHK(hipMemcpy(host_out, b->p, n * f, hipMemcpyDeviceToHost));
             return DESIRE_OK;
         }
     }
@@ -469,9 +464,9 @@ extern "C" int desire_device_buffer(desire_handle* h, const char* name, void** d
     if (!h || !name || !dev_ptr || !bytes) return fail(DESIRE_ERR_ARG, "null argument");
     if (!std::strcmp(name, "scene_grid_grad") && !(scene_grad_on(h) && h->training))
         return fail(DESIRE_ERR_STATE, "scene_grid_grad needs training mode and desire_set_option(h, \"scene_grad\", 1)");
-    auto it = h->ws.find(name);
-    if (it == h->ws.end()) return fail(DESIRE_ERR_ARG, std::string("unknown buffer: ") + name);
-    *dev_ptr = it->second.p; *bytes = it->second.bytes;
+    const DevBuf* b = h->ws.find(name);
+    if (!b) return fail(DESIRE_ERR_ARG, std::string("unknown buffer: ") + name);
+    *dev_ptr = b->p; *bytes = b->bytes;
     return DESIRE_OK;
 }
 

@@ -34,12 +34,12 @@ ClassLayout class_layout(const desire_ctx* h, bool pad, const int* counts) {
 }
 IocView ioc_view(desire_ctx* h, const IocView* cls) {
     if (!cls)
-        return IocView{-1, h->d.mno, h->d.n_scenes, 0, 0, h->R, 0, 0, 0, W(h, "HxHy"), W(h, "p_last"), static_cast<uint8_t*>(h->ws["valid"].p),
-                       static_cast<int32_t*>(h->ws["grid_of_scene"].p)};
+        return IocView{-1, h->d.mno, h->d.n_scenes, 0, 0, h->R, 0, 0, 0, W(h, "HxHy"), W(h, "p_last"), Wt<uint8_t>(h, "valid"),
+                       Wt<int32_t>(h, "grid_of_scene")};
     IocView v = *cls;
     v.Hx = W(h, "ci_Hx") + v.agent_off * 2 * h->d.H; v.p_last = W(h, "ci_pl") + v.agent_off * 2;
-    v.valid = static_cast<uint8_t*>(h->ws["ci_valid"].p) + v.agent_off; v.gos = static_cast<int32_t*>(h->ws["ci_gos"].p) + v.win_off;
-    v.cmap = static_cast<const int32_t*>(h->ws["ci_map"].p) + (size_t)v.cls * h->A; v.win = static_cast<const int32_t*>(h->ws["ci_win"].p) + (size_t)v.cls * h->d.n_scenes;
+    v.valid = Wt<uint8_t>(h, "ci_valid") + v.agent_off; v.gos = Wt<int32_t>(h, "ci_gos") + v.win_off;
+    v.cmap = Wt<const int32_t>(h, "ci_map") + (size_t)v.cls * h->A; v.win = Wt<const int32_t>(h, "ci_win") + (size_t)v.cls * h->d.n_scenes;
     v.Y = W(h, "ci_Y") + v.row_off * h->d.T_pred * 2; v.score = W(h, "ci_score") + v.row_off;
     return v;
 }
@@ -59,17 +59,13 @@ int compact_setup(desire_ctx* h) {
         const ClassLayout a = class_layout(h, false, nullptr), b = class_layout(h, true, nullptr);
         Ac = std::max({a.agents, b.agents, A}); Rc = std::max({a.rows, b.rows, ioc_save_rows(h)}); Wc = std::max(a.wins, b.wins);
     }
-    struct WS { const char* n; size_t bytes; };
-    const WS list[] = {{"cp_amap", A * sizeof(int32_t)}, {"cp_inv", A * sizeof(int32_t)}, {"cp_count", 8 * sizeof(int32_t)}, {"cp_HxHy", A * 2 * d.H * f},
+    const WsItem list[] = {{"cp_amap", A * sizeof(int32_t)}, {"cp_inv", A * sizeof(int32_t)}, {"cp_count", 8 * sizeof(int32_t)}, {"cp_HxHy", A * 2 * d.H * f},
                        {"cp_plast", A * 2 * f}, {"cp_params", A * 2 * d.L * f}, {"cp_Y0", R * (size_t)d.T_pred * 2 * f},
                        {"cp_past", A * (size_t)d.T_obs * 3 * f}, {"cp_fut", A * (size_t)d.T_pred * 3 * f}, {"cp_valid2", A}};
-    const WS list_ioc[] = {{"ci_win", 4 * (size_t)d.n_scenes * sizeof(int32_t)}, {"ci_map", 4 * A * sizeof(int32_t)}, {"ci_Hx", Ac * 2 * d.H * f}, {"ci_pl", Ac * 2 * f},
+    const WsItem list_ioc[] = {{"ci_win", 4 * (size_t)d.n_scenes * sizeof(int32_t)}, {"ci_map", 4 * A * sizeof(int32_t)}, {"ci_Hx", Ac * 2 * d.H * f}, {"ci_pl", Ac * 2 * f},
                            {"ci_valid", Ac}, {"ci_gos", Wc * sizeof(int32_t)}, {"ci_Y", Rc * (size_t)d.T_pred * 2 * f}, {"ci_score", Rc * f}};      // (+ a partial padded tile per class)
-    for (const WS& w : list)
-        if (!h->ws[w.n].p && h->ws[w.n].alloc(w.bytes)) return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for ") + w.n);
-    if (h->d.flags & DESIRE_FLAG_COMPACT_IOC)
-        for (const WS& w : list_ioc)
-            if (!h->ws[w.n].p && h->ws[w.n].alloc(w.bytes)) return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for ") + w.n);
+    if (int rc = ws_ensure(h, list)) return rc;
+    if (h->d.flags & DESIRE_FLAG_COMPACT_IOC) { if (int rc = ws_ensure(h, list_ioc)) return rc; }
     if (!h->cp_ev) HIPCHK(hipEventCreateWithFlags(&h->cp_ev, hipEventDisableTiming));
     if (!h->cp_host) {
         int32_t* p = nullptr;
@@ -83,12 +79,11 @@ int compact_setup(desire_ctx* h) {
 // the present-agent scan (+ the slot-class scan) over `valid`, and the event desire_sample / desire_ioc_refine wait on
 static int compact_scans(desire_ctx* h, hipStream_t s) {
     const desire_dims& d = h->d;
-    launch_present_scan(static_cast<const uint8_t*>(h->ws["valid"].p), h->A, static_cast<int32_t*>(h->ws["cp_amap"].p), static_cast<int32_t*>(h->ws["cp_inv"].p),
-                        static_cast<int32_t*>(h->ws["cp_count"].p), h->cp_host, s);
+    launch_present_scan(Wt<const uint8_t>(h, "valid"), h->A, Wt<int32_t>(h, "cp_amap"), Wt<int32_t>(h, "cp_inv"), Wt<int32_t>(h, "cp_count"), h->cp_host, s);
     if (compact_ioc(h)) {
         const ClassLayout L = class_layout(h, ioc_plan(h).padded, nullptr);
-        launch_class_scan(static_cast<const uint8_t*>(h->ws["valid"].p), d.n_scenes, d.mno, L.n, L.m, d.K, h->ci_min_rows, static_cast<int32_t*>(h->ws["ci_win"].p),
-                          static_cast<int32_t*>(h->ws["ci_map"].p), static_cast<int32_t*>(h->ws["cp_count"].p) + 4, h->cp_host + 4, s);
+        launch_class_scan(Wt<const uint8_t>(h, "valid"), d.n_scenes, d.mno, L.n, L.m, d.K, h->ci_min_rows, Wt<int32_t>(h, "ci_win"),
+                          Wt<int32_t>(h, "ci_map"), Wt<int32_t>(h, "cp_count") + 4, h->cp_host + 4, s);
     }
     if (!compact_dyn(h)) HIPCHK(hipEventRecord(h->cp_ev, s));             // (device-side counts: nobody waits, and the call stays capturable)
     h->cp_pending = true;
@@ -103,6 +98,34 @@ static int compact_wait(desire_ctx* h, hipStream_t s) {
         return fail(DESIRE_ERR_STATE, "DESIRE_FLAG_COMPACT_* read the present-agent counts back: not capturable in a hipGraph");
     HIPCHK(hipEventSynchronize(h->cp_ev));
     return DESIRE_OK;
+}
+// the mapped present-agent count word: read back after compact_wait (an out-of-range value is an error), or as a GUESS of P for choices that are about
+// speed only (which variant of a row GEMM): whatever the word holds -- the previous call's count, or this one's if the scan has already run.  The
+// guess is never a bound: the grids are the worst case's and the kernels read the real count.
+static int present_count(const desire_ctx* h, int* P) {
+    *P = *static_cast<volatile int32_t*>(h->cp_host);
+    return (*P < 0 || *P > h->A) ? fail(DESIRE_ERR_HIP, "present-agent scan returned a count out of range") : 0;
+}
+static int count_hint(const desire_ctx* h) {
+    const int P = *static_cast<volatile int32_t*>(h->cp_host);
+    return (P < 0 || P > h->A) ? 0 : P;
+}
+
+// the fp32 weights of the GRU encoder `prefix` ("enc_x" / "enc_y")
+void enc_weights(desire_ctx* h, const char* prefix, EncArgs& e) {
+    const std::string p(prefix);
+    e.wx_g = D(h, (p + "/gk").c_str()); e.b_g = D(h, (p + "/gb").c_str()); e.wx_c = D(h, (p + "/ck").c_str()); e.b_c = D(h, (p + "/cb").c_str());
+    e.Whg = D4(h, (p + "/Whg").c_str()); e.Whc = D4(h, (p + "/Whc").c_str());
+}
+
+// batch statistics of one conv layer's output x [n, P, C] (dims.bn_mode != 0: the conv ran with a linear epilogue): normalise + activate in place,
+// 1: per sample (k_instnorm_act), 2: over the whole batch.  Training keeps the pre-norm tensor next to the activation for the backward.
+static void batch_stats_act(desire_ctx* h, const char* layer, float* x, int n, int P, int C, int sig, hipStream_t s) {
+    const std::string l(layer);
+    const float* ga = D(h, (l + "/gamma").c_str()); const float* be = D(h, (l + "/beta").c_str());
+    if (h->training) launch_copy_f32(W(h, (l.substr(l.rfind('/') + 1) + "_pre").c_str()), x, (size_t)n * P * C, s);
+    if (h->d.bn_mode == 2) launch_batchnorm_act(x, (size_t)n, P, C, ga, be, sig, W(h, "bn_part"), W(h, "bn_stat"), s);
+    else launch_instnorm_act(x, n, P, C, ga, be, sig, s);
 }
 
 extern "C" int desire_encode(desire_handle* h, const float* dev_past, const float* dev_fut, void* stream) {
@@ -124,49 +147,41 @@ extern "C" int desire_encode(desire_handle* h, const float* dev_past, const floa
     h->cp_enc = false;
     int Ae = A;
     const float* pastE = dev_past; const float* futE = dev_fut;
-    float* HxE = W(h, "HxHy"); float* plE = W(h, "p_last"); uint8_t* validE = static_cast<uint8_t*>(h->ws["valid"].p);
+    float* HxE = W(h, "HxHy"); float* plE = W(h, "p_last"); uint8_t* validE = Wt<uint8_t>(h, "valid");
     float* paramsE = W(h, "params");
     const int32_t* amap = nullptr;
     if (enc_c) {
         if (int rc = compact_setup(h)) return rc;
         if (dyn) {
-            dynP = static_cast<const int32_t*>(h->ws["cp_count"].p);
-            // a GUESS of P for choices that are about speed only (which variant of a row GEMM): whatever the mapped word holds -- the previous call's count, or
-            // this one's if the scan has already run.  Never a bound: the grids are the worst case's and the kernels read the real count.
-            hintP = *static_cast<volatile int32_t*>(h->cp_host);
-            if (hintP < 0 || hintP > A) hintP = 0;
+            dynP = Wt<const int32_t>(h, "cp_count");
+            hintP = count_hint(h);
         }
         launch_valid_from_frames(dev_past, d.n_scenes, d.T_obs, d.mno, validE, s);
         if (int rc = compact_scans(h, s)) return rc;
         if (int rc = compact_wait(h, s)) return rc;
         int P = A;                                                       // device-side counts: the worst case sizes the launches
-        if (!dyn) {
-            P = *static_cast<volatile int32_t*>(h->cp_host);
-            if (P < 0 || P > A) return fail(DESIRE_ERR_HIP, "present-agent scan returned a count out of range");
-        }
+        if (!dyn) { if (int rc = present_count(h, &P)) return rc; }
         h->cp_P = dyn ? -1 : P; h->cp_enc = true; Ae = P;
         launch_fill_f32(W(h, "HxHy"), (size_t)A * 2 * H, 0.f, s); launch_fill_f32(W(h, "p_last"), (size_t)A * 2, 0.f, s);
         if (d.posterior) launch_fill_f32(W(h, "params"), (size_t)A * 2 * d.L, 0.f, s);
         if (P == 0) { HIPCHK(hipGetLastError()); return DESIRE_OK; }
-        amap = static_cast<const int32_t*>(h->ws["cp_amap"].p);
+        amap = Wt<const int32_t>(h, "cp_amap");
         launch_gather_frames(dev_past, W(h, "cp_past"), amap, P, d.T_obs, d.mno, s, dynP);
         if (d.posterior) launch_gather_frames(dev_fut, W(h, "cp_fut"), amap, P, d.T_pred, d.mno, s, dynP);
         pastE = W(h, "cp_past"); futE = W(h, "cp_fut");
-        HxE = W(h, "cp_HxHy"); plE = W(h, "cp_plast"); validE = static_cast<uint8_t*>(h->ws["cp_valid2"].p); paramsE = W(h, "cp_params");
+        HxE = W(h, "cp_HxHy"); plE = W(h, "cp_plast"); validE = Wt<uint8_t>(h, "cp_valid2"); paramsE = W(h, "cp_params");
     }
     EncArgs e{};
     e.n_scenes = enc_c ? 1 : d.n_scenes; e.mno = enc_c ? Ae : d.mno; e.sx = d.sx; e.sy = d.sy; e.H = H;
     e.frames = pastE; e.T = d.T_obs;
-    e.wx_g = D(h, "enc_x/gk"); e.b_g = D(h, "enc_x/gb"); e.wx_c = D(h, "enc_x/ck"); e.b_c = D(h, "enc_x/cb");
-    e.Whg = D4(h, "enc_x/Whg"); e.Whc = D4(h, "enc_x/Whc");
+    enc_weights(h, "enc_x", e);
     e.out = HxE; e.ldo = 2 * H; e.p_last = plE; e.valid = validE;
     e.dyn = DynCount{dynP, 1, hintP};
     if (h->training) { e.sv_r = W(h, "ex_sv_r"); e.sv_u = W(h, "ex_sv_u"); e.sv_c = W(h, "ex_sv_c"); e.sv_h = W(h, "ex_sv_h"); e.sv_x = W(h, "ex_sv_x"); }
     const EncArgs ex = e;
     if (d.posterior) {
         e.frames = futE; e.T = d.T_pred;
-        e.wx_g = D(h, "enc_y/gk"); e.b_g = D(h, "enc_y/gb"); e.wx_c = D(h, "enc_y/ck"); e.b_c = D(h, "enc_y/cb");
-        e.Whg = D4(h, "enc_y/Whg"); e.Whc = D4(h, "enc_y/Whc");
+        enc_weights(h, "enc_y", e);
         e.out = HxE + H; e.p_last = nullptr; e.valid = nullptr;
         if (h->training) { e.sv_r = W(h, "ey_sv_r"); e.sv_u = W(h, "ey_sv_u"); e.sv_c = W(h, "ey_sv_c"); e.sv_h = W(h, "ey_sv_h"); e.sv_x = W(h, "ey_sv_x"); }
     }
@@ -198,23 +213,17 @@ extern "C" int desire_encode(desire_handle* h, const float* dev_past, const floa
         c.in = W(h, "vae_in"); c.out = W(h, "c1"); c.w_raw = D(h, "vae_enc/conv1/raw");
         c.scale = D(h, "vae_enc/conv1/scale"); c.shift = D(h, "vae_enc/conv1/shift");
         const bool pobn = d.bn_mode != 0;                 // batch statistics: linear conv epilogue, then a normalise + activate pass per layer
-        auto norm = [&](const char* layer, float* x, int n, int P, int C, int sig) {     // 1: per sample (k_instnorm_act), 2: over the whole batch
-            const float* ga = D(h, (std::string(layer) + "/gamma").c_str()); const float* be = D(h, (std::string(layer) + "/beta").c_str());
-            if (h->training)            // the batch-statistics backward needs the pre-norm tensor: kept next to the activation
-                launch_copy_f32(W(h, (std::string(layer).substr(std::string(layer).rfind('/') + 1) + "_pre").c_str()), x, (size_t)n * P * C, s);
-            if (d.bn_mode == 2) launch_batchnorm_act(x, (size_t)n, P, C, ga, be, sig, W(h, "bn_part"), W(h, "bn_stat"), s);
-            else launch_instnorm_act(x, n, P, C, ga, be, sig, s);
-        };
+        auto norm = [&](const char* layer, float* x, int P, int C) { batch_stats_act(h, layer, x, Ae, P, C, 0, s); };
         if (pobn) c.mode = 3;
-        { Timer t(h, s, "conv1"); launch_conv1(c, s); if (pobn) norm("vae_enc/conv1", W(h, "c1"), Ae, 256, 32, 0); }
+        { Timer t(h, s, "conv1"); launch_conv1(c, s); if (pobn) norm("vae_enc/conv1", W(h, "c1"), 256, 32); }
         c.in = W(h, "c1"); c.out = W(h, "c2"); c.Wp = D4(h, "vae_enc/conv2/W");
         c.scale = D(h, "vae_enc/conv2/scale"); c.shift = D(h, "vae_enc/conv2/shift");
         if (d.bf16 == 1) { c.Wp = D4(h, "vae_enc/conv2/W16"); Timer t(h, s, "conv2"); launch_conv2_bf16(c, s); }
-        else { Timer t(h, s, "conv2"); launch_conv2(c, s); if (pobn) norm("vae_enc/conv2", W(h, "c2"), Ae, 64, 64, 0); }
+        else { Timer t(h, s, "conv2"); launch_conv2(c, s); if (pobn) norm("vae_enc/conv2", W(h, "c2"), 64, 64); }
         c.in = W(h, "c2"); c.out = W(h, "c3"); c.Wp = D4(h, "vae_enc/conv3/W");
         c.scale = D(h, "vae_enc/conv3/scale"); c.shift = D(h, "vae_enc/conv3/shift");
         if (d.bf16 == 1) { c.Wp = D4(h, "vae_enc/conv3/W16"); Timer t(h, s, "conv3"); launch_conv3_bf16(c, s); }
-        else { Timer t(h, s, "conv3"); launch_conv3(c, s); if (pobn) norm("vae_enc/conv3", W(h, "c3"), Ae, 16, 128, 0); }
+        else { Timer t(h, s, "conv3"); launch_conv3(c, s); if (pobn) norm("vae_enc/conv3", W(h, "c3"), 16, 128); }
         g = GemmArgs{};
         g.A = W(h, "c3"); g.lda = 2048; g.M = Ae; g.K = 2048; g.Bp = D4(h, "vae_enc/fc/W"); g.G = 2048 / 8;
         g.NT = (2 * d.L + 31) / 32; g.out = paramsE; g.ldo = 2 * d.L; g.N = 2 * d.L; g.p0 = D(h, "vae_enc/fc/b");
@@ -238,15 +247,12 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
     const float* HxS = W(h, "HxHy"); const float* plS = W(h, "p_last"); float* Yout = W(h, "Y0");
     const bool compact = compact_rows(h);
     const bool dyn = compact && compact_dyn(h);
-    const int32_t* dynP = dyn ? static_cast<const int32_t*>(h->ws["cp_count"].p) : nullptr;      // device-side count: launches sized for P = A
+    const int32_t* dynP = dyn ? Wt<const int32_t>(h, "cp_count") : nullptr;      // device-side count: launches sized for P = A
     h->cp_last = compact;
     if (compact) {
         if (int rc = compact_wait(h, s)) return rc;
         int P = h->A;
-        if (!dyn) {
-            P = *static_cast<volatile int32_t*>(h->cp_host);
-            if (P < 0 || P > h->A) return fail(DESIRE_ERR_HIP, "present-agent scan returned a count out of range");
-        }
+        if (!dyn) { if (int rc = present_count(h, &P)) return rc; }
         h->cp_P = dyn ? -1 : P;
         R = P * d.K; mno = P;
         const size_t RT2 = (size_t)h->R * d.T_pred * 2;
@@ -255,7 +261,7 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
             HIPCHK(hipGetLastError());
             return DESIRE_OK;
         }
-        const int32_t* amap = static_cast<const int32_t*>(h->ws["cp_amap"].p);
+        const int32_t* amap = Wt<const int32_t>(h, "cp_amap");
         Timer t(h, s, "compact_gather");
         if (!h->cp_enc) {           // (an encoder stack that ran compact has left all three in place)
             launch_gather_agents(W(h, "HxHy"), W(h, "cp_HxHy"), amap, P, 2 * H, s, dynP);
@@ -264,21 +270,15 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
         }
         HxS = W(h, "cp_HxHy"); plS = W(h, "cp_plast"); Yout = W(h, "cp_Y0");
     }
-    if (compact) { Timer t(h, s, "reparam"); launch_reparam_c(W(h, "cp_params"), dev_eps, W(h, "z"), static_cast<const int32_t*>(h->ws["cp_amap"].p), mno, d.K, d.mno, d.L, d.posterior, s, dynP); }
+    if (compact) { Timer t(h, s, "reparam"); launch_reparam_c(W(h, "cp_params"), dev_eps, W(h, "z"), Wt<const int32_t>(h, "cp_amap"), mno, d.K, d.mno, d.L, d.posterior, s, dynP); }
     else { Timer t(h, s, "reparam"); launch_reparam(W(h, "params"), dev_eps, W(h, "z"), R, d.L, d.K, d.mno, d.posterior, s); }
-    auto normd = [&](const char* layer, float* x, int P, int C, int sig) {          // batch statistics of the decoder layers (see desire_encode)
-        const float* ga = D(h, (std::string(layer) + "/gamma").c_str()); const float* be = D(h, (std::string(layer) + "/beta").c_str());
-        if (h->training)
-            launch_copy_f32(W(h, (std::string(layer).substr(std::string(layer).rfind('/') + 1) + "_pre").c_str()), x, (size_t)R * P * C, s);
-        if (d.bn_mode == 2) launch_batchnorm_act(x, (size_t)R, P, C, ga, be, sig, W(h, "bn_part"), W(h, "bn_stat"), s);
-        else launch_instnorm_act(x, R, P, C, ga, be, sig, s);
-    };
+    auto normd = [&](const char* layer, float* x, int P, int C, int sig) { batch_stats_act(h, layer, x, R, P, C, sig, s); };
     GemmArgs g{};
     g.A = W(h, "z"); g.lda = d.L; g.M = R; g.K = d.L; g.Bp = D4(h, "vae_dec/deconv1/W"); g.G = d.L / 8;
     g.NT = 64; g.out = W(h, "d1"); g.ldo = 2048; g.N = 2048;
     g.p0 = D(h, "vae_dec/deconv1/scale"); g.p1 = D(h, "vae_dec/deconv1/shift"); g.chmod = 128;
     int hintS = 0;                                                       // count hint for this call's launches (see desire_encode)
-    if (dyn) { const int hp = *static_cast<volatile int32_t*>(h->cp_host); hintS = (hp > 0 && hp <= h->A) ? hp : 0; }
+    if (dyn) hintS = count_hint(h);
     g.dyn = DynCount{dynP, d.K, hintS}; g.M_hint = hintS * d.K;
     // six-product sample generation (the fp32 kernels' accuracy class on the bf16 matrix pipe): dims.bf16 = 3, and dims.bf16 = 2 as well --
     // two-piece operands are an IOC-kernel matter (sample generation must not move Y0 by more than fp32 rounding)
@@ -351,7 +351,7 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
         Timer t(h, s, "compact_scatter");
         const size_t RT2 = (size_t)h->R * d.T_pred * 2;
         launch_fill_f32(W(h, "Y0"), RT2, 0.f, s); launch_fill_f32(dev_Yhat, RT2, 0.f, s);
-        launch_scatter_rows(Yout, W(h, "Y0"), dev_Yhat, static_cast<const int32_t*>(h->ws["cp_amap"].p), mno, d.K, d.mno, d.T_pred * 2, s, dynP);
+        launch_scatter_rows(Yout, W(h, "Y0"), dev_Yhat, Wt<const int32_t>(h, "cp_amap"), mno, d.K, d.mno, d.T_pred * 2, s, dynP);
     } else
         launch_copy_f32(dev_Yhat, W(h, "Y0"), (size_t)R * d.T_pred * 2, s);
     HIPCHK(hipGetLastError());
@@ -359,16 +359,14 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
 }
 
 int ioc_cluster_exchange(desire_ctx* h, size_t n_groups, bool reset_err, hipStream_t s) {
-    if (!h->ws.count("hex") && (h->ws["hex"].alloc((size_t)2 * h->R * h->d.H * sizeof(float)) || h->ws["grp_cnt"].alloc(((size_t)h->R / 32 + 1) * sizeof(int)) ||
-                                h->ws["ioc_err"].alloc(sizeof(int))))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the cluster exchange buffers");
-    HIPCHK(hipMemsetAsync(h->ws["grp_cnt"].p, 0, n_groups * sizeof(int), s));
-    if (reset_err) HIPCHK(hipMemsetAsync(h->ws["ioc_err"].p, 0, sizeof(int), s));
+    if (int rc = ws_ensure(h, {{"hex", (size_t)2 * h->R * h->d.H * sizeof(float)}, {"grp_cnt", ((size_t)h->R / 32 + 1) * sizeof(int)}, {"ioc_err", sizeof(int)}})) return rc;
+    HIPCHK(hipMemsetAsync(W(h, "grp_cnt"), 0, n_groups * sizeof(int), s));
+    if (reset_err) HIPCHK(hipMemsetAsync(W(h, "ioc_err"), 0, sizeof(int), s));
     return DESIRE_OK;
 }
 int ioc_cluster_check(desire_ctx* h, hipStream_t s, const char* what) {
     int err = 0;
-    HIPCHK(hipMemcpyAsync(&err, h->ws["ioc_err"].p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&err, W(h, "ioc_err"), sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return err ? fail(DESIRE_ERR_HIP, std::string(what) + " hand-off timed out (workgroups of a group were not co-resident)") : DESIRE_OK;
 }
@@ -401,16 +399,13 @@ static int ioc_core(desire_handle* h, const IocView& v, hipStream_t s) {
     if (!p.fp32_weights()) { a.Wsoc = D4(h, "ioc/Wsoc16"); a.Wg = D4(h, "ioc/Wg16"); a.Wc = D4(h, "ioc/Wc16"); a.Wreg = D4(h, "ioc/Wreg16"); }
     if (p.cluster()) {
         if (int rc = ioc_cluster_exchange(h, (size_t)v.R / v.mno, true, s)) return rc;
-        a.hex = W(h, "hex"); a.grp_cnt = static_cast<int*>(h->ws["grp_cnt"].p); a.err = static_cast<int*>(h->ws["ioc_err"].p);
+        a.hex = W(h, "hex"); a.grp_cnt = Wt<int>(h, "grp_cnt"); a.err = Wt<int>(h, "ioc_err");
     }
     if (p.nspl > 1) {
         const size_t tiles = ((size_t)v.R + 31) / 32, tiles_max = ((size_t)h->R + 31) / 32;
-        if ((!h->ws.count("hex_s") || !h->ws["hex_s"].p || !h->ws["cnt_s"].p) &&
-            (h->ws["hex_s"].alloc(tiles_max * 2 * 4 * 32 * d.H * sizeof(float)) || h->ws["cnt_s"].alloc(tiles_max * sizeof(int))))
-            return fail(DESIRE_ERR_HIP, "hipMalloc failed for the bin-split exchange buffers");
+        if (int rc = ws_ensure(h, {{"hex_s", tiles_max * 2 * 4 * 32 * d.H * sizeof(float)}, {"cnt_s", tiles_max * sizeof(int)}})) return rc;
         // the error word is mapped host memory: no read-back (and no stream synchronisation) per call; a timed-out hand-off is
-        // reported by the NEXT call on this handle.  Allocated and checked on its own (a failure here must not leave a later call
-        // with exchange buffers and a null word); the kernels write it with system-scope atomics.
+        // reported by the NEXT call on this handle.  The kernels write it with system-scope atomics.
         if (!h->host_err) {
             if (hipHostMalloc(reinterpret_cast<void**>(&h->host_err), sizeof(int), hipHostMallocMapped) != hipSuccess || !h->host_err)
                 { h->host_err = nullptr; return fail(DESIRE_ERR_HIP, "hipHostMalloc failed for the bin-split error word"); }
@@ -423,12 +418,12 @@ static int ioc_core(desire_handle* h, const IocView& v, hipStream_t s) {
         // (a fill KERNEL, not hipMemsetAsync: memset nodes of a captured graph were seen to run out of order on replay -- section 6a --
         //  and a counter that still holds the previous pass's arrivals lets every member read its peers' slots before they are written)
         launch_fill_f32(W(h, "cnt_s"), tiles, 0.f, s);
-        a.hex = W(h, "hex_s"); a.grp_cnt = static_cast<int*>(h->ws["cnt_s"].p); a.err = h->host_err;
+        a.hex = W(h, "hex_s"); a.grp_cnt = Wt<int>(h, "cnt_s"); a.err = h->host_err;
         a.nspl = p.nspl;
     }
 #ifdef DESIRE_IOC_TIMING
-    if (!h->ws.count("dbg")) { h->ws["dbg"].alloc(10 * sizeof(long long)); }
-    a.dbg = static_cast<long long*>(h->ws["dbg"].p);
+    if (int rc = ws_ensure(h, {{"dbg", 10 * sizeof(long long)}})) return rc;
+    a.dbg = Wt<long long>(h, "dbg");
 #endif
     // training-mode forward: one launch per refinement pass, each keeping its own activations and the positions it ran on (the pass's input is
     // DETACHED where it enters the features -- cells, bins, velocity embedding -- and Y_p = Y_{p-1} + dY_p carries the gradient: DESIGN.md section 8)
@@ -481,24 +476,17 @@ extern "C" int desire_ioc_refine(desire_handle* h, float* dev_Yhat, float* dev_s
     if (ioc_plan(h).fwd == IocFwd::STEPWISE) {        // one launch of the agent-sharded kernel per step, a single rank (ioc_plan.h)
         if (h->training) return fail(DESIRE_ERR_STATE, "training supports up to 128 agents per scene");
         const size_t RH = (size_t)h->R * d.H;
-        if ((!h->ws.count("stw_h") || !h->ws["stw_h"].p || !h->ws["stw_sc"].p) &&
-            ((!h->ws["stw_h"].p && h->ws["stw_h"].alloc(2 * RH * sizeof(float))) || (!h->ws["stw_sc"].p && h->ws["stw_sc"].alloc((size_t)h->R * sizeof(float)))))
-            return fail(DESIRE_ERR_HIP, "hipMalloc failed for the step-wise IOC state");
+        if (int rc = ws_ensure(h, {{"stw_h", 2 * RH * sizeof(float)}, {"stw_sc", (size_t)h->R * sizeof(float)}})) return rc;
         float* hb[2] = {W(h, "stw_h"), W(h, "stw_h") + RH};
         const int NTs = d.H / 32, KXs = d.E_v + d.C + 2 * d.H;
         for (int it = 0; it < d.iters; ++it) {
             launch_hx_rows(hb[1], W(h, "HxHy"), 2 * d.H, d.n_scenes, d.K, d.mno, d.H, s);       // h_{-1} = Hx of the row's agent
             Timer tm(h, s, "ioc");                                                            // (one profile entry per pass, as for the persistent kernels)
             for (int t = 0; t < d.T_pred; ++t) {
-                IocStepArgs q{};
-                q.t = t; q.rank = 0; q.nranks = 1; q.m_loc = d.mno; q.n_scenes = d.n_scenes; q.K = d.K; q.R = h->R;
-                q.H = d.H; q.T = d.T_pred; q.Gh = d.Gh; q.Gw = d.Gw; q.G = d.grid_size; q.nb_w = d.nb_w; q.nb_h = d.nb_h;
-                q.Yall = dev_Yhat; q.plast_all = W(h, "p_last"); q.valid_all = static_cast<const uint8_t*>(h->ws["valid"].p); q.Hall = hb[(t + 1) & 1];
+                IocStepArgs q = ioc_step_args(h, t);
+                q.rank = 0; q.nranks = 1;
+                q.Yall = dev_Yhat; q.plast_all = W(h, "p_last"); q.valid_all = Wt<const uint8_t>(h, "valid"); q.Hall = hb[(t + 1) & 1];
                 q.st_h = hb[(t + 1) & 1]; q.st_h_out = hb[t & 1]; q.st_score = W(h, "stw_sc");
-                q.grids = h->grids; q.grid_of_scene = static_cast<const int32_t*>(h->ws["grid_of_scene"].p);
-                q.w_vel = D(h, "ioc/vel_w"); q.b_vel = D(h, "ioc/vel_b"); q.Wsoc = D4(h, "ioc/Wsoc"); q.b_soc = D(h, "ioc/soc_b");
-                q.Wg = D4(h, "ioc/Wg"); q.Wc = D4(h, "ioc/Wc"); q.b_g = D(h, "ioc/gb"); q.b_c = D(h, "ioc/cb"); q.w_score = D(h, "ioc/score_w");
-                q.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
                 if (d.bf16 == 2 || d.bf16 == 3) {
                     q.np = d.bf16 == 3 ? 3 : 2;
                     q.Wsoc = D4(h, "ioc/Wsoc16l"); q.Wg = D4(h, "ioc/Wg16"); q.Wc = D4(h, "ioc/Wc16");
@@ -529,10 +517,10 @@ extern "C" int desire_ioc_refine(desire_handle* h, float* dev_Yhat, float* dev_s
         for (int c = 0; c < L.n; ++c) {
             if (L.c[c].n_scenes == 0) continue;
             IocView v = ioc_view(h, &L.c[c]);
-            if (dyn) v.dynN = static_cast<const int32_t*>(h->ws["cp_count"].p) + 4 + c;
+            if (dyn) v.dynN = Wt<const int32_t>(h, "cp_count") + 4 + c;
             {
                 Timer t(h, s, "ioc_repack");
-                launch_cls_gather_agents(W(h, "HxHy"), 2 * d.H, W(h, "p_last"), static_cast<const int32_t*>(h->ws["grid_of_scene"].p), v.cmap, v.win, v.n_scenes, v.mno,
+                launch_cls_gather_agents(W(h, "HxHy"), 2 * d.H, W(h, "p_last"), Wt<const int32_t>(h, "grid_of_scene"), v.cmap, v.win, v.n_scenes, v.mno,
                                          v.Hx, v.p_last, v.valid, v.gos, s, v.dynN);
                 launch_cls_rows(dev_Yhat, v.Y, v.cmap, v.n_scenes, v.mno, d.K, d.mno, T2, 0, s, v.gpt, v.dynN);
             }

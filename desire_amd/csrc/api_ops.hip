@@ -32,10 +32,7 @@ extern "C" int desire_scene_cnn(desire_handle* h, const float* dev_image, int32_
     if (Hi != 4 * d.Gh || Wi != 4 * d.Gw) return fail(DESIRE_ERR_ARG, "scene image must be [n_grids, 4*Gh, 4*Gw, 3]");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t n1 = (size_t)d.n_grids * (Hi / 2) * (Wi / 2) * 16, n2 = (size_t)d.n_grids * d.Gh * d.Gw * 32;
-    if (!h->ws.count("scnn1")) {
-        if (h->ws["scnn1"].alloc(n1 * sizeof(float)) || h->ws["scnn2"].alloc(n2 * sizeof(float)))
-            return fail(DESIRE_ERR_HIP, "hipMalloc failed for the scene CNN workspace");
-    }
+    if (int rc = ws_ensure(h, {{"scnn1", n1 * sizeof(float)}, {"scnn2", n2 * sizeof(float)}})) return rc;
     { Timer t(h, s, "scene_cnn");
       launch_conv_direct(dev_image, D(h, "scene_cnn/conv1/w"), D(h, "scene_cnn/conv1/b"), W(h, "scnn1"), d.n_grids, Hi, Wi, 3, 16, 2, 1, s);
       launch_conv_direct(W(h, "scnn1"), D(h, "scene_cnn/conv2/w"), D(h, "scene_cnn/conv2/b"), W(h, "scnn2"), d.n_grids, Hi / 2, Wi / 2, 16, 32, 2, 1, s);
@@ -59,9 +56,8 @@ extern "C" int desire_losses(desire_handle* h, const float* dev_fut, const float
     if (!d.posterior) return fail(DESIRE_ERR_STATE, "losses need the posterior path (dims.posterior = 1)");
     if (d.ref_compat) return fail(DESIRE_ERR_STATE, "ref_compat has no trajectory head: the reference's cost has undefined inputs (model/model.py:342)");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    launch_loss_mask(static_cast<const uint8_t*>(h->ws["valid"].p), dev_fut, static_cast<uint8_t*>(h->ws["lmask"].p), W(h, "nfut"),
-                     d.n_scenes, d.mno, d.T_pred, s);
-    launch_losses(W(h, "params"), dev_Yhat, dev_fut, static_cast<const uint8_t*>(h->ws["lmask"].p), W(h, "nfut"), dev_kld, dev_recon,
+    launch_loss_mask(Wt<const uint8_t>(h, "valid"), dev_fut, Wt<uint8_t>(h, "lmask"), W(h, "nfut"), d.n_scenes, d.mno, d.T_pred, s);
+    launch_losses(W(h, "params"), dev_Yhat, dev_fut, Wt<const uint8_t>(h, "lmask"), W(h, "nfut"), dev_kld, dev_recon,
                   dev_cost, d.n_scenes, d.mno, d.K, d.T_pred, d.L, d.sx, d.sy, s);
     HIPCHK(hipGetLastError());
     return DESIRE_OK;
@@ -136,12 +132,11 @@ extern "C" int desire_rollout(desire_handle* h, const float* dev_past, const flo
     if (num < 1) return fail(DESIRE_ERR_ARG, "num must be >= 1");
     const desire_dims& d = h->d;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!h->ws.count("roll_h") && h->ws["roll_h"].alloc((size_t)h->A * d.H * sizeof(float))) return fail(DESIRE_ERR_HIP, "hipMalloc failed");
+    if (int rc = ws_ensure(h, {{"roll_h", (size_t)h->A * d.H * sizeof(float)}})) return rc;
     EncArgs e{};
     e.n_scenes = d.n_scenes; e.mno = d.mno; e.sx = d.sx; e.sy = d.sy; e.H = d.H;
     e.frames = dev_past; e.T = d.T_obs;
-    e.wx_g = D(h, "enc_x/gk"); e.b_g = D(h, "enc_x/gb"); e.wx_c = D(h, "enc_x/ck"); e.b_c = D(h, "enc_x/cb");
-    e.Whg = D4(h, "enc_x/Whg"); e.Whc = D4(h, "enc_x/Whc");
+    enc_weights(h, "enc_x", e);
     e.out = W(h, "roll_h"); e.ldo = d.H;
     e.n_roll = num; e.w5 = D(h, "gauss_head/w"); e.b5 = D(h, "gauss_head/b"); e.normals = dev_normals; e.roll_out = dev_out;
     { Timer t(h, s, "rollout"); launch_encoder(e, s); }
@@ -195,7 +190,7 @@ extern "C" int desire_ranked_errors(desire_handle* h, const float* dev_Yhat, con
     }
     int sc = 0, kc = 0;
     if (!sample_errors_geometry(d.mno, d.K, d.T_pred, &sc, &kc)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the error kernel's LDS");
-    launch_ranked_errors(dev_Yhat, dev_fut, dev_order, W(h, "rank_tab"), static_cast<int32_t*>(h->ws.at("rank_cnt").p), dev_out, d.n_scenes,
+    launch_ranked_errors(dev_Yhat, dev_fut, dev_order, W(h, "rank_tab"), Wt<int32_t>(h, "rank_cnt"), dev_out, d.n_scenes,
                          d.mno, d.K, d.T_pred, n_top, hz, d.sx, d.sy, unit_x, unit_y, static_cast<hipStream_t>(stream));
     HIPCHK(hipGetLastError());
     return DESIRE_OK;

@@ -64,7 +64,7 @@ int desire_pack_all(desire_ctx* h) {
     bad |= up("ioc/Wc", pack_b(E + H, H, rowmajor(hw["ioc/candidate/kernel"], H, 0)));
     {   // transposed blocks for the IOC BPTT: B(k', n') = W[row0 + n'][k']
         const auto& gk = hw["ioc/gates/kernel"]; const auto& ck = hw["ioc/candidate/kernel"];
-        const auto& wr = hw["ioc/reg/w"]; const auto& ws = hw["ioc/social_fc/w"];
+        const auto& wr = hw["ioc/reg/w"]; const auto& wsoc = hw["ioc/social_fc/w"];
         const int xr = d.E_v + d.C;                      // first e_r row of the GRU kernels
         const int T2 = 2 * d.T_pred, KR = (T2 + 7) / 8 * 8;
         bad |= up("ioc/WgT_h", pack_b(2 * H, H, [&](int k, int n) { return gk[(size_t)(E + n) * 2 * H + k]; }));
@@ -76,7 +76,7 @@ int desire_pack_all(desire_ctx* h) {
         bad |= up("ioc/WrT", pack_b(KR, H, [&](int k, int n) { return k < T2 ? wr[(size_t)n * T2 + k] : 0.f; }));
         std::vector<float> all;
         for (int b = 0; b < B; ++b) {
-            auto pk = pack_b(H, H, [&](int k, int n) { return ws[((size_t)b * H + n) * H + k]; });
+            auto pk = pack_b(H, H, [&](int k, int n) { return wsoc[((size_t)b * H + n) * H + k]; });
             all.insert(all.end(), pk.begin(), pk.end());
         }
         bad |= up("ioc/WsT", all);
@@ -90,7 +90,7 @@ int desire_pack_all(desire_ctx* h) {
                         for (int lane = 0; lane < 64; ++lane)
                             for (int j = 0; j < 4; ++j)
                                 tc[((((size_t)b * T16 + ct) * T16 + g) * 64 + lane) * 4 + j] =
-                                    ws[((size_t)b * H + 16 * ct + (lane & 15)) * H + 16 * g + 4 * (lane >> 4) + j];
+                                    wsoc[((size_t)b * H + 16 * ct + (lane & 15)) * H + 16 * g + 4 * (lane >> 4) + j];
             bad |= up("ioc/WsT_c", tc);
         }
     }
@@ -98,7 +98,7 @@ int desire_pack_all(desire_ctx* h) {
                                          // dims.bf16 = 3: [hi | mid | lo], one more piece of the remainder (w = hi + mid + lo exactly)
         const size_t np_default = d.bf16 == 3 ? 3 : 2;
         const auto& gk = hw["ioc/gates/kernel"]; const auto& ck = hw["ioc/candidate/kernel"];
-        const auto& wr = hw["ioc/reg/w"]; const auto& ws = hw["ioc/social_fc/w"];
+        const auto& wr = hw["ioc/reg/w"]; const auto& wsoc = hw["ioc/social_fc/w"];
         auto lin = [](int g, int hi, int e) { return 16 * g + 8 * hi + e; };
         auto chain = [](int g, int hi, int e) { const int hb = g >> 1, r = 8 * (g & 1) + e; return 32 * hb + (r & 3) + 8 * (r >> 2) + 4 * hi; };
         // vals = one fp32 value per bf16 slot.  While the repack maps are being built (pack_mode 1: values are index codes) the
@@ -124,14 +124,14 @@ int desire_pack_all(desire_ctx* h) {
         bad |= up_split("ioc/Wreg16", pack_vals16(H, 2 * d.T_pred, lin, [&](int k, int n) { return wr[(size_t)k * 2 * d.T_pred + n]; }));
         std::vector<float> all;
         for (int b = 0; b < B; ++b) {
-            const auto pv = pack_vals16(H, H, chain, [&](int k, int n) { return ws[((size_t)b * H + k) * H + n]; });
+            const auto pv = pack_vals16(H, H, chain, [&](int k, int n) { return wsoc[((size_t)b * H + k) * H + n]; });
             all.insert(all.end(), pv.begin(), pv.end());
         }
         bad |= up_split("ioc/Wsoc16", all);
         if (d.mno > 128 || d.H == 256) {     // shapes served by the step-wise split kernel (k_ioc_step<.., NP>): the pooled operand is a plain
             std::vector<float> alll;          // fp32 tile there, so the social weights are wanted in plain k order as well
             for (int b = 0; b < B; ++b) {
-                const auto pv = pack_vals16(H, H, lin, [&](int k, int n) { return ws[((size_t)b * H + k) * H + n]; });
+                const auto pv = pack_vals16(H, H, lin, [&](int k, int n) { return wsoc[((size_t)b * H + k) * H + n]; });
                 alll.insert(alll.end(), pv.begin(), pv.end());
             }
             bad |= up_split("ioc/Wsoc16l", alll);
@@ -154,7 +154,7 @@ int desire_pack_all(desire_ctx* h) {
                     return n < H ? gk[(size_t)(E + n) * 2 * H + k] : n < 2 * H ? gk[(size_t)(xr + n - H) * 2 * H + k] : (n - 2 * H < d.E_v ? gk[(size_t)(n - 2 * H) * 2 * H + k] : 0.f); }));
                 std::vector<float> allT;
                 for (int b = 0; b < B; ++b) {
-                    const auto pv = pack_vals16(H, H, lin, [&](int k, int n) { return ws[((size_t)b * H + n) * H + k]; });
+                    const auto pv = pack_vals16(H, H, lin, [&](int k, int n) { return wsoc[((size_t)b * H + n) * H + k]; });
                     allT.insert(allT.end(), pv.begin(), pv.end());
                 }
                 bad |= up_split("ioc/WsT16", allT);
@@ -187,7 +187,7 @@ int desire_pack_all(desire_ctx* h) {
     }
     if (d.bf16 == 1) {   // bf16 operand packs of the IOC kernel (kernels_bf16.hip)
         const auto& gk = hw["ioc/gates/kernel"]; const auto& ck = hw["ioc/candidate/kernel"];
-        const auto& wr = hw["ioc/reg/w"]; const auto& ws = hw["ioc/social_fc/w"];
+        const auto& wr = hw["ioc/reg/w"]; const auto& wsoc = hw["ioc/social_fc/w"];
         auto lin = [](int g, int hi, int e) { return 16 * g + 8 * hi + e; };
         // chain order: k-slot (hi, e) of group g = 2*hb + g2 holds hidden 32*hb + rowmap(8*g2 + e, hi), the accumulator
         // row a lane of the pooling MFMA owns (rowmap(r, hi) = (r&3) + 8*(r>>2) + 4*hi)
@@ -197,7 +197,7 @@ int desire_pack_all(desire_ctx* h) {
         bad |= up("ioc/Wreg16", pack_b16(H, 2 * d.T_pred, lin, [&](int k, int n) { return wr[(size_t)k * 2 * d.T_pred + n]; }));
         std::vector<float> all;
         for (int b = 0; b < B; ++b) {
-            auto pk = pack_b16(H, H, chain, [&](int k, int n) { return ws[((size_t)b * H + k) * H + n]; });
+            auto pk = pack_b16(H, H, chain, [&](int k, int n) { return wsoc[((size_t)b * H + k) * H + n]; });
             all.insert(all.end(), pk.begin(), pk.end());
         }
         bad |= up("ioc/Wsoc16", all);
@@ -257,7 +257,7 @@ int desire_pack_all(desire_ctx* h) {
     }
     {   // the same weights for the row-compacted pooling (16x16x4 MFMA tiles, kernels_rnn.hip k_ioc<..., CP>): per bin, per
         // 16-column tile ct and 16-k group g, lane (col = lane&15, q = lane>>4) holds W_b[16g + 4q + 0..3][16ct + col]
-        const auto& ws = hw["ioc/social_fc/w"];
+        const auto& wsoc = hw["ioc/social_fc/w"];
         const int T16 = H / 16;
         std::vector<float> all((size_t)B * H * H);
         for (int b = 0; b < B; ++b)
@@ -266,7 +266,7 @@ int desire_pack_all(desire_ctx* h) {
                     for (int lane = 0; lane < 64; ++lane)
                         for (int j = 0; j < 4; ++j)
                             all[((((size_t)b * T16 + ct) * T16 + g) * 64 + lane) * 4 + j] =
-                                ws[((size_t)b * H + 16 * g + 4 * (lane >> 4) + j) * H + 16 * ct + (lane & 15)];
+                                wsoc[((size_t)b * H + 16 * g + 4 * (lane >> 4) + j) * H + 16 * ct + (lane & 15)];
         bad |= up("ioc/Wsoc_c", all);
     }
     bad |= up("ioc/soc_b", hw["ioc/social_fc/b"]);

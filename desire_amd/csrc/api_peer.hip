@@ -29,6 +29,20 @@ PeerLayout peer_layout(const desire_ctx* h) {
 }
 }  // namespace
 
+// What every launch of the step-wise kernel shares: step and shape, scene grids, the fp32 ioc/* weights, the bin table.  The callers add what
+// differs: rank and peers, the state pointers, the split packs with their plo_* offsets.
+IocStepArgs ioc_step_args(desire_ctx* h, int t) {
+    const desire_dims& d = h->d;
+    IocStepArgs a{};
+    a.t = t; a.m_loc = d.mno; a.n_scenes = d.n_scenes; a.K = d.K; a.R = h->R;
+    a.H = d.H; a.T = d.T_pred; a.Gh = d.Gh; a.Gw = d.Gw; a.G = d.grid_size; a.nb_w = d.nb_w; a.nb_h = d.nb_h;
+    a.grids = h->grids; a.grid_of_scene = Wt<const int32_t>(h, "grid_of_scene");
+    a.w_vel = D(h, "ioc/vel_w"); a.b_vel = D(h, "ioc/vel_b"); a.Wsoc = D4(h, "ioc/Wsoc"); a.b_soc = D(h, "ioc/soc_b");
+    a.Wg = D4(h, "ioc/Wg"); a.Wc = D4(h, "ioc/Wc"); a.b_g = D(h, "ioc/gb"); a.b_c = D(h, "ioc/cb"); a.w_score = D(h, "ioc/score_w");
+    a.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
+    return a;
+}
+
 extern "C" int desire_peer_export(desire_handle* h, uint8_t* handle_out64, size_t* bytes_out) {
     if (int rc = desire_ready(h)) return rc;
     if (!handle_out64) return fail(DESIRE_ERR_ARG, "null argument");
@@ -49,11 +63,9 @@ extern "C" int desire_peer_export(desire_handle* h, uint8_t* handle_out64, size_
             return fail(DESIRE_ERR_HIP, "hipHostMalloc failed for the peer error word");
         }
         *h->peer_err = 0;
-        for (const char* nm : {"peer_epoch", "peer_score", "peer_hT"}) h->ws[nm].release();          // (export after a close: no leak)
-        if (h->ws["peer_epoch"].alloc(sizeof(unsigned)) || h->ws["peer_score"].alloc((size_t)h->R * sizeof(float)) ||
-            h->ws["peer_hT"].alloc((size_t)h->R * h->d.H * sizeof(float)))
-            return fail(DESIRE_ERR_HIP, "hipMalloc failed for the peer buffers");
-        HIPCHK(hipMemset(h->ws["peer_epoch"].p, 0, sizeof(unsigned)));
+        // (export after a close: the three are still held and are used again)
+        if (int rc = ws_ensure(h, {{"peer_epoch", sizeof(unsigned)}, {"peer_score", (size_t)h->R * sizeof(float)}, {"peer_hT", (size_t)h->R * h->d.H * sizeof(float)}})) return rc;
+        HIPCHK(hipMemset(W(h, "peer_epoch"), 0, sizeof(unsigned)));
     }
     hipIpcMemHandle_t hd;
     HIPCHK(hipIpcGetMemHandle(&hd, h->peer_region));
@@ -148,22 +160,20 @@ extern "C" int desire_ioc_peer_pass(desire_handle* h, float* dev_Y, float* dev_s
     const unsigned pp = (unsigned)(T + 2);
     PeerFlags flags{};
     for (int r = 0; r < G; ++r) flags.f[r] = static_cast<const unsigned*>(h->peer_base[r]);
-    unsigned* epoch = static_cast<unsigned*>(h->ws["peer_epoch"].p);
+    unsigned* epoch = Wt<unsigned>(h, "peer_epoch");
     char* mine = static_cast<char*>(h->peer_region);
     float* Hpar[2] = {reinterpret_cast<float*>(mine + l.H0), reinterpret_cast<float*>(mine + l.H1)};
     for (int it = 0; it < d.iters; ++it) {
         launch_peer_epoch(epoch, s);
         launch_peer_wait(flags, G, epoch, pp, (unsigned)-1, h->peer_err, s);          // every peer has finished the previous pass: nobody reads my region
-        launch_peer_publish(static_cast<const uint8_t*>(h->ws["valid"].p), W(h, "p_last"), dev_Y, W(h, "HxHy"), 2 * d.H,
+        launch_peer_publish(Wt<const uint8_t>(h, "valid"), W(h, "p_last"), dev_Y, W(h, "HxHy"), 2 * d.H,
                             reinterpret_cast<uint8_t*>(mine + l.valid), reinterpret_cast<float*>(mine + l.plast), reinterpret_cast<float*>(mine + l.Y),
                             Hpar[1], d.n_scenes, d.K, d.mno, T, d.H, s);              // h_{-1} goes to parity 1 (= (0 - 1) & 1)
         launch_peer_set(reinterpret_cast<unsigned*>(mine), epoch, pp, 1u, s);
         for (int t = 0; t < T; ++t) {
             launch_peer_wait(flags, G, epoch, pp, (unsigned)(t + 1), h->peer_err, s);
-            IocStepArgs a{};
-            a.t = t; a.rank = h->peer_rank; a.nranks = G; a.m_loc = d.mno; a.n_scenes = d.n_scenes; a.K = d.K; a.R = h->R;
-            a.H = d.H; a.T = T; a.Gh = d.Gh; a.Gw = d.Gw; a.G = d.grid_size; a.nb_w = d.nb_w; a.nb_h = d.nb_h;
-            a.peer = 1;
+            IocStepArgs a = ioc_step_args(h, t);
+            a.rank = h->peer_rank; a.nranks = G; a.peer = 1;
             for (int r = 0; r < G; ++r) {
                 const char* b = static_cast<const char*>(h->peer_base[r]);
                 a.vp[r] = reinterpret_cast<const uint8_t*>(b + l.valid); a.plp[r] = reinterpret_cast<const float*>(b + l.plast);
@@ -171,10 +181,6 @@ extern "C" int desire_ioc_peer_pass(desire_handle* h, float* dev_Y, float* dev_s
             }
             a.st_h = Hpar[(t + 1) & 1]; a.st_h_out = Hpar[t & 1]; a.st_score = W(h, "peer_score");
             a.st_h_copy = (t == T - 1) ? W(h, "peer_hT") : nullptr;
-            a.grids = h->grids; a.grid_of_scene = static_cast<const int32_t*>(h->ws["grid_of_scene"].p);
-            a.w_vel = D(h, "ioc/vel_w"); a.b_vel = D(h, "ioc/vel_b"); a.Wsoc = D4(h, "ioc/Wsoc"); a.b_soc = D(h, "ioc/soc_b");
-            a.Wg = D4(h, "ioc/Wg"); a.Wc = D4(h, "ioc/Wc"); a.b_g = D(h, "ioc/gb"); a.b_c = D(h, "ioc/cb"); a.w_score = D(h, "ioc/score_w");
-            a.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
             { Timer tm(h, s, "ioc_step"); launch_ioc_step(a, s); }
             launch_peer_set(reinterpret_cast<unsigned*>(mine), epoch, pp, (unsigned)(t + 2), s);
         }
@@ -195,15 +201,10 @@ extern "C" int desire_ioc_step(desire_handle* h, int32_t t, int32_t rank, int32_
     if (t < 0 || t >= d.T_pred || nranks < 1 || rank < 0 || rank >= nranks) return fail(DESIRE_ERR_ARG, "bad step / rank");
     if ((long)d.mno * nranks > 256) return fail(DESIRE_ERR_ARG, "agent-sharded IOC: at most 256 agents per scene over all ranks");
     if (d.bf16 == 1) return fail(DESIRE_ERR_STATE, "agent-sharded IOC runs on fp32 operands");
-    IocStepArgs a{};
-    a.t = t; a.rank = rank; a.nranks = nranks; a.m_loc = d.mno; a.n_scenes = d.n_scenes; a.K = d.K; a.R = h->R;
-    a.H = d.H; a.T = d.T_pred; a.Gh = d.Gh; a.Gw = d.Gw; a.G = d.grid_size; a.nb_w = d.nb_w; a.nb_h = d.nb_h;
+    IocStepArgs a = ioc_step_args(h, t);
+    a.rank = rank; a.nranks = nranks;
     a.Yall = dev_Yall; a.plast_all = dev_plast_all; a.valid_all = dev_valid_all; a.Hall = dev_Hall;
     a.st_h = dev_h_state; a.st_h_out = dev_h_state; a.st_score = dev_score_state;
-    a.grids = h->grids; a.grid_of_scene = static_cast<const int32_t*>(h->ws["grid_of_scene"].p);
-    a.w_vel = D(h, "ioc/vel_w"); a.b_vel = D(h, "ioc/vel_b"); a.Wsoc = D4(h, "ioc/Wsoc"); a.b_soc = D(h, "ioc/soc_b");
-    a.Wg = D4(h, "ioc/Wg"); a.Wc = D4(h, "ioc/Wc"); a.b_g = D(h, "ioc/gb"); a.b_c = D(h, "ioc/cb"); a.w_score = D(h, "ioc/score_w");
-    a.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
     { Timer tm(h, s, "ioc_step"); launch_ioc_step(a, s); }
     HIPCHK(hipGetLastError());
@@ -217,7 +218,7 @@ extern "C" int desire_ioc_finish(desire_handle* h, const float* dev_h_state, con
     if (!dev_h_state || !dev_score_state || !dev_Y || !dev_score) return fail(DESIRE_ERR_ARG, "null argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int T2 = 2 * d.T_pred;
-    if (!h->ws.count("ioc_dY") && h->ws["ioc_dY"].alloc((size_t)h->R * T2 * sizeof(float))) return fail(DESIRE_ERR_HIP, "hipMalloc failed");
+    if (int rc = ws_ensure(h, {{"ioc_dY", (size_t)h->R * T2 * sizeof(float)}})) return rc;
     GemmArgs g{};
     g.A = dev_h_state; g.lda = d.H; g.M = h->R; g.K = d.H; g.Bp = D4(h, "ioc/Wreg"); g.G = d.H / 8; g.NT = (T2 + 31) / 32;
     g.out = W(h, "ioc_dY"); g.ldo = T2; g.N = T2; g.p0 = D(h, "ioc/reg_b");

@@ -26,7 +26,7 @@ void tn(desire_ctx* h, const float* A, int lda, const float* Gm, int ldg, long M
     long sl = big_tiles ? 512 / big_tiles : 2048 / blocks;
     if (sl < 1) sl = 1; if (sl > (big_tiles ? 512 : 256)) sl = big_tiles ? 512 : 256;
     const long maxsl = (M + 63) / 64; if (sl > maxsl) sl = maxsl;
-    while ((size_t)sl * Kd * N * sizeof(float) > h->ws["tn_partial"].bytes && sl > 1) sl /= 2;
+    while ((size_t)sl * Kd * N * sizeof(float) > h->ws.bytes("tn_partial") && sl > 1) sl /= 2;
     a.nslices = (int)sl; a.partial = W(h, "tn_partial");
     launch_gemm_tn(a, out, ldo, accumulate, s);
 }
@@ -130,10 +130,10 @@ struct BwdPass {
 BwdPass make_pass(desire_ctx* h, const float* dev_past, const float* dev_fut, const float* dev_eps, hipStream_t s) {
     BwdPass bp{};
     bp.h = h; bp.s = s; bp.past = dev_past; bp.fut = dev_fut; bp.eps = dev_eps;
-    bp.valid = static_cast<const uint8_t*>(h->ws["lmask"].p);
+    bp.valid = Wt<const uint8_t>(h, "lmask");
     const bool c = bp.rows_compact = h->cp_last, ce = bp.enc_compact = c && h->cp_enc;
     bp.n_present = c ? h->cp_P : 0;
-    bp.amap = c ? static_cast<const int32_t*>(h->ws["cp_amap"].p) : nullptr;
+    bp.amap = c ? Wt<const int32_t>(h, "cp_amap") : nullptr;
     bp.rows_s = c ? (long)bp.n_present * h->d.K : (long)h->R; bp.mno_s = c ? bp.n_present : h->d.mno;
     bp.Hx_s = c ? W(h, "cp_HxHy") : W(h, "HxHy"); bp.dHx_s = c ? W(h, "cp_dHx_rows") : W(h, "dHx_rows");
     bp.agents_e = ce ? bp.n_present : h->A; bp.mno_e = ce ? bp.n_present : h->d.mno;
@@ -145,13 +145,12 @@ BwdPass make_pass(desire_ctx* h, const float* dev_past, const float* dev_fut, co
 // and no hipMalloc falls between the launches of a call that may be under stream capture (everything else: desire_set_training).
 int backward_alloc(desire_ctx* h) {
     const size_t R = h->R, A = h->A, RS = ioc_save_rows(h), T = h->d.T_pred, H = h->d.H, f = sizeof(float);
-    if (h->cp_last && (ensure(h, "cp_dY0", R * T * 2 * f) || ensure(h, "cp_dHx_rows", R * H * f) || ensure(h, "cp_dHx", A * H * f)))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the compact-row gradient buffers");
-    if (h->cp_last && h->cp_enc && (ensure(h, "cp_dparams", A * 2 * h->d.L * f) || ensure(h, "cp_dHxHy", A * 2 * H * f) || ensure(h, "dHxHy_ioc", A * H * f)))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the compact encoder gradient buffers");
-    if (h->ci_last && (ensure(h, "ci_dYr", RS * T * 2 * f) || ensure(h, "ci_dscore", RS * f) || ensure(h, "ci_dscoreT", RS * T * f) ||
-                       ensure(h, "ci_dHx_rows", RS * H * f) || ensure(h, "ci_dHx", A * H * f) || ensure(h, "dHxHy_ioc", A * H * f)))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the slot-class gradient buffers");
+    if (h->cp_last) { if (int rc = ws_ensure(h, {{"cp_dY0", R * T * 2 * f}, {"cp_dHx_rows", R * H * f}, {"cp_dHx", A * H * f}})) return rc; }
+    if (h->cp_last && h->cp_enc) { if (int rc = ws_ensure(h, {{"cp_dparams", A * 2 * h->d.L * f}, {"cp_dHxHy", A * 2 * H * f}, {"dHxHy_ioc", A * H * f}})) return rc; }
+    if (h->ci_last) {
+        if (int rc = ws_ensure(h, {{"ci_dYr", RS * T * 2 * f}, {"ci_dscore", RS * f}, {"ci_dscoreT", RS * T * f}, {"ci_dHx_rows", RS * H * f}, {"ci_dHx", A * H * f},
+                                   {"dHxHy_ioc", A * H * f}})) return rc;
+    }
     return DESIRE_OK;
 }
 
@@ -192,8 +191,7 @@ int loss_grads(const BwdPass& bp) {
     launch_fill_f32(W(h, "Gflat"), h->n_params, 0.f, s);
     // loss mask: present at the last observed frame and in at least one target frame; every loss term below is masked per
     // target frame (model/model.py:351-366).  `valid` (presence at the last observed frame) stays what social pooling uses.
-    launch_loss_mask(static_cast<const uint8_t*>(h->ws["valid"].p), bp.fut, static_cast<uint8_t*>(h->ws["lmask"].p), W(h, "nfut"),
-                     d.n_scenes, d.mno, d.T_pred, s);
+    launch_loss_mask(Wt<const uint8_t>(h, "valid"), bp.fut, Wt<uint8_t>(h, "lmask"), W(h, "nfut"), d.n_scenes, d.mno, d.T_pred, s);
     launch_count_valid(bp.valid, h->A, W(h, "nvalid"), s);
     launch_loss_grad_y(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred, d.sx, d.sy, s);
     if (bp.rows_compact) launch_gather_rows(W(h, "dY0"), W(h, "cp_dY0"), bp.amap, bp.n_present, d.K, d.mno, d.T_pred * 2, s);
@@ -248,20 +246,20 @@ int ioc_pass_bwd(const BwdPass& bp, const IocView& v, bool first_view, int pass,
     q.WgT_h = D4(h, "ioc/WgT_h"); q.WgT_er = D4(h, "ioc/WgT_er"); q.WgT_ev = D4(h, "ioc/WgT_ev"); q.WsT = D4(h, "ioc/WsT"); q.WsT_c = D4(h, "ioc/WsT_c");
     q.dag = W(h, "ioc_dag"); q.dac = W(h, "ioc_dac"); q.rh = W(h, "ioc_rh"); q.hprev = W(h, "ioc_hprev");
     q.dpre_r = W(h, "ioc_dpre_r"); q.dpre_v = W(h, "ioc_dpre_v"); q.vel = W(h, "ioc_vel"); q.pooled = W(h, "ioc_pooled");
-    q.pool_flags = static_cast<unsigned long long*>(h->ws["ioc_pool_flags"].p);
+    q.pool_flags = Wt<unsigned long long>(h, "ioc_pool_flags");
     q.dHx_rows = g.dHx;
     q.bin_tab = d.bin_mode == 1 ? W(h, "bin_tab") : nullptr;
     const IocBwd bwd = ioc_plan(d, true, v.mno, v.gpt, v.R).bwd; const bool cl_bwd = bwd == IocBwd::CLUSTER;
     q.bias_part = cl_bwd ? nullptr : W(h, "bias_part");           // (the cluster form keeps the separate column-sum passes)
     if (cl_bwd) {
         if (int rc = ioc_cluster_exchange(h, (size_t)v.R / v.mno, first_view && last_pass, s)) return rc;
-        if (launch_ioc_bwd_cluster(q, static_cast<int*>(h->ws["grp_cnt"].p), static_cast<int*>(h->ws["ioc_err"].p), s))
+        if (launch_ioc_bwd_cluster(q, Wt<int>(h, "grp_cnt"), Wt<int>(h, "ioc_err"), s))
             return fail(DESIRE_ERR_STATE, "cluster-form IOC backward does not serve this shape");
     } else if (bwd == IocBwd::X3) {      // split-bf16 operands in the data-gradient contractions
         q.WcT_h = D4(h, "ioc/WcT16"); q.WgT_h = D4(h, "ioc/WgT16"); q.WsT = D4(h, "ioc/WsT16");
 #ifdef DESIRE_IOC_TIMING
-        if (!h->ws.count("dbgb")) { h->ws["dbgb"].alloc(12 * sizeof(long long)); }
-        q.dbg = static_cast<long long*>(h->ws["dbgb"].p);
+        if (int rc = ws_ensure(h, {{"dbgb", 12 * sizeof(long long)}})) return rc;
+        q.dbg = Wt<long long>(h, "dbgb");
 #endif
         launch_ioc_bwd_x3(q, s);
 #ifdef DESIRE_IOC_TIMING
@@ -277,10 +275,9 @@ int ioc_pass_bwd(const BwdPass& bp, const IocView& v, bool first_view, int pass,
         sa.dag = q.dag; sa.dac = q.dac; sa.Y = q.Y0; sa.gos = v.gos; sa.wcat = W(h, "sg_wcat");
         sa.R = (int)v.R; sa.T = T; sa.H = H; sa.K = d.K; sa.mno = v.mno; sa.gpt = v.gpt; sa.ngrp = v.ngrp; sa.Gh = d.Gh; sa.Gw = d.Gw;
         sa.n_keys = d.n_grids * d.Gh * d.Gw; sa.key_bits = scene_key_bits(sa.n_keys);
-        sa.ds = W(h, "sg_ds"); sa.keys = static_cast<uint32_t*>(h->ws["sg_keys"].p); sa.idx = static_cast<int32_t*>(h->ws["sg_idx"].p);
-        SceneSortBufs sb{h->ws["sg_tmp"].p, h->ws["sg_tmp"].bytes, static_cast<uint32_t*>(h->ws["sg_keys_sorted"].p),
-                         static_cast<int32_t*>(h->ws["sg_idx_sorted"].p), static_cast<int32_t*>(h->ws["sg_beg"].p),
-                         static_cast<int32_t*>(h->ws["sg_end"].p), W(h, "sg_part")};
+        sa.ds = W(h, "sg_ds"); sa.keys = Wt<uint32_t>(h, "sg_keys"); sa.idx = Wt<int32_t>(h, "sg_idx");
+        SceneSortBufs sb{Wt<void>(h, "sg_tmp"), h->ws.bytes("sg_tmp"), Wt<uint32_t>(h, "sg_keys_sorted"), Wt<int32_t>(h, "sg_idx_sorted"),
+                         Wt<int32_t>(h, "sg_beg"), Wt<int32_t>(h, "sg_end"), W(h, "sg_part")};
         if (launch_scene_grid_grad(sa, sb, W(h, "scene_grid_grad"), scene_first ? 0 : 1, s))
             return fail(DESIRE_ERR_HIP, "scene-grid gradient: launch failed");
         scene_first = false;
@@ -298,8 +295,8 @@ int ioc_pass_bwd(const BwdPass& bp, const IocView& v, bool first_view, int pass,
         // one output tile row = one bin (128 columns): each contracts only the (row, t) pairs that hold a neighbour in ITS bin, from
         // per-bin row lists built out of the flags -- 23 % of the rows at the bench's density, where skipping whole 32-row chunks
         // by their OR-ed flags still visited about half of them, zero rows and all
-        int* bl_counts = static_cast<int*>(h->ws["bin_counts"].p); int* bl_base = static_cast<int*>(h->ws["bin_base"].p);
-        int* bl_total = static_cast<int*>(h->ws["bin_total"].p); int* bl_list = static_cast<int*>(h->ws["bin_list"].p);
+        int* bl_counts = Wt<int>(h, "bin_counts"); int* bl_base = Wt<int>(h, "bin_base");
+        int* bl_total = Wt<int>(h, "bin_total"); int* bl_list = Wt<int>(h, "bin_list");
         launch_bin_lists(pflags, RT, B, bl_counts, bl_base, bl_total, bl_list, s);
         tn(h, q.pooled, B * H, q.dpre_r, H, RT, B * H, H, G(h, "ioc/social_fc/w"), H, acc, s, pflags, H, bl_list, bl_base, bl_total);
     } else
@@ -463,7 +460,7 @@ int cvae_enc_bwd(const BwdPass& bp) {
     const int H = d.H, V = h->V, L = d.L, Ae = bp.agents_e;
     const bool bn1 = d.bn_mode != 0;
     launch_reparam_bwd(W(h, "dz"), bp.eps, W(h, "params"), bp.valid, W(h, "nvalid"), W(h, "dparams"), d.n_scenes, d.mno, d.K, L, s,
-                       bp.rows_compact ? static_cast<const int32_t*>(h->ws["cp_inv"].p) : nullptr, bp.n_present);
+                       bp.rows_compact ? Wt<const int32_t>(h, "cp_inv") : nullptr, bp.n_present);
     if (bp.enc_compact) launch_gather_agents(W(h, "dparams"), W(h, "cp_dparams"), bp.amap, bp.n_present, 2 * L, s);
     const float* dparE = bp.enc_compact ? W(h, "cp_dparams") : W(h, "dparams");
     if (Ae <= 0) return DESIRE_OK;
@@ -588,7 +585,7 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
     if (int rc = desire_ready(h)) return rc;
     if (!h->training) return fail(DESIRE_ERR_STATE, "desire_set_training(h, 1) and a training-mode desire_forward come first");
     if (!dev_past || !dev_fut || !dev_eps) return fail(DESIRE_ERR_ARG, "null argument");
-    if (scene_grad_on(h) && !h->ws.count("sg_wcat")) return fail(DESIRE_ERR_STATE, "scene-gradient buffers missing");
+    if (scene_grad_on(h) && !h->ws.find("sg_wcat")) return fail(DESIRE_ERR_STATE, "scene-gradient buffers missing");
     if (int rc = backward_alloc(h)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const BwdPass bp = make_pass(h, dev_past, dev_fut, dev_eps, s);

@@ -4,6 +4,7 @@
 #include "../../include/desire_hip.h"
 #include "ioc_plan.h"
 #include "kernels.h"
+#include "workspace.h"
 
 #include <hip/hip_runtime.h>
 
@@ -22,16 +23,8 @@ int desire_fail(int code, const std::string& msg);            // sets the thread
             return fail(DESIRE_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_));            \
     } while (0)
 
-struct DevBuf {
-    void* p = nullptr; size_t bytes = 0;
-    int alloc(size_t b) {
-        bytes = b;
-        hipError_t e = hipMalloc(&p, b ? b : 4);
-        return e == hipSuccess ? 0 : -1;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; }
-    float* f() const { return static_cast<float*>(p); }
-};
+inline int dev_malloc(void** p, size_t bytes) { return hipMalloc(p, bytes) == hipSuccess ? 0 : -1; }      // the allocator of workspace.h
+inline void dev_free(void* p) { (void)hipFree(p); }
 
 struct Prof { std::string name; hipEvent_t e0, e1; };
 
@@ -53,8 +46,8 @@ struct desire_ctx {
     std::map<std::string, Embed> emb;                        // weights whose logical layout differs from the physical one
     std::map<std::string, std::vector<float>> host_w;       // raw weights as set
     std::map<std::string, size_t> want;                      // name -> element count
-    std::map<std::string, DevBuf> dev;                       // raw / packed / folded device tensors
-    std::map<std::string, DevBuf> ws;                        // workspace
+    Workspace dev{dev_malloc, dev_free};                     // raw / packed / folded device tensors (workspace.h)
+    Workspace ws{dev_malloc, dev_free};                      // workspace
     bool finalized = false;
     std::vector<void*> graphs;                               // instantiated hipGraphExec_t of desire_graph_end
     std::vector<float> bin_tab_host;                         // log-polar bin table (20 floats) when dims.bin_mode == 1
@@ -75,7 +68,8 @@ struct desire_ctx {
     bool cp_host_counts = false;                             // desire_set_option("compact_host_counts", 1): inference reads the counts back like training does (A/B)
     bool cp_last = false;                                    // the last desire_sample ran compacted (desire_backward follows it, not the flag)
     // desire_build_windows*: plain pointers, cached at creation -- a feeder thread may run the builder while the owner thread runs a forward or a backward on
-    // the same handle (desire_amd/prefetch.py: DeviceWindowFeeder), and those insert workspace entries lazily: the builder must not walk the map
+    // the same handle (desire_amd/prefetch.py: DeviceWindowFeeder), and those allocate workspace entries lazily (allocation inserts; reads do not): the
+    // builder must not walk the map
     int32_t* bw_starts = nullptr; int32_t* bw_err = nullptr;
     std::vector<Prof> prof;
     std::vector<std::string> prof_name_store;
@@ -114,9 +108,16 @@ inline int train_x3_mask(const desire_ctx* h) { return 15 & ~h->d.train_fp32_mas
 inline int wgrad_pieces(const desire_ctx* h) { return (h->d.bf16 == 2 && (train_x3_mask(h) & 1)) ? 2 : 0; }     // bf16 pieces per operand of the weight-gradient reductions (0: fp32)
 inline bool dgrad_split(const desire_ctx* h) { return h->d.bf16 == 2 && (train_x3_mask(h) & 2); }               // split-bf16 operands in the two large data-gradient convolutions
 
-inline const float* D(desire_ctx* h, const char* name) { return h->dev.at(name).f(); }
-inline const float4* D4(desire_ctx* h, const char* name) { return reinterpret_cast<const float4*>(h->dev.at(name).f()); }
-inline float* W(desire_ctx* h, const char* name) { return h->ws.at(name).f(); }
+// Lookups by name: nullptr for a name that was never allocated (workspace.h: they neither insert nor throw)
+inline const float* D(desire_ctx* h, const char* name) { return h->dev.get(name); }
+inline const float4* D4(desire_ctx* h, const char* name) { return h->dev.get<const float4>(name); }
+inline float* W(desire_ctx* h, const char* name) { return h->ws.get(name); }
+template <class T> T* Wt(desire_ctx* h, const char* name) { return h->ws.get<T>(name); }      // the non-float workspace buffers
+// every buffer of a list (workspace.h: ensure_all); a failure is reported by name
+template <size_t N> int ws_ensure(desire_ctx* h, const WsItem (&list)[N]) {
+    std::string failed;
+    return h->ws.ensure_all(list, N, &failed) ? fail(DESIRE_ERR_HIP, "hipMalloc failed for " + failed) : 0;
+}
 
 // Packed fragment order: out[((nt*G + g)*64 + lane)*4 + i] = W(k = 8g + 4*(lane>>5) + i, n = nt*32 + (lane&31))
 std::vector<float> pack_b(int K, int N, const std::function<float(int, int)>& at);
@@ -169,7 +170,8 @@ int ioc_cluster_exchange(desire_ctx* h, size_t n_groups, bool reset_err, hipStre
 int ioc_cluster_check(desire_ctx* h, hipStream_t s, const char* what);
 void ioc_timing_report(const long long* dbg, const char* const* names, int n, hipStream_t s);      // DESIRE_IOC_TIMING: per-phase cycle counters -> stderr
 int desire_pack_all(desire_ctx* h);                            // (re)builds every packed / folded device tensor from host_w
-__attribute__((visibility("hidden"))) int ensure(desire_ctx* h, const char* name, size_t bytes);     // workspace buffer `name` of at least `bytes` (train.hip; non-zero: hipMalloc failed; not an exported symbol)
 int scene_grad_setup(desire_ctx* h);                           // buffers of the scene-grid gradient (train.hip; idempotent, training mode only)
 inline bool scene_grad_on(const desire_ctx* h) { return h->scene_grad || h->img_set; }      // images attached imply the grid gradient
+void enc_weights(desire_ctx* h, const char* prefix, EncArgs& e);     // the fp32 GRU weights of the encoder "enc_x" / "enc_y" (api_forward.hip)
+IocStepArgs ioc_step_args(desire_ctx* h, int t);               // what every launch of the step-wise IOC kernel shares (api_peer.hip)
 int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)

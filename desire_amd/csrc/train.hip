@@ -8,12 +8,6 @@
 #include <cstdio>
 #include <cstring>
 
-int ensure(desire_ctx* h, const char* name, size_t bytes) {
-    if (h->ws.count(name) && h->ws[name].bytes >= bytes) return 0;
-    if (h->ws.count(name)) h->ws[name].release();
-    return h->ws[name].alloc(bytes);
-}
-
 namespace {
 
 // ---- optimiser state lives next to the gradients: Wflat (master weights), Mflat, Vflat, all in Gflat's layout ----
@@ -192,9 +186,7 @@ int build_repack_maps(desire_ctx* h) {
     const int rc = desire_pack_all(h);
     h->pack_mode = 0; h->host_w = std::move(real);
     if (rc) return rc;
-    if (ensure(h, "Wflat", h->n_params * sizeof(float)) || ensure(h, "Mflat", h->n_params * sizeof(float)) ||
-        ensure(h, "Vflat", h->n_params * sizeof(float)))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the optimiser state");
+    if (int rc2 = ws_ensure(h, {{"Wflat", h->n_params * sizeof(float)}, {"Mflat", h->n_params * sizeof(float)}, {"Vflat", h->n_params * sizeof(float)}})) return rc2;
     HIPCHK(hipMemcpy(W(h, "Wflat"), flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(W(h, "Mflat"), 0, h->n_params * sizeof(float)));
     HIPCHK(hipMemset(W(h, "Vflat"), 0, h->n_params * sizeof(float)));
@@ -206,11 +198,11 @@ int build_repack_maps(desire_ctx* h) {
         if (is3 || is6) {      // split [hi | lo] (or [p0 | p1 | p2]) pack: v = index code per bf16 slot
             const size_t np = is6 ? 3 : 2;
             const std::string real_name = name.substr(0, name.size() - 3);
-            auto it = h->dev.find(real_name);
-            if (it == h->dev.end() || it->second.bytes != (np * v.size() + (np * v.size() & 1)) * 2)
+            const DevBuf* op = h->dev.find(real_name.c_str());
+            if (!op || op->bytes != (np * v.size() + (np * v.size() & 1)) * 2)
                 return fail(DESIRE_ERR_STATE, "repack map: split operand " + real_name + " changed shape");
             std::vector<uint16_t> dev16(np * v.size() + (np * v.size() & 1));
-            HIPCHK(hipMemcpy(dev16.data(), it->second.p, it->second.bytes, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(dev16.data(), op->p, op->bytes, hipMemcpyDeviceToHost));
             std::vector<uint32_t> ix(v.size());
             for (size_t i = 0; i < v.size(); ++i) {
                 uint32_t u; std::memcpy(&u, &v[i], 4);
@@ -224,16 +216,16 @@ int build_repack_maps(desire_ctx* h) {
                     want -= bf16_to_f32(b);
                 }
             }
-            segs16.push_back(Seg16{static_cast<uint16_t*>(it->second.p), (unsigned long long)all_idx.size(), (unsigned long long)v.size(), (unsigned long long)np});
+            segs16.push_back(Seg16{static_cast<uint16_t*>(op->p), (unsigned long long)all_idx.size(), (unsigned long long)v.size(), (unsigned long long)np});
             all_idx.insert(all_idx.end(), ix.begin(), ix.end());
             while (all_idx.size() % 4) all_idx.push_back(0);
             continue;
         }
-        auto it = h->dev.find(name);
-        if (it == h->dev.end() || it->second.bytes != v.size() * sizeof(float))
+        const DevBuf* op = h->dev.find(name.c_str());
+        if (!op || op->bytes != v.size() * sizeof(float))
             return fail(DESIRE_ERR_STATE, "repack map: operand " + name + " changed shape");
         devcopy.resize(v.size());
-        HIPCHK(hipMemcpy(devcopy.data(), it->second.p, it->second.bytes, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(devcopy.data(), op->p, op->bytes, hipMemcpyDeviceToHost));
         bool gather = true;
         std::vector<uint32_t> ix(v.size());
         for (size_t i = 0; i < v.size() && gather; ++i) {
@@ -249,35 +241,34 @@ int build_repack_maps(desire_ctx* h) {
             return fail(DESIRE_ERR_STATE, "repack map: operand " + name + " is not a gather of the weights");
         }
         if (folded) continue;
-        segs.push_back(Seg{it->second.f(), (unsigned long long)all_idx.size(), (unsigned long long)v.size()});
+        segs.push_back(Seg{op->f(), (unsigned long long)all_idx.size(), (unsigned long long)v.size()});
         all_idx.insert(all_idx.end(), ix.begin(), ix.end());
         while (all_idx.size() % 4) all_idx.push_back(0);
     }
     h->captured.clear();
-    if (ensure(h, "repack_idx", all_idx.size() * sizeof(uint32_t)) || ensure(h, "repack_segs", segs.size() * sizeof(Seg)) ||
-        ensure(h, "repack_segs16", std::max<size_t>(1, segs16.size()) * sizeof(Seg16)))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the repack maps");
-    if (!segs16.empty()) HIPCHK(hipMemcpy(h->ws["repack_segs16"].p, segs16.data(), segs16.size() * sizeof(Seg16), hipMemcpyHostToDevice));
+    if (int rc2 = ws_ensure(h, {{"repack_idx", all_idx.size() * sizeof(uint32_t)}, {"repack_segs", segs.size() * sizeof(Seg)},
+                                {"repack_segs16", std::max<size_t>(1, segs16.size()) * sizeof(Seg16)}})) return rc2;
+    if (!segs16.empty()) HIPCHK(hipMemcpy(W(h, "repack_segs16"), segs16.data(), segs16.size() * sizeof(Seg16), hipMemcpyHostToDevice));
     h->n_seg16 = (int)segs16.size();
-    HIPCHK(hipMemcpy(h->ws["repack_idx"].p, all_idx.data(), all_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->ws["repack_segs"].p, segs.data(), segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(W(h, "repack_idx"), all_idx.data(), all_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(W(h, "repack_segs"), segs.data(), segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
     h->n_seg = (int)segs.size();
     return DESIRE_OK;
 }
 
 int repack(desire_ctx* h, hipStream_t s) {
     h->img_stale = true;                                   // scene_cnn/* may have moved: an inference forward reruns the scene CNN
-    hipLaunchKernelGGL(k_repack, dim3(64, h->n_seg), dim3(256), 0, s, static_cast<const Seg*>(h->ws["repack_segs"].p),
-                       static_cast<const uint32_t*>(h->ws["repack_idx"].p), W(h, "Wflat"));
+    hipLaunchKernelGGL(k_repack, dim3(64, h->n_seg), dim3(256), 0, s, Wt<const Seg>(h, "repack_segs"),
+                       Wt<const uint32_t>(h, "repack_idx"), W(h, "Wflat"));
     if (h->n_seg16)
-        hipLaunchKernelGGL(k_repack_split, dim3(64, h->n_seg16), dim3(256), 0, s, static_cast<const Seg16*>(h->ws["repack_segs16"].p),
-                           static_cast<const uint32_t*>(h->ws["repack_idx"].p), W(h, "Wflat"));
+        hipLaunchKernelGGL(k_repack_split, dim3(64, h->n_seg16), dim3(256), 0, s, Wt<const Seg16>(h, "repack_segs16"),
+                           Wt<const uint32_t>(h, "repack_idx"), W(h, "Wflat"));
     for (const char* n : {"vae_enc/conv1", "vae_enc/conv2", "vae_enc/conv3", "vae_dec/deconv1", "vae_dec/deconv2",
                           "vae_dec/deconv3", "vae_dec/deconv4"}) {
         const std::string p(n);
         const int C = (int)h->slots.at(p + "/b").n;
-        hipLaunchKernelGGL(k_refold, dim3((C + 63) / 64), dim3(64), 0, s, W(h, "Wflat"), h->dev.at(p + "/shift").f(),
-                           h->dev.at(p + "/scale").f(), h->slots.at(p + "/b").off, h->slots.at(p + "/bn/beta").off,
+        hipLaunchKernelGGL(k_refold, dim3((C + 63) / 64), dim3(64), 0, s, W(h, "Wflat"), h->dev.get((p + "/shift").c_str()),
+                           h->dev.get((p + "/scale").c_str()), h->slots.at(p + "/b").off, h->slots.at(p + "/bn/beta").off,
                            h->slots.at(p + "/bn/moving_mean").off, C);
     }
     HIPCHK(hipGetLastError());
@@ -292,15 +283,15 @@ int scene_grad_setup(desire_ctx* h) {
     const desire_dims& d = h->d;
     const size_t n = ioc_save_rows(h) * d.T_pred, nk = (size_t)d.n_grids * d.Gh * d.Gw, f = sizeof(float);
     const int bits = scene_key_bits((long)nk);
-    const struct { const char* n; size_t bytes; } bufs[] = {
+    const WsItem bufs[] = {
         {"sg_ds", n * 32 * f}, {"sg_part", n * 32 * f}, {"sg_keys", n * 4}, {"sg_keys_sorted", n * 4}, {"sg_idx", n * 4}, {"sg_idx_sorted", n * 4},
         {"sg_beg", nk * 4}, {"sg_end", nk * 4}, {"sg_wcat", (size_t)3 * d.H * 32 * f}, {"sg_tmp", scene_grad_sort_bytes((long)n, bits)},
         {"scene_grid_grad", nk * d.C * f},
         {"sg_col", nk * 800 * f}, {"sg_d2", nk * 32 * f}, {"sg_d1", nk * 4 * 16 * f}};        // scene CNN backward (im2col rows, data gradients)
-    for (const auto& b : bufs) {
-        const bool fresh = !h->ws.count(b.n) || h->ws[b.n].bytes < b.bytes;
-        if (ensure(h, b.n, b.bytes)) return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for scene-gradient buffer ") + b.n);
-        if (fresh && !std::strcmp(b.n, "scene_grid_grad")) HIPCHK(hipMemset(h->ws[b.n].p, 0, b.bytes));
+    for (const WsItem& b : bufs) {
+        bool fresh = false;
+        if (h->ws.ensure(b.n, b.bytes, &fresh)) return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for scene-gradient buffer ") + b.n);
+        if (fresh && !std::strcmp(b.n, "scene_grid_grad")) HIPCHK(hipMemset(W(h, b.n), 0, b.bytes));
     }
     return DESIRE_OK;
 }
@@ -338,8 +329,7 @@ extern "C" int desire_set_training(desire_handle* h, int enable) {
     const size_t RS = ioc_save_rows(h);                         // IOC buffers: rows + slack
     const size_t Tm = d.T_pred > d.T_obs ? d.T_pred : d.T_obs;
     const size_t NP = d.iters;                                  // IOC passes: each keeps its own saves
-    struct B { const char* n; size_t bytes; };
-    const B bufs[] = {
+    const WsItem bufs[] = {
         {"Gflat", h->n_params * f}, {"nvalid", 4 * f}, {"tn_partial", (size_t)96 << 20},
         {"dec_sv_r", R * T * H * f}, {"dec_sv_u", R * T * H * f}, {"dec_sv_c", R * T * H * f}, {"dec_sv_h", R * T * H * f},
         {"dY0", R * T * 2 * f}, {"dec_dag", R * T * 2 * H * f}, {"dec_dac", R * T * H * f}, {"dec_rh", R * T * H * f},
@@ -364,21 +354,18 @@ extern "C" int desire_set_training(desire_handle* h, int enable) {
         {"ey_sv_r", (size_t)h->A * T * H * f}, {"ey_sv_u", (size_t)h->A * T * H * f}, {"ey_sv_c", (size_t)h->A * T * H * f},
         {"ey_sv_h", (size_t)h->A * T * H * f}, {"ey_sv_x", (size_t)h->A * T * 2 * f},
     };
-    for (const B& b : bufs)
-        if (ensure(h, b.n, b.bytes)) return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for training buffer ") + b.n);
+    if (int rc = ws_ensure(h, bufs)) return rc;
     if (d.bn_mode != 0) {          // pre-norm copies of the seven conv layers (instance-norm / batch-norm backward)
-        const B pre[] = {{"conv1_pre", (size_t)h->A * 8192 * f}, {"conv2_pre", (size_t)h->A * 4096 * f}, {"conv3_pre", (size_t)h->A * 2048 * f},
+        const WsItem pre[] = {{"conv1_pre", (size_t)h->A * 8192 * f}, {"conv2_pre", (size_t)h->A * 4096 * f}, {"conv3_pre", (size_t)h->A * 2048 * f},
                          {"deconv1_pre", R * 2048 * f}, {"deconv2_pre", R * 4096 * f}, {"deconv3_pre", R * 8192 * f}, {"deconv4_pre", R * 1024 * f}};
-        for (const B& b : pre)
-            if (ensure(h, b.n, b.bytes)) return fail(DESIRE_ERR_HIP, std::string("hipMalloc failed for training buffer ") + b.n);
+        if (int rc = ws_ensure(h, pre)) return rc;
     }
-    if (d.bn_mode == 2 && (ensure(h, "bn_part2", (size_t)512 * 256 * f) || ensure(h, "bn_stat2", (size_t)2 * 128 * f) || ensure(h, "bn_statb", (size_t)2 * 128 * f)))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the batch-norm backward scratch");
-    if (ensure(h, "head_nll", (size_t)h->A * d.T_obs * f) || ensure(h, "head_cnt", (size_t)h->A * d.T_obs * f) || ensure(h, "head_dO", (size_t)h->A * d.T_obs * 5 * f))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the Gaussian-head loss buffers");
-    if (ensure(h, "loss_pa", (size_t)h->A * 4 * f) || ensure(h, "loss_out", 8 * f) || ensure(h, "bias_part", ((RS + 31) / 32 + 1) * 4 * H * f))
-        return fail(DESIRE_ERR_HIP, "hipMalloc failed for the loss / bias-gradient buffers");
-    HIPCHK(hipMemset(h->ws["loss_out"].p, 0, 8 * f));
+    if (d.bn_mode == 2) {          // batch-norm backward scratch
+        if (int rc = ws_ensure(h, {{"bn_part2", (size_t)512 * 256 * f}, {"bn_stat2", (size_t)2 * 128 * f}, {"bn_statb", (size_t)2 * 128 * f}})) return rc;
+    }
+    if (int rc = ws_ensure(h, {{"head_nll", (size_t)h->A * d.T_obs * f}, {"head_cnt", (size_t)h->A * d.T_obs * f}, {"head_dO", (size_t)h->A * d.T_obs * 5 * f},      // Gaussian-head loss
+                               {"loss_pa", (size_t)h->A * 4 * f}, {"loss_out", 8 * f}, {"bias_part", ((RS + 31) / 32 + 1) * 4 * H * f}})) return rc;
+    HIPCHK(hipMemset(W(h, "loss_out"), 0, 8 * f));
     if (int rc = build_repack_maps(h)) return rc;
     if (scene_grad_on(h)) { if (int rc = scene_grad_setup(h)) return rc; }
     h->adam_t = 0;
@@ -424,9 +411,8 @@ extern "C" int desire_grad_buffer(desire_handle* h, float** dev_ptr, size_t* n) 
 
 static int train_loss_enqueue(desire_handle* h, const float* dev_fut, hipStream_t s) {
     const desire_dims& d = h->d;
-    const uint8_t* valid = static_cast<const uint8_t*>(h->ws["lmask"].p);
-    launch_loss_mask(static_cast<const uint8_t*>(h->ws["valid"].p), dev_fut, static_cast<uint8_t*>(h->ws["lmask"].p), W(h, "nfut"),
-                     d.n_scenes, d.mno, d.T_pred, s);
+    const uint8_t* valid = Wt<const uint8_t>(h, "lmask");
+    launch_loss_mask(Wt<const uint8_t>(h, "valid"), dev_fut, Wt<uint8_t>(h, "lmask"), W(h, "nfut"), d.n_scenes, d.mno, d.T_pred, s);
     hipLaunchKernelGGL(k_train_loss, dim3((h->A + 63) / 64), dim3(64), 0, s, W(h, "Y0"), W(h, "Y_ref"), dev_fut, W(h, "score_sv"),
                        W(h, "params"), valid, W(h, "nfut"), W(h, "loss_pa"), d.n_scenes, d.mno, d.K, d.T_pred, d.L, d.sx, d.sy);
     hipLaunchKernelGGL(k_sum_loss, dim3(1), dim3(256), 0, s, W(h, "loss_pa"), valid, h->A, W(h, "loss_out"));
