@@ -1,5 +1,5 @@
-// api.hip -- C ABI of libdesire_hip.so (include/desire_hip.h): handle, weight repacking into MFMA
-// B-fragment order, workspace, and the launch sequence of the hot path.  Host code only.
+// api.hip -- C ABI of libdesire_hip.so (include/desire_hip.h): handle, weights as set by the caller (their packed device forms: pack.h,
+// api_pack.hip), workspace, buffer read-back and hipGraph capture.  Host code only.
 #include "ctx.h"
 
 #include <cmath>
@@ -18,49 +18,7 @@ extern "C" int desire_dims_size(void) { return (int)sizeof(desire_dims); }
 #endif
 extern "C" const char* desire_build_hash(void) { return DESIRE_SRC_HASH; }
 
-// Packed fragment order: out[((nt*G + g)*64 + lane)*4 + i] = W(k = 8g + 4*(lane>>5) + i, n = nt*32 + (lane&31))
-std::vector<float> pack_b(int K, int N, const std::function<float(int, int)>& at) {
-    const int G = (K + 7) / 8, NT = (N + 31) / 32;
-    std::vector<float> out((size_t)NT * G * 64 * 4, 0.f);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int g = 0; g < G; ++g)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int i = 0; i < 4; ++i) {
-                    const int k = 8 * g + 4 * (lane >> 5) + i, n = nt * 32 + (lane & 31);
-                    if (k < K && n < N) out[(((size_t)nt * G + g) * 64 + lane) * 4 + i] = at(k, n);
-                }
-    return out;
-}
-
-std::vector<float> pack_vals16(int K, int N, const std::function<int(int, int, int)>& kmap, const std::function<float(int, int)>& at) {
-    const int G = (K + 15) / 16, NT = (N + 31) / 32;
-    std::vector<float> o((size_t)NT * G * 64 * 8, 0.f);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int g = 0; g < G; ++g)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int k = kmap(g, lane >> 5, e), n = nt * 32 + (lane & 31);
-                    if (k >= 0 && k < K && n < N) o[(((size_t)nt * G + g) * 64 + lane) * 8 + e] = at(k, n);
-                }
-    return o;
-}
-std::vector<float> pack_b16(int K, int N, const std::function<int(int, int, int)>& kmap, const std::function<float(int, int)>& at) {
-    const int G = (K + 15) / 16, NT = (N + 31) / 32;
-    std::vector<uint16_t> o((size_t)NT * G * 64 * 8, 0);
-    for (int nt = 0; nt < NT; ++nt)
-        for (int g = 0; g < G; ++g)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int e = 0; e < 8; ++e) {
-                    const int k = kmap(g, lane >> 5, e), n = nt * 32 + (lane & 31);
-                    if (k >= 0 && k < K && n < N) o[(((size_t)nt * G + g) * 64 + lane) * 8 + e] = bf16_rne(at(k, n));
-                }
-    std::vector<float> out(o.size() / 2);
-    std::memcpy(out.data(), o.data(), o.size() * 2);
-    return out;
-}
-
 int desire_upload(desire_ctx* h, const std::string& name, const std::vector<float>& v) {
-    if (h->pack_mode == 1) { h->captured[name] = v; return 0; }
     const size_t bytes = v.size() * sizeof(float);
     const DevBuf* b = h->dev.find(name.c_str());
     if (!b || b->bytes != bytes) {                           // same shape: refresh in place (pointers stay valid); otherwise exactly the new size
@@ -100,46 +58,6 @@ void desire_extract(const desire_ctx* h, const std::string& name, const float* p
 }
 
 namespace {
-
-void shapes(desire_ctx* h, int H, std::map<std::string, size_t>& s) {
-    const desire_dims& d = h->d;
-    const int L = d.L, V = h->V;
-    const int E = d.E_v + d.C + H;
-    auto gru = [&](const std::string& p, int n_in) {
-        s[p + "/gates/kernel"] = (size_t)(n_in + H) * 2 * H;
-        s[p + "/gates/bias"] = 2 * H;
-        s[p + "/candidate/kernel"] = (size_t)(n_in + H) * H;
-        s[p + "/candidate/bias"] = H;
-    };
-    auto bn = [&](const std::string& p, int c) {
-        for (const char* n : {"beta", "gamma", "moving_mean", "moving_var"}) s[p + "/bn/" + n] = c;
-    };
-    gru("enc_x", 2); gru("enc_y", 2);
-    s["fc_c/w"] = (size_t)2 * H * V; s["fc_c/b"] = V;
-    struct CL { const char* n; int k, ci, co; };
-    for (CL c : {CL{"conv1", 5, 1, 32}, CL{"conv2", 5, 32, 64}, CL{"conv3", 5, 64, 128}}) {
-        const std::string p = std::string("vae_enc/") + c.n;
-        s[p + "/w"] = (size_t)c.k * c.k * c.ci * c.co; s[p + "/b"] = c.co; bn(p, c.co);
-    }
-    s["vae_enc/fc/w"] = (size_t)2048 * 2 * L; s["vae_enc/fc/b"] = 2 * L;
-    for (CL c : {CL{"deconv1", 4, L, 128}, CL{"deconv2", 5, 128, 64}, CL{"deconv3", 5, 64, 32}, CL{"deconv4", 5, 32, 1}}) {
-        const std::string p = std::string("vae_dec/") + c.n;
-        s[p + "/w"] = (size_t)c.k * c.k * c.ci * c.co; s[p + "/b"] = c.co; bn(p, c.co);
-    }
-    s["mask_fc/w"] = (size_t)V * H; s["mask_fc/b"] = H;
-    gru("dec", H);
-    s["head/w"] = 2 * H; s["head/b"] = 2;
-    s["ioc/vel_fc/w"] = 2 * d.E_v; s["ioc/vel_fc/b"] = d.E_v;
-    s["ioc/social_fc/w"] = (size_t)h->B * H * H; s["ioc/social_fc/b"] = H;
-    gru("ioc", E);
-    s["ioc/score/w"] = H; s["ioc/score/b"] = 1;
-    s["ioc/reg/w"] = (size_t)H * 2 * d.T_pred; s["ioc/reg/b"] = 2 * d.T_pred;
-    s["scene_cnn/conv1/w"] = 25 * 3 * 16; s["scene_cnn/conv1/b"] = 16;
-    s["scene_cnn/conv2/w"] = 25 * 16 * 32; s["scene_cnn/conv2/b"] = 32;
-    s["scene_cnn/conv3/w"] = (size_t)25 * 32 * d.C; s["scene_cnn/conv3/b"] = d.C;
-    s["temporal/w"] = (size_t)d.T_obs * 2 * 100; s["temporal/b"] = 200;
-    s["gauss_head/w"] = (size_t)H * 5; s["gauss_head/b"] = 5;       // sample()'s 5-wide output layer (model/model.py:315-321,445-449)
-}
 
 // logical -> physical embedding of every weight that has a hidden-width axis (ctx.h: Embed)
 void embeddings(desire_ctx* h) {
@@ -271,8 +189,8 @@ extern "C" int desire_create(const desire_dims* dims, desire_handle** out) {
     h->V = dims->S * dims->S;
     h->B = dims->grid_size * dims->grid_size;
     h->E = dims->E_v + dims->C + h->d.H;
-    shapes(h, h->d.H, h->want);
-    shapes(h, h->Hl, h->want_user);
+    pack::weight_shapes(h->d, h->d.H, h->V, h->B, h->want);
+    pack::weight_shapes(h->d, h->Hl, h->V, h->B, h->want_user);
     if (h->Hl != h->d.H) embeddings(h);
     const desire_dims& d = h->d;
     const size_t A = h->A, R = h->R, f = sizeof(float);

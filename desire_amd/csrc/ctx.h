@@ -4,6 +4,7 @@
 #include "../../include/desire_hip.h"
 #include "ioc_plan.h"
 #include "kernels.h"
+#include "pack.h"
 #include "workspace.h"
 
 #include <hip/hip_runtime.h>
@@ -78,8 +79,6 @@ struct desire_ctx {
     std::map<std::string, WSlot> slots;                      // natural-layout offsets in Wflat / Gflat / Mflat / Vflat
     size_t n_params = 0;
     const float* last_eps = nullptr;                         // inputs of the last training-mode forward
-    int pack_mode = 0;                                       // 1: desire_upload captures instead of uploading (index pass)
-    std::map<std::string, std::vector<float>> captured;
     int adam_t = 0;                                          // Adam step counter
     int n_seg = 0;                                           // repack segments (train.hip)
     int n_seg16 = 0;                                         // split [hi | lo] bf16 packs among them (dims.bf16 = 2)
@@ -119,21 +118,6 @@ template <size_t N> int ws_ensure(desire_ctx* h, const WsItem (&list)[N]) {
     return h->ws.ensure_all(list, N, &failed) ? fail(DESIRE_ERR_HIP, "hipMalloc failed for " + failed) : 0;
 }
 
-// Packed fragment order: out[((nt*G + g)*64 + lane)*4 + i] = W(k = 8g + 4*(lane>>5) + i, n = nt*32 + (lane&31))
-std::vector<float> pack_b(int K, int N, const std::function<float(int, int)>& at);
-// bf16 fragment order (v_mfma_f32_32x32x16_bf16): out16[((nt*G + g)*64 + lane)*8 + e] = bf16(W(k = kmap(g, lane>>5, e), n = nt*32 + (lane&31))),
-// G = ceil(K/16); returned as floats holding two bf16 bit patterns each (so the float upload path carries it)
-std::vector<float> pack_b16(int K, int N, const std::function<int(int, int, int)>& kmap, const std::function<float(int, int)>& at);
-// the same element order with the fp32 VALUES kept (one float per bf16 slot, 0 where the pack pads): source of the split
-// [hi | lo] packs of kernels_x3.hip, and -- run over index-coded weights -- of their device repack map (train.hip)
-std::vector<float> pack_vals16(int K, int N, const std::function<int(int, int, int)>& kmap, const std::function<float(int, int)>& at);
-inline uint16_t bf16_rne(float f) {
-    uint32_t u; std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline float bf16_to_f32(uint16_t b) { const uint32_t u = (uint32_t)b << 16; float f; std::memcpy(&f, &u, 4); return f; }
 // logical (caller) layout <-> physical layout of one named weight (identity when the weight has no Embed entry)
 std::vector<float> desire_embed(const desire_ctx* h, const std::string& name, const float* user);
 void desire_extract(const desire_ctx* h, const std::string& name, const float* phys, float* user);
@@ -169,7 +153,7 @@ inline size_t ioc_save_off(const desire_ctx* h, int pass, const IocView& v) { re
 int ioc_cluster_exchange(desire_ctx* h, size_t n_groups, bool reset_err, hipStream_t s);
 int ioc_cluster_check(desire_ctx* h, hipStream_t s, const char* what);
 void ioc_timing_report(const long long* dbg, const char* const* names, int n, hipStream_t s);      // DESIRE_IOC_TIMING: per-phase cycle counters -> stderr
-int desire_pack_all(desire_ctx* h);                            // (re)builds every packed / folded device tensor from host_w
+int desire_pack_all(desire_ctx* h);                            // (re)builds every device operand of pack.h's table from host_w
 int scene_grad_setup(desire_ctx* h);                           // buffers of the scene-grid gradient (train.hip; idempotent, training mode only)
 inline bool scene_grad_on(const desire_ctx* h) { return h->scene_grad || h->img_set; }      // images attached imply the grid gradient
 void enc_weights(desire_ctx* h, const char* prefix, EncArgs& e);     // the fp32 GRU weights of the encoder "enc_x" / "enc_y" (api_forward.hip)

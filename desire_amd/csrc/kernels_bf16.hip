@@ -7,7 +7,7 @@
 //         P_b^T [hidden, row i] = H^T [hidden, j] . M_b^T [j, i]            (MFMA 1: A = h^T from LDS, B = 0/1 bits)
 //     lands in registers with lane = row i and 4-row-aligned runs of the hidden index -- which IS the A-fragment
 //     layout (lane = row, 8 k per lane) of the next contraction up to a permutation of k, and the permutation is
-//     absorbed into how W_b is packed (chain order, pack_b16 in api.hip):
+//     absorbed into how W_b is packed (chain order, kmap_chain in pack.h):
 //         e_r += P_b . W_b                                                  (MFMA 2: A = cvt(P_b^T regs), B = packed W_b)
 //     every wave redoes MFMA 1 for all hidden blocks (the pipe has the headroom); 4 barriers per step instead of ~36
 //   * the neighbour bits of (row, bin) expand to bf16 0/1 B fragments through a 16-entry LDS table (one nibble ->

@@ -58,7 +58,7 @@ __global__ void k_repack(const Seg* __restrict__ segs, const uint32_t* __restric
 }
 
 // split [hi | lo] bf16 packs of kernels_x3.hip (dims.bf16 = 2): dst[i] = bf16(w), dst[n + i] = bf16(w - hi), w = Wflat[idx[i]-1]
-struct Seg16 { uint16_t* dst; unsigned long long idx_off; unsigned long long n; unsigned long long np; };     // np = pieces (2: "#x3" packs, 3: "#x6")
+struct Seg16 { uint16_t* dst; unsigned long long idx_off; unsigned long long n; unsigned long long np; };     // np = pieces (pack.h: Enc::SPLIT2 / SPLIT3)
 __device__ __forceinline__ uint16_t bf16_rne_dev(float f) {
     uint32_t u = __float_as_uint(f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
@@ -166,93 +166,49 @@ __global__ void k_sum_loss(const float* __restrict__ per_agent, const uint8_t* _
     }
 }
 
-// Builds the gather maps: the packing code (desire_pack_all) is run a second time over weights whose VALUES are their
-// own 1-based flat indices (as bit patterns); whatever it would have uploaded is then the index map of that operand.
-// Each map is verified against the real device operand, so an operand that is not a pure gather cannot slip through.
+// The master weights go to Wflat, and every gather operand of pack.h's table becomes a segment of k_repack (fp32) or k_repack_split (bf16 pieces):
+// its gather map plus the offset of its source weight in the flat buffers.  One map is alive at a time.  The folded shifts follow through k_refold.
 int build_repack_maps(desire_ctx* h) {
     std::vector<float> flat(h->n_params, 0.f);
-    auto real = h->host_w;
     for (auto& kv : h->slots) {
-        const auto& src = real.at(kv.first);
-        std::memcpy(flat.data() + kv.second.off, src.data(), kv.second.n * sizeof(float));
-        std::vector<float> coded(kv.second.n);
-        for (size_t i = 0; i < kv.second.n; ++i) {
-            const uint32_t u = (uint32_t)(kv.second.off + i + 1);
-            std::memcpy(&coded[i], &u, 4);
-        }
-        h->host_w[kv.first] = std::move(coded);
+        const auto w = h->host_w.find(kv.first);
+        if (w == h->host_w.end() || w->second.size() != kv.second.n) return fail(DESIRE_ERR_STATE, "weight not set: " + kv.first);
+        std::memcpy(flat.data() + kv.second.off, w->second.data(), kv.second.n * sizeof(float));
     }
-    h->pack_mode = 1; h->captured.clear();
-    const int rc = desire_pack_all(h);
-    h->pack_mode = 0; h->host_w = std::move(real);
-    if (rc) return rc;
-    if (int rc2 = ws_ensure(h, {{"Wflat", h->n_params * sizeof(float)}, {"Mflat", h->n_params * sizeof(float)}, {"Vflat", h->n_params * sizeof(float)}})) return rc2;
+    if (int rc = ws_ensure(h, {{"Wflat", h->n_params * sizeof(float)}, {"Mflat", h->n_params * sizeof(float)}, {"Vflat", h->n_params * sizeof(float)}})) return rc;
     HIPCHK(hipMemcpy(W(h, "Wflat"), flat.data(), flat.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(hipMemset(W(h, "Mflat"), 0, h->n_params * sizeof(float)));
     HIPCHK(hipMemset(W(h, "Vflat"), 0, h->n_params * sizeof(float)));
-    std::vector<uint32_t> all_idx; std::vector<Seg> segs; std::vector<Seg16> segs16;
-    std::vector<float> devcopy;
-    for (auto& kv : h->captured) {
-        const std::string& name = kv.first; const auto& v = kv.second;
-        const bool is3 = name.size() > 3 && name.compare(name.size() - 3, 3, "#x3") == 0, is6 = name.size() > 3 && name.compare(name.size() - 3, 3, "#x6") == 0;
-        if (is3 || is6) {      // split [hi | lo] (or [p0 | p1 | p2]) pack: v = index code per bf16 slot
-            const size_t np = is6 ? 3 : 2;
-            const std::string real_name = name.substr(0, name.size() - 3);
-            const DevBuf* op = h->dev.find(real_name.c_str());
-            if (!op || op->bytes != (np * v.size() + (np * v.size() & 1)) * 2)
-                return fail(DESIRE_ERR_STATE, "repack map: split operand " + real_name + " changed shape");
-            std::vector<uint16_t> dev16(np * v.size() + (np * v.size() & 1));
-            HIPCHK(hipMemcpy(dev16.data(), op->p, op->bytes, hipMemcpyDeviceToHost));
-            std::vector<uint32_t> ix(v.size());
-            for (size_t i = 0; i < v.size(); ++i) {
-                uint32_t u; std::memcpy(&u, &v[i], 4);
-                if (u > h->n_params) return fail(DESIRE_ERR_STATE, "repack map: split operand " + real_name + " is not a gather of the weights");
-                ix[i] = u;
-                float want = u ? flat[u - 1] : 0.f;
-                for (size_t pc = 0; pc < np; ++pc) {
-                    const uint16_t b = bf16_rne(want);
-                    if (dev16[pc * v.size() + i] != b)
-                        return fail(DESIRE_ERR_STATE, "repack map: split operand " + real_name + " does not match its map");
-                    want -= bf16_to_f32(b);
-                }
-            }
-            segs16.push_back(Seg16{static_cast<uint16_t*>(op->p), (unsigned long long)all_idx.size(), (unsigned long long)v.size(), (unsigned long long)np});
-            all_idx.insert(all_idx.end(), ix.begin(), ix.end());
-            while (all_idx.size() % 4) all_idx.push_back(0);
-            continue;
-        }
-        const DevBuf* op = h->dev.find(name.c_str());
-        if (!op || op->bytes != v.size() * sizeof(float))
-            return fail(DESIRE_ERR_STATE, "repack map: operand " + name + " changed shape");
-        devcopy.resize(v.size());
-        HIPCHK(hipMemcpy(devcopy.data(), op->p, op->bytes, hipMemcpyDeviceToHost));
-        bool gather = true;
-        std::vector<uint32_t> ix(v.size());
-        for (size_t i = 0; i < v.size() && gather; ++i) {
-            uint32_t u; std::memcpy(&u, &v[i], 4);
-            if (u > h->n_params) { gather = false; break; }
-            ix[i] = u;
-            const float want = u ? flat[u - 1] : 0.f;
-            if (std::memcmp(&want, &devcopy[i], 4) != 0) gather = false;
-        }
-        const bool folded = name.size() > 6 && (name.rfind("/scale") == name.size() - 6 || name.rfind("/shift") == name.size() - 6);
-        if (!gather) {
-            if (folded) continue;                              // handled by k_refold
-            return fail(DESIRE_ERR_STATE, "repack map: operand " + name + " is not a gather of the weights");
-        }
-        if (folded) continue;
-        segs.push_back(Seg{op->f(), (unsigned long long)all_idx.size(), (unsigned long long)v.size()});
-        all_idx.insert(all_idx.end(), ix.begin(), ix.end());
-        while (all_idx.size() % 4) all_idx.push_back(0);
+    const std::vector<pack::Operand> ops = pack::operands(h->d, h->V, h->B);
+    std::vector<Seg> segs; std::vector<Seg16> segs16;
+    size_t n_idx = 0;                                      // every map starts at a multiple of 4 indices
+    for (const pack::Operand& o : ops) {
+        if (o.kind != pack::Kind::GATHER) continue;
+        const auto sl = h->slots.find(o.src);
+        const DevBuf* op = h->dev.find(o.name.c_str());
+        if (sl == h->slots.end() || !op || op->bytes != pack::bytes(o, sl->second.n))
+            return fail(DESIRE_ERR_STATE, "repack map: operand " + o.name + " changed shape");
+        if (o.enc == pack::Enc::BF16) return fail(DESIRE_ERR_STATE, "repack map: the bf16 operand " + o.name + " has no device repack");
+        const unsigned long long n = pack::slots(o, sl->second.n), np = pack::pieces(o.enc);
+        if (np) segs16.push_back(Seg16{static_cast<uint16_t*>(op->p), (unsigned long long)n_idx, n, np});
+        else segs.push_back(Seg{op->f(), (unsigned long long)n_idx, n});
+        n_idx += (n + 3) / 4 * 4;
     }
-    h->captured.clear();
-    if (int rc2 = ws_ensure(h, {{"repack_idx", all_idx.size() * sizeof(uint32_t)}, {"repack_segs", segs.size() * sizeof(Seg)},
-                                {"repack_segs16", std::max<size_t>(1, segs16.size()) * sizeof(Seg16)}})) return rc2;
+    if (int rc = ws_ensure(h, {{"repack_idx", n_idx * sizeof(uint32_t)}, {"repack_segs", segs.size() * sizeof(Seg)},
+                               {"repack_segs16", std::max<size_t>(1, segs16.size()) * sizeof(Seg16)}})) return rc;
+    HIPCHK(hipMemset(W(h, "repack_idx"), 0, n_idx * sizeof(uint32_t)));
+    size_t i3 = 0, i16 = 0;
+    for (const pack::Operand& o : ops) {
+        if (o.kind != pack::Kind::GATHER) continue;
+        const WSlot& sl = h->slots.find(o.src)->second;
+        std::vector<uint32_t> m = pack::gather_map(o, sl.n);
+        for (uint32_t& j : m) if (j) j += (uint32_t)sl.off;
+        const size_t off = pack::pieces(o.enc) ? segs16[i16++].idx_off : segs[i3++].idx_off;
+        HIPCHK(hipMemcpy(Wt<uint32_t>(h, "repack_idx") + off, m.data(), m.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
     if (!segs16.empty()) HIPCHK(hipMemcpy(W(h, "repack_segs16"), segs16.data(), segs16.size() * sizeof(Seg16), hipMemcpyHostToDevice));
-    h->n_seg16 = (int)segs16.size();
-    HIPCHK(hipMemcpy(W(h, "repack_idx"), all_idx.data(), all_idx.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(W(h, "repack_segs"), segs.data(), segs.size() * sizeof(Seg), hipMemcpyHostToDevice));
-    h->n_seg = (int)segs.size();
+    h->n_seg = (int)segs.size(); h->n_seg16 = (int)segs16.size();
     return DESIRE_OK;
 }
 
@@ -263,8 +219,7 @@ int repack(desire_ctx* h, hipStream_t s) {
     if (h->n_seg16)
         hipLaunchKernelGGL(k_repack_split, dim3(64, h->n_seg16), dim3(256), 0, s, Wt<const Seg16>(h, "repack_segs16"),
                            Wt<const uint32_t>(h, "repack_idx"), W(h, "Wflat"));
-    for (const char* n : {"vae_enc/conv1", "vae_enc/conv2", "vae_enc/conv3", "vae_dec/deconv1", "vae_dec/deconv2",
-                          "vae_dec/deconv3", "vae_dec/deconv4"}) {
+    for (const char* n : pack::conv_layers) {
         const std::string p(n);
         const int C = (int)h->slots.at(p + "/b").n;
         hipLaunchKernelGGL(k_refold, dim3((C + 63) / 64), dim3(64), 0, s, W(h, "Wflat"), h->dev.get((p + "/shift").c_str()),
