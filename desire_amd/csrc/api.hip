@@ -143,7 +143,7 @@ extern "C" int desire_set_option(desire_handle* h, const char* name, int32_t val
     else if (nm == "train_fp32_mask") d.train_fp32_mask = value;
     else if (nm == "flags") d.flags = value;
     else if (nm == "compact_host_counts") {    // DESIRE_FLAG_COMPACT_*, inference: 1 = read the scans' counts back and size the launches exactly (one host wait per
-        h->cp_host_counts = value != 0;        // desire_encode, not capturable -- what training always does); 0 (default) = device-side counts (kernels.h: DynCount)
+        h->cp_host_counts = value != 0;        // desire_encode, not capturable -- what training always does); 0 (default) = device-side counts (dyn_count.h: DynCount)
         h->cp_pending = false; h->cp_enc = false;
         return DESIRE_OK;
     }

@@ -44,7 +44,7 @@ IocView ioc_view(desire_ctx* h, const IocView* cls) {
     return v;
 }
 // DEVICE-SIDE COUNTS (round 6): in inference with frozen batch-norm the host never learns how many agents are present -- every compacted launch is
-// sized for the worst case and reads its count from the scans' device words (kernels.h: DynCount), so a compacted call has no host wait and can be
+// sized for the worst case and reads its count from the scans' device words (dyn_count.h: DynCount), so a compacted call has no host wait and can be
 // captured in a hipGraph.  Training keeps the read-back (its backward sizes two dozen reductions from P), and so do per-sample batch statistics
 // (bn_mode 1: the normalisation kernels are not count-aware) and desire_set_option("compact_host_counts", 1) -- the A/B switch.
 bool compact_dyn(const desire_ctx* h) { return !h->training && h->d.bn_mode == 0 && !h->cp_host_counts; }
@@ -100,8 +100,11 @@ static int compact_wait(desire_ctx* h, hipStream_t s) {
     return DESIRE_OK;
 }
 // the mapped present-agent count word: read back after compact_wait (an out-of-range value is an error), or as a GUESS of P for choices that are about
-// speed only (which variant of a row GEMM): whatever the word holds -- the previous call's count, or this one's if the scan has already run.  The
-// guess is never a bound: the grids are the worst case's and the kernels read the real count.
+// speed only: whatever the word holds -- the previous call's count, or this one's if the scan has already run (under hipGraph capture always the
+// previous call's, baked into the graph).  It picks the variant of a row GEMM (GemmArgs.M_hint) and, as DynCount.hint (dyn_count.h), it SHRINKS the grids
+// of the strided launches -- the encoder pair, deconv2, deconv3 and the six-product forms of those two -- from the worst case to hint * 1.25 + 256
+// units (dyn_units).  The guess is never a bound on the work: every kernel reads the real count, and a strided kernel serves a count above its grid
+// with further trips of its tile loop.
 static int present_count(const desire_ctx* h, int* P) {
     *P = *static_cast<volatile int32_t*>(h->cp_host);
     return (*P < 0 || *P > h->A) ? fail(DESIRE_ERR_HIP, "present-agent scan returned a count out of range") : 0;

@@ -343,7 +343,7 @@ __device__ __forceinline__ void nb_publish_occ(unsigned long long oc, unsigned* 
 // the same for the IOC kernels' padded tiles (IocArgs.gpt > 0): -1 = a dead row
 __device__ __forceinline__ int ioc_agent_of_row(int r, int K, int mno, int gpt, int ngrp);
 
-// ---- device-side row counts (kernels.h: DynCount) ----------------------------------------------------------------------------------------------
+// ---- device-side row counts (dyn_count.h: DynCount) ----------------------------------------------------------------------------------------------
 // DYN_N(a, field, first): a.field = cnt[0] * mul when the launch carries a device-side count; the workgroup returns when its first unit `first` lies
 // beyond it (wave-uniform, before any barrier).  DYN_P: the per-row stages' pseudo-scene of P present agents (mno = P, R = P * K).
 #define DYN_N(a, field, first)                                                                     \

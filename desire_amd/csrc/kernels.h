@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dyn_count.h"      // DynCount (a row count known on the device only), dyn_units (the grid of a strided launch), the list of strided launchers
 #include "ioc_lds.h"
 
 // dynamic LDS above 64 KiB must be opted into once per kernel: the kernel K, opted in, as the pointer the runtime queries take
@@ -19,20 +20,6 @@ inline void launch_big_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, con
     hipLaunchKernelGGL(K, grid, block, lds, s, args...);
 }
 
-// A launch whose row count is known on the DEVICE only (DESIRE_FLAG_COMPACT_*, inference: the present agents of a batch / the windows seated in a
-// slot class, counted by kernels_compact.hip's scans).  The host sizes the grid -- and picks the kernel variant -- for the worst case and the kernel
-// replaces its count by cnt[0] * mul in its first instructions; workgroups beyond it exit before they touch memory.  No read-back, no host wait, the
-// call is hipGraph-capturable.  cnt == nullptr (every other launch): the count in the argument block stands.
-// hint: a GUESS of cnt[0] (the previous call's count, read from the scans' mapped word without waiting; 0 = none).  It only ever shrinks a GRID: launchers of
-// kernels that stride over their tiles (k_encoder_pair, k_deconv2/3 and their six-product forms) size the grid for hint * 1.25 + slack instead of the worst case,
-// and a count above that is still served -- more slowly -- by the stride loop.
-struct DynCount { const int32_t* cnt; int mul; int hint; };
-// units (rows / samples / agents) a strided launch is sized for: the worst case in the arguments, or the hinted count with a quarter of slack
-inline int dyn_units(int worst, const DynCount& d) {
-    if (!d.cnt || d.hint <= 0) return worst;
-    const long g = (long)d.hint * d.mul, want = g + g / 4 + 256;
-    return (int)(want < (long)worst ? want : (long)worst);
-}
 
 enum { EPI_BIAS = 0, EPI_BIAS_RELU = 1, EPI_SCALE_SHIFT_ELU = 2, EPI_NONE = 3, EPI_ELUGRAD = 4, EPI_SIGGRAD = 5 };
 

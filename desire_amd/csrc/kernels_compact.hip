@@ -51,7 +51,7 @@ void launch_present_scan(const uint8_t* valid, int A, int32_t* amap, int32_t* in
 // launch size most of an uncapped grid would be workgroups that exit at once (0.1 ms of dead dispatches per step on 512 SDD windows)
 static inline unsigned cp_grid(long n) { const long b = (n + 255) / 256; return (unsigned)(b < 8192 ? (b < 1 ? 1 : b) : 8192); }
 #define CP_FOR(i, total) for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < (long)(total); i += (long)gridDim.x * blockDim.x)
-// (dynP, here and below: the count on the DEVICE -- the host passes the worst case as P for the grid and the kernel reads the real one; kernels.h: DynCount)
+// (dynP, here and below: the count on the DEVICE -- the host passes the worst case as P for the grid and the kernel reads the real one; dyn_count.h: DynCount)
 __global__ void k_gather_agents(const float* __restrict__ in, float* __restrict__ out, const int32_t* __restrict__ amap, int P, int ld, const int32_t* __restrict__ dynP) {
     if (dynP) P = dynP[0];
     CP_FOR(i, (long)P * ld) {

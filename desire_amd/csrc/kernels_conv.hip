@@ -152,7 +152,7 @@ __global__ __launch_bounds__(DS_WG) void k_deconv2(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float out_s[];     // [4][64 px][64 co]
     const int lane = lane_id(), w = wave_id();
     const int hf = w & 1, sp = w >> 1;
-    // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (kernels.h: DynCount.hint) that the real count exceeds
+    // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (dyn_count.h: DynCount.hint) that the real count exceeds
     DYN_N(a, n, blockIdx.x * 4)
     for (int bx = blockIdx.x; bx * 4 < a.n; bx += gridDim.x) {
         const int s0 = bx * 4 + sp * 2;
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(NS * 64) void k_deconv3(ConvArgs a) {
     float* zero_row = smem;                                            // [96] floats, 256-byte aligned (dynamic LDS base)
     float* in_s = smem + 128;                                          // [NS][64][LDP]
     const int lane = lane_id(), w = wave_id(), tid = threadIdx.x;
-    // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (kernels.h: DynCount.hint) that the real count exceeds
+    // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (dyn_count.h: DynCount.hint) that the real count exceeds
     DYN_N(a, n, blockIdx.x * NS)
     for (int bx = blockIdx.x; bx * NS < a.n; bx += gridDim.x) {
         const int s0 = bx * NS;

@@ -171,7 +171,7 @@ __device__ __forceinline__ void encoder_tile(const EncArgs& a, int blk) {
 }
 template <int H, int TM, bool ROLL = false>
 __global__ __launch_bounds__((H / 32) * (TM / 32) * 64) void k_encoder(EncArgs a) {
-    DYN_N(a, mno, blockIdx.x * TM)                 // (device-side count: one pseudo-scene of mno = P present agents, kernels.h: DynCount)
+    DYN_N(a, mno, blockIdx.x * TM)                 // (device-side count: one pseudo-scene of mno = P present agents, dyn_count.h: DynCount)
     encoder_tile<H, TM, ROLL>(a, blockIdx.x);
 }
 // past and future encoders in ONE launch (they are independent and each is latency-bound: A/32 workgroups stepping through T
@@ -179,7 +179,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64) void k_encoder(EncArgs a
 template <int H, int TM>
 __global__ __launch_bounds__((H / 32) * (TM / 32) * 64) void k_encoder_pair(EncArgs a0, EncArgs a1, int nb0) {
     if (a0.dyn.cnt) {
-        // device-side count: both encoders run on the same P present agents; the grid is 2 * nb0 with nb0 sized from the count hint (kernels.h: DynCount.hint) or,
+        // device-side count: both encoders run on the same P present agents; the grid is 2 * nb0 with nb0 sized from the count hint (dyn_count.h: DynCount.hint) or,
         // without one, for the worst case -- a workgroup strides over its encoder's tiles.  First half of the grid = past encoder, second half = future encoder,
         // as in the plain launch: consecutive workgroups go to consecutive XCDs, and dealing the two encoders' tiles alternately (tried) put every 40-step tile
         // of the future encoder on four of the eight XCDs
@@ -199,7 +199,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64) void k_encoder_pair(EncA
 void launch_encoder_pair(const EncArgs& a0, const EncArgs& a1, hipStream_t s) {
     constexpr int TM = 32;
     int nb0 = (a0.n_scenes * a0.mno + TM - 1) / TM, nb1 = (a1.n_scenes * a1.mno + TM - 1) / TM;
-    if (a0.dyn.cnt) nb0 = nb1 = (dyn_units(a0.n_scenes * a0.mno, a0.dyn) + TM - 1) / TM;       // (device-side count: tiles dealt alternately, grid = 2 * nb0, strided)
+    if (a0.dyn.cnt) nb0 = nb1 = (dyn_units(a0.n_scenes * a0.mno, a0.dyn) + TM - 1) / TM;       // (device-side count: grid = 2 * nb0, first half = past encoder, second half = future encoder, each strided)
     const size_t lds = (TM * (a0.H + 4) + TM * 2) * sizeof(float);
     const dim3 grid(nb0 + nb1);
     if (a0.H == 256) hipLaunchKernelGGL((k_encoder_pair<256, TM>), grid, dim3(512), lds, s, a0, a1, nb0);
@@ -441,7 +441,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
     const int cb = w % NT, mt = w / NT;
     const int tile = NSPL > 1 ? (int)blockIdx.x / NSPL : (int)blockIdx.x, member = NSPL > 1 ? (int)blockIdx.x % NSPL : 0;
     const int row0 = tile * TM;
-    IOC_DYN(a)                                          // (a slot class counted on the device: kernels.h DynCount; the grid is the worst case's)
+    IOC_DYN(a)                                          // (a slot class counted on the device: dyn_count.h DynCount; the grid is the worst case's)
     if (a.dyn.cnt && row0 >= a.R) return;
     unsigned long long my_bins = ~0ull;
     if (NSPL > 1) { my_bins = 0ull; for (int b = member; b < 64; b += NSPL) my_bins |= 1ull << b; }
@@ -966,7 +966,7 @@ __global__ __launch_bounds__((H / 32) * 64, (H / 32) <= 4 ? 1 : 2) void k_ioc_cl
     const int col = cb * 32 + (lane & 31);
     const int r8 = tid / TPR, q8 = tid % TPR;
     const int tile_pos = blockIdx.x % tpg;              // my tile inside its group
-    IOC_DYN(a)                                          // (a slot class counted on the device: kernels.h DynCount; the persistent grid is the worst case's)
+    IOC_DYN(a)                                          // (a slot class counted on the device: dyn_count.h DynCount; the persistent grid is the worst case's)
     const int n_tiles = a.R / TM;
 
     ioc_stage_wv<EV, NTHR>(wv, a.w_vel, a.b_vel, tid);

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(DS_WG, 2) void k_deconv2_x6(ConvArgs a, size_t plo)
     constexpr int RD = 4;
     const int lane = lane_id(), w = wave_id();
     const int hf = w & 1, sp = w >> 1;
-    // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (kernels.h: DynCount.hint) that the real count exceeds
+    // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (dyn_count.h: DynCount.hint) that the real count exceeds
     DYN_N(a, n, blockIdx.x * 4)
     for (int bx = blockIdx.x; bx * 4 < a.n; bx += gridDim.x) {
         const int s0 = bx * 4 + sp * 2;
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(DS_WG, 2) void k_deconv3_x6i(ConvArgs a, size_t plo
     extern __shared__ __attribute__((aligned(16))) float smem[];
     u16* img = reinterpret_cast<u16*>(smem);                           // [3][NPX + 1][LDB]
     const int lane = lane_id(), w = wave_id(), tid = threadIdx.x;
-    // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (kernels.h: DynCount.hint) that the real count exceeds
+    // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (dyn_count.h: DynCount.hint) that the real count exceeds
     DYN_N(a, n, blockIdx.x * 2)
     for (int bx = blockIdx.x; bx * 2 < a.n; bx += gridDim.x) {
         const int s0 = bx * 2;

@@ -13,6 +13,16 @@ def to_oracle_layout(win):
     return np.ascontiguousarray(win.transpose(1, 0, 2, 3).reshape(T, n * m, 3))
 
 
+def hinted_units(worst, hint, mul):
+    """Mirror of dyn_units (desire_amd/csrc/dyn_count.h) for a launch that carries a device-side count: the units (agents / samples) a strided launch
+    is sized for -- the hinted count with a quarter of slack plus 256, never above the worst case; no hint (<= 0) = the worst case.
+    tests/test_dyn_count.py holds it equal to the header over a sweep."""
+    if hint <= 0:
+        return worst
+    g = hint * mul
+    return min(worst, g + g // 4 + 256)
+
+
 def small_dims(**kw):
     base = dict(n_scenes=2, mno=32, K=4, T_obs=8, T_pred=12, H=128, L=128, n_grids=2,
                 nb_w=0.25, nb_h=0.3, sx=1.0 / 1400.0, sy=1.0 / 1100.0)

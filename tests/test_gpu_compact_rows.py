@@ -414,7 +414,7 @@ def test_training_with_the_gaussian_head_loss_keeps_every_observed_object(torch_
         assert ref > 0 and np.abs(res[0][k] - res[1][k]).max() / ref < 3e-5, k
 
 
-# ---- round 6: device-side counts (kernels.h: DynCount) -- inference sizes every compacted launch for the worst case and reads P / the class counts on the device
+# ---- round 6: device-side counts (dyn_count.h: DynCount) -- inference sizes every compacted launch for the worst case and reads P / the class counts on the device
 @pytest.mark.parametrize("kw", [dict(), dict(bf16=2), dict(bf16=3), dict(bf16=1), dict(H=64, K=3, mno=16), dict(posterior=0), dict(mno=64, n_scenes=5, K=2, n_grids=1),
                                 dict(mno=96, n_scenes=3, K=2, n_grids=1), dict(mno=128, n_scenes=3, K=2, n_grids=1, bf16=1),
                                 dict(mno=192, n_scenes=2, K=2, T_pred=8, n_grids=1),                       # step-wise IOC: the slot classes are ignored, the rows compact
