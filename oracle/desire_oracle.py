@@ -166,18 +166,44 @@ def batch_norm(x, w, prefix, bn_mode, dt):
     return ((x - mean) * (gamma / np.sqrt(var + dt(BN_EPS))) + beta).astype(dt)
 
 
+ENC_LAYERS = {"conv1": (2, "SAME"), "conv2": (2, "SAME"), "conv3": (1, "VALID")}                       # name -> (stride, padding)
+DEC_LAYERS = {"deconv1": (1, "VALID", elu), "deconv2": (1, "VALID", elu), "deconv3": (2, "SAME", elu), "deconv4": (2, "SAME", sigmoid)}
+
+
+def conv_layer(x, w, name, bn_mode="frozen", dt=np.float32, q=None, pre=False):
+    """One layer of vae_encoder: conv + bias -> batch-norm -> ELU.  x [N,Hi,Wi,Ci] NHWC.  q rounds the activations and the weights where
+    they enter the contraction; pre=True returns the contraction alone (no bias, no epilogue)."""
+    p = "vae_enc/" + name
+    stride, pad = ENC_LAYERS[name]
+    if q is not None:
+        x = conv2d(q(x), q(w[p + "/w"].astype(dt)), stride, pad)
+    else:
+        x = conv2d(x, w[p + "/w"].astype(dt), stride, pad)
+    if pre:
+        return x
+    return elu(batch_norm(x + w[p + "/b"].astype(dt), w, p, bn_mode, dt))
+
+
+def deconv_layer(x, w, name, bn_mode="frozen", dt=np.float32, q=None, pre=False):
+    """One layer of vae_decoder: transposed conv + bias -> batch-norm -> ELU (sigmoid for deconv4).  Arguments as conv_layer."""
+    p = "vae_dec/" + name
+    stride, pad, act = DEC_LAYERS[name]
+    if q is not None:
+        x = conv2d_transpose(q(x), q(w[p + "/w"].astype(dt)), stride, pad)
+    else:
+        x = conv2d_transpose(x, w[p + "/w"].astype(dt), stride, pad)
+    if pre:
+        return x
+    return act(batch_norm(x + w[p + "/b"].astype(dt), w, p, bn_mode, dt))
+
+
 def vae_encoder(vae_in, w, L, bn_mode="frozen", dt=np.float32, q=None, return_layers=False):
     """model/model.py:471-492.  vae_in [A, 1024] -> (z_mean, z_log_sigma_sq) each [A, L].
     q = bf16_round restates k_conv_gather_bf16: conv2 / conv3 round their input activations and weights."""
     x = vae_in.astype(dt).reshape(-1, 32, 32, 1)
     layers = []
-    for name, stride, pad in (("conv1", 2, "SAME"), ("conv2", 2, "SAME"), ("conv3", 1, "VALID")):
-        p = "vae_enc/" + name
-        if q is not None and name != "conv1":
-            x = conv2d(q(x), q(w[p + "/w"].astype(dt)), stride, pad) + w[p + "/b"].astype(dt)
-        else:
-            x = conv2d(x, w[p + "/w"].astype(dt), stride, pad) + w[p + "/b"].astype(dt)
-        x = elu(batch_norm(x, w, p, bn_mode, dt))
+    for name in ENC_LAYERS:
+        x = conv_layer(x, w, name, bn_mode, dt, q if name != "conv1" else None)
         layers.append(x)
     flat = x.reshape(x.shape[0], -1)                      # [A, 4*4*128] NHWC flatten
     params = flat @ w["vae_enc/fc/w"].astype(dt) + w["vae_enc/fc/b"].astype(dt)
@@ -194,14 +220,8 @@ def vae_decoder(z, w, bn_mode="frozen", dt=np.float32, return_layers=False, q=No
     the BN/ELU/sigmoid epilogues are fp32."""
     x = z.astype(dt).reshape(-1, 1, 1, z.shape[-1])
     layers = []
-    for name, stride, pad, act in (("deconv1", 1, "VALID", elu), ("deconv2", 1, "VALID", elu),
-                                   ("deconv3", 2, "SAME", elu), ("deconv4", 2, "SAME", sigmoid)):
-        p = "vae_dec/" + name
-        if q is not None and name in q_layers:
-            x = conv2d_transpose(q(x), q(w[p + "/w"].astype(dt)), stride, pad) + w[p + "/b"].astype(dt)
-        else:
-            x = conv2d_transpose(x, w[p + "/w"].astype(dt), stride, pad) + w[p + "/b"].astype(dt)
-        x = act(batch_norm(x, w, p, bn_mode, dt))
+    for name in DEC_LAYERS:
+        x = deconv_layer(x, w, name, bn_mode, dt, q if name in q_layers else None)
         layers.append(x)
     out = x.reshape(x.shape[0], -1)
     return (out, layers) if return_layers else out
@@ -311,6 +331,19 @@ def bin_margin(pos, nb_w, nb_h, G, valid=None):
     return float(min(mx, my))
 
 
+def cell_margin(pos, Gh, Gw):
+    """Smallest distance (normalised units) of any position to an edge of its scene cell (scene_cell above) -- the companion of
+    bin_margin for the scene-grid lookup.  Positions outside [0, 1) are clamped to the border cells and have no edge to cross beyond it."""
+    p = pos.astype(np.float64)
+    m = np.inf
+    for v, G in ((p[..., 1], Gh), (p[..., 0], Gw)):
+        s = v * G
+        inside = (s > -1) & (s < G + 1)
+        if inside.any():
+            m = min(m, float(np.abs(s - np.round(s))[inside].min()) / G)
+    return float(m)
+
+
 # ------------------------------------------------------------------------------------------
 # stages
 # ------------------------------------------------------------------------------------------
@@ -362,11 +395,12 @@ def social_pool(pos_t, hprev, valid_rows, d, dt, bin_tab=None):
     return pooled.reshape(d.R, d.B * d.H).astype(dt), bins
 
 
-def ioc_pass(Y, Hx_rows, p_last, valid_rows, grids, grid_of_scene, w, d, dt=np.float32, q=None, bin_tab=None):
+def ioc_pass(Y, Hx_rows, p_last, valid_rows, grids, grid_of_scene, w, d, dt=np.float32, q=None, bin_tab=None, trace=None):
     """One IOC scoring + regression pass (paper section 3.3; absent in the reference,
     model/model.py:312-313).  Returns (score [R], dY [R,T_pred,2]).
     q = bf16_round restates the bf16-operand kernel (kernels_bf16.hip): weights, x_t, h, r*h and the pooled sums are
-    rounded where they enter a matrix product; accumulation, state and gate math stay fp32."""
+    rounded where they enter a matrix product; accumulation, state and gate math stay fp32.
+    trace: a list that receives, per step, the operands of the step's contractions (pooled sums, GRU input, state before the step)."""
     qq = q or (lambda v: v)
     Wg, bg, Wc, bc = _gru_w(w, "ioc", dt)
     Wg, Wc = qq(Wg), qq(Wc)
@@ -386,6 +420,8 @@ def ioc_pass(Y, Hx_rows, p_last, valid_rows, grids, grid_of_scene, w, d, dt=np.f
         e_s = grids[gidx, cy, cx].astype(dt)
         pooled, _ = social_pool(cur, qq(h), valid_rows, d, dt, bin_tab)
         e_r = relu(qq(pooled) @ Ws + bs)
+        if trace is not None:
+            trace.append({"pooled": pooled, "x": np.concatenate([e_v, e_s, e_r], -1), "h": h})
         h = gru_cell(qq(np.concatenate([e_v, e_s, e_r], -1)), h, Wg, bg, Wc, bc, q)
         score = score + (h @ wsc[:, 0] + bsc[0])
         prev = cur

@@ -18,14 +18,9 @@ def grads_case():
     from desire_amd import _lib
     from oracle import desire_torch as OT
     d = small_dims(n_scenes=2, mno=32, K=3, T_obs=6, T_pred=7, n_grids=1)
-    w = init_weights(d, 41)
+    from tests.stage_reference import spread_weights
     # spread the K samples (a fresh init gives K nearly identical futures, which makes the ranking gradients vanish)
-    for k in w:
-        if k.startswith("vae_dec/") and k.endswith("/w"):
-            w[k] = w[k] * 3
-    w["mask_fc/w"] = w["mask_fc/w"] * 20
-    w["head/w"] = w["head/w"] * 4
-    w["ioc/score/w"] = w["ioc/score/w"] * 3
+    w = spread_weights(init_weights(d, 41))
     past, fut, eps, grids, gos = make_case(d, seed=42, n_absent=4)
     vals, ref = OT.loss_and_grads(to_oracle_layout(past), to_oracle_layout(fut), eps, grids, gos, w, d)
     h = _lib.Handle(d)
