@@ -26,7 +26,9 @@ EXPORTS = [
     "desire_set_option", "desire_train_loss_async", "desire_set_head_loss",
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
     "desire_rank_samples", "desire_ranked_errors",
+    "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill",
 ]
+RNG_BITS, RNG_NORMAL, RNG_LATENT = 0, 1, 2          # desire_rng_fill kinds (DESIRE_RNG_*)
 
 
 class DesireDims(C.Structure):
@@ -120,6 +122,10 @@ def load() -> C.CDLL:
     lib.desire_device_buffer.argtypes = [vp, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     lib.desire_ioc_step.argtypes = [vp, i32, i32, i32, f32p, f32p, vp, f32p, f32p, f32p, vp]
     lib.desire_ioc_finish.argtypes = [vp, f32p, f32p, f32p, f32p, vp]
+    lib.desire_set_rng.argtypes = [vp, C.c_uint64, C.c_uint32, vp]
+    lib.desire_set_rng_origin.argtypes = [vp, C.c_uint32, C.c_uint32]
+    lib.desire_rng_state.argtypes = [vp, C.POINTER(C.c_uint32), vp]
+    lib.desire_rng_fill.argtypes = [vp, C.c_uint64, C.c_uint32, C.c_uint64, i32, vp, C.c_size_t, vp]
     lib.desire_set_profiling.argtypes = [vp, C.c_int]
     lib.desire_get_profile.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
     for n in EXPORTS:
@@ -190,6 +196,25 @@ class Handle:
 
     def sample(self, eps_ptr: int, yhat_ptr: int, stream: int = 0) -> None:
         _chk(self.lib.desire_sample(self._h, eps_ptr, yhat_ptr, stream or None))
+
+    def set_rng(self, seed: int, draw: int = 0, stream: int = 0) -> None:
+        """Switches the device generator on (or re-seeds it): afterwards eps_ptr = 0 is legal in sample / forward / backward, one draw per call."""
+        _chk(self.lib.desire_set_rng(self._h, int(seed) & (2 ** 64 - 1), int(draw) & 0xFFFFFFFF, stream or None))
+
+    def set_rng_origin(self, scene_base: int = 0, slot_base: int = 0) -> None:
+        """Global index of the call's first window and of the handle's first slot (host values: baked into a captured graph)."""
+        _chk(self.lib.desire_set_rng_origin(self._h, int(scene_base) & 0xFFFFFFFF, int(slot_base) & 0xFFFFFFFF))
+
+    def rng_state(self, stream: int = 0) -> Tuple[int, int]:
+        """(next, used) draw counters; synchronises the stream."""
+        out = (C.c_uint32 * 2)()
+        _chk(self.lib.desire_rng_state(self._h, out, stream or None))
+        return int(out[0]), int(out[1])
+
+    def rng_fill(self, seed: int, stream_id: int, first: int, kind: int, out_ptr: int, n: int, stream: int = 0) -> None:
+        """n elements of the fill stream (seed, stream_id) from element `first`: RNG_BITS (uint32) or RNG_NORMAL (fp32); RNG_LATENT writes the eps
+        [n_scenes, K, mno, L] of draw `stream_id` at the handle's origin (first = 0, n = R * L)."""
+        _chk(self.lib.desire_rng_fill(self._h, int(seed) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, int(first), int(kind), out_ptr, int(n), stream or None))
 
     def ioc_refine(self, yhat_ptr: int, score_ptr: int, stream: int = 0) -> None:
         _chk(self.lib.desire_ioc_refine(self._h, yhat_ptr, score_ptr, stream or None))

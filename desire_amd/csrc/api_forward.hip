@@ -240,10 +240,11 @@ extern "C" int desire_encode(desire_handle* h, const float* dev_past, const floa
 
 extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_Yhat, void* stream) {
     if (int rc = desire_ready(h)) return rc;
-    if (!dev_eps || !dev_Yhat) return fail(DESIRE_ERR_ARG, "null argument");
+    if (!dev_Yhat || (!dev_eps && !h->rng_state)) return fail(DESIRE_ERR_ARG, "null argument");      // (dev_eps == NULL: legal after desire_set_rng)
     const desire_dims& d = h->d;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int H = d.H;
+    if (!dev_eps) launch_rng_begin(h->rng_state, s);           // a sampling call that generates its eps is one draw, whatever it then runs
     // per-row stages: all R = A*K rows, or (DESIRE_FLAG_COMPACT_ROWS) the K*P rows of the P present agents laid out as one pseudo-scene of P
     // slots (kernels_compact.hip) -- the kernels below are the same either way, they only see (R, K, mno) and the agent-level inputs
     int R = h->R, mno = d.mno;
@@ -273,7 +274,12 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
         }
         HxS = W(h, "cp_HxHy"); plS = W(h, "cp_plast"); Yout = W(h, "cp_Y0");
     }
-    if (compact) { Timer t(h, s, "reparam"); launch_reparam_c(W(h, "cp_params"), dev_eps, W(h, "z"), Wt<const int32_t>(h, "cp_amap"), mno, d.K, d.mno, d.L, d.posterior, s, dynP); }
+    if (!dev_eps) {          // the generator's twins (kernels_rng.hip): eps computed in the kernel from rng_state.used
+        Timer t(h, s, "reparam");
+        if (compact) launch_reparam_c_rng(W(h, "cp_params"), rng_args(h), W(h, "z"), Wt<const int32_t>(h, "cp_amap"), mno, d.K, d.mno, d.L, d.posterior, s, dynP);
+        else launch_reparam_rng(W(h, "params"), rng_args(h), W(h, "z"), R, d.L, d.K, d.mno, d.posterior, s);
+    }
+    else if (compact) { Timer t(h, s, "reparam"); launch_reparam_c(W(h, "cp_params"), dev_eps, W(h, "z"), Wt<const int32_t>(h, "cp_amap"), mno, d.K, d.mno, d.L, d.posterior, s, dynP); }
     else { Timer t(h, s, "reparam"); launch_reparam(W(h, "params"), dev_eps, W(h, "z"), R, d.L, d.K, d.mno, d.posterior, s); }
     auto normd = [&](const char* layer, float* x, int P, int C, int sig) { batch_stats_act(h, layer, x, R, P, C, sig, s); };
     GemmArgs g{};

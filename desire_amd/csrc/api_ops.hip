@@ -1,6 +1,7 @@
 // api_ops.hip -- the stand-alone ops of the ABI: integer paths, scene CNN, losses, the reference's literal tensors, window builder, Gaussian head,
 // rollout, ADE / FDE.  Host code only; split out of api.hip in round 5.
 #include "ctx.h"
+#include "philox.h"
 
 #include <cmath>
 #include <cstdio>
@@ -192,6 +193,61 @@ extern "C" int desire_ranked_errors(desire_handle* h, const float* dev_Yhat, con
     if (!sample_errors_geometry(d.mno, d.K, d.T_pred, &sc, &kc)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the error kernel's LDS");
     launch_ranked_errors(dev_Yhat, dev_fut, dev_order, W(h, "rank_tab"), Wt<int32_t>(h, "rank_cnt"), dev_out, d.n_scenes,
                          d.mno, d.K, d.T_pred, n_top, hz, d.sx, d.sy, unit_x, unit_y, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
+// ---- the device generator (philox.h, kernels_rng.hip): the packing of its counters is stated in include/desire_hip.h ------------------------
+namespace {
+int rng_check_packing(const desire_ctx* h, uint32_t slot_base) {
+    const desire_dims& d = h->d;
+    if (d.L > PHILOX_MAX_L) return fail(DESIRE_ERR_ARG, "the generator's counter holds latents up to L = 4096");
+    if (d.K >= PHILOX_MAX_K) return fail(DESIRE_ERR_ARG, "the generator's counter holds sample indices k < 8192");
+    if ((uint64_t)slot_base + (uint64_t)d.mno > (uint64_t)PHILOX_MAX_SLOT) return fail(DESIRE_ERR_ARG, "the generator's counter holds global slots (slot_base + mno) up to 512");
+    return 0;
+}
+}  // namespace
+
+extern "C" int desire_set_rng(desire_handle* h, uint64_t seed, uint32_t draw, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null argument");
+    if (int rc = rng_check_packing(h, h->rng_slot_base)) return rc;
+    if (!h->rng_state) {          // the first call allocates the words (never a sampling call); later calls are one kernel and capturable
+        if (int rc = ws_ensure(h, {{"rng_state", 4 * sizeof(uint32_t)}})) return rc;
+        h->rng_state = Wt<uint32_t>(h, "rng_state");
+    }
+    launch_rng_set(h->rng_state, seed, draw, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
+extern "C" int desire_set_rng_origin(desire_handle* h, uint32_t scene_base, uint32_t slot_base) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null argument");
+    if (int rc = rng_check_packing(h, slot_base)) return rc;
+    h->rng_scene_base = scene_base; h->rng_slot_base = slot_base;
+    return DESIRE_OK;
+}
+
+extern "C" int desire_rng_state(desire_handle* h, uint32_t* host_out2, void* stream) {
+    if (!h || !host_out2) return fail(DESIRE_ERR_ARG, "null argument");
+    if (!h->rng_state) return fail(DESIRE_ERR_STATE, "desire_set_rng comes first");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIPCHK(hipMemcpyAsync(host_out2, h->rng_state, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return DESIRE_OK;
+}
+
+extern "C" int desire_rng_fill(desire_handle* h, uint64_t seed, uint32_t stream_id, uint64_t first, int32_t kind, void* dev_out, size_t n, void* stream) {
+    if (!h || !dev_out) return fail(DESIRE_ERR_ARG, "null argument");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (kind == DESIRE_RNG_BITS || kind == DESIRE_RNG_NORMAL) {
+        if (first + (uint64_t)n < first) return fail(DESIRE_ERR_ARG, "first + n passes 2^64");
+        launch_rng_fill(seed, stream_id, first, kind == DESIRE_RNG_NORMAL, dev_out, n, s);
+    } else if (kind == DESIRE_RNG_LATENT) {       // the eps [n_scenes, K, mno, L] of draw `stream_id` at the handle's origin: k_reparam_rng in prior mode
+        if (int rc = rng_check_packing(h, h->rng_slot_base)) return rc;
+        if (first != 0 || n != (size_t)h->R * h->d.L) return fail(DESIRE_ERR_ARG, "DESIRE_RNG_LATENT writes the whole eps: first = 0, n = R * L");
+        const RngArgs g{nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, h->rng_scene_base, h->rng_slot_base};
+        launch_reparam_rng(nullptr, g, static_cast<float*>(dev_out), h->R, h->d.L, h->d.K, h->d.mno, 0, s);
+    } else return fail(DESIRE_ERR_ARG, "kind must be DESIRE_RNG_BITS, DESIRE_RNG_NORMAL or DESIRE_RNG_LATENT");
     HIPCHK(hipGetLastError());
     return DESIRE_OK;
 }

@@ -459,8 +459,10 @@ int cvae_enc_bwd(const BwdPass& bp) {
     desire_ctx* h = bp.h; hipStream_t s = bp.s; const desire_dims& d = h->d;
     const int H = d.H, V = h->V, L = d.L, Ae = bp.agents_e;
     const bool bn1 = d.bn_mode != 0;
-    launch_reparam_bwd(W(h, "dz"), bp.eps, W(h, "params"), bp.valid, W(h, "nvalid"), W(h, "dparams"), d.n_scenes, d.mno, d.K, L, s,
-                       bp.rows_compact ? Wt<const int32_t>(h, "cp_inv") : nullptr, bp.n_present);
+    const int32_t* inv = bp.rows_compact ? Wt<const int32_t>(h, "cp_inv") : nullptr;
+    if (bp.eps) launch_reparam_bwd(W(h, "dz"), bp.eps, W(h, "params"), bp.valid, W(h, "nvalid"), W(h, "dparams"), d.n_scenes, d.mno, d.K, L, s, inv, bp.n_present);
+    else launch_reparam_bwd_rng(W(h, "dz"), rng_args(h), W(h, "params"), bp.valid, W(h, "nvalid"), W(h, "dparams"), d.n_scenes, d.mno, d.K, L, s, inv,
+                                bp.n_present);      // eps regenerated from rng_state.used: the draw of the forward this backward follows
     if (bp.enc_compact) launch_gather_agents(W(h, "dparams"), W(h, "cp_dparams"), bp.amap, bp.n_present, 2 * L, s);
     const float* dparE = bp.enc_compact ? W(h, "cp_dparams") : W(h, "dparams");
     if (Ae <= 0) return DESIRE_OK;
@@ -584,7 +586,7 @@ int encoder_bwd(const BwdPass& bp, const char* label, const std::string& slot, c
 extern "C" int desire_backward(desire_handle* h, const float* dev_past, const float* dev_fut, const float* dev_eps, void* stream) {
     if (int rc = desire_ready(h)) return rc;
     if (!h->training) return fail(DESIRE_ERR_STATE, "desire_set_training(h, 1) and a training-mode desire_forward come first");
-    if (!dev_past || !dev_fut || !dev_eps) return fail(DESIRE_ERR_ARG, "null argument");
+    if (!dev_past || !dev_fut || (!dev_eps && !h->rng_state)) return fail(DESIRE_ERR_ARG, "null argument");      // (dev_eps == NULL: legal after desire_set_rng)
     if (scene_grad_on(h) && !h->ws.find("sg_wcat")) return fail(DESIRE_ERR_STATE, "scene-gradient buffers missing");
     if (int rc = backward_alloc(h)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);

@@ -72,6 +72,8 @@ struct desire_ctx {
     // the same handle (desire_amd/prefetch.py: DeviceWindowFeeder), and those allocate workspace entries lazily (allocation inserts; reads do not): the
     // builder must not walk the map
     int32_t* bw_starts = nullptr; int32_t* bw_err = nullptr;
+    // desire_set_rng: the generator's device words "rng_state" (next, used, seed_lo, seed_hi; nullptr = off) and the origin of desire_set_rng_origin
+    uint32_t* rng_state = nullptr; uint32_t rng_scene_base = 0, rng_slot_base = 0;
     std::vector<Prof> prof;
     std::vector<std::string> prof_name_store;
     // ---- training (train.hip) ----
@@ -158,4 +160,5 @@ int scene_grad_setup(desire_ctx* h);                           // buffers of the
 inline bool scene_grad_on(const desire_ctx* h) { return h->scene_grad || h->img_set; }      // images attached imply the grid gradient
 void enc_weights(desire_ctx* h, const char* prefix, EncArgs& e);     // the fp32 GRU weights of the encoder "enc_x" / "enc_y" (api_forward.hip)
 IocStepArgs ioc_step_args(desire_ctx* h, int t);               // what every launch of the step-wise IOC kernel shares (api_peer.hip)
+inline RngArgs rng_args(const desire_ctx* h) { return RngArgs{h->rng_state, 0u, 0u, 0u, h->rng_scene_base, h->rng_slot_base}; }      // the handle's generator
 int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)

@@ -38,6 +38,21 @@ void launch_gemm_rows(const GemmArgs& a, int epi, hipStream_t s);
 void launch_reparam(const float* params, const float* eps, float* z, int R, int L, int K, int mno,
                     int posterior, hipStream_t s);
 
+// ---- device generator (kernels_rng.hip, philox.h; desire_set_rng) ----
+// What a generating kernel draws from: the handle's device words st = (next, used, seed_lo, seed_hi) -- the draw is st.used -- or, st == nullptr,
+// the explicit (seed, draw); the origin is the global index of the call's first window and of the handle's first slot (host values, by argument).
+struct RngArgs { const uint32_t* st; uint32_t seed_lo, seed_hi, draw; uint32_t scene_base, slot_base; };
+void launch_rng_set(uint32_t* st, uint64_t seed, uint32_t draw, hipStream_t s);        // next = used = draw, the seed words
+void launch_rng_begin(uint32_t* st, hipStream_t s);                                    // used = next; next += 1
+// out[i] = element first + i of the fill stream (seed, stream_id): raw words, or normals
+void launch_rng_fill(uint64_t seed, uint32_t stream_id, uint64_t first, int normals, void* out, uint64_t n, hipStream_t s);
+// the twins of launch_reparam / launch_reparam_c / launch_reparam_bwd that generate eps instead of reading it
+void launch_reparam_rng(const float* params, const RngArgs& g, float* z, int R, int L, int K, int mno, int posterior, hipStream_t s);
+void launch_reparam_c_rng(const float* params_c, const RngArgs& g, float* z, const int32_t* amap, int P, int K, int mno, int L, int posterior,
+                          hipStream_t s, const int32_t* dynP = nullptr);
+void launch_reparam_bwd_rng(const float* dz, const RngArgs& g, const float* params, const uint8_t* valid, const float* nvalid, float* dparams,
+                            int n_scenes, int mno, int K, int L, hipStream_t s, const int32_t* inv, int P);
+
 struct MaskArgs {
     const float* xhat; int R; int V; int H; int K; int mno;
     int Hl;                                        // logical width: the softmax runs over columns [0, Hl) (Hl < H: zero-padded tile)

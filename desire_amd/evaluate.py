@@ -74,7 +74,8 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     mean_k, n_all, n_windows = np.zeros(2, np.float64), 0, 0
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
-        model.predict(past, top=top, seed=args.seed)
+        # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
+        model.predict(past, top=top, seed=args.seed, device_rng=bool(getattr(args, "device_rng", False)), window_base=n_windows)
         Y, score = model.final_output, model.final_states
         ranked = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units=units).astype(np.float64)
         best = model.evaluate_ranked(Y, score, fut, top=K, horizons=hz, units=units).astype(np.float64)

@@ -244,22 +244,40 @@ class DESIREModel(object):
 
     # ---- the hot path ---------------------------------------------------------------------------
     def forward(self, x_batch: Sequence[np.ndarray], y_batch: Optional[Sequence[np.ndarray]] = None,
-                eps: Optional[np.ndarray] = None, seed: int = 0, grid_of_scene=None):
+                eps: Optional[np.ndarray] = None, seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0):
         """x_batch: loader windows [T_obs, MNO, 3] (DataLoader.next_batch x); y_batch: future windows
         [T_pred, MNO, 3] or None (prior sampling).  Returns (Yhat [n, K, mno, T_pred, 2] normalised,
-        score [n, K, mno]) as torch tensors on the GPU."""
+        score [n, K, mno]) as torch tensors on the GPU.  device_rng / window_base: see forward_device."""
         posterior = y_batch is not None
         d = self._handle(len(x_batch), posterior).dims
         past = self._pad_windows(x_batch, d.mno)
         fut = self._pad_windows(y_batch, d.mno) if posterior else None
-        out = self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene)
+        out = self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
         self.input_data, self.target_data = x_batch, y_batch
         return out
 
-    def forward_device(self, past, fut=None, eps=None, seed: int = 0, grid_of_scene=None):
+    def _eps(self, h, shape, eps, seed: int, device_rng: bool, window_base: int):
+        """The eps tensor of a call, or None when the handle draws it itself (device_rng: the counter-based generator of desire_set_rng, seeded
+        with `seed` at draw 0 and window origin `window_base` -- a window's noise then depends on its GLOBAL index, not on how the batch was cut)."""
+        torch = self.torch
+        if device_rng:
+            if eps is not None:
+                raise ValueError("device_rng draws eps on the device: eps must be None")
+            h.set_rng(seed, 0, torch.cuda.current_stream().cuda_stream)
+            h.set_rng_origin(window_base, 0)
+            return None
+        if eps is None:
+            g = torch.Generator(device=self.device).manual_seed(seed)
+            return torch.randn(shape, generator=g, device=self.device, dtype=torch.float32)
+        if torch.is_tensor(eps):
+            return eps.reshape(shape)
+        return torch.as_tensor(np.ascontiguousarray(eps, np.float32), device=self.device).reshape(shape)
+
+    def forward_device(self, past, fut=None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0):
         """forward() on windows that are already in HBM: past [n, T_obs, mno, 3], fut [n, T_pred, mno, 3] or None -- float32 device
         tensors in the loader's layout with the slot axis padded to the model's mno (what desire_amd.prefetch's feeders and
-        forward_from_video produce).  Nothing here touches the host except the launches themselves."""
+        forward_from_video produce).  Nothing here touches the host except the launches themselves.  device_rng=True: no eps tensor exists;
+        the kernels draw the latent noise from (seed, draw 0, window_base + window, k, slot, latent) where they consume it."""
         torch = self.torch
         n = int(past.shape[0])
         posterior = fut is not None
@@ -267,18 +285,12 @@ class DESIREModel(object):
         d = h.dims
         if tuple(past.shape[1:]) != (d.T_obs, d.mno, 3) or (posterior and tuple(fut.shape[1:]) != (d.T_pred, d.mno, 3)):
             raise ValueError("window lengths must be (seq_length, pred_length) and the slot axis max_num_obj padded to %d" % d.mno)
-        if eps is None:
-            g = torch.Generator(device=self.device).manual_seed(seed)
-            eps_t = torch.randn((d.R, d.L), generator=g, device=self.device, dtype=torch.float32)
-        elif torch.is_tensor(eps):
-            eps_t = eps.reshape(d.R, d.L)
-        else:
-            eps_t = torch.as_tensor(np.ascontiguousarray(eps, np.float32), device=self.device).reshape(d.R, d.L)
+        eps_t = self._eps(h, (d.R, d.L), eps, seed, device_rng, window_base)
         self._attach_scene(h, n, grid_of_scene)
         Y = torch.empty((n, d.K, d.mno, d.T_pred, 2), device=self.device, dtype=torch.float32)
         score = torch.empty((n, d.K, d.mno), device=self.device, dtype=torch.float32)
         stream = torch.cuda.current_stream().cuda_stream
-        h.forward(past.data_ptr(), fut.data_ptr() if posterior else 0, eps_t.data_ptr(), Y.data_ptr(),
+        h.forward(past.data_ptr(), fut.data_ptr() if posterior else 0, 0 if eps_t is None else eps_t.data_ptr(), Y.data_ptr(),
                   score.data_ptr(), stream)
         self._keep = (past, fut, eps_t)            # keep inputs alive until the stream has consumed them
         self.final_output, self.final_states = Y, score
@@ -326,7 +338,7 @@ class DESIREModel(object):
 
     # ---- training (train.py:140-181 runs only `cost`; the Adam op of model/model.py:386-403 is never applied) ----
     def train_step(self, x_batch: Sequence[np.ndarray], y_batch: Sequence[np.ndarray], eps: Optional[np.ndarray] = None,
-                   seed: int = 0, group=None, sync: bool = True, grid_of_scene=None):
+                   seed: int = 0, group=None, sync: bool = True, grid_of_scene=None, device_rng: bool = False, window_base: int = 0):
         """One optimiser step on a batch of loader windows: forward (posterior path), backward, gradient mean over
         the data-parallel ranks (RCCL all-reduce of ONE flat buffer when torch.distributed is initialised),
         clip_by_global_norm(args.grad_clip), Adam(args.learning_rate).  Returns the loss terms of DESIGN.md section 8
@@ -334,12 +346,14 @@ class DESIREModel(object):
         whose .get() returns them later (see train_step_device)."""
         d = self._handle(len(x_batch), True).dims
         out = self.train_step_device(self._pad_windows(x_batch, d.mno), self._pad_windows(y_batch, d.mno), eps, seed, group, sync,
-                                     grid_of_scene=grid_of_scene)
+                                     grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
         self.input_data, self.target_data = x_batch, y_batch
         return out
 
-    def train_step_device(self, past, fut, eps=None, seed: int = 0, group=None, sync: bool = True, grid_of_scene=None):
-        """train_step on windows already in HBM (forward_device's layout).  sync=False: nothing waits for the GPU -- the loss terms
+    def train_step_device(self, past, fut, eps=None, seed: int = 0, group=None, sync: bool = True, grid_of_scene=None, device_rng: bool = False,
+                          window_base: int = 0):
+        """train_step on windows already in HBM (forward_device's layout).  device_rng=True: the step holds no eps tensor -- the forward draws
+        it and the backward regenerates the same draw.  sync=False: nothing waits for the GPU -- the loss terms
         go to a device buffer (desire_train_loss_async), a pinned copy is enqueued, and the returned PendingLoss reads them when asked,
         normally one step later (desire_amd/train.py): the host runs ahead of the device and the loader thread is never starved by a
         read-back in the middle of every step."""
@@ -358,10 +372,10 @@ class DESIREModel(object):
             if pending is not None:                   # resumed run: Adam moments and step counter of the checkpoint
                 h.set_opt_state(pending)
             self._configure_head_loss(h)
-        self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene)
+        self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
         past, fut, eps_t = self._keep
         stream = torch.cuda.current_stream().cuda_stream
-        h.backward(past.data_ptr(), fut.data_ptr(), eps_t.data_ptr(), stream)
+        h.backward(past.data_ptr(), fut.data_ptr(), 0 if eps_t is None else eps_t.data_ptr(), stream)
         allreduce_mean_(h.grad_tensor(), group)
         clip = float(getattr(self.args, "grad_clip", 0.0) or 0.0)
         if clip > 0:
@@ -397,7 +411,8 @@ class DESIREModel(object):
             self._weights_ver = self._version
         return self._weights
 
-    def forward_from_video(self, frames, starts: Sequence[int], posterior: bool = True, eps=None, seed: int = 0):
+    def forward_from_video(self, frames, starts: Sequence[int], posterior: bool = True, eps=None, seed: int = 0, device_rng: bool = False,
+                           window_base: int = 0):
         """Device-side batching: `frames` [F, max_num_obj, 3] is one preprocessed video
         (DataLoader.data[i]); the windows starting at `starts` are cut and slot-assigned on the GPU exactly like the x of
         DataLoader(seq_length = seq_length + pred_length).next_batch (slots ranked over the window plus the loader's one
@@ -411,15 +426,11 @@ class DESIREModel(object):
         fut = torch.empty((n, d.T_pred, d.mno, 3), device=self.device)
         stream = torch.cuda.current_stream().cuda_stream
         h.build_windows(fr.data_ptr(), fr.shape[0], fr.shape[1], starts, past.data_ptr(), fut.data_ptr(), stream, lookahead=1)
-        if eps is None:
-            g = torch.Generator(device=self.device).manual_seed(seed)
-            eps_t = torch.randn((d.R, d.L), generator=g, device=self.device, dtype=torch.float32)
-        else:
-            eps_t = torch.as_tensor(np.ascontiguousarray(eps, np.float32), device=self.device).reshape(d.R, d.L)
+        eps_t = self._eps(h, (d.R, d.L), eps, seed, device_rng, window_base)
         self._attach_scene(h, n)
         Y = torch.empty((n, d.K, d.mno, d.T_pred, 2), device=self.device, dtype=torch.float32)
         score = torch.empty((n, d.K, d.mno), device=self.device, dtype=torch.float32)
-        h.forward(past.data_ptr(), fut.data_ptr() if posterior else 0, eps_t.data_ptr(), Y.data_ptr(), score.data_ptr(), stream)
+        h.forward(past.data_ptr(), fut.data_ptr() if posterior else 0, 0 if eps_t is None else eps_t.data_ptr(), Y.data_ptr(), score.data_ptr(), stream)
         self._keep = (fr, past, fut, eps_t)
         self.final_output, self.final_states = Y, score
         return Y, score, past, fut
@@ -437,22 +448,24 @@ class DESIREModel(object):
         return out.cpu().numpy()
 
     # ---- ranking by IOC score (desire_rank_samples / desire_ranked_errors) ---------------------------------
-    def predict(self, x_batch: Sequence[np.ndarray], top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None):
+    def predict(self, x_batch: Sequence[np.ndarray], top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False,
+                window_base: int = 0):
         """The `top` most plausible futures of every agent of a batch of observed loader windows [T_obs, MNO, 3], ranked by IOC score
         (prior sampling: no future given).  See predict_device for the result."""
         d = self._handle(len(x_batch), False).dims
-        out = self.predict_device(self._pad_windows(x_batch, d.mno), top, eps, seed, grid_of_scene=grid_of_scene)
+        out = self.predict_device(self._pad_windows(x_batch, d.mno), top, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng,
+                                  window_base=window_base)
         self.input_data, self.target_data = x_batch, None
         return out
 
-    def predict_device(self, past, top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None):
+    def predict_device(self, past, top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0):
         """predict() on windows already in HBM (forward_device's layout).  Returns a dict of device tensors: "traj" [n, mno, top, T_pred, 2]
         IN PIXELS, best-scored first; "score" [n, mno, top]; "order" [n, mno, K] int32 (sample indices by descending score, ties to the
         lower index); "present" [n, mno] bool (id != 0 at the last observed frame -- the rows of absent agents are whatever the forward
         left, zeros under the default padding-skipping flags, and their order is the identity).  top=None: default_top(K).  All K samples
         and scores stay available as self.final_output / self.final_states."""
         torch = self.torch
-        Y, score = self.forward_device(past, None, eps, seed, grid_of_scene=grid_of_scene)
+        Y, score = self.forward_device(past, None, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
         n = int(past.shape[0])
         h = self._handle(n, False)
         d = h.dims
@@ -568,7 +581,8 @@ class DESIREModel(object):
             cache[key] = (sub, self._version)
         return sub
 
-    def sample(self, sess, traj, grid, dimensions, true_traj, num=10, mode: Optional[str] = None, normals=None, seed: int = 0):
+    def sample(self, sess, traj, grid, dimensions, true_traj, num=10, mode: Optional[str] = None, normals=None, seed: int = 0,
+               device_rng: bool = False):
         """traj [obs, MNO, 3] observed frames; returns [obs+num, MNO, 3]: the observed frames followed by `num` predicted
         frames in pixel units, ids carried over from the last observed frame (model/model.py:680-688).  `sess` is ignored;
         `dimensions` = (width, height) of the frame in pixels (default: args.img_width / img_height).
@@ -580,7 +594,7 @@ class DESIREModel(object):
 
         mode "rollout" is the reference's loop (:623-688) on the device in one launch: warm-up over the observed
         frames, then per step the 5-wide Gaussian head "gauss_head/w|b" -> a draw (`normals` [num, MNO, 2] ~ N(0,1), or
-        torch's generator seeded with `seed`) -> clip to <= 1.0 in normalised units (:666-669) -> fed back as the next input.
+        torch's generator seeded with `seed`, or with device_rng=True the library's own desire_rng_fill stream (seed, stream 0)) -> clip to <= 1.0 in normalised units (:666-669) -> fed back as the next input.
         Like the reference, objects with id 0 are stepped too and keep id 0.  `true_traj` only feeds the reference's cost
         print-outs (:649,684-685) and is unused.
         mode "ioc": the top-scored IOC-refined sample of the frozen-spec forward (prior path); `grid` may be a [Gh,Gw,C]
@@ -612,7 +626,12 @@ class DESIREModel(object):
             h = sub._handle(1, False)
             d = h.dims
             past = sub._pad_windows([traj], d.mno)
-            if normals is None:
+            if device_rng:
+                if normals is not None:
+                    raise ValueError("device_rng fills the rollout's normals on the device: normals must be None")
+                nrm = torch.empty((num, d.A, 2), device=self.device, dtype=torch.float32)
+                h.rng_fill(seed, 0, 0, _lib.RNG_NORMAL, nrm.data_ptr(), nrm.numel(), torch.cuda.current_stream().cuda_stream)
+            elif normals is None:
                 g = torch.Generator(device=self.device).manual_seed(seed)
                 nrm = torch.randn((num, d.A, 2), generator=g, device=self.device, dtype=torch.float32)
             else:
@@ -632,7 +651,7 @@ class DESIREModel(object):
                              % (num, t_pred))
         if grid is not None and np.ndim(grid) == 3:
             sub.set_scene_grids(np.asarray(grid, np.float32)[None], [0])
-        Y, score = sub.forward([traj], None, seed=seed)
+        Y, score = sub.forward([traj], None, seed=seed, device_rng=device_rng)
         d = sub._handle(1, False).dims
         best = score[0].argmax(dim=0)                                        # [mno]
         idx = best.view(1, -1, 1, 1).expand(1, d.mno, d.T_pred, 2)

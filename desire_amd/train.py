@@ -26,6 +26,15 @@ from typing import Callable, List, Sequence, Tuple
 import numpy as np
 
 
+def _noise(args, step: int, rank: int, world: int) -> dict:
+    """Where a training step's latent noise comes from: torch.randn seeded per (step, rank), or with --device_rng the device generator seeded per
+    step on every rank alike, each rank at the global index of its first window (dist.shard_windows) -- the step's noise is then the one-rank step's."""
+    if not getattr(args, "device_rng", False):
+        return {"seed": args.seed + step * world + rank}
+    from .dist import shard_windows
+    return {"seed": args.seed + step, "device_rng": True, "window_base": shard_windows(int(args.batch_size), rank, world)[0]}
+
+
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="DESIRE training on MI355X (flags of the reference's train.py:28-88)")
     p.add_argument("--rnn_size", type=int, default=512)
@@ -56,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--save_dir", type=str, default="save")
     p.add_argument("--max_steps", type=int, default=0, help="stop after this many optimiser steps (0 = all epochs)")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--device_rng", action="store_true",
+                   help="draw the latent noise on the device (counter-based Philox, desire_set_rng) instead of torch.randn: no eps tensor, and a "
+                        "window's noise depends on (seed, step, its index in the global batch), not on the rank count or the batch cut")
     p.add_argument("--fix_id0", action="store_true", help="keep SDD track id 0 (the reference drops it)")
     p.add_argument("--ioc_iters", type=int, default=1, help="IOC refinement passes")
     p.add_argument("--bf16", type=str, default="", choices=["", "f32", "x3", "split"],
@@ -201,7 +213,7 @@ def train(args, data_loader=None, model=None, log: Callable[[str], None] = print
             start = time.time()
             xval, _, dval = data_loader.next_batch()
             past, fut = split_windows(shard_batch(xval, rank, world), t_obs)
-            terms = model.train_step(past, fut, seed=args.seed + steps * world + rank, grid_of_scene=_gos(grid_of_video, shard_batch(dval, rank, world)))
+            terms = model.train_step(past, fut, **_noise(args, steps, rank, world), grid_of_scene=_gos(grid_of_video, shard_batch(dval, rank, world)))
             losses.append(terms["loss"])
             steps += 1
             if rank == 0:
@@ -304,7 +316,7 @@ def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred,
             if last is not None and bt.epoch != last[2]:
                 _report(args, model, last[0], last[1], last[2], rank, log)
             bt.wait()
-            pl = model.train_step_device(bt.past, bt.fut, seed=args.seed + steps * world + rank, sync=False,
+            pl = model.train_step_device(bt.past, bt.fut, **_noise(args, steps, rank, world), sync=False,
                                          grid_of_scene=_gos(getattr(model, "_grid_of_video", None), bt.d))
             if reporting:                                 # the epoch's last batch is evaluated after the feeder has moved on: keep a copy
                 last = (bt.past.clone(), bt.fut.clone(), bt.epoch)

@@ -187,7 +187,8 @@ int desire_set_scene_images(desire_handle* h, const float* dev_images, int32_t H
 int desire_encode(desire_handle* h, const float* dev_past, const float* dev_fut, void* stream);
 
 /* Reparameterise + CVAE decoder + mask fc + GRU decoder (model/model.py:260-289).
- * dev_eps [R, L]; dev_Yhat [R, T_pred, 2] out (normalised coordinates). */
+ * dev_eps [R, L]; dev_Yhat [R, T_pred, 2] out (normalised coordinates).  dev_eps may be NULL after desire_set_rng: the call then draws its
+ * eps on the device (one draw per call; see "device generator" below). */
 int desire_sample(desire_handle* h, const float* dev_eps, float* dev_Yhat, void* stream);
 
 /* IOC scoring + regression refinement, dims.iters passes (paper; model/model.py:312-313).
@@ -199,6 +200,41 @@ int desire_ioc_refine(desire_handle* h, float* dev_Yhat, float* dev_score, void*
 /* encode + sample + ioc_refine, the unit bench.py times. */
 int desire_forward(desire_handle* h, const float* dev_past, const float* dev_fut, const float* dev_eps,
                    float* dev_Yhat, float* dev_score, void* stream);
+
+/* ---- device generator: the latent noise drawn where it is consumed (csrc/philox.h, csrc/kernels_rng.hip) ----
+ * Philox4x32-10 (Salmon et al., SC'11: multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85, ten rounds), key = the 64-bit seed
+ * as (lo, hi).  A 32-bit word x becomes the uniform u = ((x >> 9) + 0.5) * 2^-23 (exact in fp32, never 0 or 1); Box-Muller on the word pairs
+ * (x0, x1) and (x2, x3) -- r = sqrtf(-2 logf(u1)), t = 2 pi u2, normals r cosf(t) and r sinf(t) -- makes four normals of one block, |n| <= 5.77.
+ * THE COUNTERS ARE PART OF THIS CONTRACT (tests/rng_reference.py restates them in numpy, bit for bit):
+ *     word   latent eps                                fill op (desire_rng_fill, kinds BITS / NORMAL)
+ *     c0     (l >> 2) | slot << 10 | k << 19           low word of the block index
+ *     c1     scene_base + scene   (modulo 2^32)        high word of the block index
+ *     c2     draw                                      the caller's stream_id
+ *     c3     0                                         1
+ * Latent l of sample k of (window scene_base + scene, slot slot_base + slot) in draw `draw` is normal l & 3 of that block (L % 8 == 0: whole
+ * blocks); element e of a fill stream is word / normal e & 3 of block e >> 2.  The packing holds L <= 4096, slot_base + mno <= 512 and K < 8192.
+ * So a window's noise does not depend on its position in the batch, the batch size, the rank count, the padding width or DESIRE_FLAG_COMPACT_*.
+ *
+ * desire_set_rng switches the generator on, or re-seeds it: next draw = `draw`.  The first call allocates four device words (next, used, seed);
+ * every call sets them with one kernel, stream-ordered and capturable (the first call is not).  Afterwards dev_eps == NULL is legal in
+ * desire_sample, desire_forward and desire_backward (before: DESIRE_ERR_ARG, as ever).  A sampling call with NULL eps does, ON THE DEVICE,
+ * used = next; next += 1, and draws with `used` -- a replayed hipGraph therefore advances by itself, and setting the words again replays the
+ * same noise.  desire_backward(NULL) regenerates the eps of `used` and does not advance: a training step keeps no eps.  A non-NULL dev_eps takes
+ * the kernels it always took and leaves the counter alone.  Dims outside the packing: DESIRE_ERR_ARG. */
+int desire_set_rng(desire_handle* h, uint64_t seed, uint32_t draw, void* stream);
+/* The global index of the call's first window and of the handle's first slot (an agent-sharded handle whose mno is a shard).  Host-side values,
+ * passed to the kernels as ARGUMENTS: a captured graph keeps the origin it was captured with.  Default (0, 0). */
+int desire_set_rng_origin(desire_handle* h, uint32_t scene_base, uint32_t slot_base);
+/* host_out[0] = next (the draw the next sampling call will use), host_out[1] = used (the draw of the last one).  Synchronises the stream. */
+int desire_rng_state(desire_handle* h, uint32_t host_out[2], void* stream);
+#define DESIRE_RNG_BITS 0     /* dev_out: n uint32, the raw stream */
+#define DESIRE_RNG_NORMAL 1   /* dev_out: n fp32 normals */
+#define DESIRE_RNG_LATENT 2   /* dev_out: fp32 [n_scenes, K, mno, L] = exactly the eps a NULL-eps call of this handle uses in draw `stream_id` with key
+                                 `seed` at the handle's current origin; first must be 0 and n = R * L.  For tests, and for keeping a draw. */
+/* Stand-alone fill: dev_out[i] = element first + i of the stream (seed, stream_id), so a fill equals the matching slice of any longer one.
+ * Needs no desire_set_rng and does not touch the draw counter.  Callers of desire_rollout / desire_gaussian_sample, which keep taking
+ * dev_normals, fill them with kind DESIRE_RNG_NORMAL.  Stream-ordered, capturable. */
+int desire_rng_fill(desire_handle* h, uint64_t seed, uint32_t stream_id, uint64_t first, int32_t kind, void* dev_out, size_t n, void* stream);
 
 /* Intermediates kept in the handle's workspace, for parity tests:
  * "Hx" [A,H], "Hy" [A,H], "vae_in" [A,V], "z_mean" [A,L], "z_log_sigma_sq" [A,L], "z" [R,L],
@@ -361,6 +397,7 @@ int desire_set_training(desire_handle* h, int enable);
  * also fills the gradients of "gauss_head/w|b" -- the head desire_rollout / sample() read, which no other term reaches -- and adds
  * the term's gradient to the X encoder's, step by step.  weight = 0 (default) switches the term off. */
 int desire_set_head_loss(desire_handle* h, float weight);
+/* (dev_eps == NULL after desire_set_rng: the eps of the forward's draw is regenerated, see "device generator") */
 int desire_backward(desire_handle* h, const float* dev_past, const float* dev_fut, const float* dev_eps, void* stream);
 int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream);
 int desire_grad_buffer(desire_handle* h, float** dev_ptr, size_t* n);
