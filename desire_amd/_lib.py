@@ -26,9 +26,9 @@ EXPORTS = [
     "desire_set_option", "desire_train_loss_async", "desire_set_head_loss",
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
     "desire_rank_samples", "desire_ranked_errors",
-    "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill",
+    "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
 ]
-RNG_BITS, RNG_NORMAL, RNG_LATENT = 0, 1, 2          # desire_rng_fill kinds (DESIRE_RNG_*)
+RNG_BITS, RNG_NORMAL, RNG_LATENT, RNG_ROLLOUT = 0, 1, 2, 3          # desire_rng_fill kinds (DESIRE_RNG_*)
 
 
 class DesireDims(C.Structure):
@@ -97,6 +97,7 @@ def load() -> C.CDLL:
     lib.desire_rank_samples.argtypes = [vp, f32p, f32p, i32, vp, f32p, f32p, vp]
     lib.desire_ranked_errors.argtypes = [vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
+    lib.desire_rollout_samples.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
     lib.desire_backward.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_get_grad.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float), C.c_size_t, vp]
@@ -213,7 +214,8 @@ class Handle:
 
     def rng_fill(self, seed: int, stream_id: int, first: int, kind: int, out_ptr: int, n: int, stream: int = 0) -> None:
         """n elements of the fill stream (seed, stream_id) from element `first`: RNG_BITS (uint32) or RNG_NORMAL (fp32); RNG_LATENT writes the eps
-        [n_scenes, K, mno, L] of draw `stream_id` at the handle's origin (first = 0, n = R * L)."""
+        [n_scenes, K, mno, L] of draw `stream_id` at the handle's origin (first = 0, n = R * L), RNG_ROLLOUT the normals [n_scenes, K, mno, T_pred, 2]
+        of a generating rollout_samples (first = 0, n = R * T_pred * 2)."""
         _chk(self.lib.desire_rng_fill(self._h, int(seed) & (2 ** 64 - 1), int(stream_id) & 0xFFFFFFFF, int(first), int(kind), out_ptr, int(n), stream or None))
 
     def ioc_refine(self, yhat_ptr: int, score_ptr: int, stream: int = 0) -> None:
@@ -257,6 +259,11 @@ class Handle:
 
     def rollout(self, past_ptr: int, normals_ptr: int, num: int, out_ptr: int, stream: int = 0) -> None:
         _chk(self.lib.desire_rollout(self._h, past_ptr, normals_ptr, num, out_ptr, stream or None))
+
+    def rollout_samples(self, past_ptr: int, normals_ptr: int, yhat_ptr: int, stream: int = 0) -> None:
+        """K head rollouts per agent in the sample layout: yhat [R, T_pred, 2], normals [R, T_pred, 2] or 0 (after set_rng: drawn in the kernel,
+        one draw per call)."""
+        _chk(self.lib.desire_rollout_samples(self._h, past_ptr or None, normals_ptr or None, yhat_ptr or None, stream or None))
 
     def ade_fde(self, yhat_ptr: int, fut_ptr: int, out_ptr: int, stream: int = 0) -> None:
         _chk(self.lib.desire_ade_fde(self._h, yhat_ptr, fut_ptr, out_ptr, stream or None))

@@ -145,6 +145,39 @@ extern "C" int desire_rollout(desire_handle* h, const float* dev_past, const flo
     return DESIRE_OK;
 }
 
+// K rollouts per agent in the sample layout: the warm-up above ONCE per agent into "roll_h" (k_encoder, no prediction step), then k_rollout
+// (kernels_rollout.hip) over the R = A * K rows, each from its agent's state.  dev_normals == NULL: drawn in the kernel (one draw of the generator).
+static int rollout_check_packing(const desire_ctx* h);
+extern "C" int desire_rollout_samples(desire_handle* h, const float* dev_past, const float* dev_normals, float* dev_Yhat, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_past) return fail(DESIRE_ERR_ARG, "dev_past is NULL");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to roll out into");
+    if (!dev_normals) {
+        if (!h->rng_state) return fail(DESIRE_ERR_ARG, "dev_normals is NULL and desire_set_rng has not been called");
+        if (int rc = rollout_check_packing(h)) return rc;
+    }
+    if (int rc = desire_ready(h)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = ws_ensure(h, {{"roll_h", (size_t)h->A * d.H * sizeof(float)}})) return rc;
+    if (!dev_normals) launch_rng_begin(h->rng_state, s);       // one draw per generating call
+    EncArgs e{};
+    e.n_scenes = d.n_scenes; e.mno = d.mno; e.sx = d.sx; e.sy = d.sy; e.H = d.H;
+    e.frames = dev_past; e.T = d.T_obs;
+    enc_weights(h, "enc_x", e);
+    e.out = W(h, "roll_h"); e.ldo = d.H;
+    { Timer t(h, s, "rollout_warmup"); launch_encoder(e, s); }
+    RollArgs r{};
+    r.h_T = W(h, "roll_h"); r.R = h->R; r.K = d.K; r.mno = d.mno; r.H = d.H; r.T = d.T_pred;
+    r.wx_g = e.wx_g; r.b_g = e.b_g; r.wx_c = e.wx_c; r.b_c = e.b_c; r.Whg = e.Whg; r.Whc = e.Whc;
+    r.w5 = D(h, "gauss_head/w"); r.b5 = D(h, "gauss_head/b");
+    r.normals = dev_normals; r.g = rng_args(h); r.Y = dev_Yhat;
+    { Timer t(h, s, "rollout_samples"); launch_rollout_samples(r, s); }
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 extern "C" int desire_ade_fde(desire_handle* h, const float* dev_Yhat, const float* dev_fut, float* dev_out, void* stream) {
     if (!h || !dev_Yhat || !dev_fut || !dev_out) return fail(DESIRE_ERR_ARG, "null argument");
     const desire_dims& d = h->d;
@@ -207,6 +240,12 @@ int rng_check_packing(const desire_ctx* h, uint32_t slot_base) {
     return 0;
 }
 }  // namespace
+// the rollout counter packs the step where the latent counter packs the latent: T_pred <= 2048 on top of the latent's limits
+static int rollout_check_packing(const desire_ctx* h) {
+    if (int rc = rng_check_packing(h, h->rng_slot_base)) return rc;
+    if (h->d.T_pred > PHILOX_MAX_T) return fail(DESIRE_ERR_ARG, "the generator's rollout counter holds steps up to T_pred = 2048");
+    return 0;
+}
 
 extern "C" int desire_set_rng(desire_handle* h, uint64_t seed, uint32_t draw, void* stream) {
     if (!h) return fail(DESIRE_ERR_ARG, "null argument");
@@ -247,7 +286,12 @@ extern "C" int desire_rng_fill(desire_handle* h, uint64_t seed, uint32_t stream_
         if (first != 0 || n != (size_t)h->R * h->d.L) return fail(DESIRE_ERR_ARG, "DESIRE_RNG_LATENT writes the whole eps: first = 0, n = R * L");
         const RngArgs g{nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, h->rng_scene_base, h->rng_slot_base};
         launch_reparam_rng(nullptr, g, static_cast<float*>(dev_out), h->R, h->d.L, h->d.K, h->d.mno, 0, s);
-    } else return fail(DESIRE_ERR_ARG, "kind must be DESIRE_RNG_BITS, DESIRE_RNG_NORMAL or DESIRE_RNG_LATENT");
+    } else if (kind == DESIRE_RNG_ROLLOUT) {      // the normals [R, T_pred, 2] of draw `stream_id` at the handle's origin: k_rollout's own device function
+        if (int rc = rollout_check_packing(h)) return rc;
+        if (first != 0 || n != (size_t)h->R * h->d.T_pred * 2) return fail(DESIRE_ERR_ARG, "DESIRE_RNG_ROLLOUT writes the whole tensor: first = 0, n = R * T_pred * 2");
+        const RngArgs g{nullptr, (uint32_t)seed, (uint32_t)(seed >> 32), stream_id, h->rng_scene_base, h->rng_slot_base};
+        launch_rollout_normals(g, static_cast<float*>(dev_out), h->R, h->d.T_pred, h->d.K, h->d.mno, s);
+    } else return fail(DESIRE_ERR_ARG, "kind must be DESIRE_RNG_BITS, DESIRE_RNG_NORMAL, DESIRE_RNG_LATENT or DESIRE_RNG_ROLLOUT");
     HIPCHK(hipGetLastError());
     return DESIRE_OK;
 }

@@ -42,6 +42,12 @@ void launch_reparam(const float* params, const float* eps, float* z, int R, int 
 // What a generating kernel draws from: the handle's device words st = (next, used, seed_lo, seed_hi) -- the draw is st.used -- or, st == nullptr,
 // the explicit (seed, draw); the origin is the global index of the call's first window and of the handle's first slot (host values, by argument).
 struct RngArgs { const uint32_t* st; uint32_t seed_lo, seed_hi, draw; uint32_t scene_base, slot_base; };
+// the generator's inputs as a kernel sees them: the handle's device words, or (st == nullptr) explicit values
+struct RngKey { uint32_t lo, hi, draw; };
+__device__ __forceinline__ RngKey rng_key(const RngArgs& g) {
+    if (g.st) return RngKey{g.st[2], g.st[3], g.st[1]};
+    return RngKey{g.seed_lo, g.seed_hi, g.draw};
+}
 void launch_rng_set(uint32_t* st, uint64_t seed, uint32_t draw, hipStream_t s);        // next = used = draw, the seed words
 void launch_rng_begin(uint32_t* st, hipStream_t s);                                    // used = next; next += 1
 // out[i] = element first + i of the fill stream (seed, stream_id): raw words, or normals
@@ -104,6 +110,20 @@ struct EncArgs {
 void launch_encoder(const EncArgs& a, hipStream_t s);
 void launch_encoder_pair(const EncArgs& past, const EncArgs& fut, hipStream_t s);   // both encoders, one launch (same H)
 void launch_encoder_bf16(const EncArgs& a, hipStream_t s);    // kernels_bf16.hip; Whg / Whc = bf16 packs
+
+// ---- K head rollouts per agent in the sample layout (kernels_rollout.hip; desire_rollout_samples) ----
+// Row r = (scene * K + k) * mno + slot starts from its agent's warmed-up state h_T[agent] and runs T steps of head -> draw -> clip -> GRU (the "enc_x"
+// cell).  normals [R, T, 2], or nullptr: the kernel computes them from the rollout counter of philox.h (g), never stored.
+struct RollArgs {
+    const float* h_T; int R; int K; int mno; int H; int T;  // h_T [A, H]: the X encoder's state after the observed frames
+    const float* wx_g; const float* b_g; const float* wx_c; const float* b_c; const float4* Whg; const float4* Whc;   // as EncArgs
+    const float* w5; const float* b5;                       // head [H, 5], [5]
+    const float* normals; RngArgs g;
+    float* Y;                                               // [R, T, 2] out, normalised units, clipped to <= 1
+};
+void launch_rollout_samples(const RollArgs& a, hipStream_t s);
+// out [R, T, 2] = the normals a generating launch_rollout_samples draws with g (desire_rng_fill, kind DESIRE_RNG_ROLLOUT; kernels_rng.hip)
+void launch_rollout_normals(const RngArgs& g, float* out, int R, int T, int K, int mno, hipStream_t s);
 
 struct DecArgs {
     const float* xz; const float* Hx; int ldhx; const float* p_last;

@@ -51,12 +51,6 @@ void launch_rng_fill(uint64_t seed, uint32_t stream_id, uint64_t first, int norm
                        static_cast<uint32_t*>(out), n);
 }
 
-// the generator's inputs as a kernel sees them: the handle's device words, or (st == nullptr) explicit values
-struct RngKey { uint32_t lo, hi, draw; };
-__device__ __forceinline__ RngKey rng_key(const RngArgs& g) {
-    if (g.st) return RngKey{g.st[2], g.st[3], g.st[1]};
-    return RngKey{g.seed_lo, g.seed_hi, g.draw};
-}
 __device__ __forceinline__ float4 reparam4(const float* __restrict__ params, size_t a, int L, int l, const float e[4]) {
     const float4 mu = *reinterpret_cast<const float4*>(params + a * 2 * L + l), ls = *reinterpret_cast<const float4*>(params + a * 2 * L + L + l);
     float4 z;                                            // k_reparam: mu + sd * eps is one fma
@@ -85,6 +79,27 @@ void launch_reparam_rng(const float* params, const RngArgs& g, float* z, int R, 
     const long n = (long)R * (L >> 2);
     if (n <= 0) return;
     hipLaunchKernelGGL(k_reparam_rng, dim3(rng_grid(n)), dim3(256), 0, s, params, g, z, R, L, K, mno, posterior);
+}
+
+// ---- the normals of a generating desire_rollout_samples, [R, T, 2]: one lane per Philox block = steps 2b, 2b + 1 of a row (k_rollout computes the same
+// blocks with the same device function and never stores them) ----
+__global__ void k_rollout_normals(RngArgs g, float* __restrict__ out, int R, int T, int K, int mno) {
+    const int T2 = (T + 1) >> 1;
+    const RngKey key = rng_key(g);
+    RNG_FOR(i, (long)R * T2) {
+        const int r = (int)(i / T2), t = (int)(i - (long)r * T2) << 1;
+        const int sk = r / mno, slot = r - sk * mno, sc = sk / K, k = sk - sc * K;
+        float n[4];
+        philox_roll4(key.lo, key.hi, key.draw, g.scene_base + (uint32_t)sc, (uint32_t)k, g.slot_base + (uint32_t)slot, (uint32_t)t, n);
+        float* o = out + ((size_t)r * T + t) * 2;
+        o[0] = n[0]; o[1] = n[1];
+        if (t + 1 < T) { o[2] = n[2]; o[3] = n[3]; }
+    }
+}
+void launch_rollout_normals(const RngArgs& g, float* out, int R, int T, int K, int mno, hipStream_t s) {
+    const long n = (long)R * ((T + 1) >> 1);
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_rollout_normals, dim3(rng_grid(n)), dim3(256), 0, s, g, out, R, T, K, mno);
 }
 
 // ---- k_reparam_c's twin: compact row r' = k * P + a' (kernels_compact.hip); the counter is the ORIGINAL (scene, k, slot) of amap[a'], never r' ----

@@ -2,7 +2,8 @@
 device, errors per horizon of the best-scored sample (top-1), of the best among the top N by score and of the best of all K.
 
     python -m desire_amd.evaluate --checkpoint save/social_model-400.npz --data_dir data/ --max_num_obj 32 --d_dim 128 \\
-        --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json]
+        --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json] \\
+        [--generator cvae|rollout]
 
 The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
@@ -28,6 +29,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--units", type=str, default="px",
                    help="px (pixels), norm (normalised units) or a factor on pixels, e.g. 0.2 for the paper's 1/5 resolution")
     p.add_argument("--max_windows", type=int, default=0, help="stop after this many windows (0 = all)")
+    p.add_argument("--generator", type=str, default="cvae", choices=("cvae", "rollout"),
+                   help="what draws the K samples that the IOC stage scores: cvae (the CVAE decoder) or rollout (K rollouts of the reference's Gaussian head "
+                        "per agent, desire_rollout_samples; needs a checkpoint trained with --head_loss_weight > 0)")
     p.add_argument("--out", type=str, default=None, help="write the result JSON here (default: standard output only)")
     return p
 
@@ -65,6 +69,7 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     if model is None:
         model = DESIREModel.restore(args, args.checkpoint)
     K = int(args.num_samples)
+    generator = str(getattr(args, "generator", "cvae") or "cvae")
     top = int(args.eval_top or default_top(K))
     hz = parse_horizons(args.eval_horizons, t_pred)
     units = args.units if args.units in ("px", "norm") else float(args.units)
@@ -75,7 +80,8 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
-        model.predict(past, top=top, seed=args.seed, device_rng=bool(getattr(args, "device_rng", False)), window_base=n_windows)
+        gen = {} if generator == "cvae" else {"generator": generator}
+        model.predict(past, top=top, seed=args.seed, device_rng=bool(getattr(args, "device_rng", False)), window_base=n_windows, **gen)
         Y, score = model.final_output, model.final_states
         ranked = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units=units).astype(np.float64)
         best = model.evaluate_ranked(Y, score, fut, top=K, horizons=hz, units=units).astype(np.float64)
@@ -96,7 +102,7 @@ def evaluate(args, data_loader=None, model=None) -> dict:
         mean_k += ev[c, 0:2].sum(0)
         n_all += int(c.sum())
         n_windows += len(xs)
-    res = {"checkpoint": args.checkpoint, "units": args.units, "seed": int(args.seed), "K": K, "top": top, "horizons": hz,
+    res = {"checkpoint": args.checkpoint, "generator": generator, "units": args.units, "seed": int(args.seed), "K": K, "top": top, "horizons": hz,
            "windows": n_windows, "agents": [int(a) for a in agents]}
     for k in names:
         m = sums[k] / np.maximum(agents, 1)[:, None]

@@ -448,24 +448,99 @@ class DESIREModel(object):
         return out.cpu().numpy()
 
     # ---- ranking by IOC score (desire_rank_samples / desire_ranked_errors) ---------------------------------
+    def rollout_samples(self, x_batch: Sequence[np.ndarray], normals=None, seed: int = 0, device_rng: bool = False, window_base: int = 0):
+        """K rollouts of the Gaussian head per agent of a batch of observed loader windows [T_obs, MNO, 3], in ONE launch and in the sample layout:
+        returns Y [n, K, mno, T_pred, 2] (normalised units, clipped to <= 1.0) on the GPU -- what forward() returns as Yhat, from the reference's
+        own generator (sample(mode="rollout") K times).  normals [n, K, mno, T_pred, 2] ~ N(0,1) (array or device tensor), or None: torch's
+        generator seeded with `seed`, or with device_rng=True drawn in the kernel from (seed, draw 0, window_base + window, k, slot, step) -- no
+        noise tensor exists then.  Objects with id 0 are stepped like any other."""
+        d = self._handle(len(x_batch), False).dims
+        out = self.rollout_samples_device(self._pad_windows(x_batch, d.mno), normals, seed, device_rng=device_rng, window_base=window_base)
+        self.input_data, self.target_data = x_batch, None
+        return out
+
+    def rollout_samples_device(self, past, normals=None, seed: int = 0, device_rng: bool = False, window_base: int = 0):
+        """rollout_samples() on windows already in HBM (forward_device's layout)."""
+        torch = self.torch
+        n = int(past.shape[0])
+        h = self._handle(n, False)
+        d = h.dims
+        if tuple(past.shape[1:]) != (d.T_obs, d.mno, 3):
+            raise ValueError("windows must be seq_length frames with the slot axis max_num_obj padded to %d" % d.mno)
+        stream = torch.cuda.current_stream().cuda_stream
+        shape = (d.R, d.T_pred, 2)
+        if device_rng:
+            if normals is not None:
+                raise ValueError("device_rng draws the rollout's normals on the device: normals must be None")
+            h.set_rng(seed, 0, stream)
+            h.set_rng_origin(window_base, 0)
+            nrm = None
+        elif normals is None:
+            g = torch.Generator(device=self.device).manual_seed(seed)
+            nrm = torch.randn(shape, generator=g, device=self.device, dtype=torch.float32)
+        elif torch.is_tensor(normals):
+            nrm = normals.to(device=self.device, dtype=torch.float32).reshape(shape).contiguous()
+        else:
+            nrm = torch.as_tensor(np.ascontiguousarray(normals, np.float32), device=self.device).reshape(shape)
+        Y = torch.empty((n, d.K, d.mno, d.T_pred, 2), device=self.device, dtype=torch.float32)
+        h.rollout_samples(past.data_ptr(), 0 if nrm is None else nrm.data_ptr(), Y.data_ptr(), stream)
+        self._keep = (past, nrm)                   # keep inputs alive until the stream has consumed them
+        return Y
+
+    def _rollout_forward_device(self, past, normals, seed: int, grid_of_scene, device_rng: bool, window_base: int):
+        """forward_device() with the head rollout as the generator: encode (the IOC stage reads its Hx, last positions and presence flags), K
+        rollouts per agent, IOC scoring + refinement.  Returns (Y, score) like forward_device."""
+        torch = self.torch
+        if not getattr(self, "_head_given", False):
+            import warnings
+            warnings.warn("generator='rollout' reads gauss_head/w|b, which train_step trains only with args.head_loss_weight > 0; this "
+                          "model's head holds its random initial values (train it, pass weights= with a trained head, or use generator='cvae')",
+                          stacklevel=3)
+        n = int(past.shape[0])
+        h = self._handle(n, False)
+        d = h.dims
+        if tuple(past.shape[1:]) != (d.T_obs, d.mno, 3):
+            raise ValueError("windows must be seq_length frames with the slot axis max_num_obj padded to %d" % d.mno)
+        self._attach_scene(h, n, grid_of_scene)
+        stream = torch.cuda.current_stream().cuda_stream
+        h.encode(past.data_ptr(), 0, stream)
+        Y = self.rollout_samples_device(past, normals, seed, device_rng=device_rng, window_base=window_base)
+        score = torch.empty((n, d.K, d.mno), device=self.device, dtype=torch.float32)
+        h.ioc_refine(Y.data_ptr(), score.data_ptr(), stream)
+        self.final_output, self.final_states, self.cost = Y, score, None
+        return Y, score
+
     def predict(self, x_batch: Sequence[np.ndarray], top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False,
-                window_base: int = 0):
+                window_base: int = 0, generator: str = "cvae", normals=None):
         """The `top` most plausible futures of every agent of a batch of observed loader windows [T_obs, MNO, 3], ranked by IOC score
         (prior sampling: no future given).  See predict_device for the result."""
         d = self._handle(len(x_batch), False).dims
         out = self.predict_device(self._pad_windows(x_batch, d.mno), top, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng,
-                                  window_base=window_base)
+                                  window_base=window_base, generator=generator, normals=normals)
         self.input_data, self.target_data = x_batch, None
         return out
 
-    def predict_device(self, past, top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0):
+    def predict_device(self, past, top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0,
+                       generator: str = "cvae", normals=None):
         """predict() on windows already in HBM (forward_device's layout).  Returns a dict of device tensors: "traj" [n, mno, top, T_pred, 2]
         IN PIXELS, best-scored first; "score" [n, mno, top]; "order" [n, mno, K] int32 (sample indices by descending score, ties to the
         lower index); "present" [n, mno] bool (id != 0 at the last observed frame -- the rows of absent agents are whatever the forward
         left, zeros under the default padding-skipping flags, and their order is the identity).  top=None: default_top(K).  All K samples
-        and scores stay available as self.final_output / self.final_states."""
+        and scores stay available as self.final_output / self.final_states.
+        generator "cvae" (default): the K samples of the CVAE decoder (forward_device).  "rollout": K rollouts of the Gaussian head per agent
+        (rollout_samples; `normals` [n, K, mno, T_pred, 2] or None as there, `eps` must be None), scored and refined by the same IOC stage -- the
+        reference's generator under the same ranking; warns like sample(mode="rollout") while the head is untrained."""
         torch = self.torch
-        Y, score = self.forward_device(past, None, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
+        if generator == "cvae":
+            if normals is not None:
+                raise ValueError("`normals` are the head rollout's draws: pass generator='rollout' with them")
+            Y, score = self.forward_device(past, None, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
+        elif generator == "rollout":
+            if eps is not None:
+                raise ValueError("`eps` is the CVAE's latent noise: generator='rollout' takes `normals`")
+            Y, score = self._rollout_forward_device(past, normals, seed, grid_of_scene, device_rng, window_base)
+        else:
+            raise ValueError("generator must be 'cvae' (the CVAE decoder's samples) or 'rollout' (the Gaussian head's rollouts), got %r" % (generator,))
         n = int(past.shape[0])
         h = self._handle(n, False)
         d = h.dims

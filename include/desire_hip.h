@@ -206,13 +206,15 @@ int desire_forward(desire_handle* h, const float* dev_past, const float* dev_fut
  * as (lo, hi).  A 32-bit word x becomes the uniform u = ((x >> 9) + 0.5) * 2^-23 (exact in fp32, never 0 or 1); Box-Muller on the word pairs
  * (x0, x1) and (x2, x3) -- r = sqrtf(-2 logf(u1)), t = 2 pi u2, normals r cosf(t) and r sinf(t) -- makes four normals of one block, |n| <= 5.77.
  * THE COUNTERS ARE PART OF THIS CONTRACT (tests/rng_reference.py restates them in numpy, bit for bit):
- *     word   latent eps                                fill op (desire_rng_fill, kinds BITS / NORMAL)
- *     c0     (l >> 2) | slot << 10 | k << 19           low word of the block index
- *     c1     scene_base + scene   (modulo 2^32)        high word of the block index
- *     c2     draw                                      the caller's stream_id
- *     c3     0                                         1
+ *     word   latent eps                                fill op (desire_rng_fill, kinds BITS / NORMAL)     head rollout (desire_rollout_samples)
+ *     c0     (l >> 2) | slot << 10 | k << 19           low word of the block index                        (t >> 1) | slot << 10 | k << 19
+ *     c1     scene_base + scene   (modulo 2^32)        high word of the block index                       scene_base + scene   (modulo 2^32)
+ *     c2     draw                                      the caller's stream_id                             draw
+ *     c3     0                                         1                                                  2
  * Latent l of sample k of (window scene_base + scene, slot slot_base + slot) in draw `draw` is normal l & 3 of that block (L % 8 == 0: whole
  * blocks); element e of a fill stream is word / normal e & 3 of block e >> 2.  The packing holds L <= 4096, slot_base + mno <= 512 and K < 8192.
+ * Step t of rollout k of (window scene_base + scene, slot slot_base + slot) in draw `draw` takes normals 2 (t & 1) (the x draw) and 2 (t & 1) + 1 (the
+ * y draw) of its block, so one block serves two steps; that packing holds T_pred <= 2048 on top of the slot and K limits.
  * So a window's noise does not depend on its position in the batch, the batch size, the rank count, the padding width or DESIRE_FLAG_COMPACT_*.
  *
  * desire_set_rng switches the generator on, or re-seeds it: next draw = `draw`.  The first call allocates four device words (next, used, seed);
@@ -231,9 +233,11 @@ int desire_rng_state(desire_handle* h, uint32_t host_out[2], void* stream);
 #define DESIRE_RNG_NORMAL 1   /* dev_out: n fp32 normals */
 #define DESIRE_RNG_LATENT 2   /* dev_out: fp32 [n_scenes, K, mno, L] = exactly the eps a NULL-eps call of this handle uses in draw `stream_id` with key
                                  `seed` at the handle's current origin; first must be 0 and n = R * L.  For tests, and for keeping a draw. */
+#define DESIRE_RNG_ROLLOUT 3  /* dev_out: fp32 [n_scenes, K, mno, T_pred, 2] = exactly the normals a NULL-normals desire_rollout_samples of this handle uses in
+                                 draw `stream_id` with key `seed` at the handle's current origin; first must be 0 and n = R * T_pred * 2. */
 /* Stand-alone fill: dev_out[i] = element first + i of the stream (seed, stream_id), so a fill equals the matching slice of any longer one.
  * Needs no desire_set_rng and does not touch the draw counter.  Callers of desire_rollout / desire_gaussian_sample, which keep taking
- * dev_normals, fill them with kind DESIRE_RNG_NORMAL.  Stream-ordered, capturable. */
+ * dev_normals, fill them with kind DESIRE_RNG_NORMAL (desire_rollout_samples draws its own: see there).  Stream-ordered, capturable. */
 int desire_rng_fill(desire_handle* h, uint64_t seed, uint32_t stream_id, uint64_t first, int32_t kind, void* dev_out, size_t n, void* stream);
 
 /* Intermediates kept in the handle's workspace, for parity tests:
@@ -303,6 +307,19 @@ int desire_gaussian_sample(desire_handle* h, const float* dev_params, const floa
  * back as the next input (:680-681).  dev_out [num, A, 2], normalised units.  Objects with id 0 are stepped like any other
  * (the reference does the same and carries the id over, :680). */
 int desire_rollout(desire_handle* h, const float* dev_past, const float* dev_normals, int32_t num, float* dev_out, void* stream);
+/* K of those rollouts per agent in ONE launch, written in the sample layout, so that everything that takes desire_sample's dev_Yhat takes this one
+ * too (desire_ioc_refine, desire_rank_samples, desire_ranked_errors, desire_ade_fde).  dev_past [n_scenes, T_obs, mno, 3] as above; dev_Yhat
+ * [R, T_pred, 2] out, normalised units, row r = (scene * K + k) * mno + slot; dev_normals [R, T_pred, 2] ~ N(0,1) in the same row order.  The warm-up
+ * runs once per agent (into a private state buffer: "Hx" of the forward path is untouched), then T_pred steps for each of the agent's K rows: head,
+ * draw, clip to <= 1.0, feed back.  Row (scene, k, slot) is the rollout desire_rollout(num = T_pred) produces for that agent from the normals of that
+ * row -- the same function; the head's dot products are summed in another (fixed) order, so the last bits may differ.  A row's result does not depend
+ * on the rest of the batch.  Objects with id 0 are stepped like any other; DESIRE_FLAG_COMPACT_* are ignored.  dev_normals may be NULL after
+ * desire_set_rng: the normals are then computed in the kernel from the rollout counter of the device generator (one draw per call: used = next;
+ * next += 1 on the device; desire_set_rng_origin applies; dims outside the packing, T_pred > 2048 among them: DESIRE_ERR_ARG), never stored;
+ * desire_rng_fill(kind DESIRE_RNG_ROLLOUT) writes the same values out.  NULL normals before desire_set_rng, a NULL dev_past / dev_Yhat and a
+ * ref_compat handle are DESIRE_ERR_ARG, and nothing is launched.  No host wait, no read-back; the first call allocates the state buffer, later calls
+ * are capturable. */
+int desire_rollout_samples(desire_handle* h, const float* dev_past, const float* dev_normals, float* dev_Yhat, void* stream);
 /* N4: evaluation harness: dev_out [A,4] = (ADE mean-of-K, FDE mean-of-K, ADE best-of-K, FDE best-of-K) over the target frames
  * the object is present in (FDE: the last such frame); zeros for an object absent from every target frame. */
 int desire_ade_fde(desire_handle* h, const float* dev_Yhat, const float* dev_fut, float* dev_out, void* stream);
