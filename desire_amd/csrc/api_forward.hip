@@ -114,6 +114,13 @@ static int count_hint(const desire_ctx* h) {
     return (P < 0 || P > h->A) ? 0 : P;
 }
 
+// the packed operand(s) stage st reads under form f (gen_plan.h: the one place that names them)
+static const float4* gen_op(desire_ctx* h, GenStage st, GenForm f) { return D4(h, gen_operands(st, f).a); }
+static void gen_op2(desire_ctx* h, GenStage st, GenForm f, const float4*& Whg, const float4*& Whc) {
+    const GenOps o = gen_operands(st, f);
+    Whg = D4(h, o.a); Whc = D4(h, o.b);
+}
+
 // the fp32 weights of the GRU encoder `prefix` ("enc_x" / "enc_y")
 void enc_weights(desire_ctx* h, const char* prefix, EncArgs& e) {
     const std::string p(prefix);
@@ -138,6 +145,7 @@ extern "C" int desire_encode(desire_handle* h, const float* dev_past, const floa
     if (d.posterior && !dev_fut) return fail(DESIRE_ERR_ARG, "dims.posterior=1 needs dev_fut");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int H = d.H, A = h->A;
+    const GenPlan plan = gen_plan(h);
     // DESIRE_FLAG_COMPACT_ROWS: the encoder stack is per-agent as well.  `valid` is read off the last observed frame first, the scans run, the host
     // learns P, and the GRU encoders + CVAE encoder run on the P present agents as ONE pseudo-scene of P slots (frames gathered to [1, T, P, 3]);
     // HxHy / p_last / params are scattered back for the stages that keep the caller's layout (IOC, losses).  Ae = agents the stack runs on.
@@ -188,11 +196,11 @@ extern "C" int desire_encode(desire_handle* h, const float* dev_past, const floa
         e.out = HxE + H; e.p_last = nullptr; e.valid = nullptr;
         if (h->training) { e.sv_r = W(h, "ey_sv_r"); e.sv_u = W(h, "ey_sv_u"); e.sv_c = W(h, "ey_sv_c"); e.sv_h = W(h, "ey_sv_h"); e.sv_x = W(h, "ey_sv_x"); }
     }
-    if (d.bf16 == 1) {
+    if (plan.encoder == GenForm::BF16) {
         EncArgs e16 = ex;
-        e16.Whg = D4(h, "enc_x/Whg16"); e16.Whc = D4(h, "enc_x/Whc16");
+        gen_op2(h, GenStage::ENC_X, plan.encoder, e16.Whg, e16.Whc);
         { Timer t(h, s, "encoder_x"); launch_encoder_bf16(e16, s); }
-        if (d.posterior) { e.Whg = D4(h, "enc_y/Whg16"); e.Whc = D4(h, "enc_y/Whc16"); Timer t(h, s, "encoder_y"); launch_encoder_bf16(e, s); }
+        if (d.posterior) { gen_op2(h, GenStage::ENC_Y, plan.encoder, e.Whg, e.Whc); Timer t(h, s, "encoder_y"); launch_encoder_bf16(e, s); }
     } else if (d.posterior) {      // the two encoders are independent and latency-bound: one launch
         Timer t(h, s, "encoder_xy"); launch_encoder_pair(ex, e, s);
     } else { Timer t(h, s, "encoder_x"); launch_encoder(ex, s); }
@@ -215,17 +223,17 @@ extern "C" int desire_encode(desire_handle* h, const float* dev_past, const floa
         c.n = Ae; c.dyn = DynCount{dynP, 1, hintP};
         c.in = W(h, "vae_in"); c.out = W(h, "c1"); c.w_raw = D(h, "vae_enc/conv1/raw");
         c.scale = D(h, "vae_enc/conv1/scale"); c.shift = D(h, "vae_enc/conv1/shift");
-        const bool pobn = d.bn_mode != 0;                 // batch statistics: linear conv epilogue, then a normalise + activate pass per layer
+        const bool pobn = plan.batch_stats;               // batch statistics: linear conv epilogue, then a normalise + activate pass per layer
         auto norm = [&](const char* layer, float* x, int P, int C) { batch_stats_act(h, layer, x, Ae, P, C, 0, s); };
         if (pobn) c.mode = 3;
         { Timer t(h, s, "conv1"); launch_conv1(c, s); if (pobn) norm("vae_enc/conv1", W(h, "c1"), 256, 32); }
-        c.in = W(h, "c1"); c.out = W(h, "c2"); c.Wp = D4(h, "vae_enc/conv2/W");
+        c.in = W(h, "c1"); c.out = W(h, "c2"); c.Wp = gen_op(h, GenStage::CONV2, plan.conv23);
         c.scale = D(h, "vae_enc/conv2/scale"); c.shift = D(h, "vae_enc/conv2/shift");
-        if (d.bf16 == 1) { c.Wp = D4(h, "vae_enc/conv2/W16"); Timer t(h, s, "conv2"); launch_conv2_bf16(c, s); }
+        if (plan.conv23 == GenForm::BF16) { Timer t(h, s, "conv2"); launch_conv2_bf16(c, s); }
         else { Timer t(h, s, "conv2"); launch_conv2(c, s); if (pobn) norm("vae_enc/conv2", W(h, "c2"), 64, 64); }
-        c.in = W(h, "c2"); c.out = W(h, "c3"); c.Wp = D4(h, "vae_enc/conv3/W");
+        c.in = W(h, "c2"); c.out = W(h, "c3"); c.Wp = gen_op(h, GenStage::CONV3, plan.conv23);
         c.scale = D(h, "vae_enc/conv3/scale"); c.shift = D(h, "vae_enc/conv3/shift");
-        if (d.bf16 == 1) { c.Wp = D4(h, "vae_enc/conv3/W16"); Timer t(h, s, "conv3"); launch_conv3_bf16(c, s); }
+        if (plan.conv23 == GenForm::BF16) { Timer t(h, s, "conv3"); launch_conv3_bf16(c, s); }
         else { Timer t(h, s, "conv3"); launch_conv3(c, s); if (pobn) norm("vae_enc/conv3", W(h, "c3"), 16, 128); }
         g = GemmArgs{};
         g.A = W(h, "c3"); g.lda = 2048; g.M = Ae; g.K = 2048; g.Bp = D4(h, "vae_enc/fc/W"); g.G = 2048 / 8;
@@ -244,6 +252,7 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
     const desire_dims& d = h->d;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int H = d.H;
+    const GenPlan plan = gen_plan(h);
     if (!dev_eps) launch_rng_begin(h->rng_state, s);           // a sampling call that generates its eps is one draw, whatever it then runs
     // per-row stages: all R = A*K rows, or (DESIRE_FLAG_COMPACT_ROWS) the K*P rows of the P present agents laid out as one pseudo-scene of P
     // slots (kernels_compact.hip) -- the kernels below are the same either way, they only see (R, K, mno) and the agent-level inputs
@@ -283,77 +292,74 @@ extern "C" int desire_sample(desire_handle* h, const float* dev_eps, float* dev_
     else { Timer t(h, s, "reparam"); launch_reparam(W(h, "params"), dev_eps, W(h, "z"), R, d.L, d.K, d.mno, d.posterior, s); }
     auto normd = [&](const char* layer, float* x, int P, int C, int sig) { batch_stats_act(h, layer, x, R, P, C, sig, s); };
     GemmArgs g{};
-    g.A = W(h, "z"); g.lda = d.L; g.M = R; g.K = d.L; g.Bp = D4(h, "vae_dec/deconv1/W"); g.G = d.L / 8;
+    g.A = W(h, "z"); g.lda = d.L; g.M = R; g.K = d.L; g.Bp = gen_op(h, GenStage::DECONV1, plan.deconv1); g.G = d.L / 8;
     g.NT = 64; g.out = W(h, "d1"); g.ldo = 2048; g.N = 2048;
     g.p0 = D(h, "vae_dec/deconv1/scale"); g.p1 = D(h, "vae_dec/deconv1/shift"); g.chmod = 128;
     int hintS = 0;                                                       // count hint for this call's launches (see desire_encode)
     if (dyn) hintS = count_hint(h);
     g.dyn = DynCount{dynP, d.K, hintS}; g.M_hint = hintS * d.K;
-    // six-product sample generation (the fp32 kernels' accuracy class on the bf16 matrix pipe): dims.bf16 = 3, and dims.bf16 = 2 as well --
-    // two-piece operands are an IOC-kernel matter (sample generation must not move Y0 by more than fp32 rounding)
-    const bool x6gen = ((d.bf16 == 3 && !h->training) || (d.bf16 == 2 && (!h->training || (train_x3_mask(h) & 8)))) && d.bn_mode == 0 && !d.ref_compat;
-    if (d.bf16 == 1 && d.L <= 512 && !(d.L & 15)) { g.Bp = D4(h, "vae_dec/deconv1/W16"); Timer t(h, s, "deconv1"); launch_deconv1_bf16(g, s); }
-    else if (x6gen && rows_x6_supported(d.L, 64)) { g.Bp = D4(h, "vae_dec/deconv1/W6"); Timer t(h, s, "deconv1"); launch_deconv1_x6(g, s); }
-    else if (d.bn_mode != 0) {
-        Timer t(h, s, "deconv1"); launch_gemm_rows(g, EPI_NONE, s);
-        normd("vae_dec/deconv1", W(h, "d1"), 16, 128, 0);
-    }
-    else { Timer t(h, s, "deconv1"); launch_gemm_rows(g, EPI_SCALE_SHIFT_ELU, s); }
+    const bool pobn = plan.batch_stats;
+    { Timer t(h, s, "deconv1");
+      switch (plan.deconv1) {
+          case GenForm::BF16: launch_deconv1_bf16(g, s); break;
+          case GenForm::X6: launch_deconv1_x6(g, s); break;
+          case GenForm::FP32: launch_gemm_rows(g, pobn ? EPI_NONE : EPI_SCALE_SHIFT_ELU, s); if (pobn) normd("vae_dec/deconv1", W(h, "d1"), 16, 128, 0);
+      } }
     ConvArgs c{};
     c.n = R; c.dyn = DynCount{dynP, d.K, hintS};
-    const bool pobn = d.bn_mode != 0;
     if (pobn) c.mode = 3;
-    c.in = W(h, "d1"); c.out = W(h, "d2"); c.Wp = D4(h, "vae_dec/deconv2/W");
+    c.in = W(h, "d1"); c.out = W(h, "d2"); c.Wp = gen_op(h, GenStage::DECONV2, plan.deconv2);
     c.scale = D(h, "vae_dec/deconv2/scale"); c.shift = D(h, "vae_dec/deconv2/shift");
-    // dims.bf16 = 3: six-product forms of the two large transposed convolutions and of the decoder (frozen batch-norm, inference)
-    if (d.bf16 == 1) { c.Wp = D4(h, "vae_dec/deconv2/W16"); Timer t(h, s, "deconv2"); launch_deconv2_bf16(c, s); }
-    else if (x6gen) { c.Wp = D4(h, "vae_dec/deconv2/W6"); Timer t(h, s, "deconv2"); launch_deconv2_x6(c, s, (h->training && (d.flags & DESIRE_FLAG_TRAIN_FWD_3P)) ? 2 : 3); }
-    else { Timer t(h, s, "deconv2"); launch_deconv2(c, s);
-           if (pobn) normd("vae_dec/deconv2", W(h, "d2"), 64, 64, 0); }
-    c.in = W(h, "d2"); c.out = W(h, "d3"); c.Wp = D4(h, "vae_dec/deconv3/W");
+    { Timer t(h, s, "deconv2");
+      switch (plan.deconv2) {
+          case GenForm::BF16: launch_deconv2_bf16(c, s); break;
+          case GenForm::X6: launch_deconv2_x6(c, s, plan.np); break;
+          case GenForm::FP32: launch_deconv2(c, s); if (pobn) normd("vae_dec/deconv2", W(h, "d2"), 64, 64, 0);
+      } }
+    c.in = W(h, "d2"); c.out = W(h, "d3"); c.Wp = gen_op(h, GenStage::DECONV3, plan.deconv3);
     c.scale = D(h, "vae_dec/deconv3/scale"); c.shift = D(h, "vae_dec/deconv3/shift");
-    const bool fuse34 = d.bf16 == 1 && !(d.flags & DESIRE_FLAG_NO_FUSE34);       // bf16: deconv3+deconv4 in one kernel, d3 never written
-    // (the six-product form of that fusion was measured and dropped: 15.4 ms against 11.9 + 2.5 for the two kernels -- the tap products cost
-    //  the contracting waves more than the d3 pass did)
-    if (fuse34) {
-        c.Wp = D4(h, "vae_dec/deconv3/W16"); c.w_raw = D(h, "vae_dec/deconv4/W16"); c.out = W(h, "xhat");
+    const float* w4 = D(h, gen_operands(GenStage::DECONV4, plan.deconv4()).a);       // fused: the tap-product pack; else deconv4's raw taps
+    if (plan.fuse34) {
+        c.w_raw = w4; c.out = W(h, "xhat");
         Timer t(h, s, "deconv34");
         launch_deconv34_bf16(c, D(h, "vae_dec/deconv4/scale"), D(h, "vae_dec/deconv4/shift"), s);
     } else {
-        if (d.bf16 == 1) { c.Wp = D4(h, "vae_dec/deconv3/W16"); Timer t(h, s, "deconv3"); launch_deconv3_bf16(c, s); }
-        else if (x6gen) { c.Wp = D4(h, "vae_dec/deconv3/W6"); Timer t(h, s, "deconv3"); launch_deconv3_x6(c, s, (h->training && (d.flags & DESIRE_FLAG_TRAIN_FWD_3P)) ? 2 : 3); }
-        else { Timer t(h, s, "deconv3"); launch_deconv3(c, s);
-               if (pobn) normd("vae_dec/deconv3", W(h, "d3"), 256, 32, 0); }
-        c.in = W(h, "d3"); c.out = W(h, "xhat"); c.w_raw = D(h, "vae_dec/deconv4/raw");
+        { Timer t(h, s, "deconv3");
+          switch (plan.deconv3) {
+              case GenForm::BF16: launch_deconv3_bf16(c, s); break;
+              case GenForm::X6: launch_deconv3_x6(c, s, plan.np); break;
+              case GenForm::FP32: launch_deconv3(c, s); if (pobn) normd("vae_dec/deconv3", W(h, "d3"), 256, 32, 0);
+          } }
+        c.in = W(h, "d3"); c.out = W(h, "xhat"); c.w_raw = w4;
         c.scale = D(h, "vae_dec/deconv4/scale"); c.shift = D(h, "vae_dec/deconv4/shift");
         { Timer t(h, s, "deconv4"); launch_deconv4(c, s);
           if (pobn) normd("vae_dec/deconv4", W(h, "xhat"), 1024, 1, 1); }
     }
     MaskArgs m{};
     m.xhat = W(h, "xhat"); m.R = R; m.V = h->V; m.H = H; m.Hl = h->Hl; m.K = d.K; m.mno = mno;
-    m.Wp = D4(h, "mask/W"); m.bias = D(h, "mask/b"); m.Hx = HxS; m.ldhx = 2 * H; m.xz = W(h, "xz");
+    m.Wp = gen_op(h, GenStage::MASK, plan.mask); m.bias = D(h, "mask/b"); m.Hx = HxS; m.ldhx = 2 * H; m.xz = W(h, "xz");
     m.dyn = DynCount{dynP, 1, hintS};
     if (h->training) m.sv_p = W(h, "mask_sv_p");
-    if (d.bf16 == 1) { m.Wp = D4(h, "mask/W16"); Timer t(h, s, "mask_fc"); launch_mask_bf16(m, s); }
-    else if (x6gen && (H == 64 || H == 128) && h->V % 128 == 0) { m.Wp = D4(h, "mask/W6"); Timer t(h, s, "mask_fc"); launch_mask_x6(m, s); }
-    else { Timer t(h, s, "mask_fc"); launch_mask(m, s); }
+    { Timer t(h, s, "mask_fc");
+      switch (plan.mask) {
+          case GenForm::BF16: launch_mask_bf16(m, s); break;
+          case GenForm::X6: launch_mask_x6(m, s); break;
+          case GenForm::FP32: launch_mask(m, s);
+      } }
     DecArgs a{};
     a.xz = W(h, "xz"); a.Hx = HxS; a.ldhx = 2 * H; a.p_last = plS;
     a.R = R; a.K = d.K; a.mno = mno; a.H = H; a.T = d.T_pred;
-    a.Wxg = D4(h, "dec/Wxg"); a.Wxc = D4(h, "dec/Wxc"); a.Whg = D4(h, "dec/Whg"); a.Whc = D4(h, "dec/Whc");
+    a.Wxg = D4(h, "dec/Wxg"); a.Wxc = D4(h, "dec/Wxc"); gen_op2(h, GenStage::DECODER, plan.decoder, a.Whg, a.Whc);
     a.b_g = D(h, "dec/gb"); a.b_c = D(h, "dec/cb"); a.w_head = D(h, "head/w"); a.b_head = D(h, "head/b");
     a.Y = Yout; a.hdump = nullptr; a.dyn = DynCount{dynP, 1, hintS};
     if (d.ref_compat) { a.T = d.n_dec; a.hdump = W(h, "dec_states"); }       // model/model.py:280-285: 7 steps, the states are the output
     if (h->training) { a.hdump = W(h, "dec_sv_h"); a.sv_r = W(h, "dec_sv_r"); a.sv_u = W(h, "dec_sv_u"); a.sv_c = W(h, "dec_sv_c"); }
-    if (d.bf16 == 1) {
-        a.Whg = D4(h, "dec/Whg16"); a.Whc = D4(h, "dec/Whc16");
-        Timer t(h, s, "decoder"); launch_decoder_bf16(a, s);
-    } else
-    if (x6gen && decoder_x6_supported(H)) {
-        a.Whg = D4(h, "dec/Whg6"); a.Whc = D4(h, "dec/Whc6");
-        Timer t(h, s, "decoder"); launch_decoder_x6(a, s, (h->training && (d.flags & DESIRE_FLAG_TRAIN_FWD_3P)) ? 2 : 3);
-    } else
-    { Timer t(h, s, "decoder"); launch_decoder(a, s); }
+    { Timer t(h, s, "decoder");
+      switch (plan.decoder) {
+          case GenForm::BF16: launch_decoder_bf16(a, s); break;
+          case GenForm::X6: launch_decoder_x6(a, s, plan.np); break;
+          case GenForm::FP32: launch_decoder(a, s);
+      } }
     if (d.ref_compat)      // model/model.py:286-289: each state [H] re-read as T_obs points (x, y) -> [A, n_dec, T_obs, 2]
         launch_copy_cols(dev_Yhat, W(h, "dec_states"), (size_t)R * d.n_dec, h->Hl, H, s);
     else if (compact) {     // back to the caller's row layout; rows of absent agents are zeros (the cost masks them, model/model.py:351-366)

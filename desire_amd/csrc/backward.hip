@@ -17,7 +17,7 @@ void tn(desire_ctx* h, const float* A, int lda, const float* Gm, int ldg, long M
     // row lists serve the 128 x 128 tile form only (one tile row = one flag block of 128 columns); anything else keeps the flag words
     if (rowlist && !(fcols == 128 && N > 64 && gemm_tn_big_tiles(a) > 0)) a.rowlist = nullptr;
     if (a.rowlist) a.flags = nullptr;
-    a.np = wgrad_pieces(h);
+    a.np = gen_plan(h).wgrad_pieces;
     // slices.  Split operands: the large forms keep two workgroups per CU and a workgroup's time per chunk does not depend on its MFMA count
     // (it waits for its operands), so ONE full round of 512 workgroups is best -- 680 took 2.56 ms where 512 take 1.87.  fp32 operands: the
     // kernel is bound by the matrix pipe, tiles that hang over Kd / N finish early, and more workgroups than slots balance that (4.16 vs 5.22 ms)
@@ -428,12 +428,12 @@ int cvae_dec_bwd(const BwdPass& bp) {
     launch_conv1(c, s);
     if (bn1) norm_bwd(bp, W(h, "dconv3"), W(h, "deconv3_pre"), W(h, "d3"), (int)Rs, 256, 32, D(h, "vae_dec/deconv3/gamma"), 0);
     ConvWgradArgs wg{};
-    wg.np = wgrad_pieces(h);
+    wg.np = gen_plan(h).wgrad_pieces;
     wg.S = W(h, "d2"); wg.Cs = 64; wg.Ps = 8; wg.Lg = W(h, "dconv3"); wg.Cl = 32; wg.Pl = 16; wg.stride = 2; wg.pad = 1;
     wg.n = (int)Rs; wg.partial = W(h, "tn_partial");
     launch_conv_wgrad(wg, NSL, G(h, "vae_dec/deconv3/w"), s);
     if (!bn1) colsum(h, W(h, "dconv3"), 32, Rs * 256, 32, G(h, "vae_dec/deconv3/b"), 0, s);
-    const bool x3 = dgrad_split(h);
+    const bool x3 = gen_plan(h).dgrad_split;
     c.in = W(h, "dconv3"); c.out = W(h, "dconv2"); c.Wp = D4(h, x3 ? "vae_dec/deconv3/Wbwd16" : "vae_dec/deconv3/Wbwd");
     c.scale = D(h, "vae_dec/deconv2/scale"); c.shift = c.scale; c.yprev = W(h, "d2");
     if (x3) launch_conv2_x3(c, s); else launch_conv2(c, s);
@@ -478,7 +478,7 @@ int cvae_enc_bwd(const BwdPass& bp) {
         launch_gemm_rows(g, EPI_ELUGRAD, s);
     const int NSL = Ae >= 2048 ? 64 : (Ae >= 256 ? 16 : 4);
     ConvWgradArgs wg{};
-    wg.np = wgrad_pieces(h);
+    wg.np = gen_plan(h).wgrad_pieces;
     wg.n = Ae; wg.partial = W(h, "tn_partial");
     wg.S = W(h, "dconvE3"); wg.Cs = 128; wg.Ps = 4; wg.Lg = W(h, "c2"); wg.Cl = 64; wg.Pl = 8; wg.stride = 1; wg.pad = 0;
     launch_conv_wgrad(wg, NSL, G(h, "vae_enc/conv3/w"), s);

@@ -2,6 +2,7 @@
 // train.hip and backward.hip (training ABI).  Host code only.
 #pragma once
 #include "../../include/desire_hip.h"
+#include "gen_plan.h"
 #include "ioc_plan.h"
 #include "kernels.h"
 #include "pack.h"
@@ -103,11 +104,8 @@ struct Timer {
     ~Timer() { if (on) (void)hipEventRecord(h->prof[idx].e1, s); }
 };
 
-// which parts of the training step use split operands under dims.bf16 = 2 (1: weight-gradient reductions, 2: data-gradient
-// convolutions, 4: IOC BPTT, 8: six-product sample generation in the forward pass): everything dims.train_fp32_mask does not hold back
-inline int train_x3_mask(const desire_ctx* h) { return 15 & ~h->d.train_fp32_mask; }
-inline int wgrad_pieces(const desire_ctx* h) { return (h->d.bf16 == 2 && (train_x3_mask(h) & 1)) ? 2 : 0; }     // bf16 pieces per operand of the weight-gradient reductions (0: fp32)
-inline bool dgrad_split(const desire_ctx* h) { return h->d.bf16 == 2 && (train_x3_mask(h) & 2); }               // split-bf16 operands in the two large data-gradient convolutions
+// the kernel forms of sample generation and of the matching parts of the training step, for the handle as it stands (gen_plan.h)
+inline GenPlan gen_plan(const desire_ctx* h) { return gen_plan(h->d, h->training, h->V); }
 
 // Lookups by name: nullptr for a name that was never allocated (workspace.h: they neither insert nor throw)
 inline const float* D(desire_ctx* h, const char* name) { return h->dev.get(name); }

@@ -67,8 +67,7 @@ struct MaskArgs {
     DynCount dyn;                                  // one pseudo-scene of P = cnt[0] present agents: mno = P, R = P * K (DynCount)
 };
 void launch_mask(const MaskArgs& a, hipStream_t s);
-// six-product forms of deconv1 and the mask fc (kernels_x6.hip; weight pointers = three-piece packs)
-bool rows_x6_supported(int K, int NT);
+// six-product forms of deconv1 and the mask fc (kernels_x6.hip; weight pointers = three-piece packs; shapes: gen_plan.h)
 void launch_deconv1_x6(const GemmArgs& a, hipStream_t s);
 void launch_mask_x6(const MaskArgs& a, hipStream_t s);
 
@@ -177,8 +176,7 @@ void launch_ioc_x3(const IocArgs& a, hipStream_t s);
 void launch_ioc_x6(const IocArgs& a, hipStream_t s);
 void launch_ioc_x6r2(const IocArgs& a, hipStream_t s);             // ... on 64-row tiles, two row blocks per wave (kernels_x6r2.hip)
 void launch_ioc_x3r2(const IocArgs& a, hipStream_t s);             // ... with two-piece operands (dims.bf16 = 2)
-// sample generation with three-piece operands (kernels_x6.hip, dims.bf16 = 3)
-bool decoder_x6_supported(int H);
+// sample generation with three-piece operands (kernels_x6.hip, dims.bf16 = 3; shapes: gen_plan.h)
 void launch_decoder_x6(const DecArgs& a, hipStream_t s, int np = 3);      // np = 2 (training-mode form only): two-piece operands
 void launch_deconv2_x6(const ConvArgs& a, hipStream_t s, int np = 3);      // np = 2: the first two pieces of the packs, three products (training-mode forward)
 void launch_deconv3_x6(const ConvArgs& a, hipStream_t s, int np = 3);

@@ -168,7 +168,6 @@ static void launch_dec6(const DecArgs& a, hipStream_t s, int np) {
     }
     launch_big_lds<k_decoder_x6<H, false>>(dim3((a.R + 31) / 32), dim3((H / 32) * 64), lds, s, a);
 }
-bool decoder_x6_supported(int H) { return H == 64 || H == 128 || H == 256; }
 void launch_decoder_x6(const DecArgs& a, hipStream_t s, int np) {
     if (a.H == 256) launch_dec6<256>(a, s, np); else if (a.H == 128) launch_dec6<128>(a, s, np); else launch_dec6<64>(a, s, np);
 }
@@ -529,7 +528,6 @@ __global__ __launch_bounds__(DS_WG, 2) void k_mask_x6(MaskArgs a) {
     }
 }
 }  // namespace
-bool rows_x6_supported(int K, int NT) { return (K % 16) == 0 && K <= 128 && NT % 16 == 0; }
 // a.Bp = the three-piece pack; a.K a multiple of 16; a.NT a multiple of 16 (deconv1: 64 n-tiles)
 void launch_deconv1_x6(const GemmArgs& a, hipStream_t s) {
     const size_t lds = (size_t)3 * ILO6 * sizeof(u16);

@@ -463,3 +463,51 @@ def test_hidden_256_and_large_scenes_have_a_split_ioc_form(torch_cuda, kw, mode)
     else:
         assert es < max(2.0 * ef, 2e-6), (es, ef)
     assert np.abs(ss - ref["score"]).max() < 5e-3
+
+
+# ---- the sample-generation plan (gen_plan.h): handles whose plans name the same kernels on the same packs give the same bits --------
+def _plan_case():
+    """The smallest shape at which all five six-product sample stages are served (H = 64: mask fc and decoder, L = 64: deconv1), with absent slots."""
+    from tests.stage_reference import spread_weights
+    d = small_dims(H=64, L=64, mno=4, n_scenes=2, K=2, T_pred=5)
+    return d, spread_weights(init_weights(d, 51)), make_case(d, seed=52)
+
+
+def _sampled_Y0(torch, d, w, case, training):
+    from desire_amd import _lib
+    past, fut, eps, grids, gos = case
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+    p, f, e, g = t(past), t(fut), t(eps), t(grids)
+    h = _lib.Handle(d); h.set_weights(w)
+    h.set_scene_grids(g.data_ptr(), gos)
+    if training:
+        h.set_training(True)
+    Y = torch.zeros((d.R, d.T_pred, 2), device="cuda"); sc = torch.zeros((d.R,), device="cuda")
+    h.forward(p.data_ptr(), f.data_ptr(), e.data_ptr(), Y.data_ptr(), sc.data_ptr())
+    torch.cuda.synchronize()
+    Y0 = h.read_buffer("Y0", (d.R, d.T_pred, 2))
+    h.close()
+    assert np.isfinite(Y0).all() and np.abs(Y0).max() > 0
+    return Y0
+
+
+def test_training_forward_held_back_to_fp32_samples_the_fp32_bits(torch_cuda):
+    """dims.bf16 = 2 with train_fp32_mask = 8: the plan gives every sample stage of the training forward the fp32 save-keeping kernels on the
+    fp32 packs, as under dims.bf16 = 0 -- Y0 bit for bit.  (An fp32 <-> six-product swap of a stage is invisible to every oracle tolerance.)"""
+    d, w, case = _plan_case()
+    Y0a = _sampled_Y0(torch_cuda, d.replace(bf16=0), w, case, training=True)
+    Y0b = _sampled_Y0(torch_cuda, d.replace(bf16=2, train_fp32_mask=8), w, case, training=True)
+    assert np.array_equal(Y0a, Y0b), float(np.abs(Y0a - Y0b).max())
+    Y0x = _sampled_Y0(torch_cuda, d.replace(bf16=2), w, case, training=True)      # (mask 0: the six-product kernels, other bits)
+    assert not np.array_equal(Y0a, Y0x)
+
+
+def test_inference_samples_the_same_bits_under_two_and_three_piece_modes(torch_cuda):
+    """dims.bf16 = 2 and 3, inference: the plan gives both the six-product kernels with np = 3 on the same three-piece packs -- Y0 bit for bit
+    (the piece count of the mode is an IOC-kernel matter)."""
+    d, w, case = _plan_case()
+    Y0a = _sampled_Y0(torch_cuda, d.replace(bf16=2), w, case, training=False)
+    Y0b = _sampled_Y0(torch_cuda, d.replace(bf16=3), w, case, training=False)
+    assert np.array_equal(Y0a, Y0b), float(np.abs(Y0a - Y0b).max())
+    Y0f = _sampled_Y0(torch_cuda, d.replace(bf16=0), w, case, training=False)      # (not the fp32 kernels again)
+    assert not np.array_equal(Y0a, Y0f)
