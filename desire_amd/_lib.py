@@ -25,10 +25,11 @@ EXPORTS = [
     "desire_graph_begin", "desire_graph_end", "desire_graph_launch", "desire_rollout", "desire_build_windows_la", "desire_adam_state",
     "desire_set_option", "desire_train_loss_async", "desire_set_head_loss",
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
-    "desire_rank_samples", "desire_ranked_errors",
+    "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
 ]
 RNG_BITS, RNG_NORMAL, RNG_LATENT, RNG_ROLLOUT = 0, 1, 2, 3          # desire_rng_fill kinds (DESIRE_RNG_*)
+KDE_LOG_FLOOR = -20.0                                               # desire_kde_nll: the clip of a frame's log-density (Trajectron++'s)
 
 
 class DesireDims(C.Structure):
@@ -96,6 +97,7 @@ def load() -> C.CDLL:
     lib.desire_ade_fde.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_rank_samples.argtypes = [vp, f32p, f32p, i32, vp, f32p, f32p, vp]
     lib.desire_ranked_errors.argtypes = [vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, f32p, vp]
+    lib.desire_kde_nll.argtypes = [vp, f32p, f32p, f32p, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, f32p, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
     lib.desire_rollout_samples.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
@@ -282,6 +284,15 @@ class Handle:
         hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
         _chk(self.lib.desire_ranked_errors(self._h, yhat_ptr, fut_ptr, order_ptr, int(n_top), hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size,
                                            C.c_float(unit_x), C.c_float(unit_y), out_ptr, stream or None))
+
+    def kde_nll(self, yhat_ptr: int, fut_ptr: int, score_ptr: int, horizons, unit_x: float, unit_y: float, log_floor: float, out_ptr: int,
+                frame_ptr: int = 0, stream: int = 0) -> None:
+        """out [A, len(horizons), 2] = (mean, final) negative log-density of the ground truth under a Gaussian KDE of the agent's K samples, per
+        frame, clipped below at log_floor, over the counted frames before each horizon; score_ptr = 0: equal weights, else softmax(score).  The
+        density is per unit^2 of (unit_x, unit_y), as in ranked_errors.  frame [A, T_pred] (optional): the per-frame log-densities."""
+        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+        _chk(self.lib.desire_kde_nll(self._h, yhat_ptr or None, fut_ptr or None, score_ptr or None, hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size,
+                                     C.c_float(unit_x), C.c_float(unit_y), C.c_float(log_floor), out_ptr or None, frame_ptr or None, stream or None))
 
     def set_training(self, on: bool) -> None:
         _chk(self.lib.desire_set_training(self._h, int(on)))

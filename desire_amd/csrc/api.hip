@@ -209,6 +209,8 @@ extern "C" int desire_create(const desire_dims* dims, desire_handle** out) {
         // desire_ranked_errors: (ADE_h, FDE_h) of every sample for the 8 horizons a call accepts, counted frames of every agent -- here, so that
         // no call allocates and a captured call never has to
         {"rank_tab", d.ref_compat ? 0 : R * 16 * f}, {"rank_cnt", d.ref_compat ? 0 : A * 8 * sizeof(int32_t)},
+        // desire_kde_nll: the K weights of every agent (the score layout) and its (den, h2), for the same reason
+        {"kde_w", d.ref_compat ? 0 : R * f}, {"kde_st", d.ref_compat ? 0 : A * 2 * f},
     };
     if (int rc = ws_ensure(h, list)) { desire_destroy(h); return rc; }
     for (const WsItem& w : list) (void)hipMemset(W(h, w.n), 0, w.bytes);

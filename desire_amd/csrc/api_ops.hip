@@ -230,6 +230,35 @@ extern "C" int desire_ranked_errors(desire_handle* h, const float* dev_Yhat, con
     return DESIRE_OK;
 }
 
+// ---- KDE log-likelihood of the ground truth under the K samples (kernels_kde.hip): the contract is stated in include/desire_hip.h ----
+extern "C" int desire_kde_nll(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const float* dev_score, const int32_t* host_horizons,
+                              int32_t n_h, float unit_x, float unit_y, float log_floor, float* dev_out, float* dev_frame, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_fut) return fail(DESIRE_ERR_ARG, "dev_fut is NULL");
+    if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (!dev_out) return fail(DESIRE_ERR_ARG, "dev_out is NULL");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to fit a density to");
+    if (n_h < 1 || n_h > 8) return fail(DESIRE_ERR_ARG, "n_h must be 1..8");
+    RankHz hz{};
+    hz.n = n_h;
+    for (int i = 0; i < n_h; ++i) {
+        hz.h[i] = host_horizons[i];
+        if (hz.h[i] < 1 || hz.h[i] > d.T_pred) return fail(DESIRE_ERR_ARG, "host_horizons[" + std::to_string(i) + "] must be 1..T_pred");
+        if (i && hz.h[i] <= hz.h[i - 1]) return fail(DESIRE_ERR_ARG, "host_horizons must be strictly increasing");
+    }
+    if (!std::isfinite(unit_x) || !(unit_x > 0.f)) return fail(DESIRE_ERR_ARG, "unit_x must be finite and > 0");
+    if (!std::isfinite(unit_y) || !(unit_y > 0.f)) return fail(DESIRE_ERR_ARG, "unit_y must be finite and > 0");
+    if (!std::isfinite(log_floor)) return fail(DESIRE_ERR_ARG, "log_floor must be finite");
+    int sa = 0;
+    if (!kde_geometry(d.T_pred, &sa)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the KDE kernel's LDS");
+    launch_kde_nll(dev_Yhat, dev_fut, dev_score, W(h, "kde_w"), W(h, "kde_st"), dev_out, dev_frame, d.n_scenes, d.mno, d.K, d.T_pred, hz,
+                   d.sx, d.sy, unit_x, unit_y, log_floor, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- the device generator (philox.h, kernels_rng.hip): the packing of its counters is stated in include/desire_hip.h ------------------------
 namespace {
 int rng_check_packing(const desire_ctx* h, uint32_t slot_base) {

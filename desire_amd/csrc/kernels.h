@@ -257,6 +257,12 @@ bool sample_errors_geometry(int mno, int K, int T, int* SC, int* KC);      // fa
 void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order, float* tab, int32_t* cnt, float* out, int n_scenes, int mno,
                           int K, int T, int n_top, const RankHz& hz, float sx, float sy, float ux, float uy, hipStream_t s);
 
+// ---- KDE log-likelihood (kernels_kde.hip) ----
+bool kde_geometry(int T, int* SA);                         // agents per workgroup; false: one agent's T_pred frame values do not fit the LDS
+// w [R] (the score layout) and st [A, 2] = (den, h2) are scratch of the call (the handle's "kde_w" / "kde_st"); score and frame may be nullptr
+void launch_kde_nll(const float* Y, const float* fut, const float* score, float* w, float* st, float* out, float* frame, int n_scenes, int mno,
+                    int K, int T, const RankHz& hz, float sx, float sy, float ux, float uy, float log_floor, hipStream_t s);
+
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);
 void launch_loss_grad_y(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, const float* nvalid, float* dY,

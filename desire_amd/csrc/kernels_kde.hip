@@ -1,0 +1,205 @@
+// kernels_kde.hip -- KDE log-likelihood of the ground truth under an agent's K samples (desire_kde_nll; the contract, operation by operation,
+// is in include/desire_hip.h).
+//
+//   k_kde_weights  one lane per agent: the K weights (softmax of the scores, or 1 / K), written once in the score layout, and (den, h2)
+//   k_kde_nll      one workgroup = SA whole agents.  A lane owns one (agent, t) pair: for one (window, k) Y is contiguous over (slot, t), so a wave
+//                  reads 512 contiguous bytes per sample, at a stride of mno * T_pred * 2 floats between samples.  Up to 24 samples the lane keeps
+//                  its K differences and weights in registers (Y comes from HBM once, three passes over registers); beyond, every pass re-reads
+//                  them -- a workgroup's share of Y is a few hundred KiB and stays in L2.  The frame values go to LDS; after the barrier one lane
+//                  per agent walks its frames in increasing t (the fixed summation order) and writes the two columns of every horizon.
+//
+// No atomics, no host synchronisation, horizons by value: a result is a fixed sequence of fp32 operations per (agent, t), so it does not depend on
+// the grid or on the rest of the batch, and the call can be captured in a graph.
+#include "common.h"
+#include "kernels.h"
+#include "../../include/desire_hip.h"
+
+#include <cfloat>
+
+#pragma clang fp contract(off)                 // the contract rounds every operation once
+
+namespace {
+
+constexpr int KD_THREADS = 256;
+constexpr int KD_LDS_BYTES = 60 * 1024;        // dynamic LDS (below the 64 KiB a launch gets without asking for more)
+constexpr float KD_LOG_2PI = 1.8378770664093453f;
+
+__global__ __launch_bounds__(KD_THREADS) void k_kde_weights(const float* __restrict__ score, float* __restrict__ w, float* __restrict__ st, int A,
+                                                            int mno, int K) {
+    const int a = blockIdx.x * KD_THREADS + threadIdx.x;
+    if (a >= A) return;
+    const int scene = a / mno, slot = a - scene * mno;
+    const size_t row0 = (size_t)scene * K * mno + slot;            // row of sample k: row0 + k * mno
+    bool uniform = score == nullptr;
+    float mx = -FLT_MAX, sum = 0.f;
+    if (!uniform) {
+        for (int k = 0; k < K; ++k) {
+            const float s = score[row0 + (size_t)k * mno];
+            if (!(fabsf(s) <= FLT_MAX)) uniform = true;            // NaN, +-inf
+            mx = fmaxf(mx, s);
+        }
+    }
+    if (!uniform)
+        for (int k = 0; k < K; ++k) sum += expf(score[row0 + (size_t)k * mno] - mx);
+    const float u = 1.f / (float)K;
+    float den = 0.f, s2 = 0.f;
+    bool one = false;
+    for (int k = 0; k < K; ++k) {
+        const float wk = uniform ? u : expf(score[row0 + (size_t)k * mno] - mx) / sum;
+        w[row0 + (size_t)k * mno] = wk;
+        den += wk * (1.f - wk);
+        s2 += wk * wk;
+        one = one || wk == 1.f;
+    }
+    const float n_eff = 1.f / s2;
+    st[2 * (size_t)a] = one ? 0.f : den;                            // (a weight of exactly 1: degenerate, as den <= 0 is)
+    st[2 * (size_t)a + 1] = powf(n_eff, -1.f / 3.f);
+}
+
+// KC > 0: K <= KC, the lane's differences and weights live in registers.  KC == 0: any K, re-read in every pass.
+template <int KC>
+__global__ __launch_bounds__(KD_THREADS) void k_kde_nll(const float* __restrict__ Y, const float* __restrict__ fut, const float* __restrict__ w,
+                                                        const float* __restrict__ st, float* __restrict__ out, float* __restrict__ frame, int A,
+                                                        int mno, int K, int T, int SA, int vec, float sx, float sy, float ux, float uy,
+                                                        float log_floor, RankHz hz) {
+    extern __shared__ float kd_sm[];
+    __shared__ int hzs[8];
+    const int Tp = T | 1;                                           // odd row stride: the walk below is bank-conflict free
+    float* val = kd_sm;
+    float* cm = kd_sm + (size_t)SA * Tp;
+    const int tid = threadIdx.x;
+    const int a0 = blockIdx.x * SA, na = min(SA, A - a0);
+    if (tid < 8) hzs[tid] = tid < hz.n ? hz.h[tid] : 0;
+
+    for (int i = tid; i < na * T; i += KD_THREADS) {
+        const int s = i / T, t = i - s * T, a = a0 + s;
+        const int scene = a / mno, slot = a - scene * mno;
+        const float* f = fut + (((size_t)scene * T + t) * mno + slot) * 3;
+        const bool counted = f[0] != 0.f;
+        float v = 0.f;
+        if (counted) {
+            const float gx = f[1] * sx, gy = f[2] * sy;
+            const size_t row0 = (size_t)scene * K * mno + slot;
+            const float* yp = Y + (row0 * T + t) * 2;               // sample k: + k * ystride
+            const size_t ystride = (size_t)mno * T * 2;
+            const float* wp = w + row0;                             // sample k: + k * mno
+            const float den = st[2 * (size_t)a], h2 = st[2 * (size_t)a + 1];
+            auto diff = [&](int k, float& dx, float& dy) {
+                const float* p = yp + (size_t)k * ystride;
+                float y0, y1;
+                if (vec) { const float2 y = *reinterpret_cast<const float2*>(p); y0 = y.x; y1 = y.y; }
+                else { y0 = p[0]; y1 = p[1]; }
+                dx = (y0 - gx) * ux; dy = (y1 - gy) * uy;
+            };
+            v = log_floor;
+            float mx = 0.f, my = 0.f, cxx = 0.f, cyy = 0.f, cxy = 0.f;
+            if constexpr (KC > 0) {
+                float dx[KC], dy[KC], wk[KC];
+#pragma unroll
+                for (int k = 0; k < KC; ++k)
+                    if (k < K) { diff(k, dx[k], dy[k]); wk[k] = wp[(size_t)k * mno]; }
+#pragma unroll
+                for (int k = 0; k < KC; ++k)
+                    if (k < K) { mx += wk[k] * dx[k]; my += wk[k] * dy[k]; }
+#pragma unroll
+                for (int k = 0; k < KC; ++k)
+                    if (k < K) {
+                        const float cx = dx[k] - mx, cy = dy[k] - my;
+                        cxx += wk[k] * (cx * cx); cyy += wk[k] * (cy * cy); cxy += wk[k] * (cx * cy);
+                    }
+                cxx /= den; cyy /= den; cxy /= den;
+                const float det = cxx * cyy - cxy * cxy;
+                if (den > 0.f && det > DESIRE_KDE_MIN_DET_RATIO * cxx * cyy) {
+                    const float dd = det * h2, c2 = 2.f * cxy;
+                    float M = -INFINITY, S = 0.f;
+#pragma unroll
+                    for (int k = 0; k < KC; ++k)
+                        if (k < K) {
+                            const float q = (-0.5f * ((cyy * (dx[k] * dx[k]) - c2 * (dx[k] * dy[k])) + cxx * (dy[k] * dy[k]))) / dd;
+                            dx[k] = q;
+                            M = fmaxf(M, q);
+                        }
+#pragma unroll
+                    for (int k = 0; k < KC; ++k)
+                        if (k < K) S += wk[k] * expf(dx[k] - M);
+                    const float l = M + logf(S) - KD_LOG_2PI - 0.5f * logf(det) - logf(h2);
+                    if (l > log_floor) v = l;
+                }
+            } else {
+                for (int k = 0; k < K; ++k) {
+                    float dx, dy; diff(k, dx, dy);
+                    const float wk = wp[(size_t)k * mno];
+                    mx += wk * dx; my += wk * dy;
+                }
+                for (int k = 0; k < K; ++k) {
+                    float dx, dy; diff(k, dx, dy);
+                    const float wk = wp[(size_t)k * mno];
+                    const float cx = dx - mx, cy = dy - my;
+                    cxx += wk * (cx * cx); cyy += wk * (cy * cy); cxy += wk * (cx * cy);
+                }
+                cxx /= den; cyy /= den; cxy /= den;
+                const float det = cxx * cyy - cxy * cxy;
+                if (den > 0.f && det > DESIRE_KDE_MIN_DET_RATIO * cxx * cyy) {
+                    const float dd = det * h2, c2 = 2.f * cxy;
+                    auto quad = [&](int k) {
+                        float dx, dy; diff(k, dx, dy);
+                        return (-0.5f * ((cyy * (dx * dx) - c2 * (dx * dy)) + cxx * (dy * dy))) / dd;
+                    };
+                    float M = -INFINITY, S = 0.f;
+                    for (int k = 0; k < K; ++k) M = fmaxf(M, quad(k));
+                    for (int k = 0; k < K; ++k) S += wp[(size_t)k * mno] * expf(quad(k) - M);
+                    const float l = M + logf(S) - KD_LOG_2PI - 0.5f * logf(det) - logf(h2);
+                    if (l > log_floor) v = l;
+                }
+            }
+        }
+        val[s * Tp + t] = v;
+        cm[s * Tp + t] = counted ? 1.f : 0.f;
+        if (frame) frame[(size_t)a * T + t] = v;
+    }
+    __syncthreads();
+
+    const int n_h = hz.n, h_max = hzs[n_h - 1];
+    for (int s = tid; s < na; s += KD_THREADS) {
+        const float* vr = val + s * Tp;
+        const float* mr = cm + s * Tp;
+        float* o = out + (size_t)(a0 + s) * n_h * 2;
+        float sum = 0.f, last = 0.f;
+        int np = 0, hi = 0;
+        for (int t = 0; t < h_max; ++t) {
+            if (mr[t] != 0.f) { last = vr[t]; sum += last; ++np; }
+            if (t + 1 == hzs[hi]) {
+                o[2 * hi] = np ? -(sum / (float)np) : 0.f;
+                o[2 * hi + 1] = np ? -last : 0.f;
+                ++hi;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+// Whole agents per workgroup: as many as 256 (agent, t) pairs hold, one when T_pred is longer than that (the lanes then loop over its frames).
+bool kde_geometry(int T, int* SA) {
+    const int sa = max(1, KD_THREADS / T);
+    if ((size_t)sa * (size_t)(T | 1) * 8 > (size_t)KD_LDS_BYTES) return false;
+    *SA = sa;
+    return true;
+}
+
+void launch_kde_nll(const float* Y, const float* fut, const float* score, float* w, float* st, float* out, float* frame, int n_scenes, int mno,
+                    int K, int T, const RankHz& hz, float sx, float sy, float ux, float uy, float log_floor, hipStream_t s) {
+    int SA = 1;
+    if (!kde_geometry(T, &SA)) return;                                // (refused by the caller before it gets here)
+    const int A = n_scenes * mno;
+    hipLaunchKernelGGL(k_kde_weights, dim3((A + KD_THREADS - 1) / KD_THREADS), dim3(KD_THREADS), 0, s, score, w, st, A, mno, K);
+    const size_t lds = (size_t)SA * (T | 1) * 8;
+    const int vec = (reinterpret_cast<uintptr_t>(Y) & 7) == 0;
+    const dim3 grid((A + SA - 1) / SA), block(KD_THREADS);
+    if (K <= 8)
+        hipLaunchKernelGGL(k_kde_nll<8>, grid, block, lds, s, Y, fut, w, st, out, frame, A, mno, K, T, SA, vec, sx, sy, ux, uy, log_floor, hz);
+    else if (K <= 24)
+        hipLaunchKernelGGL(k_kde_nll<24>, grid, block, lds, s, Y, fut, w, st, out, frame, A, mno, K, T, SA, vec, sx, sy, ux, uy, log_floor, hz);
+    else
+        hipLaunchKernelGGL(k_kde_nll<0>, grid, block, lds, s, Y, fut, w, st, out, frame, A, mno, K, T, SA, vec, sx, sy, ux, uy, log_floor, hz);
+}

@@ -3,7 +3,7 @@ device, errors per horizon of the best-scored sample (top-1), of the best among 
 
     python -m desire_amd.evaluate --checkpoint save/social_model-400.npz --data_dir data/ --max_num_obj 32 --d_dim 128 \\
         --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json] \\
-        [--generator cvae|rollout]
+        [--generator cvae|rollout] [--nll]
 
 The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
@@ -32,6 +32,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--generator", type=str, default="cvae", choices=("cvae", "rollout"),
                    help="what draws the K samples that the IOC stage scores: cvae (the CVAE decoder) or rollout (K rollouts of the reference's Gaussian head "
                         "per agent, desire_rollout_samples; needs a checkpoint trained with --head_loss_weight > 0)")
+    p.add_argument("--nll", action="store_true",
+                   help="also report the KDE negative log-likelihood of the ground truth under the K samples per horizon (mean over the frames "
+                        "and final frame; density per unit^2 of --units, log clipped at -20), with equal weights and with weights softmax(IOC score)")
     p.add_argument("--out", type=str, default=None, help="write the result JSON here (default: standard output only)")
     return p
 
@@ -60,6 +63,7 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     """Runs the walk; returns the result dict main() prints.  `data_loader` / `model` may be injected (tests)."""
     from .data_loader import DataLoader
     from .model import DESIREModel, default_top
+    from ._lib import KDE_LOG_FLOOR
     if args.pred_length is None:
         args.pred_length = args.seq_length
     t_obs, t_pred = int(args.seq_length), int(args.pred_length)
@@ -77,6 +81,9 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     sums = {k: np.zeros((len(hz), 2), np.float64) for k in names}
     agents = np.zeros(len(hz), np.int64)
     mean_k, n_all, n_windows = np.zeros(2, np.float64), 0, 0
+    nll = bool(getattr(args, "nll", False))
+    nll_sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("uniform", "score_weighted")}
+    nll_floored, nll_frames = 0, 0
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
@@ -86,6 +93,9 @@ def evaluate(args, data_loader=None, model=None) -> dict:
         ranked = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units=units).astype(np.float64)
         best = model.evaluate_ranked(Y, score, fut, top=K, horizons=hz, units=units).astype(np.float64)
         ev = model.evaluate(Y, fut).astype(np.float64)
+        if nll:
+            nll_u, fr = model.evaluate_nll(Y, score, fut, horizons=hz, units=units, log_floor=KDE_LOG_FLOOR, return_frames=True)
+            nll_w = model.evaluate_nll(Y, score, fut, horizons=hz, units=units, weighted=True, log_floor=KDE_LOG_FLOOR)
         pw, fw = np.stack(past), np.stack(fut)
         mno = ranked.shape[0] // pw.shape[0]
         valid = np.zeros((pw.shape[0], mno), bool)
@@ -98,9 +108,16 @@ def evaluate(args, data_loader=None, model=None) -> dict:
             sums["top1"][i] += ranked[c, i, 0:2].sum(0)
             sums["best_of_top"][i] += ranked[c, i, 2:4].sum(0)
             sums["best_of_K"][i] += best[c, i, 2:4].sum(0)
+            if nll:
+                nll_sums["uniform"][i] += nll_u[c, i].astype(np.float64).sum(0)
+                nll_sums["score_weighted"][i] += nll_w[c, i].astype(np.float64).sum(0)
         c = (valid & seen.any(1)).reshape(-1)
         mean_k += ev[c, 0:2].sum(0)
         n_all += int(c.sum())
+        if nll:                                      # the counted frames of those agents, and how many of them sit on the floor (equal weights)
+            cf = (valid[:, None, :] & seen).transpose(0, 2, 1).reshape(fr.shape)
+            nll_frames += int(cf.sum())
+            nll_floored += int((cf & (fr <= np.float32(KDE_LOG_FLOOR))).sum())
         n_windows += len(xs)
     res = {"checkpoint": args.checkpoint, "generator": generator, "units": args.units, "seed": int(args.seed), "K": K, "top": top, "horizons": hz,
            "windows": n_windows, "agents": [int(a) for a in agents]}
@@ -110,6 +127,12 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     # mean-of-K comes from the ADE / FDE harness: normalised units, the whole prediction
     res["mean_of_K"] = {"ade": float(mean_k[0] / max(n_all, 1)), "fde": float(mean_k[1] / max(n_all, 1)), "units": "norm", "horizon": t_pred,
                         "agents": n_all}
+    if nll:
+        res["kde_nll"] = {"log_floor": KDE_LOG_FLOOR}
+        for k in ("uniform", "score_weighted"):
+            m = nll_sums[k] / np.maximum(agents, 1)[:, None]
+            res["kde_nll"][k] = {"mean": [float(v) for v in m[:, 0]], "final": [float(v) for v in m[:, 1]]}
+        res["kde_nll"].update({"floored_frames": nll_floored, "frames": nll_frames})
     return res
 
 

@@ -579,6 +579,34 @@ class DESIREModel(object):
         h.ranked_errors(Y.data_ptr(), fut.data_ptr(), order.data_ptr(), top, hz, ux, uy, out.data_ptr(), stream)
         return out.cpu().numpy()
 
+    def evaluate_nll(self, Y, score, fut_windows, horizons=None, units="px", weighted: bool = False, log_floor: float = _lib.KDE_LOG_FLOOR,
+                     return_frames: bool = False):
+        """[A, n_h, 2] = per horizon (mean, final) KDE negative log-likelihood of the ground truth under the agent's K samples: at every counted
+        frame a Gaussian kernel density (Scott's bandwidth, scipy.stats.gaussian_kde's fit) over the K sampled positions, its log at the ground
+        truth clipped below at log_floor, averaged over the counted frames before the horizon / taken at the last of them; zeros where there is
+        none.  weighted=False: equal weights; True: the weights softmax(score) that the ranking loss trains the IOC scores as.  The density is
+        per unit^2: units, horizons and `fut_windows` as in evaluate_ranked.  return_frames=True: also the per-frame log-densities [A, T_pred]
+        (0 where a frame is not counted)."""
+        torch = self.torch
+        n = int(Y.shape[0])
+        h = self._handles.get((n, 0, 0)) or self._handle(n, True)
+        d = h.dims
+        hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
+        if units == "norm":
+            ux, uy = 1.0, 1.0
+        else:
+            f = 1.0 if units == "px" else float(units)
+            ux, uy = f / d.sx, f / d.sy
+        if weighted and score is None:
+            raise ValueError("weighted=True needs the IOC scores")
+        fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
+        stream = torch.cuda.current_stream().cuda_stream
+        out = torch.empty((d.A, len(hz), 2), device=self.device, dtype=torch.float32)
+        frames = torch.empty((d.A, d.T_pred), device=self.device, dtype=torch.float32) if return_frames else None
+        h.kde_nll(Y.data_ptr(), fut.data_ptr(), score.data_ptr() if weighted else 0, hz, ux, uy, float(log_floor), out.data_ptr(),
+                  frames.data_ptr() if return_frames else 0, stream)
+        return (out.cpu().numpy(), frames.cpu().numpy()) if return_frames else out.cpu().numpy()
+
     # ---- checkpoints (train.py:114,197-206 saves TF checkpoints; here: a named fp32 archive) -----------------
     def save(self, path: str) -> None:
         from .formats import save_weights

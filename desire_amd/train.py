@@ -101,6 +101,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--report_ranked", action="store_true",
                    help="after every epoch, on the same batch: errors of the paper's protocol in pixels -- ADE / FDE per horizon of the sample the IOC "
                         "scores best (top-1) and of the best among the --eval_top best-scored samples")
+    p.add_argument("--report_nll", action="store_true",
+                   help="after every epoch, on the same batch: KDE negative log-likelihood of the ground truth under the K prior samples over the "
+                        "whole prediction (per pixel^2, log clipped at -20), with equal weights and with weights softmax(IOC score)")
     p.add_argument("--eval_top", type=int, default=None, help="samples per agent the ranked report keeps (default: 10 %% of --num_samples, at least 1)")
     p.add_argument("--eval_horizons", type=str, default=None,
                    help="horizons of the ranked report in frames, comma separated and increasing, e.g. 3,6,9,12 (default: quarters of --pred_length)")
@@ -278,11 +281,33 @@ def _report_ranked(args, model, past, fut, epoch, rank, log) -> None:
             epoch, rank, "[" + ", ".join(str(h) for h in hz) + "]", fmt(0), fmt(1), top, fmt(2), fmt(3), int(there.sum())))
 
 
+def _report_nll(args, model, past, fut, epoch, rank, log) -> None:
+    """--report_nll: the proper scoring rule next to the ranked errors.  The batch, the prior samples (same seed) and the agents of _report_ade; a
+    Gaussian KDE of every agent's K samples per frame, once with equal weights and once with softmax(IOC score), mean over the whole prediction."""
+    import torch
+    if torch.is_tensor(past):
+        Y, score = model.forward_device(past, None, seed=args.seed)
+        pw, fw = past.cpu().numpy(), fut.cpu().numpy()
+    else:
+        Y, score = model.forward(past, None, seed=args.seed)
+        pw, fw = np.stack([np.asarray(p) for p in past]), np.stack([np.asarray(f) for f in fut])
+    T = int(Y.shape[3])
+    ev = [model.evaluate_nll(Y, score, fut, horizons=[T], units="px", weighted=wt) for wt in (False, True)]
+    there = np.zeros(ev[0].shape[0], bool)
+    m = pw.shape[2]
+    there.reshape(pw.shape[0], -1)[:, :m] = (pw[:, -1, :, 0] != 0) & (fw[:, :, :, 0] != 0).all(1)
+    if there.any():
+        u, w = (e[there, 0, 0].astype(np.float64).mean() for e in ev)
+        log("epoch {} rank {}: KDE NLL px @h={}: uniform = {:.4f}, score-weighted = {:.4f} ({} agents)".format(epoch, rank, T, u, w, int(there.sum())))
+
+
 def _report(args, model, past, fut, epoch, rank, log) -> None:
     if getattr(args, "report_ade", False):
         _report_ade(args, model, past, fut, epoch, rank, log)
     if getattr(args, "report_ranked", False):
         _report_ranked(args, model, past, fut, epoch, rank, log)
+    if getattr(args, "report_nll", False):
+        _report_nll(args, model, past, fut, epoch, rank, log)
 
 
 def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred, losses) -> List[float]:
@@ -308,7 +333,7 @@ def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred,
 
     steps = 0
     last = None
-    reporting = getattr(args, "report_ade", False) or getattr(args, "report_ranked", False)
+    reporting = getattr(args, "report_ade", False) or getattr(args, "report_ranked", False) or getattr(args, "report_nll", False)
     try:
         for bt in feeder:
             start = time.time()

@@ -344,6 +344,40 @@ int desire_rank_samples(desire_handle* h, const float* dev_score, const float* d
 int desire_ranked_errors(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const int32_t* dev_order, int32_t n_top,
                          const int32_t* host_horizons, int32_t n_h, float unit_x, float unit_y, float* dev_out, void* stream);
 
+/* ---- KDE log-likelihood of the ground truth under an agent's K samples: the proper scoring rule next to the best-of-n errors.  Layouts and the
+ * counting rule are desire_ranked_errors': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot, dev_fut [n_scenes, T_pred, mno, 3],
+ * frame t of agent a counts when dev_fut[scene, t, slot, 0] != 0.  dev_score [R] (the IOC scores, desire_forward's layout) or NULL.
+ * All arithmetic is fp32; every operation is rounded once (no fused multiply-add), every sum over k runs in increasing k from 0.f.  For a counted
+ * (a, t), with g = (fut_x * sx, fut_y * sy):
+ *   1 weights     NULL dev_score: w_k = 1.f / K.  Else m = max_j s_j, e_k = expf(s_k - m), w_k = e_k / sum_j e_j -- once per agent; an agent with
+ *                 any non-finite score gets 1.f / K.
+ *   2 differences d_k = ((Y[r_k, t, 0] - g_x) * unit_x, (Y[r_k, t, 1] - g_y) * unit_y): the density is evaluated at the origin of the
+ *                 differences, so no large coordinate enters a moment.
+ *   3 mean        m = sum_k w_k * d_k.
+ *   4 covariance  c_k = d_k - m; den = sum_k w_k * (1.f - w_k) (the cancellation-free form of 1 - sum w^2);
+ *                 (Cxx, Cyy, Cxy) = (sum_k w_k * (c_kx * c_kx), sum_k w_k * (c_ky * c_ky), sum_k w_k * (c_kx * c_ky)) / den -- numpy's
+ *                 cov(aweights = w), what scipy.stats.gaussian_kde fits.
+ *   5 bandwidth   n_eff = 1.f / sum_k w_k * w_k; h2 = powf(n_eff, -1.f / 3.f): Scott's factor squared in two dimensions (scipy's default).
+ *   6 degenerate  when den <= 0 (K = 1), when a weight is exactly 1.f (a one-hot score: the other weights are then below 2^-24 and the moments
+ *                 above would be theirs alone), or when !(det > DESIRE_KDE_MIN_DET_RATIO * Cxx * Cyy) with det = Cxx * Cyy - Cxy * Cxy:
+ *                 coincident, collinear (K = 2 among them) and non-finite samples.
+ *   7 log-density q_k = (-0.5f * ((Cyy * (d_kx * d_kx) - (2.f * Cxy) * (d_kx * d_ky)) + Cxx * (d_ky * d_ky))) / (det * h2); M = max_k q_k;
+ *                 l = M + logf(sum_k w_k * expf(q_k - M)) - logf(2 pi) - 0.5f * logf(det) - logf(h2), left to right.  The frame's value is l where
+ *                 l > log_floor, else log_floor (a NaN among them); log_floor for a degenerate frame.  Trajectron++ clips at -20.
+ *   8 outputs     dev_frame [A, T_pred] (may be NULL) = that value, 0 for a frame that is not counted.  dev_out [A, n_h, 2] = (-(sum of the frame
+ *                 values over the counted t < h, in increasing t, / their number), -(the value at the last counted frame < h)); two zeros
+ *                 when nothing is counted before h.
+ * The density is per (unit of the caller)^2: scaling both units by c shifts every unfloored value by -2 log c.  A result depends on its agent's
+ * rows, scores and targets only -- not on the grid, the batch or DESIRE_FLAG_COMPACT_*.  An absent slot's zero rows are coincident samples: it
+ * reports the floor, so the call needs no validity input.  No float atomics: bitwise reproducible.  host_horizons as in desire_ranked_errors
+ * (strictly increasing, 1 .. T_pred, n_h <= 8, read at call time, by value).  Stream-ordered, capturable, no host wait; the per-agent weights
+ * live in scratch that desire_create allocated, a call never allocates.  K has no limit of its own.  A NULL handle / dev_Yhat / dev_fut /
+ * dev_out / host_horizons, bad horizons, a non-finite log_floor, a unit that is not finite and > 0, a ref_compat handle and a T_pred beyond the
+ * kernel's LDS (7680 frames): DESIRE_ERR_ARG, and nothing is launched. */
+#define DESIRE_KDE_MIN_DET_RATIO 1e-5f
+int desire_kde_nll(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const float* dev_score, const int32_t* host_horizons,
+                   int32_t n_h, float unit_x, float unit_y, float log_floor, float* dev_out, float* dev_frame, void* stream);
+
 /* ---- hipGraph capture: desire_graph_begin(h, stream); any stream-ordered desire_* calls on that stream (desire_forward,
  * desire_backward, desire_clip_grads, desire_ioc_step ...) ; desire_graph_end -> graph id; desire_graph_launch replays them with
  * the SAME device pointers.  For launch-bound shapes (small batches, the training step, the agent-sharded IOC loop).  Calls
