@@ -25,10 +25,11 @@ EXPORTS = [
     "desire_graph_begin", "desire_graph_end", "desire_graph_launch", "desire_rollout", "desire_build_windows_la", "desire_adam_state",
     "desire_set_option", "desire_train_loss_async", "desire_set_head_loss",
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
-    "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll",
+    "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
 ]
 RNG_BITS, RNG_NORMAL, RNG_LATENT, RNG_ROLLOUT = 0, 1, 2, 3          # desire_rng_fill kinds (DESIRE_RNG_*)
+DIST_FINAL, DIST_MEAN, DIST_MAX = 0, 1, 2                           # desire_select_diverse metrics (DESIRE_DIST_*)
 KDE_LOG_FLOOR = -20.0                                               # desire_kde_nll: the clip of a frame's log-density (Trajectron++'s)
 
 
@@ -98,6 +99,7 @@ def load() -> C.CDLL:
     lib.desire_rank_samples.argtypes = [vp, f32p, f32p, i32, vp, f32p, f32p, vp]
     lib.desire_ranked_errors.argtypes = [vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, f32p, vp]
     lib.desire_kde_nll.argtypes = [vp, f32p, f32p, f32p, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, f32p, f32p, vp]
+    lib.desire_select_diverse.argtypes = [vp, f32p, vp, f32p, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, vp, f32p, f32p, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
     lib.desire_rollout_samples.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
@@ -293,6 +295,18 @@ class Handle:
         hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
         _chk(self.lib.desire_kde_nll(self._h, yhat_ptr or None, fut_ptr or None, score_ptr or None, hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size,
                                      C.c_float(unit_x), C.c_float(unit_y), C.c_float(log_floor), out_ptr or None, frame_ptr or None, stream or None))
+
+    def select_diverse(self, yhat_ptr: int, order_ptr: int, score_ptr: int, metric: int, t_end: int, radius: float, unit_x: float, unit_y: float,
+                       n_top: int, order_out_ptr: int, count_ptr: int, mass_ptr: int = 0, top_y_ptr: int = 0, top_score_ptr: int = 0,
+                       stream: int = 0) -> None:
+        """Score-ordered non-maximum suppression: walking order [A, K] (rank_samples') best first, a sample is kept unless it lies within
+        `radius` (metric DIST_FINAL / DIST_MEAN / DIST_MAX over the frames t < t_end, distances scaled by (unit_x, unit_y) as in ranked_errors) of
+        one already kept.  order_out [A, K] int32 = the kept samples, then the suppressed ones; count [A] int32 = the number kept; optionally
+        mass [A, K] = the softmax(score) weight each kept sample absorbed (score_ptr = 0: equal weights) and the rows / scores of the first
+        n_top entries -> top_y [A, n_top, T_pred, 2], top_score [A, n_top]."""
+        _chk(self.lib.desire_select_diverse(self._h, yhat_ptr or None, order_ptr or None, score_ptr or None, int(metric), int(t_end), C.c_float(radius),
+                                            C.c_float(unit_x), C.c_float(unit_y), int(n_top), order_out_ptr or None, count_ptr or None,
+                                            mass_ptr or None, top_y_ptr or None, top_score_ptr or None, stream or None))
 
     def set_training(self, on: bool) -> None:
         _chk(self.lib.desire_set_training(self._h, int(on)))

@@ -259,6 +259,36 @@ extern "C" int desire_kde_nll(desire_handle* h, const float* dev_Yhat, const flo
     return DESIRE_OK;
 }
 
+// ---- score-ordered non-maximum suppression of the K samples (kernels_select.hip): the contract is stated in include/desire_hip.h.  The checks
+// that need no handle come first, so a caller's constants can be validated before a handle exists. ----
+extern "C" int desire_select_diverse(desire_handle* h, const float* dev_Yhat, const int32_t* dev_order, const float* dev_score, int32_t metric,
+                                     int32_t t_end, float radius, float unit_x, float unit_y, int32_t n_top, int32_t* dev_order_out,
+                                     int32_t* dev_count, float* dev_mass, float* dev_top_Y, float* dev_top_score, void* stream) {
+    if (metric < DESIRE_DIST_FINAL || metric > DESIRE_DIST_MAX) return fail(DESIRE_ERR_ARG, "metric must be DESIRE_DIST_FINAL, _MEAN or _MAX (0..2)");
+    if (!std::isfinite(radius) || radius < 0.f) return fail(DESIRE_ERR_ARG, "radius must be finite and >= 0");
+    if (!std::isfinite(unit_x) || !(unit_x > 0.f)) return fail(DESIRE_ERR_ARG, "unit_x must be finite and > 0");
+    if (!std::isfinite(unit_y) || !(unit_y > 0.f)) return fail(DESIRE_ERR_ARG, "unit_y must be finite and > 0");
+    if (t_end < 1) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    if (n_top < 1) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_order) return fail(DESIRE_ERR_ARG, "dev_order is NULL");
+    if (!dev_order_out) return fail(DESIRE_ERR_ARG, "dev_order_out is NULL");
+    if (!dev_count) return fail(DESIRE_ERR_ARG, "dev_count is NULL");
+    if (dev_top_score && !dev_score) return fail(DESIRE_ERR_ARG, "dev_score is NULL (dev_top_score is gathered from it)");
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to select from");
+    if (t_end > d.T_pred) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    if (n_top > d.K) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
+    int sc = 0, g = 0;
+    if (!select_geometry(d.mno, d.K, metric, t_end, &sc, &g))
+        return fail(DESIRE_ERR_ARG, "K samples of t_end frames do not fit the selection kernel's LDS: K * (8 * (frames | 1) + 20) + 8 must be <= 61440");
+    launch_select_diverse(dev_Yhat, dev_order, dev_score, dev_order_out, dev_count, dev_mass, dev_top_Y, dev_top_score, d.n_scenes, d.mno, d.K,
+                          d.T_pred, metric, t_end, n_top, radius, unit_x, unit_y, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- the device generator (philox.h, kernels_rng.hip): the packing of its counters is stated in include/desire_hip.h ------------------------
 namespace {
 int rng_check_packing(const desire_ctx* h, uint32_t slot_base) {

@@ -263,6 +263,14 @@ bool kde_geometry(int T, int* SA);                         // agents per workgro
 void launch_kde_nll(const float* Y, const float* fut, const float* score, float* w, float* st, float* out, float* frame, int n_scenes, int mno,
                     int K, int T, const RankHz& hz, float sx, float sy, float ux, float uy, float log_floor, hipStream_t s);
 
+// ---- score-ordered non-maximum suppression (kernels_select.hip) ----
+// slots per workgroup and lanes per agent; false: one agent's K rows of staged frames do not fit the LDS (the limit is stated in desire_hip.h)
+bool select_geometry(int mno, int K, int metric, int t_end, int* SC, int* G);
+// score, mass, top_Y and top_score may be nullptr; no scratch
+void launch_select_diverse(const float* Y, const int32_t* order, const float* score, int32_t* order_out, int32_t* count, float* mass, float* top_Y,
+                           float* top_score, int n_scenes, int mno, int K, int T, int metric, int t_end, int n_top, float radius, float ux,
+                           float uy, hipStream_t s);
+
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);
 void launch_loss_grad_y(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, const float* nvalid, float* dY,

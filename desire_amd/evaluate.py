@@ -3,7 +3,7 @@ device, errors per horizon of the best-scored sample (top-1), of the best among 
 
     python -m desire_amd.evaluate --checkpoint save/social_model-400.npz --data_dir data/ --max_num_obj 32 --d_dim 128 \\
         --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json] \\
-        [--generator cvae|rollout] [--nll]
+        [--generator cvae|rollout] [--nll] [--select nms --nms_radius 20 [--nms_metric final|mean|max] [--nms_horizon 12]]
 
 The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
@@ -35,6 +35,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--nll", action="store_true",
                    help="also report the KDE negative log-likelihood of the ground truth under the K samples per horizon (mean over the frames "
                         "and final frame; density per unit^2 of --units, log clipped at -20), with equal weights and with weights softmax(IOC score)")
+    p.add_argument("--select", type=str, default="score", choices=("score", "nms"),
+                   help="score: the top N by IOC score (default).  nms: also report the best of the N most plausible MUTUALLY DISTINCT futures -- "
+                        "score-ordered non-maximum suppression on the device (desire_select_diverse), see --nms_radius")
+    p.add_argument("--nms_radius", type=float, default=None, help="--select nms: two futures closer than this many pixels are one (required then)")
+    p.add_argument("--nms_metric", type=str, default="final", choices=("final", "mean", "max"),
+                   help="--select nms: the distance of two futures -- at the last frame, the mean over the frames, or the largest over the frames")
+    p.add_argument("--nms_horizon", type=int, default=None, help="--select nms: frames the distance looks at (default: all of --pred_length)")
     p.add_argument("--out", type=str, default=None, help="write the result JSON here (default: standard output only)")
     return p
 
@@ -84,6 +91,11 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     nll = bool(getattr(args, "nll", False))
     nll_sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("uniform", "score_weighted")}
     nll_floored, nll_frames = 0, 0
+    nms = str(getattr(args, "select", "score") or "score") == "nms"
+    if nms and getattr(args, "nms_radius", None) is None:
+        raise ValueError("--select nms needs --nms_radius (pixels)")
+    nms_kw = dict(select="nms", nms_radius=args.nms_radius, nms_metric=args.nms_metric, nms_horizon=args.nms_horizon) if nms else {}
+    nms_sums, nms_count, nms_present = np.zeros((len(hz), 2), np.float64), 0, 0
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
@@ -93,6 +105,9 @@ def evaluate(args, data_loader=None, model=None) -> dict:
         ranked = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units=units).astype(np.float64)
         best = model.evaluate_ranked(Y, score, fut, top=K, horizons=hz, units=units).astype(np.float64)
         ev = model.evaluate(Y, fut).astype(np.float64)
+        if nms:
+            distinct, kept = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units=units, return_count=True, **nms_kw)
+            distinct = distinct.astype(np.float64)
         if nll:
             nll_u, fr = model.evaluate_nll(Y, score, fut, horizons=hz, units=units, log_floor=KDE_LOG_FLOOR, return_frames=True)
             nll_w = model.evaluate_nll(Y, score, fut, horizons=hz, units=units, weighted=True, log_floor=KDE_LOG_FLOOR)
@@ -108,11 +123,16 @@ def evaluate(args, data_loader=None, model=None) -> dict:
             sums["top1"][i] += ranked[c, i, 0:2].sum(0)
             sums["best_of_top"][i] += ranked[c, i, 2:4].sum(0)
             sums["best_of_K"][i] += best[c, i, 2:4].sum(0)
+            if nms:
+                nms_sums[i] += distinct[c, i, 2:4].sum(0)
             if nll:
                 nll_sums["uniform"][i] += nll_u[c, i].astype(np.float64).sum(0)
                 nll_sums["score_weighted"][i] += nll_w[c, i].astype(np.float64).sum(0)
         c = (valid & seen.any(1)).reshape(-1)
         mean_k += ev[c, 0:2].sum(0)
+        if nms:                                      # samples kept per agent present at the last observed frame
+            nms_count += int(kept[valid.reshape(-1)].sum())
+            nms_present += int(valid.sum())
         n_all += int(c.sum())
         if nll:                                      # the counted frames of those agents, and how many of them sit on the floor (equal weights)
             cf = (valid[:, None, :] & seen).transpose(0, 2, 1).reshape(fr.shape)
@@ -127,6 +147,11 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     # mean-of-K comes from the ADE / FDE harness: normalised units, the whole prediction
     res["mean_of_K"] = {"ade": float(mean_k[0] / max(n_all, 1)), "fde": float(mean_k[1] / max(n_all, 1)), "units": "norm", "horizon": t_pred,
                         "agents": n_all}
+    if nms:
+        m = nms_sums / np.maximum(agents, 1)[:, None]
+        res["select"] = {"mode": "nms", "radius_px": float(args.nms_radius), "metric": str(args.nms_metric),
+                         "horizon": int(args.nms_horizon or t_pred), "mean_count": float(nms_count / max(nms_present, 1)), "present_agents": nms_present,
+                         "best_of_top_distinct": {"ade": [float(v) for v in m[:, 0]], "fde": [float(v) for v in m[:, 1]]}}
     if nll:
         res["kde_nll"] = {"log_floor": KDE_LOG_FLOOR}
         for k in ("uniform", "score_weighted"):

@@ -510,18 +510,37 @@ class DESIREModel(object):
         self.final_output, self.final_states, self.cost = Y, score, None
         return Y, score
 
+    @staticmethod
+    def _nms_args(select: str, nms_radius, nms_metric: str, nms_horizon, T_pred: int):
+        """None for select="score"; (metric, t_end, radius in pixels) for select="nms"."""
+        if select == "score":
+            return None
+        if select != "nms":
+            raise ValueError("select must be 'score' (the best-scored samples) or 'nms' (score-ordered non-maximum suppression), got %r" % (select,))
+        if nms_radius is None:
+            raise ValueError("select='nms' needs nms_radius (pixels)")
+        metrics = {"final": _lib.DIST_FINAL, "mean": _lib.DIST_MEAN, "max": _lib.DIST_MAX}
+        if nms_metric not in metrics:
+            raise ValueError("nms_metric must be 'final', 'mean' or 'max', got %r" % (nms_metric,))
+        t_end = T_pred if nms_horizon is None else int(nms_horizon)
+        if not 1 <= t_end <= T_pred:
+            raise ValueError("nms_horizon must be 1..pred_length (%d), got %d" % (T_pred, t_end))
+        return metrics[nms_metric], t_end, float(nms_radius)
+
     def predict(self, x_batch: Sequence[np.ndarray], top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False,
-                window_base: int = 0, generator: str = "cvae", normals=None):
+                window_base: int = 0, generator: str = "cvae", normals=None, select: str = "score", nms_radius=None, nms_metric: str = "final",
+                nms_horizon=None):
         """The `top` most plausible futures of every agent of a batch of observed loader windows [T_obs, MNO, 3], ranked by IOC score
         (prior sampling: no future given).  See predict_device for the result."""
         d = self._handle(len(x_batch), False).dims
         out = self.predict_device(self._pad_windows(x_batch, d.mno), top, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng,
-                                  window_base=window_base, generator=generator, normals=normals)
+                                  window_base=window_base, generator=generator, normals=normals, select=select, nms_radius=nms_radius,
+                                  nms_metric=nms_metric, nms_horizon=nms_horizon)
         self.input_data, self.target_data = x_batch, None
         return out
 
     def predict_device(self, past, top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0,
-                       generator: str = "cvae", normals=None):
+                       generator: str = "cvae", normals=None, select: str = "score", nms_radius=None, nms_metric: str = "final", nms_horizon=None):
         """predict() on windows already in HBM (forward_device's layout).  Returns a dict of device tensors: "traj" [n, mno, top, T_pred, 2]
         IN PIXELS, best-scored first; "score" [n, mno, top]; "order" [n, mno, K] int32 (sample indices by descending score, ties to the
         lower index); "present" [n, mno] bool (id != 0 at the last observed frame -- the rows of absent agents are whatever the forward
@@ -529,8 +548,15 @@ class DESIREModel(object):
         and scores stay available as self.final_output / self.final_states.
         generator "cvae" (default): the K samples of the CVAE decoder (forward_device).  "rollout": K rollouts of the Gaussian head per agent
         (rollout_samples; `normals` [n, K, mno, T_pred, 2] or None as there, `eps` must be None), scored and refined by the same IOC stage -- the
-        reference's generator under the same ranking; warns like sample(mode="rollout") while the head is untrained."""
+        reference's generator under the same ranking; warns like sample(mode="rollout") while the head is untrained.
+        select "score" (default): the `top` best-scored samples.  "nms": the `top` most plausible MUTUALLY DISTINCT futures -- walking the samples
+        best-scored first, one is kept unless it lies within nms_radius pixels (required) of one already kept, by nms_metric "final" (distance at
+        the last frame), "mean" (mean distance over the frames) or "max" (largest distance) over the first nms_horizon frames (None: all).
+        "traj", "score" and "order" then follow the diverse order (the kept samples, then the suppressed ones best-scored first, so there are
+        always `top` distinct samples), and the dict gains "count" [n, mno] int32 (samples kept) and "prob" [n, mno, top] (the softmax(score)
+        mass each returned sample absorbed; 0 for a suppressed one)."""
         torch = self.torch
+        nms = self._nms_args(select, nms_radius, nms_metric, None, 1)        # refuse a bad selection before the forward runs (the horizon: below)
         if generator == "cvae":
             if normals is not None:
                 raise ValueError("`normals` are the head rollout's draws: pass generator='rollout' with them")
@@ -550,20 +576,38 @@ class DESIREModel(object):
         order = torch.empty((n, d.mno, d.K), device=self.device, dtype=torch.int32)
         traj = torch.empty((n, d.mno, top, d.T_pred, 2), device=self.device, dtype=torch.float32)
         sc = torch.empty((n, d.mno, top), device=self.device, dtype=torch.float32)
-        h.rank_samples(score.data_ptr(), Y.data_ptr(), top, order.data_ptr(), traj.data_ptr(), sc.data_ptr(),
-                       torch.cuda.current_stream().cuda_stream)
+        stream = torch.cuda.current_stream().cuda_stream
+        if nms is None:
+            h.rank_samples(score.data_ptr(), Y.data_ptr(), top, order.data_ptr(), traj.data_ptr(), sc.data_ptr(), stream)
+            traj /= torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)
+            return {"traj": traj, "score": sc, "order": order, "present": past[:, -1, :, 0] != 0}
+        metric, t_end, radius = self._nms_args(select, nms_radius, nms_metric, nms_horizon, d.T_pred)
+        by_score = torch.empty((n, d.mno, d.K), device=self.device, dtype=torch.int32)
+        count = torch.empty((n, d.mno), device=self.device, dtype=torch.int32)
+        mass = torch.empty((n, d.mno, d.K), device=self.device, dtype=torch.float32)
+        h.rank_samples(score.data_ptr(), 0, top, by_score.data_ptr(), 0, 0, stream)
+        h.select_diverse(Y.data_ptr(), by_score.data_ptr(), score.data_ptr(), metric, t_end, radius, 1.0 / d.sx, 1.0 / d.sy, top, order.data_ptr(),
+                         count.data_ptr(), mass.data_ptr(), traj.data_ptr(), sc.data_ptr(), stream)
         traj /= torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)
-        return {"traj": traj, "score": sc, "order": order, "present": past[:, -1, :, 0] != 0}
+        return {"traj": traj, "score": sc, "order": order, "present": past[:, -1, :, 0] != 0, "count": count,
+                "prob": mass[:, :, :top].contiguous()}
 
-    def evaluate_ranked(self, Y, score, fut_windows, top: Optional[int] = None, horizons=None, units="px") -> np.ndarray:
+    def evaluate_ranked(self, Y, score, fut_windows, top: Optional[int] = None, horizons=None, units="px", select: str = "score", nms_radius=None,
+                        nms_metric: str = "final", nms_horizon=None, return_count: bool = False) -> np.ndarray:
         """[A, n_h, 4] = per horizon (ADE, FDE of the best-scored sample, best ADE, best FDE among the `top` best-scored samples) over the
         target frames before the horizon the object is present in; zeros where there is none.  horizons in frames (default
         default_horizons(T_pred)), top default default_top(K); units "px" (pixels), "norm" (normalised units, evaluate()'s) or a float f
-        = f x pixels (0.2: the paper's 1/5 resolution).  `fut_windows` as in evaluate()."""
+        = f x pixels (0.2: the paper's 1/5 resolution).  `fut_windows` as in evaluate().
+        select="nms" (nms_radius in pixels, nms_metric, nms_horizon as in predict_device): the order by score goes through the non-maximum
+        suppression first, so columns 2 and 3 become "best of the `top` most plausible distinct futures" (columns 0 and 1 are unchanged: the
+        best-scored sample is always kept first).  return_count=True: also the number of samples kept per agent [A] (select="nms" only)."""
         torch = self.torch
         n = int(Y.shape[0])
         h = self._handles.get((n, 0, 0)) or self._handle(n, True)
         d = h.dims
+        nms = self._nms_args(select, nms_radius, nms_metric, nms_horizon, d.T_pred)
+        if return_count and nms is None:
+            raise ValueError("return_count needs select='nms'")
         top = default_top(d.K) if top is None else int(top)
         hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
         if units == "norm":
@@ -576,8 +620,14 @@ class DESIREModel(object):
         order = torch.empty((d.A, d.K), device=self.device, dtype=torch.int32)
         out = torch.empty((d.A, len(hz), 4), device=self.device, dtype=torch.float32)
         h.rank_samples(score.data_ptr(), 0, top, order.data_ptr(), 0, 0, stream)
+        if nms is not None:
+            diverse = torch.empty_like(order)
+            count = torch.empty((d.A,), device=self.device, dtype=torch.int32)
+            h.select_diverse(Y.data_ptr(), order.data_ptr(), score.data_ptr(), nms[0], nms[1], nms[2], 1.0 / d.sx, 1.0 / d.sy, top,
+                             diverse.data_ptr(), count.data_ptr(), 0, 0, 0, stream)
+            order = diverse
         h.ranked_errors(Y.data_ptr(), fut.data_ptr(), order.data_ptr(), top, hz, ux, uy, out.data_ptr(), stream)
-        return out.cpu().numpy()
+        return (out.cpu().numpy(), count.cpu().numpy()) if return_count else out.cpu().numpy()
 
     def evaluate_nll(self, Y, score, fut_windows, horizons=None, units="px", weighted: bool = False, log_floor: float = _lib.KDE_LOG_FLOOR,
                      return_frames: bool = False):

@@ -378,6 +378,44 @@ int desire_ranked_errors(desire_handle* h, const float* dev_Yhat, const float* d
 int desire_kde_nll(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const float* dev_score, const int32_t* host_horizons,
                    int32_t n_h, float unit_x, float unit_y, float log_floor, float* dev_out, float* dev_frame, void* stream);
 
+/* ---- n mutually distinct futures per agent: score-ordered non-maximum suppression of the K samples.  Layouts are desire_rank_samples': agent
+ * a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot; dev_order [A, K] int32 from desire_rank_samples (any permutation per agent: the
+ * processing order); dev_score [R] or NULL.  The output dev_order_out [A, K] is again an order: desire_ranked_errors and the row gather take it
+ * unchanged.  All arithmetic is fp32; every operation is rounded once (no fused multiply-add).
+ *   1 distance    for samples k, k' of one agent and a frame t: a = (Y[r_k, t, 0] - Y[r_k', t, 0]) * unit_x; b = (Y[r_k, t, 1] - Y[r_k', t, 1]) * unit_y;
+ *                 q_t = a * a + b * b (symmetric in k, k' bit for bit).  r2 = radius * radius.
+ *   2 near        DESIRE_DIST_FINAL: q_{t_end - 1} < r2.
+ *                 DESIRE_DIST_MAX:   m < r2, with m = q_0, then for t = 1 .. t_end - 1: m = q_t where q_t > m or q_t is a NaN, else m.
+ *                 DESIRE_DIST_MEAN:  s / (float)t_end < radius, with s = 0.f, then for t = 0 .. t_end - 1: s = s + sqrtf(q_t).
+ *                 The comparison is strict and false for a NaN: a NaN is never near.
+ *   3 greedy pass for j = 0 .. K-1 the candidate is k = dev_order[a, j].  It is KEPT iff it is near no sample kept before it; otherwise it is OWNED by
+ *                 the first kept sample, in keeping order, that it is near.
+ *   4 order       dev_order_out[a, :] = the kept samples in keeping order, then the owned ones in processing order: a permutation whenever the
+ *                 input row is one.  dev_count[a] = the number kept, >= 1.  radius == 0: nothing is near, dev_order_out == dev_order, count K.
+ *                 An absent slot's zero rows coincide: for any radius > 0 its count is 1 and its order the input's -- no validity input needed.
+ *   5 mass        dev_mass [A, K] (may be NULL).  The weights w are desire_kde_nll's step 1 (NULL dev_score or any non-finite score of the agent:
+ *                 1.f / K; else m = max_j s_j, e_k = expf(s_k - m), w_k = e_k / sum_j e_j, sums in increasing k).  dev_mass[a, i], i < count =
+ *                 the sum of w over kept sample i and the samples it owns, in processing order from 0.f; 0.f for i >= count.
+ *   6 gather      dev_top_Y [A, n_top, T_pred, 2] and dev_top_score [A, n_top] (each may be NULL; dev_top_score needs dev_score): the rows / scores
+ *                 of the first n_top entries of dev_order_out, as desire_rank_samples gathers them.  When count < n_top the tail is the
+ *                 best-scored suppressed samples: always n_top distinct samples.
+ *   7 bad indices dev_order is read only through a range check: an agent whose row holds an index outside 0 .. K-1 gets count 0, the identity
+ *                 order and zero mass (its gather is the identity order's).  No case reads outside dev_Yhat.
+ * A result depends on its agent's rows, order and scores only -- not on the grid, the rest of the batch, DESIRE_FLAG_COMPACT_* or the state of the
+ * last desire_encode.  No atomics: bitwise reproducible.  One launch, stream-ordered, capturable, no host wait, no allocation and no scratch.
+ * LDS plan: one workgroup stages the frames it walks (F = 1 for DESIRE_DIST_FINAL, else t_end) of all K samples of a chunk of slots; one agent
+ * must fit: K * (8 * (F | 1) + 20) + 8 <= 61440 bytes -- e.g. (K 20, t_end 40), (K 130, t_end 9), (K 3, t_end 200), K up to 176 at t_end 40.
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing is launched: a metric outside 0 .. 2; a radius that is negative or not finite; a
+ * unit that is not finite and > 0; t_end outside 1 .. T_pred; n_top outside 1 .. K; a NULL dev_Yhat / dev_order / dev_order_out / dev_count;
+ * dev_top_score without dev_score; a NULL handle; a ref_compat handle; a (K, t_end) beyond the LDS plan. */
+#define DESIRE_DIST_FINAL 0   /* squared distance at frame t_end - 1 */
+#define DESIRE_DIST_MEAN  1   /* mean over t < t_end of the per-frame distance */
+#define DESIRE_DIST_MAX   2   /* largest per-frame squared distance over t < t_end */
+int desire_select_diverse(desire_handle* h, const float* dev_Yhat, const int32_t* dev_order, const float* dev_score,
+                          int32_t metric, int32_t t_end, float radius, float unit_x, float unit_y, int32_t n_top,
+                          int32_t* dev_order_out, int32_t* dev_count, float* dev_mass,
+                          float* dev_top_Y, float* dev_top_score, void* stream);
+
 /* ---- hipGraph capture: desire_graph_begin(h, stream); any stream-ordered desire_* calls on that stream (desire_forward,
  * desire_backward, desire_clip_grads, desire_ioc_step ...) ; desire_graph_end -> graph id; desire_graph_launch replays them with
  * the SAME device pointers.  For launch-bound shapes (small batches, the training step, the agent-sharded IOC loop).  Calls
