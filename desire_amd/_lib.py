@@ -25,7 +25,7 @@ EXPORTS = [
     "desire_graph_begin", "desire_graph_end", "desire_graph_launch", "desire_rollout", "desire_build_windows_la", "desire_adam_state",
     "desire_set_option", "desire_train_loss_async", "desire_set_head_loss",
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
-    "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse",
+    "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse", "desire_joint_metrics",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
 ]
 RNG_BITS, RNG_NORMAL, RNG_LATENT, RNG_ROLLOUT = 0, 1, 2, 3          # desire_rng_fill kinds (DESIRE_RNG_*)
@@ -100,6 +100,8 @@ def load() -> C.CDLL:
     lib.desire_ranked_errors.argtypes = [vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, f32p, vp]
     lib.desire_kde_nll.argtypes = [vp, f32p, f32p, f32p, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, f32p, f32p, vp]
     lib.desire_select_diverse.argtypes = [vp, f32p, vp, f32p, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, vp, f32p, f32p, f32p, vp]
+    lib.desire_joint_metrics.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, f32p, f32p,
+                                         vp, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
     lib.desire_rollout_samples.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
@@ -307,6 +309,21 @@ class Handle:
         _chk(self.lib.desire_select_diverse(self._h, yhat_ptr or None, order_ptr or None, score_ptr or None, int(metric), int(t_end), C.c_float(radius),
                                             C.c_float(unit_x), C.c_float(unit_y), int(n_top), order_out_ptr or None, count_ptr or None,
                                             mass_ptr or None, top_y_ptr or None, top_score_ptr or None, stream or None))
+
+    def joint_metrics(self, yhat_ptr: int, fut_ptr: int, present_ptr: int, score_ptr: int, horizons, n_top: int, radius: float, unit_x: float,
+                      unit_y: float, cnt_ptr: int, jorder_ptr: int, first_ptr: int = 0, jerr_ptr: int = 0, jscore_ptr: int = 0, out_ptr: int = 0,
+                      stream: int = 0) -> None:
+        """The K samples of a window as K joint futures: first [n, K + 1, mno] int32 = the first frame at which a slot comes within `radius` of
+        another slot of its (window, k) (T_pred: never; row K: the ground truth), cnt [n, K + 1, n_h, 2] int32 = (slots touching, slots taking
+        part) before each horizon, jerr [n, K, n_h, 2] = (JADE_h, JFDE_h), jscore [n, K] = the summed score, jorder [n, K] int32 = its order
+        (rank_samples' rule), out [n, n_h, 4] = (JADE, JFDE of the best-scored joint sample, best JADE, best JFDE among the n_top best-scored).
+        Exactly one of fut_ptr (evaluation) and present_ptr ([A] uint8, prediction time: no jerr / out); distances are scaled by (unit_x, unit_y)
+        as in ranked_errors."""
+        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+        _chk(self.lib.desire_joint_metrics(self._h, yhat_ptr or None, fut_ptr or None, present_ptr or None, score_ptr or None,
+                                           hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, int(n_top), C.c_float(radius), C.c_float(unit_x),
+                                           C.c_float(unit_y), first_ptr or None, cnt_ptr or None, jerr_ptr or None, jscore_ptr or None,
+                                           jorder_ptr or None, out_ptr or None, stream or None))
 
     def set_training(self, on: bool) -> None:
         _chk(self.lib.desire_set_training(self._h, int(on)))

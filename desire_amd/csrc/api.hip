@@ -211,6 +211,8 @@ extern "C" int desire_create(const desire_dims* dims, desire_handle** out) {
         {"rank_tab", d.ref_compat ? 0 : R * 16 * f}, {"rank_cnt", d.ref_compat ? 0 : A * 8 * sizeof(int32_t)},
         // desire_kde_nll: the K weights of every agent (the score layout) and its (den, h2), for the same reason
         {"kde_w", d.ref_compat ? 0 : R * f}, {"kde_st", d.ref_compat ? 0 : A * 2 * f},
+        // desire_joint_metrics: the K joint scores of every window and its (JADE_h, JFDE_h) for 8 horizons, for the calls that do not ask for them
+        {"joint_js", d.ref_compat ? 0 : (size_t)d.n_scenes * d.K * f}, {"joint_je", d.ref_compat ? 0 : (size_t)d.n_scenes * d.K * 16 * f},
     };
     if (int rc = ws_ensure(h, list)) { desire_destroy(h); return rc; }
     for (const WsItem& w : list) (void)hipMemset(W(h, w.n), 0, w.bytes);

@@ -289,6 +289,49 @@ extern "C" int desire_select_diverse(desire_handle* h, const float* dev_Yhat, co
     return DESIRE_OK;
 }
 
+// ---- the K samples of a window as K joint futures (kernels_joint.hip): the contract is stated in include/desire_hip.h ----
+extern "C" int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present,
+                                    const float* dev_score, const int32_t* host_horizons, int32_t n_h, int32_t n_top, float radius, float unit_x,
+                                    float unit_y, int32_t* dev_first, int32_t* dev_cnt, float* dev_jerr, float* dev_jscore, int32_t* dev_jorder,
+                                    float* dev_out, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_cnt) return fail(DESIRE_ERR_ARG, "dev_cnt is NULL");
+    if (!dev_jorder) return fail(DESIRE_ERR_ARG, "dev_jorder is NULL");
+    if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
+    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    if (!dev_fut && dev_jerr) return fail(DESIRE_ERR_ARG, "dev_jerr needs dev_fut (the errors are against the ground truth)");
+    if (!dev_fut && dev_out) return fail(DESIRE_ERR_ARG, "dev_out needs dev_fut (the errors are against the ground truth)");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read joint futures from");
+    if (n_top < 1 || n_top > d.K) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
+    if (n_h < 1 || n_h > 8) return fail(DESIRE_ERR_ARG, "n_h must be 1..8");
+    RankHz hz{};
+    hz.n = n_h;
+    for (int i = 0; i < n_h; ++i) {
+        hz.h[i] = host_horizons[i];
+        if (hz.h[i] < 1 || hz.h[i] > d.T_pred) return fail(DESIRE_ERR_ARG, "host_horizons[" + std::to_string(i) + "] must be 1..T_pred");
+        if (i && hz.h[i] <= hz.h[i - 1]) return fail(DESIRE_ERR_ARG, "host_horizons must be strictly increasing");
+    }
+    if (!std::isfinite(radius) || radius < 0.f) return fail(DESIRE_ERR_ARG, "radius must be finite and >= 0");
+    if (!std::isfinite(unit_x) || !(unit_x > 0.f)) return fail(DESIRE_ERR_ARG, "unit_x must be finite and > 0");
+    if (!std::isfinite(unit_y) || !(unit_y > 0.f)) return fail(DESIRE_ERR_ARG, "unit_y must be finite and > 0");
+    const bool errors = dev_jerr || dev_out;           // the per-agent table is desire_ranked_errors' own kernel's: its limit on T_pred comes with it
+    int sc = 0, kc = 0;
+    if (errors && !sample_errors_geometry(d.mno, d.K, d.T_pred, &sc, &kc))
+        return fail(DESIRE_ERR_ARG, "dev_jerr / dev_out: T_pred is too long for the error kernel's LDS (desire_ranked_errors' limit)");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (errors)
+        launch_sample_errors(dev_Yhat, dev_fut, W(h, "rank_tab"), Wt<int32_t>(h, "rank_cnt"), d.n_scenes, d.mno, d.K, d.T_pred, hz, d.sx, d.sy,
+                             unit_x, unit_y, s);
+    launch_joint_metrics(dev_Yhat, dev_fut, dev_present, dev_score, errors ? W(h, "rank_tab") : nullptr, dev_first, dev_cnt,
+                         errors ? (dev_jerr ? dev_jerr : W(h, "joint_je")) : nullptr, dev_jscore ? dev_jscore : W(h, "joint_js"), dev_jorder, dev_out,
+                         d.n_scenes, d.mno, d.K, d.T_pred, n_top, hz, d.sx, d.sy, unit_x, unit_y, radius, s);
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- the device generator (philox.h, kernels_rng.hip): the packing of its counters is stated in include/desire_hip.h ------------------------
 namespace {
 int rng_check_packing(const desire_ctx* h, uint32_t slot_base) {

@@ -257,6 +257,10 @@ bool sample_errors_geometry(int mno, int K, int T, int* SC, int* KC);      // fa
 void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order, float* tab, int32_t* cnt, float* out, int n_scenes, int mno,
                           int K, int T, int n_top, const RankHz& hz, float sx, float sy, float ux, float uy, hipStream_t s);
 
+// the table alone, for a caller that reduces it itself (desire_joint_metrics)
+void launch_sample_errors(const float* Y, const float* fut, float* tab, int32_t* cnt, int n_scenes, int mno, int K, int T, const RankHz& hz,
+                          float sx, float sy, float ux, float uy, hipStream_t s);
+
 // ---- KDE log-likelihood (kernels_kde.hip) ----
 bool kde_geometry(int T, int* SA);                         // agents per workgroup; false: one agent's T_pred frame values do not fit the LDS
 // w [R] (the score layout) and st [A, 2] = (den, h2) are scratch of the call (the handle's "kde_w" / "kde_st"); score and frame may be nullptr
@@ -270,6 +274,13 @@ bool select_geometry(int mno, int K, int metric, int t_end, int* SC, int* G);
 void launch_select_diverse(const float* Y, const int32_t* order, const float* score, int32_t* order_out, int32_t* count, float* mass, float* top_Y,
                            float* top_score, int n_scenes, int mno, int K, int T, int metric, int t_end, int n_top, float radius, float ux,
                            float uy, hipStream_t s);
+
+// ---- joint (scene-level) metrics of the K samples (kernels_joint.hip) ----
+int joint_chunk_frames(int mno, int T);                    // frames of a (window, k) unit that one pass of the LDS plan holds (T: no chunking)
+// exactly one of fut / present; score, tab (the filled "rank_tab"; with it jerr), first and out may be nullptr; jscore and jorder never
+void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* tab, int32_t* first,
+                          int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
+                          const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
 
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);

@@ -203,8 +203,9 @@ bool sample_errors_geometry(int mno, int K, int T, int* SC, int* KC) {
     return true;
 }
 
-void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order, float* tab, int32_t* cnt, float* out, int n_scenes, int mno,
-                          int K, int T, int n_top, const RankHz& hz, float sx, float sy, float ux, float uy, hipStream_t s) {
+// The table alone: tab [R, hz.n, 2] and cnt [A, hz.n] (desire_joint_metrics sums the same rows per (window, k)).
+void launch_sample_errors(const float* Y, const float* fut, float* tab, int32_t* cnt, int n_scenes, int mno, int K, int T, const RankHz& hz,
+                          float sx, float sy, float ux, float uy, hipStream_t s) {
     int SC = 1, KC = 1;
     if (!sample_errors_geometry(mno, K, T, &SC, &KC)) return;         // (refused by the caller before it gets here)
     const int n_sc = (mno + SC - 1) / SC, n_kc = (K + KC - 1) / KC;
@@ -212,6 +213,13 @@ void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order
     const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
     hipLaunchKernelGGL(k_sample_errors, dim3((unsigned)((size_t)n_scenes * n_sc * n_kc)), dim3(RK_THREADS), lds, s, Y, fut, tab, cnt, mno, K, T,
                        SC, KC, n_sc, n_kc, vec, sx, sy, ux, uy, hz);
+}
+
+void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order, float* tab, int32_t* cnt, float* out, int n_scenes, int mno,
+                          int K, int T, int n_top, const RankHz& hz, float sx, float sy, float ux, float uy, hipStream_t s) {
+    int SC = 1, KC = 1;
+    if (!sample_errors_geometry(mno, K, T, &SC, &KC)) return;         // (refused by the caller before it gets here)
+    launch_sample_errors(Y, fut, tab, cnt, n_scenes, mno, K, T, hz, sx, sy, ux, uy, s);
     const size_t n = (size_t)n_scenes * mno * hz.n;
     hipLaunchKernelGGL(k_ranked_pick, dim3((unsigned)((n + RK_THREADS - 1) / RK_THREADS)), dim3(RK_THREADS), 0, s, tab, cnt, order, out,
                        n_scenes * mno, mno, K, hz.n, n_top);

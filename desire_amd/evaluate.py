@@ -3,7 +3,8 @@ device, errors per horizon of the best-scored sample (top-1), of the best among 
 
     python -m desire_amd.evaluate --checkpoint save/social_model-400.npz --data_dir data/ --max_num_obj 32 --d_dim 128 \\
         --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json] \\
-        [--generator cvae|rollout] [--nll] [--select nms --nms_radius 20 [--nms_metric final|mean|max] [--nms_horizon 12]]
+        [--generator cvae|rollout] [--nll] [--select nms --nms_radius 20 [--nms_metric final|mean|max] [--nms_horizon 12]] \\
+        [--joint [--collision_radius 10]]
 
 The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
@@ -42,6 +43,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--nms_metric", type=str, default="final", choices=("final", "mean", "max"),
                    help="--select nms: the distance of two futures -- at the last frame, the mean over the frames, or the largest over the frames")
     p.add_argument("--nms_horizon", type=int, default=None, help="--select nms: frames the distance looks at (default: all of --pred_length)")
+    p.add_argument("--joint", action="store_true",
+                   help="also report the K samples of a window as K JOINT futures of the scene (desire_joint_metrics): JADE / JFDE per horizon of the "
+                        "joint sample with the best summed score and of the best among the top N, and the collision rate of the predicted joint futures "
+                        "next to the ground truth's under the same rule, see --collision_radius")
+    p.add_argument("--collision_radius", type=float, default=None,
+                   help="--joint: two agents closer than this many pixels in a frame touch (default: 0, nothing touches)")
     p.add_argument("--out", type=str, default=None, help="write the result JSON here (default: standard output only)")
     return p
 
@@ -96,6 +103,9 @@ def evaluate(args, data_loader=None, model=None) -> dict:
         raise ValueError("--select nms needs --nms_radius (pixels)")
     nms_kw = dict(select="nms", nms_radius=args.nms_radius, nms_metric=args.nms_metric, nms_horizon=args.nms_horizon) if nms else {}
     nms_sums, nms_count, nms_present = np.zeros((len(hz), 2), np.float64), 0, 0
+    joint = bool(getattr(args, "joint", False))
+    j_sums, j_windows = np.zeros((len(hz), 4), np.float64), np.zeros(len(hz), np.int64)
+    j_cnt = {k: np.zeros((len(hz), 2), np.int64) for k in ("top1", "all_K", "ground_truth")}      # (touching, taking part)
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
@@ -111,6 +121,15 @@ def evaluate(args, data_loader=None, model=None) -> dict:
         if nll:
             nll_u, fr = model.evaluate_nll(Y, score, fut, horizons=hz, units=units, log_floor=KDE_LOG_FLOOR, return_frames=True)
             nll_w = model.evaluate_nll(Y, score, fut, horizons=hz, units=units, weighted=True, log_floor=KDE_LOG_FLOOR)
+        if joint:                                    # per window: the call counts by the targets' ids alone
+            jm = model.evaluate_joint(Y, score, fut, top=top, horizons=hz, units=units, collision_radius=getattr(args, "collision_radius", None))
+            cnt = jm["cnt"].astype(np.int64)
+            takes = cnt[:, 0, :, 1] > 0                                                          # [n, n_h]
+            j_sums += np.where(takes[:, :, None], jm["out"].astype(np.float64), 0.0).sum(0)
+            j_windows += takes.sum(0)
+            j_cnt["top1"] += cnt[np.arange(cnt.shape[0]), jm["order"][:, 0]].sum(0)
+            j_cnt["all_K"] += cnt[:, :K].sum((0, 1))
+            j_cnt["ground_truth"] += cnt[:, K].sum(0)
         pw, fw = np.stack(past), np.stack(fut)
         mno = ranked.shape[0] // pw.shape[0]
         valid = np.zeros((pw.shape[0], mno), bool)
@@ -158,6 +177,13 @@ def evaluate(args, data_loader=None, model=None) -> dict:
             m = nll_sums[k] / np.maximum(agents, 1)[:, None]
             res["kde_nll"][k] = {"mean": [float(v) for v in m[:, 0]], "final": [float(v) for v in m[:, 1]]}
         res["kde_nll"].update({"floored_frames": nll_floored, "frames": nll_frames})
+    if joint:
+        m = j_sums / np.maximum(j_windows, 1)[:, None]
+        rate = {k: [float(v[i, 0] / max(int(v[i, 1]), 1)) for i in range(len(hz))] for k, v in j_cnt.items()}
+        res["joint"] = {"collision_radius_px": float(getattr(args, "collision_radius", None) or 0.0), "windows": [int(v) for v in j_windows],
+                        "top1": {"jade": [float(v) for v in m[:, 0]], "jfde": [float(v) for v in m[:, 1]]},
+                        "best_of_top": {"jade": [float(v) for v in m[:, 2]], "jfde": [float(v) for v in m[:, 3]]},
+                        "collision_rate": rate, "slots": [int(v) for v in j_cnt["ground_truth"][:, 1]]}
     return res
 
 

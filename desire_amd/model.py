@@ -516,7 +516,8 @@ class DESIREModel(object):
         if select == "score":
             return None
         if select != "nms":
-            raise ValueError("select must be 'score' (the best-scored samples) or 'nms' (score-ordered non-maximum suppression), got %r" % (select,))
+            raise ValueError("select must be 'score' (the best-scored samples), 'nms' (score-ordered non-maximum suppression) or 'joint' (the best-scored "
+                             "joint samples of the window), got %r" % (select,))
         if nms_radius is None:
             raise ValueError("select='nms' needs nms_radius (pixels)")
         metrics = {"final": _lib.DIST_FINAL, "mean": _lib.DIST_MEAN, "max": _lib.DIST_MAX}
@@ -529,18 +530,19 @@ class DESIREModel(object):
 
     def predict(self, x_batch: Sequence[np.ndarray], top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False,
                 window_base: int = 0, generator: str = "cvae", normals=None, select: str = "score", nms_radius=None, nms_metric: str = "final",
-                nms_horizon=None):
+                nms_horizon=None, collision_radius=None):
         """The `top` most plausible futures of every agent of a batch of observed loader windows [T_obs, MNO, 3], ranked by IOC score
         (prior sampling: no future given).  See predict_device for the result."""
         d = self._handle(len(x_batch), False).dims
         out = self.predict_device(self._pad_windows(x_batch, d.mno), top, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng,
                                   window_base=window_base, generator=generator, normals=normals, select=select, nms_radius=nms_radius,
-                                  nms_metric=nms_metric, nms_horizon=nms_horizon)
+                                  nms_metric=nms_metric, nms_horizon=nms_horizon, collision_radius=collision_radius)
         self.input_data, self.target_data = x_batch, None
         return out
 
     def predict_device(self, past, top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0,
-                       generator: str = "cvae", normals=None, select: str = "score", nms_radius=None, nms_metric: str = "final", nms_horizon=None):
+                       generator: str = "cvae", normals=None, select: str = "score", nms_radius=None, nms_metric: str = "final", nms_horizon=None,
+                       collision_radius=None):
         """predict() on windows already in HBM (forward_device's layout).  Returns a dict of device tensors: "traj" [n, mno, top, T_pred, 2]
         IN PIXELS, best-scored first; "score" [n, mno, top]; "order" [n, mno, K] int32 (sample indices by descending score, ties to the
         lower index); "present" [n, mno] bool (id != 0 at the last observed frame -- the rows of absent agents are whatever the forward
@@ -554,9 +556,19 @@ class DESIREModel(object):
         the last frame), "mean" (mean distance over the frames) or "max" (largest distance) over the first nms_horizon frames (None: all).
         "traj", "score" and "order" then follow the diverse order (the kept samples, then the suppressed ones best-scored first, so there are
         always `top` distinct samples), and the dict gains "count" [n, mno] int32 (samples kept) and "prob" [n, mno, top] (the softmax(score)
-        mass each returned sample absorbed; 0 for a suppressed one)."""
+        mass each returned sample absorbed; 0 for a suppressed one).
+        select "joint": sample k of every agent of a window was scored and refined together, so the K samples are K joint futures of the scene;
+        entry j of EVERY agent of a window is then joint sample jorder[j] -- the order of the scores summed over the present agents
+        (desire_joint_metrics, prediction form) -- instead of each agent's own best.  "traj", "score" and "order" keep their shapes ("order" is the
+        window's joint order repeated for every slot), and the dict gains "joint_score" [n, top] and "collisions" [n, top] int32: the present agents
+        of that joint sample that come within collision_radius pixels (None: 0, nothing touches) of another one at some frame."""
         torch = self.torch
-        nms = self._nms_args(select, nms_radius, nms_metric, None, 1)        # refuse a bad selection before the forward runs (the horizon: below)
+        joint = select == "joint"
+        if collision_radius is not None and not joint:
+            raise ValueError("collision_radius belongs to select='joint'")
+        if joint and collision_radius is not None and not (np.isfinite(float(collision_radius)) and float(collision_radius) >= 0):
+            raise ValueError("collision_radius must be finite and >= 0 (pixels), got %r" % (collision_radius,))
+        nms = None if joint else self._nms_args(select, nms_radius, nms_metric, None, 1)      # refuse a bad selection before the forward runs (the horizon: below)
         if generator == "cvae":
             if normals is not None:
                 raise ValueError("`normals` are the head rollout's draws: pass generator='rollout' with them")
@@ -577,6 +589,19 @@ class DESIREModel(object):
         traj = torch.empty((n, d.mno, top, d.T_pred, 2), device=self.device, dtype=torch.float32)
         sc = torch.empty((n, d.mno, top), device=self.device, dtype=torch.float32)
         stream = torch.cuda.current_stream().cuda_stream
+        if joint:
+            present = past[:, -1, :, 0] != 0
+            pres8 = present.to(torch.uint8).contiguous()
+            cnt = torch.empty((n, d.K + 1, 1, 2), device=self.device, dtype=torch.int32)
+            jscore = torch.empty((n, d.K), device=self.device, dtype=torch.float32)
+            jorder = torch.empty((n, d.K), device=self.device, dtype=torch.int32)
+            h.joint_metrics(Y.data_ptr(), 0, pres8.data_ptr(), score.data_ptr(), [d.T_pred], top, float(collision_radius or 0.0), 1.0 / d.sx, 1.0 / d.sy,
+                            cnt.data_ptr(), jorder.data_ptr(), 0, 0, jscore.data_ptr(), 0, stream)
+            idx = jorder[:, :top].long()                                     # [n, top]: the joint samples, best first
+            w = torch.arange(n, device=self.device)[:, None]
+            traj = (Y[w, idx].permute(0, 2, 1, 3, 4) / torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)).contiguous()
+            return {"traj": traj, "score": score[w, idx].permute(0, 2, 1).contiguous(), "order": jorder[:, None, :].expand(n, d.mno, d.K).contiguous(),
+                    "present": present, "joint_score": jscore[w, idx], "collisions": cnt[:, :d.K, 0, 0][w, idx]}
         if nms is None:
             h.rank_samples(score.data_ptr(), Y.data_ptr(), top, order.data_ptr(), traj.data_ptr(), sc.data_ptr(), stream)
             traj /= torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)
@@ -628,6 +653,37 @@ class DESIREModel(object):
             order = diverse
         h.ranked_errors(Y.data_ptr(), fut.data_ptr(), order.data_ptr(), top, hz, ux, uy, out.data_ptr(), stream)
         return (out.cpu().numpy(), count.cpu().numpy()) if return_count else out.cpu().numpy()
+
+    def evaluate_joint(self, Y, score, fut_windows, top: Optional[int] = None, horizons=None, units="px", collision_radius=None) -> dict:
+        """The K samples of every window as K JOINT futures of the scene (desire_joint_metrics).  Returns numpy arrays: "jerr" [n, K, n_h, 2] =
+        (JADE_h, JFDE_h): the mean over the agents that take part before the horizon of each agent's ADE_h / FDE_h under sample k; "jscore" [n, K] the
+        scores summed over the agents that take part; "order" [n, K] the joint samples by descending joint score; "out" [n, n_h, 4] = (JADE, JFDE
+        of the best-scored joint sample, best JADE, best JFDE among the `top` best-scored); "first" [n, K + 1, mno] int32 the first frame at which an
+        agent comes within collision_radius of another agent of the same joint sample (T_pred: never), row K being the ground truth under the same
+        rule; "cnt" [n, K + 1, n_h, 2] int32 = (agents touching, agents taking part) before each horizon -- the collision rate is cnt[..., 0] /
+        cnt[..., 1].  units, horizons, top and `fut_windows` as in evaluate_ranked; collision_radius in pixels, converted to the call's unit (units
+        "norm": along x); None: radius 0, nothing touches."""
+        torch = self.torch
+        n = int(Y.shape[0])
+        h = self._handles.get((n, 0, 0)) or self._handle(n, True)
+        d = h.dims
+        top = default_top(d.K) if top is None else int(top)
+        hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
+        r_px = 0.0 if collision_radius is None else float(collision_radius)
+        if units == "norm":
+            ux, uy, radius = 1.0, 1.0, r_px * d.sx
+        else:
+            f = 1.0 if units == "px" else float(units)
+            ux, uy, radius = f / d.sx, f / d.sy, r_px * f
+        fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
+        stream = torch.cuda.current_stream().cuda_stream
+        dev, i32 = self.device, torch.int32
+        res = {"jerr": torch.empty((n, d.K, len(hz), 2), device=dev), "out": torch.empty((n, len(hz), 4), device=dev),
+               "order": torch.empty((n, d.K), device=dev, dtype=i32), "jscore": torch.empty((n, d.K), device=dev),
+               "cnt": torch.empty((n, d.K + 1, len(hz), 2), device=dev, dtype=i32), "first": torch.empty((n, d.K + 1, d.mno), device=dev, dtype=i32)}
+        h.joint_metrics(Y.data_ptr(), fut.data_ptr(), 0, 0 if score is None else score.data_ptr(), hz, top, radius, ux, uy, res["cnt"].data_ptr(),
+                        res["order"].data_ptr(), res["first"].data_ptr(), res["jerr"].data_ptr(), res["jscore"].data_ptr(), res["out"].data_ptr(), stream)
+        return {k: v.cpu().numpy() for k, v in res.items()}
 
     def evaluate_nll(self, Y, score, fut_windows, horizons=None, units="px", weighted: bool = False, log_floor: float = _lib.KDE_LOG_FLOOR,
                      return_frames: bool = False):

@@ -416,6 +416,51 @@ int desire_select_diverse(desire_handle* h, const float* dev_Yhat, const int32_t
                           int32_t* dev_order_out, int32_t* dev_count, float* dev_mass,
                           float* dev_top_Y, float* dev_top_score, void* stream);
 
+/* ---- joint (scene-level) metrics: sample k of every agent of a window was scored and refined together (the IOC stage pools over the slots of
+ * one (window, k)), so the K samples of a window are K joint futures of the scene.  This call looks at them that way: does a joint future run
+ * its agents through each other, what is the error of the best SCENE sample (min over k of the mean over the agents: JADE / JFDE), and which
+ * joint sample does the summed score prefer.  Unless noted, layouts, the counting rule, g, the per-frame error e, ADE_h / FDE_h and
+ * host_horizons are desire_ranked_errors': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot, dev_fut [n_scenes, T_pred, mno, 3],
+ * g = (fut_x * sx, fut_y * sy) rounded once, host_horizons[n_h] strictly increasing, 1 .. T_pred, n_h <= 8, read at call time, by value.  All
+ * arithmetic is fp32, every operation rounded once (no fused multiply-add); no float atomics.
+ *   1 counted     exactly one of dev_fut and dev_present is non-NULL (both or neither: DESIRE_ERR_ARG).  With dev_fut: c(a, t) =
+ *                 dev_fut[scene, t, slot, 0] != 0 (evaluation).  With dev_present [A] uint8: c(a, t) = dev_present[a] != 0 for every t (prediction
+ *                 time, no future known); dev_jerr and dev_out must then be NULL.  A slot TAKES PART BEFORE h when it has a counted frame t < h.
+ *   2 distance    for slots i != j of one (window, k) and a frame t: a = (Y[r_i, t, 0] - Y[r_j, t, 0]) * unit_x; b = (Y[r_i, t, 1] - Y[r_j, t, 1]) *
+ *                 unit_y; q = a * a + b * b (symmetric in i, j bit for bit); r2 = radius * radius.  The pair TOUCHES at t iff c(i, t) && c(j, t) &&
+ *                 q < r2: strict, false for a NaN; radius 0: nothing touches.
+ *   3 truth       with dev_fut the same rule runs on the positions g(a, t) as a pseudo-sample k = K: the collision rate of the data under the
+ *                 rule the samples are held to.
+ *   4 first       dev_first [n_scenes, K + 1, mno] int32 (may be NULL) = the smallest t at which slot i touches any other slot; T_pred when there is
+ *                 none, and for a slot that is never counted.  Row K is the ground truth; with dev_present it is filled with T_pred.
+ *   5 counts      dev_cnt [n_scenes, K + 1, n_h, 2] int32 (required) = (slots with first < h, slots taking part before h).  The rate is the caller's
+ *                 division: the library writes integers only.  With dev_present row K is all zeros (no ground truth, nobody takes part).
+ *   6 errors      only with dev_fut.  dev_jerr [n_scenes, K, n_h, 2] (may be NULL) = (JADE_h, JFDE_h): the sum of ADE_h(a, k) -- of FDE_h(a, k) --
+ *                 over the slots taking part before h, in increasing slot from 0.f, divided by (float) their number; zeros when no slot takes part.
+ *                 ADE_h / FDE_h are the bits of desire_ranked_errors' table (the call fills it with that call's kernel and shares its scratch, so
+ *                 the two calls are ordered by the stream like any two calls on one handle).
+ *   7 score       dev_jscore [n_scenes, K] (may be NULL) = the sum of dev_score[r] over the slots taking part before T_pred, in increasing slot from
+ *                 0.f; all zeros when dev_score is NULL.  dev_jorder [n_scenes, K] int32 (required) = the order of the window's K joint scores under
+ *                 desire_rank_samples' rule exactly: IEEE >, ties to the lower k, NaNs last by index.  K has no limit of its own.
+ *   8 pick        dev_out [n_scenes, n_h, 4] (may be NULL; needs dev_fut) = (JADE_h, JFDE_h of sample jorder[0]; min over j < n_top of JADE_h, and
+ *                 separately of JFDE_h, over the samples jorder[j]); the minimum keeps a NaN; four zeros where nobody takes part.  1 <= n_top <= K.
+ * At mno = 1 and n_top = K, dev_out is desire_ranked_errors' dev_out and dev_jorder desire_rank_samples' order wherever the slot takes part.
+ * A window's results depend on that window's rows, scores and targets only -- not on the grid, the batch or DESIRE_FLAG_COMPACT_*; bitwise
+ * reproducible (`first` is an integer minimum, every float sum one fixed sequence).  Stream-ordered, capturable, no host wait, no allocation: the
+ * scratch was allocated by desire_create.  LDS plan: one workgroup owns one (window, k) and stages its positions as float2 [frame][slot] (frame
+ * stride mno + 1 pairs from 32 slots on, mno below) next to 8 mno bytes of per-slot integers, 61440 bytes in all; when mno * T_pred positions do not
+ * fit (256 slots x 40 frames = 82 KB) it walks the frames in chunks of (61440 - 8 mno) / (8 stride) frames -- 28 at 256 slots -- carrying `first`
+ * across them, with the bits of an unchunked walk.  Every (mno, T_pred) of a handle is served; only dev_jerr / dev_out inherit desire_ranked_errors'
+ * limit on T_pred (about 3800 frames).
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing is launched or written: a NULL handle / dev_Yhat / dev_cnt / dev_jorder /
+ * host_horizons; bad horizons; n_top outside 1 .. K; a radius that is negative or not finite; a unit that is not finite and > 0; both or neither
+ * of dev_fut / dev_present; dev_jerr or dev_out without dev_fut; a ref_compat handle. */
+int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present,
+                         const float* dev_score, const int32_t* host_horizons, int32_t n_h, int32_t n_top,
+                         float radius, float unit_x, float unit_y,
+                         int32_t* dev_first, int32_t* dev_cnt, float* dev_jerr, float* dev_jscore, int32_t* dev_jorder,
+                         float* dev_out, void* stream);
+
 /* ---- hipGraph capture: desire_graph_begin(h, stream); any stream-ordered desire_* calls on that stream (desire_forward,
  * desire_backward, desire_clip_grads, desire_ioc_step ...) ; desire_graph_end -> graph id; desire_graph_launch replays them with
  * the SAME device pointers.  For launch-bound shapes (small batches, the training step, the agent-sharded IOC loop).  Calls
