@@ -27,9 +27,12 @@ EXPORTS = [
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
     "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse", "desire_joint_metrics",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
+    "desire_set_recon_loss", "desire_recon_weights",
 ]
 RNG_BITS, RNG_NORMAL, RNG_LATENT, RNG_ROLLOUT = 0, 1, 2, 3          # desire_rng_fill kinds (DESIRE_RNG_*)
 DIST_FINAL, DIST_MEAN, DIST_MAX = 0, 1, 2                           # desire_select_diverse metrics (DESIRE_DIST_*)
+RECON_MEAN, RECON_MIN, RECON_SOFTMIN = 0, 1, 2                      # desire_set_recon_loss / desire_recon_weights modes (DESIRE_RECON_*)
+RECON_MODES = {"mean": RECON_MEAN, "min": RECON_MIN, "softmin": RECON_SOFTMIN}      # their names on the Python surface (args.recon_loss, --recon_loss)
 KDE_LOG_FLOOR = -20.0                                               # desire_kde_nll: the clip of a frame's log-density (Trajectron++'s)
 
 
@@ -111,6 +114,8 @@ def load() -> C.CDLL:
     lib.desire_train_loss.argtypes = [vp, f32p, C.POINTER(C.c_float), vp]
     lib.desire_train_loss_async.argtypes = [vp, f32p, f32p, vp]
     lib.desire_set_head_loss.argtypes = [vp, C.c_float]
+    lib.desire_set_recon_loss.argtypes = [vp, i32, C.c_float]
+    lib.desire_recon_weights.argtypes = [vp, f32p, f32p, i32, C.c_float, f32p, f32p, vp, f32p, vp]
     lib.desire_peer_export.argtypes = [vp, C.c_char_p, C.POINTER(C.c_size_t)]
     lib.desire_peer_open.argtypes = [vp, i32, i32, i32, C.c_char_p]
     lib.desire_ioc_peer_pass.argtypes = [vp, f32p, f32p, vp]
@@ -434,6 +439,19 @@ class Handle:
     def set_head_loss(self, weight: float) -> None:
         """Weight of the reference's Gaussian-NLL term for the 5-wide output layer (model/model.py:494-550) in the training loss."""
         _chk(self.lib.desire_set_head_loss(self._h, C.c_float(float(weight))))
+
+    def set_recon_loss(self, mode: int, tau: float = 0.0) -> None:
+        """The reconstruction term of the training loss over the K samples: RECON_MEAN (default, the paper's mean), RECON_MIN (best-of-many: only
+        the sample with the smallest error carries the gradient) or RECON_SOFTMIN (a soft-min at temperature tau > 0, normalised units)."""
+        _chk(self.lib.desire_set_recon_loss(self._h, int(mode), C.c_float(float(tau))))
+
+    def recon_weights(self, fut_ptr: int, yhat_ptr: int, mode: int, tau: float = 0.0, e_ptr: int = 0, w_ptr: int = 0, winner_ptr: int = 0,
+                      recon_ptr: int = 0, stream: int = 0) -> None:
+        """Per-sample reconstruction errors e [A, K] of yhat [R, T_pred, 2] against fut, the weights w [A, K] the mode gives the K samples, the
+        sample with the smallest error winner [A] int32 and the mode's term recon [A]; each output is optional (0: kept in the workspace tensor
+        "recon_e" / "recon_w" / "recon_win" / "recon_val").  Masking as in losses()."""
+        _chk(self.lib.desire_recon_weights(self._h, fut_ptr or None, yhat_ptr or None, int(mode), C.c_float(float(tau)), e_ptr or None, w_ptr or None,
+                                           winner_ptr or None, recon_ptr or None, stream or None))
 
     def train_loss_async(self, fut_ptr: int, out8_ptr: int, stream: int = 0) -> None:
         """The loss terms of the last training-mode forward into a device buffer of 8 floats, no synchronisation (see loss_terms)."""

@@ -193,7 +193,14 @@ int loss_grads(const BwdPass& bp) {
     // target frame (model/model.py:351-366).  `valid` (presence at the last observed frame) stays what social pooling uses.
     launch_loss_mask(Wt<const uint8_t>(h, "valid"), bp.fut, Wt<uint8_t>(h, "lmask"), W(h, "nfut"), d.n_scenes, d.mno, d.T_pred, s);
     launch_count_valid(bp.valid, h->A, W(h, "nvalid"), s);
-    launch_loss_grad_y(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred, d.sx, d.sy, s);
+    if (h->recon_mode == DESIRE_RECON_MEAN) {
+        launch_loss_grad_y(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred, d.sx, d.sy, s);
+    } else {          // best-of-many / soft-min (desire_set_recon_loss): the weights of the K samples on the full layout, then the weighted gradient
+        launch_recon_weights(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "recon_e"), W(h, "recon_w"), Wt<int32_t>(h, "recon_win"), W(h, "recon_val"),
+                             d.n_scenes, d.mno, d.K, d.T_pred, h->recon_mode, h->recon_tau, d.sx, d.sy, s);
+        launch_loss_grad_y_w(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "recon_w"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred,
+                             d.sx, d.sy, s);
+    }
     if (bp.rows_compact) launch_gather_rows(W(h, "dY0"), W(h, "cp_dY0"), bp.amap, bp.n_present, d.K, d.mno, d.T_pred * 2, s);
     return DESIRE_OK;
 }
@@ -397,7 +404,7 @@ int mask_bwd(const BwdPass& bp) {
     const int H = d.H, V = h->V;
     const long Rs = bp.rows_s;
     Timer t(h, s, "bwd_mask");
-    launch_mask_bwd(W(h, "mask_sv_p"), W(h, "dxz"), bp.Hx_s, 2 * H, W(h, "dq_mask"), bp.dHx_s, (int)Rs, H, h->Hl, d.K, bp.mno_s, s);
+    launch_mask_bwd(W(h, "mask_sv_p"), W(h, "dxz"), bp.Hx_s, 2 * H, W(h, "dq_mask"), bp.dHx_s, (int)Rs, H, h->Hl, d.K, bp.mno_s, h->recon_mode != DESIRE_RECON_MEAN, s);
     colsum(h, W(h, "dq_mask"), H, Rs, H, G(h, "mask_fc/b"), 0, s);
     tn(h, W(h, "xhat"), V, W(h, "dq_mask"), H, Rs, V, H, G(h, "mask_fc/w"), H, 0, s);
     GemmArgs g{};

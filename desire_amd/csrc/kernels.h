@@ -282,10 +282,20 @@ void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* prese
                           int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
                           const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
 
+// ---- per-sample reconstruction errors and the best-of-many / soft-min weights (kernels_recon.hip) ----
+// slots per workgroup and samples per pass; false: one row of T_pred positions with its targets does not fit the LDS (7680 frames fit)
+bool recon_geometry(int mno, int K, int T, int* SC, int* KC);
+// lmask / nfut: launch_loss_mask's; e, w [A, K], win [A], val [A] are all written (none may be nullptr); mode = DESIRE_RECON_*; no scratch
+void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
+                          int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s);
+
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);
 void launch_loss_grad_y(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, const float* nvalid, float* dY,
                         int n_scenes, int mno, int K, int T, float sx, float sy, hipStream_t s);
+// the same with the weight w [A, K] of launch_recon_weights in place of 1 / K (desire_set_recon_loss, modes MIN and SOFTMIN)
+void launch_loss_grad_y_w(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, const float* nvalid, const float* w, float* dY,
+                          int n_scenes, int mno, int K, int T, float sx, float sy, hipStream_t s);
 struct DecBwdArgs {
     const float* dY0;                                      // [R,T,nw]: per-step gradient w.r.t. the head's outputs (nullptr: none)
     int nw;                                                // width of that head: 0 / 2 = the decoder's (x, y) head [H,2]; 5 = the Gaussian head [H,5]
@@ -318,7 +328,7 @@ void launch_bin_lists(const unsigned long long* flags, long M, int B, int* count
 int gemm_tn_big_tiles(const TnArgs& a);                      // workgroups per slice of the 128 x 128 / 256 x 64 forms (0: another form)
 void launch_colsum(const float* G, int ldg, long M, int N, int nslices, float* partial, float* out, int accumulate, hipStream_t s);
 void launch_mask_bwd(const float* p, const float* dxz, const float* Hx, int ldhx, float* dq, float* dHx_rows, int R, int H,
-                     int Hl, int K, int mno, hipStream_t s);
+                     int Hl, int K, int mno, bool centred, hipStream_t s);   // centred: the form for the min / soft-min reconstruction modes
 struct ConvWgradArgs { const float* S; int Cs; int Ps; const float* Lg; int Cl; int Pl; int stride; int pad; int n; float* partial; int np; };
 void launch_conv_wgrad(const ConvWgradArgs& a, int nslices, float* out, hipStream_t s);
 void launch_w1ch_grad(const float* Lg, const float* S, int n, int nslices, float* partial, float* out, hipStream_t s);

@@ -59,6 +59,32 @@ void launch_loss_grad_y(const float* Y, const float* fut, const uint8_t* valid, 
                        mno, K, T, sx, sy);
 }
 
+// ---- the same under desire_set_recon_loss (MIN / SOFTMIN): the sample's weight w[a, k] (k_recon_weights; a constant of the backward pass) in
+// place of 1 / K:  lmask(a) present(a,t) w(a,k) / (N nfut(a)) * (Y0 - gt) / ||Y0 - gt|| ------------------------------
+__global__ void k_loss_grad_y_w(const float* __restrict__ Y, const float* __restrict__ fut, const uint8_t* __restrict__ valid,
+                                const float* __restrict__ nfut, const float* __restrict__ nvalid, const float* __restrict__ w,
+                                float* __restrict__ dY, int n_scenes, int mno, int K, int T, float sx, float sy) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long R = (long)n_scenes * K * mno;
+    if (i >= R * T) return;
+    const int t = i % T;
+    const long r = i / T;
+    const int slot = r % mno, sc = r / ((long)K * mno), k = (r / mno) % K;
+    const int a = sc * mno + slot;
+    const float* f = fut + (((size_t)sc * T + t) * mno + slot) * 3;
+    const float dx = Y[i * 2] - __fmul_rn(f[1], sx), dy = Y[i * 2 + 1] - __fmul_rn(f[2], sy);
+    const float nrm = sqrtf(dx * dx + dy * dy);
+    const float g = (valid[a] && f[0] != 0.f && nrm > 0.f) ? w[(size_t)a * K + k] / (nvalid[0] * nfut[a] * nrm) : 0.f;
+    dY[i * 2] = g * dx;
+    dY[i * 2 + 1] = g * dy;
+}
+void launch_loss_grad_y_w(const float* Y, const float* fut, const uint8_t* valid, const float* nfut, const float* nvalid, const float* w, float* dY,
+                          int n_scenes, int mno, int K, int T, float sx, float sy, hipStream_t s) {
+    const long n = (long)n_scenes * K * mno * T;
+    hipLaunchKernelGGL(k_loss_grad_y_w, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Y, fut, valid, nfut, nvalid, w, dY, n_scenes,
+                       mno, K, T, sx, sy);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Decoder BPTT.  Tile = 32 rows, wave cb owns hidden columns [32cb, 32cb+32).  Per reverse step:
 //   dh_t   = dh_{t}(from t+1) + dY0_t Wo^T
@@ -797,7 +823,13 @@ void launch_colsum(const float* G, int ldg, long M, int N, int nslices, float* p
 // mask fc backward (forward: q = xhat Wm + bm, p = relu(q), beta = softmax(p), xz = beta * Hx):
 //   dbeta = dxz * Hx;  dHx_rows += dxz * beta;  dp = beta * (dbeta - sum(beta dbeta));  dq = dp * (p > 0)
 // 4 threads per row, like the forward softmax.
+// CENTRED (the min / soft-min reconstruction modes): the same dp with dbeta taken relative to c = dbeta at the row's largest p,
+//   dp = beta * ((dbeta - c) - sum(beta (dbeta - c))),
+// which is the same number for any c (sum(beta) = 1).  Where one beta is within 1e-4 of 1 -- the rows the hard min selects, as a rule --
+// dbeta - sum(beta dbeta) at that column cancels to 1e-4 of its operands and the plain form keeps three digits of dp; centred, that
+// column's term of the sum is exactly 0 and nothing cancels.  The plain form stays as it is for the mean: its bits are the default's.
 // ------------------------------------------------------------------------------------------------------------------
+template <bool CENTRED>
 __global__ __launch_bounds__(256) void k_mask_bwd(const float* __restrict__ p, const float* __restrict__ dxz,
                                                   const float* __restrict__ Hx, int ldhx, float* __restrict__ dq,
                                                   float* __restrict__ dHx_rows, int R, int H, int Hl, int K, int mno) {
@@ -818,6 +850,21 @@ __global__ __launch_bounds__(256) void k_mask_bwd(const float* __restrict__ p, c
     for (int j = 0; j < 16; ++j)
         if (j < nv) mx = fmaxf(mx, fmaxf(fmaxf(pv[j].x, pv[j].y), fmaxf(pv[j].z, pv[j].w)));
     mx = fmaxf(mx, __shfl_xor(mx, 1)); mx = fmaxf(mx, __shfl_xor(mx, 2));
+    float ctr = 0.f;
+    if (CENTRED) {                                            // the largest dbeta among the logical columns that attain the row's largest p
+        ctr = -3.0e38f;
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (j < nv) {
+                const int c0 = 16 * j + 4 * q4;
+                if (pv[j].x == mx && c0 < Hl) ctr = fmaxf(ctr, gv[j].x * hv[j].x);
+                if (pv[j].y == mx && c0 + 1 < Hl) ctr = fmaxf(ctr, gv[j].y * hv[j].y);
+                if (pv[j].z == mx && c0 + 2 < Hl) ctr = fmaxf(ctr, gv[j].z * hv[j].z);
+                if (pv[j].w == mx && c0 + 3 < Hl) ctr = fmaxf(ctr, gv[j].w * hv[j].w);
+            }
+        ctr = fmaxf(ctr, __shfl_xor(ctr, 1)); ctr = fmaxf(ctr, __shfl_xor(ctr, 2));
+        if (!(ctr > -3.0e38f)) ctr = 0.f;                     // no such column (the largest p in the padding, or NaN): the plain form
+    }
     float sum = 0.f, dot = 0.f;
 #pragma unroll
     for (int j = 0; j < 16; ++j)
@@ -827,8 +874,13 @@ __global__ __launch_bounds__(256) void k_mask_bwd(const float* __restrict__ p, c
             e.x = expf(pv[j].x - mx); e.y = expf(pv[j].y - mx); e.z = expf(pv[j].z - mx); e.w = expf(pv[j].w - mx);
             sum += (c0 < Hl ? e.x : 0.f) + (c0 + 1 < Hl ? e.y : 0.f) + (c0 + 2 < Hl ? e.z : 0.f) + (c0 + 3 < Hl ? e.w : 0.f);   // padded columns are not in the softmax
             pv[j].x = pv[j].x > 0.f ? 1.f : 0.f; pv[j].y = pv[j].y > 0.f ? 1.f : 0.f; pv[j].z = pv[j].z > 0.f ? 1.f : 0.f; pv[j].w = pv[j].w > 0.f ? 1.f : 0.f;   // relu'
-            dot += e.x * gv[j].x * hv[j].x + e.y * gv[j].y * hv[j].y + e.z * gv[j].z * hv[j].z + e.w * gv[j].w * hv[j].w;
+            if (!CENTRED) dot += e.x * gv[j].x * hv[j].x + e.y * gv[j].y * hv[j].y + e.z * gv[j].z * hv[j].z + e.w * gv[j].w * hv[j].w;
             hv[j].x *= gv[j].x; hv[j].y *= gv[j].y; hv[j].z *= gv[j].z; hv[j].w *= gv[j].w;                                     // dbeta = dxz * Hx
+            if (CENTRED) {                                    // dbeta - c; the padded columns (dq = 0 there: p = 0) stay out of the sum
+                hv[j].x = c0 < Hl ? hv[j].x - ctr : 0.f; hv[j].y = c0 + 1 < Hl ? hv[j].y - ctr : 0.f;
+                hv[j].z = c0 + 2 < Hl ? hv[j].z - ctr : 0.f; hv[j].w = c0 + 3 < Hl ? hv[j].w - ctr : 0.f;
+                dot += e.x * hv[j].x + e.y * hv[j].y + e.z * hv[j].z + e.w * hv[j].w;
+            }
             gv[j].x *= e.x; gv[j].y *= e.y; gv[j].z *= e.z; gv[j].w *= e.w;                                                     // dxz * exp(p - max)
             // (pv = relu mask, hv = dbeta, gv = dxz * e, and e itself is gv / dxz: keep e in a register set of its own)
             pv[j].x *= e.x; pv[j].y *= e.y; pv[j].z *= e.z; pv[j].w *= e.w;                                                     // mask * e
@@ -855,8 +907,9 @@ __global__ __launch_bounds__(256) void k_mask_bwd(const float* __restrict__ p, c
     }
 }
 void launch_mask_bwd(const float* p, const float* dxz, const float* Hx, int ldhx, float* dq, float* dHx_rows, int R, int H,
-                     int Hl, int K, int mno, hipStream_t s) {
-    hipLaunchKernelGGL(k_mask_bwd, dim3((R + 63) / 64), dim3(256), 0, s, p, dxz, Hx, ldhx, dq, dHx_rows, R, H, Hl, K, mno);
+                     int Hl, int K, int mno, bool centred, hipStream_t s) {
+    if (centred) hipLaunchKernelGGL(k_mask_bwd<true>, dim3((R + 63) / 64), dim3(256), 0, s, p, dxz, Hx, ldhx, dq, dHx_rows, R, H, Hl, K, mno);
+    else hipLaunchKernelGGL(k_mask_bwd<false>, dim3((R + 63) / 64), dim3(256), 0, s, p, dxz, Hx, ldhx, dq, dHx_rows, R, H, Hl, K, mno);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

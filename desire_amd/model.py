@@ -23,6 +23,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+from ._lib import RECON_MODES
 from .spec import Dims, init_weights, weight_shapes
 
 
@@ -372,6 +373,7 @@ class DESIREModel(object):
             if pending is not None:                   # resumed run: Adam moments and step counter of the checkpoint
                 h.set_opt_state(pending)
             self._configure_head_loss(h)
+            self._configure_recon_loss(h)
         self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
         past, fut, eps_t = self._keep
         stream = torch.cuda.current_stream().cuda_stream
@@ -402,6 +404,17 @@ class DESIREModel(object):
         if lam > 0.0 and hasattr(h, "set_head_loss"):
             h.set_head_loss(lam)
             self._head_given = True                   # the head is trained from now on: sample(mode="rollout") reads learned weights
+
+    def _configure_recon_loss(self, h) -> None:
+        """Hook of the reconstruction term over the K samples (args.recon_loss = "mean" | "min" | "softmin", args.recon_tau)."""
+        mode = str(getattr(self.args, "recon_loss", None) or "mean")
+        if mode not in RECON_MODES:
+            raise ValueError("args.recon_loss must be one of %s, got %r" % (", ".join(RECON_MODES), mode))
+        if mode != "mean":
+            tau = getattr(self.args, "recon_tau", None)
+            if mode == "softmin" and tau is None:
+                raise ValueError("args.recon_loss = 'softmin' needs args.recon_tau > 0")
+            h.set_recon_loss(RECON_MODES[mode], float(tau) if mode == "softmin" else 0.0)
 
     def sync_weights(self) -> Dict[str, np.ndarray]:
         """Pull the trained weights back from the device; other handles (batch sizes / prior path) are rebuilt lazily."""

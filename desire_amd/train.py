@@ -25,6 +25,8 @@ from typing import Callable, List, Sequence, Tuple
 
 import numpy as np
 
+from ._lib import RECON_MODES
+
 
 def _noise(args, step: int, rank: int, world: int) -> dict:
     """Where a training step's latent noise comes from: torch.randn seeded per (step, rank), or with --device_rng the device generator seeded per
@@ -90,6 +92,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="weight of the reference's own loss for the 5-wide Gaussian output layer (model/model.py:494-550: -log N(next position | "
                         "mux, muy, sx, sy, rho), teacher-forced over the observed frames) added to the training loss; > 0 trains gauss_head/w|b "
                         "(and the X encoder through it), i.e. what sample(mode='rollout') reads")
+    p.add_argument("--recon_loss", type=str, default="mean", choices=list(RECON_MODES),
+                   help="the reconstruction term over the K samples: mean (the paper's, default), min (best-of-many: only the sample closest to the "
+                        "observed future carries the reconstruction gradient) or softmin (a soft-min at temperature --recon_tau); KL and the IOC "
+                        "terms keep their mean over K")
+    p.add_argument("--recon_tau", type=float, default=None,
+                   help="temperature of --recon_loss softmin in normalised units, > 0 (large: the mean, small: the min); required for softmin")
     p.add_argument("--prefetch", type=int, default=2,
                    help="batches the loader thread keeps in flight (pinned staging -> copy stream -> device; desire_amd/prefetch.py); 0 = the "
                         "reference's serial loop: next_batch, copy, step, read the loss, every step (train.py:131-183)")
@@ -108,6 +116,31 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--eval_horizons", type=str, default=None,
                    help="horizons of the ranked report in frames, comma separated and increasing, e.g. 3,6,9,12 (default: quarters of --pred_length)")
     return p
+
+
+def check_recon_args(args) -> None:
+    """--recon_loss / --recon_tau: softmin needs a finite temperature > 0; a temperature without softmin is a mistake, not a default."""
+    mode = getattr(args, "recon_loss", "mean") or "mean"
+    tau = getattr(args, "recon_tau", None)
+    if mode not in RECON_MODES:
+        raise ValueError("--recon_loss must be one of %s, got %r" % (", ".join(RECON_MODES), mode))
+    if mode == "softmin":
+        if tau is None:
+            raise ValueError("--recon_loss softmin needs --recon_tau")
+        if not (np.isfinite(float(tau)) and float(tau) > 0.0):
+            raise ValueError("--recon_tau must be finite and > 0, got %r" % (tau,))
+    elif tau is not None:
+        raise ValueError("--recon_tau is the temperature of --recon_loss softmin (got --recon_loss %s)" % mode)
+
+
+def step_line(args, step: int, total: int, epoch: int, terms: dict, dt: float) -> str:
+    """The per-step log line (train.py:185-190); with --recon_loss min / softmin it also names the mode and prints the term that is trained."""
+    line = "{}/{} (epoch {}), train_loss = {:.3f}, time/batch = {:.3f}".format(step, total, epoch, terms["loss"], dt)
+    mode = getattr(args, "recon_loss", "mean") or "mean"
+    if mode != "mean":
+        tag = "softmin tau={:g}".format(float(args.recon_tau)) if mode == "softmin" else mode
+        line += ", recon[{}] = {:.5f}".format(tag, terms["recon"])
+    return line
 
 
 def parse_horizons(text, t_pred: int) -> List[int]:
@@ -174,6 +207,7 @@ def train(args, data_loader=None, model=None, log: Callable[[str], None] = print
     from .model import DESIREModel
     import torch.distributed as dist
 
+    check_recon_args(args)
     if args.pred_length is None:
         args.pred_length = args.seq_length
     t_obs, t_pred = int(args.seq_length), int(args.pred_length)
@@ -220,9 +254,8 @@ def train(args, data_loader=None, model=None, log: Callable[[str], None] = print
             losses.append(terms["loss"])
             steps += 1
             if rank == 0:
-                log("{}/{} (epoch {}), train_loss = {:.3f}, time/batch = {:.3f}".format(
-                    epoch * data_loader.num_batches + batch, args.num_epochs * data_loader.num_batches, epoch,
-                    terms["loss"], time.time() - start))
+                log(step_line(args, epoch * data_loader.num_batches + batch, args.num_epochs * data_loader.num_batches, epoch, terms,
+                              time.time() - start))
                 sys.stdout.flush()
             if rank == 0 and should_save(epoch, batch, data_loader.num_batches, args.save_every):
                 path = os.path.join(args.save_dir, "social_model-%d.npz" % (epoch * data_loader.num_batches + batch))
@@ -327,8 +360,7 @@ def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred,
         terms, epoch, batch, start = p[0].get(), p[1], p[2], p[3]
         losses.append(terms["loss"])
         if rank == 0:
-            log("{}/{} (epoch {}), train_loss = {:.3f}, time/batch = {:.3f}".format(
-                epoch * nb + batch, args.num_epochs * nb, epoch, terms["loss"], time.time() - start))
+            log(step_line(args, epoch * nb + batch, args.num_epochs * nb, epoch, terms, time.time() - start))
             sys.stdout.flush()
 
     steps = 0
@@ -367,6 +399,10 @@ def main(argv=None) -> None:
     args = build_parser().parse_args(argv)
     if args.skip_padding and args.keep_padding:
         raise SystemExit("--skip_padding and --keep_padding exclude each other")
+    try:
+        check_recon_args(args)
+    except ValueError as exc:
+        raise SystemExit(str(exc))
     # (dims.flags are derived in desire_amd/model.py: _flags_from_args -- padding skipped unless --keep_padding)
     import torch
     import torch.distributed as dist

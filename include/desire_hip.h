@@ -531,6 +531,41 @@ int desire_set_training(desire_handle* h, int enable);
  * also fills the gradients of "gauss_head/w|b" -- the head desire_rollout / sample() read, which no other term reaches -- and adds
  * the term's gradient to the X encoder's, step by step.  weight = 0 (default) switches the term off. */
 int desire_set_head_loss(desire_handle* h, float weight);
+/* ---- best-of-many / soft-min reconstruction term.  The sample-generation loss of the paper averages the K samples' errors, which pulls every
+ * sample toward the one observed future; letting the best sample (Bhattacharyya et al. 2018's best-of-many objective, Social-GAN's variety loss)
+ * or a soft-min over the samples carry the reconstruction gradient keeps the K samples apart.  Layouts, the counting rule and g are
+ * desire_ranked_errors': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot, dev_fut [n_scenes, T_pred, mno, 3], g_t =
+ * (fut_x * sx, fut_y * sy) rounded once; frame t COUNTS when dev_fut[scene, t, slot, 0] != 0; nfut[a] = the number of counted frames and lmask[a] =
+ * present at the last observed frame (the handle's "valid", left by the last desire_encode / desire_forward) && nfut[a] > 0, as in desire_losses.
+ * All arithmetic is fp32, every operation rounded once (no fused multiply-add); expf / logf are the device library's.
+ *   1 error       e[a, k] = (sum over the counted t, in increasing t from 0.f, of sqrtf(dx * dx + dy * dy)) / nfut[a], dx = Y[r_k, t, 0] - g_t.x,
+ *                 dy = Y[r_k, t, 1] - g_t.y; e[a, k] = 0 where lmask[a] = 0.
+ *   2 winner      a walk in increasing k: winner = 0, m = e[a, 0]; k replaces it when e[a, k] < m (strict: ties stay with the lower k) or when m
+ *                 is a NaN and e[a, k] is not (a NaN never wins against a number).  The walk is the same in every mode.
+ *   3 weights     DESIRE_RECON_MEAN:    w[a, k] = 1.f / K;                 recon[a] = (sum of e[a, k] in increasing k from 0.f) / K.
+ *                 DESIRE_RECON_MIN:     w[a, k] = k == winner ? 1.f : 0.f; recon[a] = m.
+ *                 DESIRE_RECON_SOFTMIN: x_k = expf(-(e[a, k] - m) / tau); S = the sum of x_k in increasing k from 0.f; w[a, k] = x_k / S;
+ *                                       recon[a] = m - tau * logf(S / K).  tau is in normalised units; tau -> inf is MEAN, tau -> 0 is MIN, and
+ *                                       d recon / d e_k = w_k exactly, so w is a constant of the backward pass.
+ * desire_recon_weights is the stand-alone op: dev_e [A, K], dev_w [A, K], dev_winner [A] int32, dev_recon [A]; each may be NULL (it then goes to
+ * the workspace tensor "recon_e" / "recon_w" / "recon_win" / "recon_val"), and what is written does not depend on which are.  It needs no training
+ * mode.  Stream-ordered, no host wait, no atomics, no scratch: bitwise reproducible; the first call allocates the four workspace tensors, later
+ * calls are capturable.  A result depends on its agent's rows and targets only -- not on the grid, the batch or DESIRE_FLAG_COMPACT_*.  K has no
+ * limit; one row of T_pred positions with its targets must fit the kernel's LDS (T_pred <= 7680).  DESIRE_ERR_ARG, and nothing is launched: a NULL
+ * handle / dev_fut / dev_Yhat, a mode outside 0 .. 2, in mode SOFTMIN a tau that is not finite or <= 0, a ref_compat handle, T_pred too long.
+ * desire_set_recon_loss chooses the term of the TRAINING loss (default DESIRE_RECON_MEAN, which leaves the launch sequence and every bit of
+ * every output as they were; tau is ignored there and in MIN).  In MIN and SOFTMIN desire_backward runs step 1 - 3 on the full layout (before the
+ * gather of DESIRE_FLAG_COMPACT_ROWS) and takes
+ *   d loss / d Y0[r_k, t] = (lmask[a] && counted(t) && nrm > 0) ? w[a, k] / (nvalid * nfut[a] * nrm) * (Y0[r_k, t] - g_t) : 0,  nrm = ||Y0[r_k, t] - g_t||,
+ * and slot 0 (recon) of desire_train_loss / desire_train_loss_async is the mean of recon[a] over the counted agents.  Nothing else changes: KL,
+ * the IOC cross-entropy (its target still uses the detached Y0) and the IOC regression term keep their mean over K.  The mode can be changed
+ * between steps (not inside a captured graph: it is a host value, baked into the capture). */
+#define DESIRE_RECON_MEAN 0
+#define DESIRE_RECON_MIN 1
+#define DESIRE_RECON_SOFTMIN 2
+int desire_set_recon_loss(desire_handle* h, int32_t mode, float tau);
+int desire_recon_weights(desire_handle* h, const float* dev_fut, const float* dev_Yhat, int32_t mode, float tau,
+                         float* dev_e, float* dev_w, int32_t* dev_winner, float* dev_recon, void* stream);
 /* (dev_eps == NULL after desire_set_rng: the eps of the forward's draw is regenerated, see "device generator") */
 int desire_backward(desire_handle* h, const float* dev_past, const float* dev_fut, const float* dev_eps, void* stream);
 int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream);
