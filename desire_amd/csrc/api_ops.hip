@@ -215,6 +215,30 @@ extern "C" int desire_ade_fde(desire_handle* h, const float* dev_Yhat, const flo
     return DESIRE_OK;
 }
 
+// ---- argument checks that the evaluation entry points share (each call keeps its own order of checks) ----
+namespace {
+// the horizon list: 1..8 frame counts, each 1..T_pred, strictly increasing
+int parse_horizons(const int32_t* host_horizons, int32_t n_h, int T_pred, RankHz* hz) {
+    if (n_h < 1 || n_h > 8) return fail(DESIRE_ERR_ARG, "n_h must be 1..8");
+    hz->n = n_h;
+    for (int i = 0; i < n_h; ++i) {
+        hz->h[i] = host_horizons[i];
+        if (hz->h[i] < 1 || hz->h[i] > T_pred) return fail(DESIRE_ERR_ARG, "host_horizons[" + std::to_string(i) + "] must be 1..T_pred");
+        if (i && hz->h[i] <= hz->h[i - 1]) return fail(DESIRE_ERR_ARG, "host_horizons must be strictly increasing");
+    }
+    return DESIRE_OK;
+}
+int check_units(float unit_x, float unit_y) {
+    if (!std::isfinite(unit_x) || !(unit_x > 0.f)) return fail(DESIRE_ERR_ARG, "unit_x must be finite and > 0");
+    if (!std::isfinite(unit_y) || !(unit_y > 0.f)) return fail(DESIRE_ERR_ARG, "unit_y must be finite and > 0");
+    return DESIRE_OK;
+}
+int check_radius(float radius) {
+    if (!std::isfinite(radius) || radius < 0.f) return fail(DESIRE_ERR_ARG, "radius must be finite and >= 0");
+    return DESIRE_OK;
+}
+}  // namespace
+
 // ---- ranking by IOC score (kernels_rank.hip): the order of every agent's K samples, the n_top best rows, the errors of the paper's protocol ----
 extern "C" int desire_rank_samples(desire_handle* h, const float* dev_score, const float* dev_Yhat, int32_t n_top, int32_t* dev_order,
                                    float* dev_top_Y, float* dev_top_score, void* stream) {
@@ -243,14 +267,8 @@ extern "C" int desire_ranked_errors(desire_handle* h, const float* dev_Yhat, con
     const desire_dims& d = h->d;
     if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no IOC score to rank by");
     if (n_top < 1 || n_top > d.K) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
-    if (n_h < 1 || n_h > 8) return fail(DESIRE_ERR_ARG, "n_h must be 1..8");
     RankHz hz{};
-    hz.n = n_h;
-    for (int i = 0; i < n_h; ++i) {
-        hz.h[i] = host_horizons[i];
-        if (hz.h[i] < 1 || hz.h[i] > d.T_pred) return fail(DESIRE_ERR_ARG, "host_horizons[" + std::to_string(i) + "] must be 1..T_pred");
-        if (i && hz.h[i] <= hz.h[i - 1]) return fail(DESIRE_ERR_ARG, "host_horizons must be strictly increasing");
-    }
+    if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
     int sc = 0, kc = 0;
     if (!sample_errors_geometry(d.mno, d.K, d.T_pred, &sc, &kc)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the error kernel's LDS");
     launch_ranked_errors(dev_Yhat, dev_fut, dev_order, W(h, "rank_tab"), Wt<int32_t>(h, "rank_cnt"), dev_out, d.n_scenes,
@@ -269,16 +287,9 @@ extern "C" int desire_kde_nll(desire_handle* h, const float* dev_Yhat, const flo
     if (!dev_out) return fail(DESIRE_ERR_ARG, "dev_out is NULL");
     const desire_dims& d = h->d;
     if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to fit a density to");
-    if (n_h < 1 || n_h > 8) return fail(DESIRE_ERR_ARG, "n_h must be 1..8");
     RankHz hz{};
-    hz.n = n_h;
-    for (int i = 0; i < n_h; ++i) {
-        hz.h[i] = host_horizons[i];
-        if (hz.h[i] < 1 || hz.h[i] > d.T_pred) return fail(DESIRE_ERR_ARG, "host_horizons[" + std::to_string(i) + "] must be 1..T_pred");
-        if (i && hz.h[i] <= hz.h[i - 1]) return fail(DESIRE_ERR_ARG, "host_horizons must be strictly increasing");
-    }
-    if (!std::isfinite(unit_x) || !(unit_x > 0.f)) return fail(DESIRE_ERR_ARG, "unit_x must be finite and > 0");
-    if (!std::isfinite(unit_y) || !(unit_y > 0.f)) return fail(DESIRE_ERR_ARG, "unit_y must be finite and > 0");
+    if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
+    if (int rc = check_units(unit_x, unit_y)) return rc;
     if (!std::isfinite(log_floor)) return fail(DESIRE_ERR_ARG, "log_floor must be finite");
     int sa = 0;
     if (!kde_geometry(d.T_pred, &sa)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the KDE kernel's LDS");
@@ -294,9 +305,8 @@ extern "C" int desire_select_diverse(desire_handle* h, const float* dev_Yhat, co
                                      int32_t t_end, float radius, float unit_x, float unit_y, int32_t n_top, int32_t* dev_order_out,
                                      int32_t* dev_count, float* dev_mass, float* dev_top_Y, float* dev_top_score, void* stream) {
     if (metric < DESIRE_DIST_FINAL || metric > DESIRE_DIST_MAX) return fail(DESIRE_ERR_ARG, "metric must be DESIRE_DIST_FINAL, _MEAN or _MAX (0..2)");
-    if (!std::isfinite(radius) || radius < 0.f) return fail(DESIRE_ERR_ARG, "radius must be finite and >= 0");
-    if (!std::isfinite(unit_x) || !(unit_x > 0.f)) return fail(DESIRE_ERR_ARG, "unit_x must be finite and > 0");
-    if (!std::isfinite(unit_y) || !(unit_y > 0.f)) return fail(DESIRE_ERR_ARG, "unit_y must be finite and > 0");
+    if (int rc = check_radius(radius)) return rc;
+    if (int rc = check_units(unit_x, unit_y)) return rc;
     if (t_end < 1) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
     if (n_top < 1) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
     if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
@@ -311,7 +321,9 @@ extern "C" int desire_select_diverse(desire_handle* h, const float* dev_Yhat, co
     if (n_top > d.K) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
     int sc = 0, g = 0;
     if (!select_geometry(d.mno, d.K, metric, t_end, &sc, &g))
-        return fail(DESIRE_ERR_ARG, "K samples of t_end frames do not fit the selection kernel's LDS: K * (8 * (frames | 1) + 20) + 8 must be <= 61440");
+        return fail(DESIRE_ERR_ARG, "K samples of t_end frames do not fit the selection kernel's LDS: K * (" + std::to_string(EVAL_PAIR_BYTES) +
+                                        " * (frames | 1) + " + std::to_string(4 * SelLds::K_WORDS) + ") + " + std::to_string(4 * SelLds::SLOT_WORDS) +
+                                        " must be <= " + std::to_string(EVAL_LDS_BYTES));
     launch_select_diverse(dev_Yhat, dev_order, dev_score, dev_order_out, dev_count, dev_mass, dev_top_Y, dev_top_score, d.n_scenes, d.mno, d.K,
                           d.T_pred, metric, t_end, n_top, radius, unit_x, unit_y, static_cast<hipStream_t>(stream));
     HIPCHK(hipGetLastError());
@@ -335,17 +347,10 @@ extern "C" int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, con
     const desire_dims& d = h->d;
     if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read joint futures from");
     if (n_top < 1 || n_top > d.K) return fail(DESIRE_ERR_ARG, "n_top must be 1..K");
-    if (n_h < 1 || n_h > 8) return fail(DESIRE_ERR_ARG, "n_h must be 1..8");
     RankHz hz{};
-    hz.n = n_h;
-    for (int i = 0; i < n_h; ++i) {
-        hz.h[i] = host_horizons[i];
-        if (hz.h[i] < 1 || hz.h[i] > d.T_pred) return fail(DESIRE_ERR_ARG, "host_horizons[" + std::to_string(i) + "] must be 1..T_pred");
-        if (i && hz.h[i] <= hz.h[i - 1]) return fail(DESIRE_ERR_ARG, "host_horizons must be strictly increasing");
-    }
-    if (!std::isfinite(radius) || radius < 0.f) return fail(DESIRE_ERR_ARG, "radius must be finite and >= 0");
-    if (!std::isfinite(unit_x) || !(unit_x > 0.f)) return fail(DESIRE_ERR_ARG, "unit_x must be finite and > 0");
-    if (!std::isfinite(unit_y) || !(unit_y > 0.f)) return fail(DESIRE_ERR_ARG, "unit_y must be finite and > 0");
+    if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
+    if (int rc = check_radius(radius)) return rc;
+    if (int rc = check_units(unit_x, unit_y)) return rc;
     const bool errors = dev_jerr || dev_out;           // the per-agent table is desire_ranked_errors' own kernel's: its limit on T_pred comes with it
     int sc = 0, kc = 0;
     if (errors && !sample_errors_geometry(d.mno, d.K, d.T_pred, &sc, &kc))

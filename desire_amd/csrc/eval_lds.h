@@ -1,0 +1,132 @@
+// eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
+// _recon.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
+// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp compiles it with g++ (tests/test_eval_lds.py).
+#pragma once
+#include <stddef.h>
+
+#include "../../include/desire_hip.h"           // DESIRE_DIST_FINAL
+
+#ifdef __HIPCC__
+#define EVAL_HD __host__ __device__
+#else
+#define EVAL_HD
+#endif
+
+constexpr int EVAL_THREADS = 256;               // lanes of a workgroup of every streaming kernel
+constexpr int EVAL_LDS_BYTES = 60 * 1024;       // dynamic LDS of a workgroup (below the 64 KiB a launch gets without asking for more)
+constexpr int EVAL_PAIR_BYTES = 8;              // a position: float2
+// in a kernel: one clause tying an element type of its carve-up to the plan its launcher sizes the LDS by
+#define EVAL_LDS_TIED(cond) static_assert(cond, "carve-up and eval_lds.h plan disagree: " #cond)
+
+EVAL_HD constexpr int eval_min(int a, int b) { return a < b ? a : b; }
+EVAL_HD constexpr int eval_max(int a, int b) { return a > b ? a : b; }
+EVAL_HD constexpr int eval_odd(int n) { return n | 1; }                 // row stride of n frames: odd, so a walk down the rows is bank-conflict free
+EVAL_HD constexpr int eval_chunks(int n, int per) { return (n + per - 1) / per; }
+
+// ---- k_sample_errors: floats.  gm, gx, gy [SC][Tp] (counted mask and targets of the slot chunk), e [KC * SC][Tp] (the errors of the chunk's rows)
+struct ErrLds {
+    int Tp, SC, KC;
+    EVAL_HD constexpr ErrLds(int T, int SC_, int KC_) : Tp(eval_odd(T)), SC(SC_), KC(KC_) {}
+    EVAL_HD constexpr int gm() const { return 0; }
+    EVAL_HD constexpr int gx() const { return SC * Tp; }
+    EVAL_HD constexpr int gy() const { return 2 * SC * Tp; }
+    EVAL_HD constexpr int e() const { return 3 * SC * Tp; }
+    EVAL_HD constexpr size_t bytes() const { return 4 * (size_t)Tp * ((size_t)3 * SC + (size_t)SC * KC); }
+};
+// The chunking: every slot of a window and as many samples as 256 rows hold, shrunk until the LDS fits; the samples are then spread evenly over
+// the chunks.  false: not even one row fits (T_pred beyond ~3800).
+inline bool sample_errors_geometry(int mno, int K, int T, int* SC, int* KC) {
+    int sc = mno, kc = eval_max(1, eval_min(K, EVAL_THREADS / sc));
+    auto over = [&] { return ErrLds(T, sc, kc).bytes() > (size_t)EVAL_LDS_BYTES; };
+    while (over() && kc > 1) kc = (kc + 1) / 2;
+    while (over() && sc > 1) sc = (sc + 1) / 2;
+    if (over()) return false;
+    *SC = sc; *KC = eval_chunks(K, eval_chunks(K, kc));
+    return true;
+}
+
+// ---- k_kde_nll: floats.  val, cm [SA][Tp] (frame value and counted mask of SA whole agents)
+struct KdeLds {
+    int Tp, SA;
+    EVAL_HD constexpr KdeLds(int T, int SA_) : Tp(eval_odd(T)), SA(SA_) {}
+    EVAL_HD constexpr int val() const { return 0; }
+    EVAL_HD constexpr int cm() const { return SA * Tp; }
+    EVAL_HD constexpr size_t bytes() const { return (size_t)SA * (size_t)Tp * 8; }
+};
+// Whole agents per workgroup: as many as 256 (agent, t) pairs hold, one when T_pred is longer than that (the lanes then loop over its frames).
+// false: one agent's T_pred frame values do not fit.
+inline bool kde_geometry(int T, int* SA) {
+    const int sa = eval_max(1, EVAL_THREADS / T);
+    if (KdeLds(T, sa).bytes() > (size_t)EVAL_LDS_BYTES) return false;
+    *SA = sa;
+    return true;
+}
+
+// ---- k_select_diverse: Yl float2 [SC][K][Tp] (Tp = staged frames | 1), then five [SC][K] words (input order, candidate state, weight, order out,
+// mass), then two [SC] words (count, range flag).  The limit this gives is stated in desire_hip.h and in desire_select_diverse's message.
+struct SelLds {
+    enum { K_WORDS = 5, SLOT_WORDS = 2 };
+    int Tp, SC, K;
+    EVAL_HD static constexpr int staged(int metric, int t_end) { return metric == DESIRE_DIST_FINAL ? 1 : t_end; }
+    EVAL_HD constexpr SelLds(int staged_, int SC_, int K_) : Tp(eval_odd(staged_)), SC(SC_), K(K_) {}
+    EVAL_HD constexpr size_t pairs() const { return (size_t)SC * K * Tp; }                  // float2 in front of the words
+    EVAL_HD constexpr int k_words(int r) const { return r * SC * K; }                       // region r of the [SC][K] words, in words behind the pairs
+    EVAL_HD constexpr int slot_words(int r) const { return K_WORDS * SC * K + r * SC; }     // region r of the [SC] words
+    EVAL_HD static constexpr size_t agent_bytes(int K, int staged_) {
+        return (size_t)K * (EVAL_PAIR_BYTES * (size_t)eval_odd(staged_) + 4 * K_WORDS) + 4 * SLOT_WORDS;
+    }
+    EVAL_HD constexpr size_t bytes() const { return (size_t)SC * agent_bytes(K, Tp); }     // (Tp | 1 == Tp)
+};
+// The slot chunk: as many agents as the LDS holds, no more than 256 / G * 2 (two agents per group of G lanes keep the tail short), spread evenly over
+// the chunks; G = the power of two >= K, 64 at most.  false: one agent does not fit.
+inline bool select_geometry(int mno, int K, int metric, int t_end, int* SC, int* G) {
+    const size_t per = SelLds::agent_bytes(K, SelLds::staged(metric, t_end));
+    if (per > (size_t)EVAL_LDS_BYTES) return false;
+    int g = 1;
+    while (g < K && g < 64) g <<= 1;
+    int sc = (int)((size_t)mno < (size_t)EVAL_LDS_BYTES / per ? (size_t)mno : (size_t)EVAL_LDS_BYTES / per);
+    sc = eval_min(sc, eval_max(1, 2 * EVAL_THREADS / g));
+    *SC = eval_chunks(mno, eval_chunks(mno, sc));
+    *G = g;
+    return true;
+}
+
+// ---- k_recon_weights: Yl float2 [KC][SC][Tp] (the rows of a pass), gl float2 [SC][Tp] (targets), cl int [SC][Tp] (frame t of the slot counts)
+struct ReconLds {
+    int Tp, SC, KC;
+    EVAL_HD constexpr ReconLds(int T, int SC_, int KC_) : Tp(eval_odd(T)), SC(SC_), KC(KC_) {}
+    EVAL_HD constexpr size_t rows() const { return (size_t)KC * SC * Tp; }                  // float2 in front of the targets
+    EVAL_HD constexpr size_t slots() const { return (size_t)SC * Tp; }                      // float2 of the targets, and ints of the flags behind them
+    EVAL_HD static constexpr size_t row_bytes(int T) { return EVAL_PAIR_BYTES * (size_t)eval_odd(T); }
+    EVAL_HD static constexpr size_t slot_bytes(int T) { return (EVAL_PAIR_BYTES + 4) * (size_t)eval_odd(T); }
+    EVAL_HD constexpr size_t bytes() const { return (size_t)KC * SC * row_bytes(Tp) + (size_t)SC * slot_bytes(Tp); }
+};
+// The slot chunk and the samples of a pass: as many rows as the LDS holds next to their slots' targets, 256 at most (one lane per row), all K samples
+// of a slot in one pass where that fits (then more, smaller workgroups), the slots spread evenly over the chunks.  false: one row with its targets
+// does not fit (T_pred beyond 3071).
+inline bool recon_geometry(int mno, int K, int T, int* SC, int* KC) {
+    const size_t per = ReconLds(T, 1, 1).bytes();                      // a row with a slot of its own: the bound below holds for every SC x KC <= cap
+    if (per > (size_t)EVAL_LDS_BYTES) return false;
+    const int cap = (int)((size_t)EVAL_THREADS < (size_t)EVAL_LDS_BYTES / per ? (size_t)EVAL_THREADS : (size_t)EVAL_LDS_BYTES / per);
+    const int sc = eval_min(mno, eval_max(1, cap / K));
+    *SC = eval_chunks(mno, eval_chunks(mno, sc));
+    *KC = eval_min(K, eval_max(1, cap / *SC));
+    return true;
+}
+
+// ---- k_joint_unit: P float2 [TC][mp] (frame stride mp = mno below 32 slots, mno + 1 from 32 on: kernels_joint.hip says why), then two [mno] ints
+// (first contact, first counted frame)
+struct JointLds {
+    int mno, TC;
+    EVAL_HD constexpr JointLds(int mno_, int TC_) : mno(mno_), TC(TC_) {}
+    EVAL_HD static constexpr int stride(int mno) { return mno >= 32 ? mno + 1 : mno; }
+    EVAL_HD constexpr size_t pairs() const { return (size_t)TC * stride(mno); }             // float2 in front of the ints
+    EVAL_HD constexpr size_t bytes() const { return pairs() * EVAL_PAIR_BYTES + (size_t)mno * 2 * 4; }
+};
+// Frames per chunk: the whole horizon when mno * T_pred positions and the two per-slot integers fit the plan, else as many frames as do.  One
+// frame of 256 slots is 2 KB, so every (mno, T_pred) a handle can have is served.
+inline int joint_chunk_frames(int mno, int T) {
+    const size_t fixed = JointLds(mno, 0).bytes(), per = JointLds(mno, 1).bytes() - fixed, fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;
+    return (int)((size_t)T < fit ? (size_t)T : fit);
+}

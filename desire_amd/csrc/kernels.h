@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include "dyn_count.h"      // DynCount (a row count known on the device only), dyn_units (the grid of a strided launch), the list of strided launchers
+#include "eval_lds.h"     // the LDS plans and geometries of the evaluation kernels: sample_errors_geometry, kde_geometry, select_geometry,
+                          // recon_geometry (false: the smallest plan does not fit the LDS), joint_chunk_frames
 #include "ioc_lds.h"
 
 // dynamic LDS above 64 KiB must be opted into once per kernel: the kernel K, opted in, as the pointer the runtime queries take
@@ -252,7 +254,6 @@ struct RankHz { int n; int h[8]; };                        // horizons in frames
 constexpr int RANK_MAX_K = 4096;                           // k_rank_select keeps an agent's K scores and its order in LDS
 void launch_rank_select(const float* score, const float* Y, int32_t* order, float* top_Y, float* top_score, int n_scenes, int mno, int K,
                         int T, int n_top, hipStream_t s);
-bool sample_errors_geometry(int mno, int K, int T, int* SC, int* KC);      // false: one row of T_pred errors does not fit the LDS
 // tab [R, hz.n, 2] and cnt [A, hz.n] are scratch of the call (the handle's "rank_tab" / "rank_cnt")
 void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order, float* tab, int32_t* cnt, float* out, int n_scenes, int mno,
                           int K, int T, int n_top, const RankHz& hz, float sx, float sy, float ux, float uy, hipStream_t s);
@@ -262,29 +263,23 @@ void launch_sample_errors(const float* Y, const float* fut, float* tab, int32_t*
                           float sx, float sy, float ux, float uy, hipStream_t s);
 
 // ---- KDE log-likelihood (kernels_kde.hip) ----
-bool kde_geometry(int T, int* SA);                         // agents per workgroup; false: one agent's T_pred frame values do not fit the LDS
 // w [R] (the score layout) and st [A, 2] = (den, h2) are scratch of the call (the handle's "kde_w" / "kde_st"); score and frame may be nullptr
 void launch_kde_nll(const float* Y, const float* fut, const float* score, float* w, float* st, float* out, float* frame, int n_scenes, int mno,
                     int K, int T, const RankHz& hz, float sx, float sy, float ux, float uy, float log_floor, hipStream_t s);
 
 // ---- score-ordered non-maximum suppression (kernels_select.hip) ----
-// slots per workgroup and lanes per agent; false: one agent's K rows of staged frames do not fit the LDS (the limit is stated in desire_hip.h)
-bool select_geometry(int mno, int K, int metric, int t_end, int* SC, int* G);
 // score, mass, top_Y and top_score may be nullptr; no scratch
 void launch_select_diverse(const float* Y, const int32_t* order, const float* score, int32_t* order_out, int32_t* count, float* mass, float* top_Y,
                            float* top_score, int n_scenes, int mno, int K, int T, int metric, int t_end, int n_top, float radius, float ux,
                            float uy, hipStream_t s);
 
 // ---- joint (scene-level) metrics of the K samples (kernels_joint.hip) ----
-int joint_chunk_frames(int mno, int T);                    // frames of a (window, k) unit that one pass of the LDS plan holds (T: no chunking)
 // exactly one of fut / present; score, tab (the filled "rank_tab"; with it jerr), first and out may be nullptr; jscore and jorder never
 void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* tab, int32_t* first,
                           int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
                           const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
 
 // ---- per-sample reconstruction errors and the best-of-many / soft-min weights (kernels_recon.hip) ----
-// slots per workgroup and samples per pass; false: one row of T_pred positions with its targets does not fit the LDS (7680 frames fit)
-bool recon_geometry(int mno, int K, int T, int* SC, int* KC);
 // lmask / nfut: launch_loss_mask's; e, w [A, K], win [A], val [A] are all written (none may be nullptr); mode = DESIRE_RECON_*; no scratch
 void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
                           int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s);

@@ -7,6 +7,9 @@
 //                  (horizon, column) walks the slots in increasing order: the counts, the sums of the per-agent (ADE_h, FDE_h), the joint score.
 //   k_joint_pick   one wave per window: the order of the K joint scores (desire_rank_samples' rule, by counting: an integer path) and the pick.
 //
+// The streaming loop over Y, the order rule, the pick and the horizon list are eval_tile.h's; the LDS plan (JointLds) and the frame chunk are
+// eval_lds.h's.
+//
 // LDS layout.  P is float2 [frame of the chunk][slot], frame stride `mp` pairs: mp = mno below 32 slots (mno then divides 32) and mno + 1 from
 // 32 on.  The items of the pair loop are numbered frame-major, so the 32 lanes of a half wave -- the group a ds_read_b64 banks over, bank =
 // (address / 4) mod 64 -- hold 32 consecutive slots of one frame (mno >= 32) or 32 / mno whole frames (mno < 32): 256 contiguous bytes, or
@@ -29,20 +32,15 @@
 // operation once need not give the same bits).  The price is a second pass over Y and the table's bytes.
 //
 // No float atomics, no host synchronisation, horizons by value: capturable, bitwise reproducible, a window's results depend on that window only.
-#include "common.h"
-#include "kernels.h"
+#include "eval_tile.h"
 
-#pragma clang fp contract(off)                 // the contract rounds every operation once
+#pragma clang fp contract(off)                 // the contract rounds every operation once (after the includes: eval_tile.h says why)
 
 namespace {
 
-constexpr int JM_THREADS = 256;
-constexpr int JM_LDS_BYTES = 60 * 1024;        // dynamic LDS (the project's plan: below the 64 KiB a launch gets without asking for more)
 constexpr int JM_BATCH = 4;                    // 16-byte loads a lane has in flight
 
-__host__ __device__ inline int jm_stride(int mno) { return mno >= 32 ? mno + 1 : mno; }
-
-__global__ __launch_bounds__(JM_THREADS) void k_joint_unit(const float* __restrict__ Y, const float* __restrict__ fut,
+__global__ __launch_bounds__(EVAL_THREADS) void k_joint_unit(const float* __restrict__ Y, const float* __restrict__ fut,
                                                            const uint8_t* __restrict__ present, const float* __restrict__ score,
                                                            const float* __restrict__ tab, int32_t* __restrict__ first_out,
                                                            int32_t* __restrict__ cnt, float* __restrict__ jerr, float* __restrict__ jscore, int mno,
@@ -50,9 +48,10 @@ __global__ __launch_bounds__(JM_THREADS) void k_joint_unit(const float* __restri
                                                            RankHz hz) {
     extern __shared__ float2 jm_sm[];
     __shared__ int hzs[8];
-    const int mp = jm_stride(mno);
+    EVAL_LDS_TIED(sizeof(float2) == EVAL_PAIR_BYTES && sizeof(int) == 4);
+    const int mp = JointLds::stride(mno);
     float2* P = jm_sm;                                                  // [TC, mp]
-    int* firstL = reinterpret_cast<int*>(P + (size_t)TC * mp);          // [mno] first contact, T = none
+    int* firstL = reinterpret_cast<int*>(P + JointLds(mno, TC).pairs());    // [mno] first contact, T = none
     int* tc0L = firstL + mno;                                           // [mno] first counted frame, T = never counted
     const int tid = threadIdx.x;
     const int scene = blockIdx.x / (K + 1), k = blockIdx.x - scene * (K + 1);
@@ -60,8 +59,8 @@ __global__ __launch_bounds__(JM_THREADS) void k_joint_unit(const float* __restri
     const size_t r0 = ((size_t)scene * K + k) * mno;                    // first row of the unit (k < K)
     const size_t U0 = r0 * T;                                           // its first (row, t) pair
     const float nanf_ = __builtin_nanf("");
-    if (tid < 8) hzs[tid] = tid < hz.n ? hz.h[tid] : 0;
-    for (int i = tid; i < mno; i += JM_THREADS) {
+    eval_stage_horizons(hzs, hz);
+    for (int i = tid; i < mno; i += EVAL_THREADS) {
         firstL[i] = T;
         tc0L[i] = (present && !gt && present[(size_t)scene * mno + i]) ? 0 : T;
     }
@@ -71,7 +70,7 @@ __global__ __launch_bounds__(JM_THREADS) void k_joint_unit(const float* __restri
     for (int t0 = 0; t0 < T && !(gt && present); t0 += TC) {
         const int tc = min(TC, T - t0), n_it = tc * mno;
         // ---- the counted mask of the chunk: (0, 0) where counted, a NaN pair where not; the ground-truth unit's positions with it
-        for (int it = tid; it < n_it; it += JM_THREADS) {
+        for (int it = tid; it < n_it; it += EVAL_THREADS) {
             const int tl = it / mno, i = it - tl * mno, t = t0 + tl;
             bool c;
             float2 v = make_float2(0.f, 0.f);
@@ -84,50 +83,19 @@ __global__ __launch_bounds__(JM_THREADS) void k_joint_unit(const float* __restri
             P[tl * mp + i] = c ? v : make_float2(nanf_, nanf_);
         }
         __syncthreads();
-        // ---- the unit's rows: contiguous over (slot, t) when the chunk is the whole horizon, else one segment of tc pairs per slot.  A quad is two
-        // (row, t) pairs at an even pair index; a quad that straddles a segment's ends, or a buffer off 16-byte alignment, takes the 8-byte path.
+        // ---- the unit's rows: contiguous over (slot, t) when the chunk is the whole horizon, else one segment of tc pairs per slot
         if (!gt) {
-            const int n_seg = chunked ? mno : 1, seg_len = chunked ? tc : mno * T, nq = seg_len / 2 + 1, n_items = n_seg * nq;
-            auto put = [&](size_t pp, float y0, float y1) {
-                const int rel = (int)(pp - U0), i = rel / T, tl = rel - i * T - t0, o = tl * mp + i;
-                if (P[o].x == P[o].x) P[o] = make_float2(y0, y1);       // counted: the marker gives way to the position
-            };
-            for (int i0 = tid; i0 < n_items; i0 += JM_THREADS * JM_BATCH) {
-                float4 v[JM_BATCH];
-                size_t ps[JM_BATCH], qq[JM_BATCH];
-                bool full[JM_BATCH];
-#pragma unroll
-                for (int u = 0; u < JM_BATCH; ++u) {
-                    const int it = i0 + u * JM_THREADS;
-                    full[u] = false;
-                    if (it >= n_items) continue;
-                    const int sg = it / nq, uq = it - sg * nq;
-                    ps[u] = U0 + (chunked ? (size_t)sg * T + t0 : 0);
-                    qq[u] = (ps[u] >> 1) + uq;
-                    const size_t p = 2 * qq[u];
-                    full[u] = vec && p >= ps[u] && p + 1 < ps[u] + seg_len;
-                    if (full[u]) v[u] = *reinterpret_cast<const float4*>(Y + 4 * qq[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < JM_BATCH; ++u) {
-                    const int it = i0 + u * JM_THREADS;
-                    if (it >= n_items) break;
-                    const size_t p = 2 * qq[u];
-                    if (full[u]) {
-                        put(p, v[u].x, v[u].y);
-                        put(p + 1, v[u].z, v[u].w);
-                    } else {
-                        for (size_t pp = p; pp < p + 2; ++pp) {
-                            if (pp < ps[u] || pp >= ps[u] + seg_len) continue;
-                            put(pp, Y[2 * pp], Y[2 * pp + 1]);
-                        }
-                    }
-                }
-            }
+            eval_stream<JM_BATCH>(
+                Y, vec, chunked ? mno : 1, chunked ? tc : mno * T, chunked ? EVAL_ONE_ROW : T,
+                [&](int sg) { return EvalSeg{U0 + (chunked ? (size_t)sg * T + t0 : 0), sg}; },
+                [&](int sg, int row, int tl, float y0, float y1) {
+                    const int o = tl * mp + (chunked ? sg : row);
+                    if (P[o].x == P[o].x) P[o] = make_float2(y0, y1);   // counted: the marker gives way to the position
+                });
             __syncthreads();
         }
         // ---- pair tests: a lane owns (i, t) and walks the partners; q is symmetric in (i, j) bit for bit (a, b only change sign)
-        for (int it = tid; it < n_it; it += JM_THREADS) {
+        for (int it = tid; it < n_it; it += EVAL_THREADS) {
             const int tl = it / mno, i = it - tl * mno;
             const float2* row = P + tl * mp;
             const float2 p = row[i];
@@ -148,7 +116,7 @@ __global__ __launch_bounds__(JM_THREADS) void k_joint_unit(const float* __restri
     // ---- outputs.  One lane per (horizon, column) walks the slots in increasing order: integers, and float sums in one fixed order from 0.f
     const size_t unit = (size_t)scene * (K + 1) + k;
     if (first_out)
-        for (int i = tid; i < mno; i += JM_THREADS) first_out[unit * mno + i] = firstL[i];
+        for (int i = tid; i < mno; i += EVAL_THREADS) first_out[unit * mno + i] = firstL[i];
     const int n_h = hz.n;
     if (tid < 2 * n_h) {
         const int hi = tid >> 1, col = tid & 1, h = hzs[hi];
@@ -172,8 +140,8 @@ __global__ __launch_bounds__(JM_THREADS) void k_joint_unit(const float* __restri
     }
 }
 
-// The order of a window's K joint scores: rank_k = #{ j : s_j before s_k }, desire_rank_samples' "before" (IEEE >, ties to the lower index, NaNs
-// last by index), read from global memory so that K has no limit.  Then out [n_h, 4] through that order, as k_ranked_pick picks.
+// The order of a window's K joint scores: rank_k = #{ j : s_j before s_k } (eval_before, desire_rank_samples' rule), read from global memory
+// so that K has no limit.  Then out [n_h, 4] through that order (eval_pick, as k_ranked_pick picks).
 __global__ __launch_bounds__(64) void k_joint_pick(const float* __restrict__ js, const float* __restrict__ jerr, const int32_t* __restrict__ cnt,
                                                    int32_t* __restrict__ jorder, float* __restrict__ out, int K, int n_h, int n_top) {
     const int scene = blockIdx.x, lane = threadIdx.x;
@@ -181,13 +149,8 @@ __global__ __launch_bounds__(64) void k_joint_pick(const float* __restrict__ js,
     int32_t* ord = jorder + (size_t)scene * K;
     for (int k = lane; k < K; k += 64) {
         const float sk = s[k];
-        const bool nk = sk != sk;
         int r = 0;
-        for (int j = 0; j < K; ++j) {
-            const float sj = s[j];
-            const bool before = (sj != sj) ? (nk && j < k) : (nk || sj > sk || (sj == sk && j < k));
-            r += before ? 1 : 0;
-        }
+        for (int j = 0; j < K; ++j) r += eval_before(s[j], j, sk, k) ? 1 : 0;
         ord[r] = k;
     }
     if (!out) return;
@@ -195,18 +158,8 @@ __global__ __launch_bounds__(64) void k_joint_pick(const float* __restrict__ js,
     __syncthreads();
     for (int hi = lane; hi < n_h; hi += 64) {
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (cnt[(((size_t)scene * (K + 1)) * n_h + hi) * 2 + 1] > 0) {  // taking part does not depend on k: row 0
-            for (int j = 0; j < n_top; ++j) {
-                const int k = ord[j];
-                const float* e = jerr + (((size_t)scene * K + k) * n_h + hi) * 2;
-                const float ade = e[0], fde = e[1];
-                if (j == 0) o = make_float4(ade, fde, ade, fde);
-                else {
-                    if (ade < o.z || ade != ade) o.z = ade;             // the minimum keeps a NaN, as k_ranked_pick's does
-                    if (fde < o.w || fde != fde) o.w = fde;
-                }
-            }
-        }
+        if (cnt[(((size_t)scene * (K + 1)) * n_h + hi) * 2 + 1] > 0)    // taking part does not depend on k: row 0
+            o = eval_pick(ord, n_top, [&](int k) { return jerr + (((size_t)scene * K + k) * n_h + hi) * 2; });
         float* op = out + ((size_t)scene * n_h + hi) * 4;
         op[0] = o.x; op[1] = o.y; op[2] = o.z; op[3] = o.w;
     }
@@ -214,20 +167,13 @@ __global__ __launch_bounds__(64) void k_joint_pick(const float* __restrict__ js,
 
 }  // namespace
 
-// Frames per chunk: the whole horizon when mno * T_pred positions and the two per-slot integers fit the plan, else as many frames as do.  One
-// frame of 256 slots is 2 KB, so every (mno, T_pred) a handle can have is served.
-int joint_chunk_frames(int mno, int T) {
-    const size_t per = (size_t)jm_stride(mno) * sizeof(float2), fixed = (size_t)mno * 2 * sizeof(int);
-    return (int)min((size_t)T, ((size_t)JM_LDS_BYTES - fixed) / per);
-}
-
 void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* tab, int32_t* first,
                           int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
                           const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
     const int TC = joint_chunk_frames(mno, T);
-    const size_t lds = (size_t)TC * jm_stride(mno) * sizeof(float2) + (size_t)mno * 2 * sizeof(int);
+    const size_t lds = JointLds(mno, TC).bytes();
     const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    hipLaunchKernelGGL(k_joint_unit, dim3((unsigned)((size_t)n_scenes * (K + 1))), dim3(JM_THREADS), lds, s, Y, fut, present, score, tab, first, cnt,
+    hipLaunchKernelGGL(k_joint_unit, dim3((unsigned)((size_t)n_scenes * (K + 1))), dim3(EVAL_THREADS), lds, s, Y, fut, present, score, tab, first, cnt,
                        jerr, jscore, mno, K, T, TC, vec, sx, sy, ux, uy, radius * radius, hz);
     hipLaunchKernelGGL(k_joint_pick, dim3(n_scenes), dim3(64), 0, s, jscore, jerr, cnt, jorder, out, K, hz.n, n_top);
 }

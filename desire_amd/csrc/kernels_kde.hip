@@ -6,46 +6,31 @@
 //                  reads 512 contiguous bytes per sample, at a stride of mno * T_pred * 2 floats between samples.  Up to 24 samples the lane keeps
 //                  its K differences and weights in registers (Y comes from HBM once, three passes over registers); beyond, every pass re-reads
 //                  them -- a workgroup's share of Y is a few hundred KiB and stays in L2.  The frame values go to LDS; after the barrier one lane
-//                  per agent walks its frames in increasing t (the fixed summation order) and writes the two columns of every horizon.
+//                  per agent walks its frames and writes the two columns of every horizon.
 //
+// The weight statistics of the scores, the horizon list and its walk are eval_tile.h's; the LDS plan is eval_lds.h's.
 // No atomics, no host synchronisation, horizons by value: a result is a fixed sequence of fp32 operations per (agent, t), so it does not depend on
 // the grid or on the rest of the batch, and the call can be captured in a graph.
-#include "common.h"
-#include "kernels.h"
-#include "../../include/desire_hip.h"
+#include "eval_tile.h"
 
-#include <cfloat>
-
-#pragma clang fp contract(off)                 // the contract rounds every operation once
+#pragma clang fp contract(off)                 // the contract rounds every operation once (after the includes: eval_tile.h says why)
 
 namespace {
 
-constexpr int KD_THREADS = 256;
-constexpr int KD_LDS_BYTES = 60 * 1024;        // dynamic LDS (below the 64 KiB a launch gets without asking for more)
 constexpr float KD_LOG_2PI = 1.8378770664093453f;
 
-__global__ __launch_bounds__(KD_THREADS) void k_kde_weights(const float* __restrict__ score, float* __restrict__ w, float* __restrict__ st, int A,
+__global__ __launch_bounds__(EVAL_THREADS) void k_kde_weights(const float* __restrict__ score, float* __restrict__ w, float* __restrict__ st, int A,
                                                             int mno, int K) {
-    const int a = blockIdx.x * KD_THREADS + threadIdx.x;
+    const int a = blockIdx.x * EVAL_THREADS + threadIdx.x;
     if (a >= A) return;
     const int scene = a / mno, slot = a - scene * mno;
     const size_t row0 = (size_t)scene * K * mno + slot;            // row of sample k: row0 + k * mno
-    bool uniform = score == nullptr;
-    float mx = -FLT_MAX, sum = 0.f;
-    if (!uniform) {
-        for (int k = 0; k < K; ++k) {
-            const float s = score[row0 + (size_t)k * mno];
-            if (!(fabsf(s) <= FLT_MAX)) uniform = true;            // NaN, +-inf
-            mx = fmaxf(mx, s);
-        }
-    }
-    if (!uniform)
-        for (int k = 0; k < K; ++k) sum += expf(score[row0 + (size_t)k * mno] - mx);
+    const EvalWeightStats ws = eval_weight_stats(score != nullptr, K, [&](int k) { return score[row0 + (size_t)k * mno]; }, [](int, float) {});
     const float u = 1.f / (float)K;
     float den = 0.f, s2 = 0.f;
     bool one = false;
     for (int k = 0; k < K; ++k) {
-        const float wk = uniform ? u : expf(score[row0 + (size_t)k * mno] - mx) / sum;
+        const float wk = ws.uniform ? u : expf(score[row0 + (size_t)k * mno] - ws.mx) / ws.sum;
         w[row0 + (size_t)k * mno] = wk;
         den += wk * (1.f - wk);
         s2 += wk * wk;
@@ -58,20 +43,21 @@ __global__ __launch_bounds__(KD_THREADS) void k_kde_weights(const float* __restr
 
 // KC > 0: K <= KC, the lane's differences and weights live in registers.  KC == 0: any K, re-read in every pass.
 template <int KC>
-__global__ __launch_bounds__(KD_THREADS) void k_kde_nll(const float* __restrict__ Y, const float* __restrict__ fut, const float* __restrict__ w,
+__global__ __launch_bounds__(EVAL_THREADS) void k_kde_nll(const float* __restrict__ Y, const float* __restrict__ fut, const float* __restrict__ w,
                                                         const float* __restrict__ st, float* __restrict__ out, float* __restrict__ frame, int A,
                                                         int mno, int K, int T, int SA, int vec, float sx, float sy, float ux, float uy,
                                                         float log_floor, RankHz hz) {
     extern __shared__ float kd_sm[];
     __shared__ int hzs[8];
-    const int Tp = T | 1;                                           // odd row stride: the walk below is bank-conflict free
-    float* val = kd_sm;
-    float* cm = kd_sm + (size_t)SA * Tp;
+    const KdeLds L(T, SA);
+    const int Tp = L.Tp;
+    float* val = kd_sm + L.val();
+    float* cm = kd_sm + L.cm();
     const int tid = threadIdx.x;
     const int a0 = blockIdx.x * SA, na = min(SA, A - a0);
-    if (tid < 8) hzs[tid] = tid < hz.n ? hz.h[tid] : 0;
+    eval_stage_horizons(hzs, hz);
 
-    for (int i = tid; i < na * T; i += KD_THREADS) {
+    for (int i = tid; i < na * T; i += EVAL_THREADS) {
         const int s = i / T, t = i - s * T, a = a0 + s;
         const int scene = a / mno, slot = a - scene * mno;
         const float* f = fut + (((size_t)scene * T + t) * mno + slot) * 3;
@@ -159,43 +145,27 @@ __global__ __launch_bounds__(KD_THREADS) void k_kde_nll(const float* __restrict_
     }
     __syncthreads();
 
-    const int n_h = hz.n, h_max = hzs[n_h - 1];
-    for (int s = tid; s < na; s += KD_THREADS) {
-        const float* vr = val + s * Tp;
-        const float* mr = cm + s * Tp;
+    const int n_h = hz.n;
+    for (int s = tid; s < na; s += EVAL_THREADS) {
         float* o = out + (size_t)(a0 + s) * n_h * 2;
-        float sum = 0.f, last = 0.f;
-        int np = 0, hi = 0;
-        for (int t = 0; t < h_max; ++t) {
-            if (mr[t] != 0.f) { last = vr[t]; sum += last; ++np; }
-            if (t + 1 == hzs[hi]) {
-                o[2 * hi] = np ? -(sum / (float)np) : 0.f;
-                o[2 * hi + 1] = np ? -last : 0.f;
-                ++hi;
-            }
-        }
+        eval_horizon_walk(cm + s * Tp, val + s * Tp, hzs, n_h, [&](int hi, float sum, float last, int np) {
+            o[2 * hi] = np ? -(sum / (float)np) : 0.f;
+            o[2 * hi + 1] = np ? -last : 0.f;
+        });
     }
 }
 
 }  // namespace
-
-// Whole agents per workgroup: as many as 256 (agent, t) pairs hold, one when T_pred is longer than that (the lanes then loop over its frames).
-bool kde_geometry(int T, int* SA) {
-    const int sa = max(1, KD_THREADS / T);
-    if ((size_t)sa * (size_t)(T | 1) * 8 > (size_t)KD_LDS_BYTES) return false;
-    *SA = sa;
-    return true;
-}
 
 void launch_kde_nll(const float* Y, const float* fut, const float* score, float* w, float* st, float* out, float* frame, int n_scenes, int mno,
                     int K, int T, const RankHz& hz, float sx, float sy, float ux, float uy, float log_floor, hipStream_t s) {
     int SA = 1;
     if (!kde_geometry(T, &SA)) return;                                // (refused by the caller before it gets here)
     const int A = n_scenes * mno;
-    hipLaunchKernelGGL(k_kde_weights, dim3((A + KD_THREADS - 1) / KD_THREADS), dim3(KD_THREADS), 0, s, score, w, st, A, mno, K);
-    const size_t lds = (size_t)SA * (T | 1) * 8;
+    hipLaunchKernelGGL(k_kde_weights, dim3((A + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, s, score, w, st, A, mno, K);
+    const size_t lds = KdeLds(T, SA).bytes();
     const int vec = (reinterpret_cast<uintptr_t>(Y) & 7) == 0;
-    const dim3 grid((A + SA - 1) / SA), block(KD_THREADS);
+    const dim3 grid((A + SA - 1) / SA), block(EVAL_THREADS);
     if (K <= 8)
         hipLaunchKernelGGL(k_kde_nll<8>, grid, block, lds, s, Y, fut, w, st, out, frame, A, mno, K, T, SA, vec, sx, sy, ux, uy, log_floor, hz);
     else if (K <= 24)

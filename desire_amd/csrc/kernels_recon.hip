@@ -2,43 +2,37 @@
 // loss (desire_set_recon_loss, desire_recon_weights; the contract, operation by operation, is in include/desire_hip.h).
 //
 //   k_recon_weights  one workgroup = (window, a chunk of SC slots).  For one (window, k) Y is contiguous over (slot, t), so the chunk's rows of KC
-//                  samples at a time are streamed into LDS with 16-byte loads, consecutive lanes on consecutive addresses (8-byte pairs where a
-//                  quad straddles the chunk's range, and for a buffer off 16-byte alignment); the chunk's targets g and counted flags are staged
-//                  once.  Then one lane per row (the fixed lane group of a row is that one lane: the contract's sum is one sequence, frame after
-//                  frame) walks its LDS row in increasing t and leaves e[a, k]; the passes over k repeat until K is done -- K has no limit.  At
-//                  the end one lane per agent walks its K errors: the strict-comparison minimum, then exp / sum / divide in increasing k.
+//                  samples at a time are streamed into LDS (eval_tile.h's streamer, one segment per sample); the chunk's targets g and counted
+//                  flags are staged once.  Then one lane per row (the fixed lane group of a row is that one lane: the contract's sum is one
+//                  sequence, frame after frame) walks its LDS row in increasing t and leaves e[a, k]; the passes over k repeat until K is
+//                  done -- K has no limit.  At the end one lane per agent walks its K errors: the strict-comparison minimum, then exp / sum /
+//                  divide in increasing k.
 //
 // LDS rows are float2 [t], row stride T | 1 pairs: odd, so the lanes of a wave -- each on its own row, the same t -- fall on distinct 8-byte
 // bank pairs; their targets are rows of the same stride, one per slot (lanes on the same slot, another k, read one address: a broadcast).
 // The errors go through the e buffer itself (global memory, written and read by the same workgroup on either side of a barrier), so no LDS is
 // spent on K.  No atomics, no scratch, no host wait: capturable, bitwise reproducible, and a result
-// depends on its agent's rows and targets only.
-#include "common.h"
-#include "kernels.h"
-#include "../../include/desire_hip.h"
+// depends on its agent's rows and targets only.  The LDS plan (ReconLds), the slot chunk and the samples of a pass are eval_lds.h's.
+#include "eval_tile.h"
 
-#pragma clang fp contract(off)                 // the contract rounds every operation once
+#pragma clang fp contract(off)                 // the contract rounds every operation once (after the includes: eval_tile.h says why)
 
 namespace {
 
-constexpr int RW_THREADS = 256;
-constexpr int RW_LDS_BYTES = 60 * 1024;        // dynamic LDS (below the 64 KiB a launch gets without asking for more)
 constexpr int RW_BATCH = 4;                    // 16-byte loads a lane has in flight
 
-// bytes of LDS per staged row, and per slot for the targets (float2) and counted flags (int)
-__host__ __device__ inline size_t rw_row_bytes(int T) { return 8 * (size_t)(T | 1); }
-__host__ __device__ inline size_t rw_slot_bytes(int T) { return 12 * (size_t)(T | 1); }
-
-__global__ __launch_bounds__(RW_THREADS) void k_recon_weights(const float* __restrict__ Y, const float* __restrict__ fut,
+__global__ __launch_bounds__(EVAL_THREADS) void k_recon_weights(const float* __restrict__ Y, const float* __restrict__ fut,
                                                               const uint8_t* __restrict__ lmask, const float* __restrict__ nfut, float* e,
                                                               float* w, int32_t* __restrict__ win, float* __restrict__ val, int n_scenes, int mno,
                                                               int K, int T, int SC, int n_sc, int KC, int vec, int mode, float tau, float sx,
                                                               float sy) {
     extern __shared__ __attribute__((aligned(16))) float2 rw_sm[];
-    const int Tp = T | 1;
+    EVAL_LDS_TIED(sizeof(float2) == EVAL_PAIR_BYTES && sizeof(int) == 4);
+    const ReconLds L_(T, SC, KC);
+    const int Tp = L_.Tp;
     float2* Yl = rw_sm;                                                 // [KC, SC, Tp]
-    float2* gl = Yl + (size_t)KC * SC * Tp;                             // [SC, Tp] the targets
-    int* cl = reinterpret_cast<int*>(gl + (size_t)SC * Tp);             // [SC, Tp] frame t of the slot counts
+    float2* gl = Yl + L_.rows();                                        // [SC, Tp] the targets
+    int* cl = reinterpret_cast<int*>(gl + L_.slots());                  // [SC, Tp] frame t of the slot counts
 
     const int tid = threadIdx.x;
     const int sc = blockIdx.x % n_sc, scene = blockIdx.x / n_sc;
@@ -46,7 +40,7 @@ __global__ __launch_bounds__(RW_THREADS) void k_recon_weights(const float* __res
     const size_t a0 = (size_t)scene * mno + slot0;                      // first agent of the chunk
 
     // ---- the chunk's targets, scaled as k_train_loss scales them, and which frames count
-    for (int i = tid; i < ns * T; i += RW_THREADS) {
+    for (int i = tid; i < ns * T; i += EVAL_THREADS) {
         const int t = i / ns, s = i - t * ns;
         const float* f = fut + (((size_t)scene * T + t) * mno + slot0 + s) * 3;
         gl[s * Tp + t] = make_float2(__fmul_rn(f[1], sx), __fmul_rn(f[2], sy));
@@ -55,45 +49,14 @@ __global__ __launch_bounds__(RW_THREADS) void k_recon_weights(const float* __res
 
     // ---- passes of KC samples: stage, then one lane per row
     const int L = ns * T;                                               // (slot, t) pairs of one k: contiguous in Y
-    const int nq = L / 2 + 1;                                           // quads that cover L pairs at either parity of their first index
     for (int k0 = 0; k0 < K; k0 += KC) {
         const int kc = min(KC, K - k0);
         __syncthreads();                                                // the rows of the pass before are done with (first pass: nothing to wait for)
-        const int n_items = kc * nq;
-        for (int i0 = tid; i0 < n_items; i0 += RW_THREADS * RW_BATCH) {
-            float4 v[RW_BATCH];
-            size_t ps[RW_BATCH], qq[RW_BATCH];
-            int kk[RW_BATCH];
-            bool full[RW_BATCH];
-#pragma unroll
-            for (int u = 0; u < RW_BATCH; ++u) {
-                const int i = i0 + u * RW_THREADS;
-                full[u] = false;
-                if (i >= n_items) continue;
-                kk[u] = i / nq;
-                ps[u] = (((size_t)scene * K + k0 + kk[u]) * mno + slot0) * T;       // first pair of the chunk's rows of sample k0 + kk
-                qq[u] = (ps[u] >> 1) + (size_t)(i - kk[u] * nq);
-                const size_t p = 2 * qq[u];
-                full[u] = vec && p >= ps[u] && p + 1 < ps[u] + L;
-                if (full[u]) v[u] = *reinterpret_cast<const float4*>(Y + 4 * qq[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < RW_BATCH; ++u) {
-                const int i = i0 + u * RW_THREADS;
-                if (i >= n_items) break;
-                const size_t p = 2 * qq[u];
-                for (size_t pp = p; pp < p + 2; ++pp) {                 // a pair outside the range belongs to a neighbouring chunk (or to nobody)
-                    if (pp < ps[u] || pp >= ps[u] + L) continue;
-                    const int off = (int)(pp - ps[u]), s = off / T, t = off - s * T;
-                    float2 y;
-                    if (full[u]) y = pp == p ? make_float2(v[u].x, v[u].y) : make_float2(v[u].z, v[u].w);
-                    else y = make_float2(Y[2 * pp], Y[2 * pp + 1]);
-                    Yl[((size_t)kk[u] * ns + s) * Tp + t] = y;
-                }
-            }
-        }
+        eval_stream<RW_BATCH>(
+            Y, vec, kc, L, T, [&](int kk) { return EvalSeg{(((size_t)scene * K + k0 + kk) * mno + slot0) * T, kk}; },      // the chunk's rows of sample k0 + kk
+            [&](int kk, int s, int t, float y0, float y1) { Yl[((size_t)kk * ns + s) * Tp + t] = make_float2(y0, y1); });
         __syncthreads();
-        for (int rw = tid; rw < kc * ns; rw += RW_THREADS) {
+        for (int rw = tid; rw < kc * ns; rw += EVAL_THREADS) {
             const int k = rw / ns, s = rw - k * ns;
             float ev = 0.f;
             if (lmask[a0 + s]) {
@@ -114,7 +77,7 @@ __global__ __launch_bounds__(RW_THREADS) void k_recon_weights(const float* __res
     __syncthreads();                                                    // every e of the chunk is written (and visible to this workgroup)
 
     // ---- one lane per agent: the walk for the minimum, then the weights and the term in increasing k
-    for (int s = tid; s < ns; s += RW_THREADS) {
+    for (int s = tid; s < ns; s += EVAL_THREADS) {
         const float* ea = e + (a0 + s) * K;
         float* wa = w + (a0 + s) * K;
         int wn = 0;
@@ -145,27 +108,13 @@ __global__ __launch_bounds__(RW_THREADS) void k_recon_weights(const float* __res
 
 }  // namespace
 
-// The slot chunk and the samples of a pass: as many rows as the LDS holds next to their slots' targets, 256 at most (one lane per row), all K samples
-// of a slot in one pass where that fits (then more, smaller workgroups), the slots spread evenly over the chunks.  false: one row does not fit.
-bool recon_geometry(int mno, int K, int T, int* SC, int* KC) {
-    const size_t per = rw_row_bytes(T) + rw_slot_bytes(T);             // a row with a slot of its own: the bound below holds for every SC x KC <= cap
-    if (per > (size_t)RW_LDS_BYTES) return false;
-    const int cap = (int)min((size_t)RW_THREADS, (size_t)RW_LDS_BYTES / per);
-    int sc = min(mno, max(1, cap / K));
-    const int n_sc = (mno + sc - 1) / sc;
-    sc = (mno + n_sc - 1) / n_sc;
-    *SC = sc;
-    *KC = min(K, max(1, cap / sc));
-    return true;
-}
-
 void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
                           int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s) {
     int SC = 1, KC = 1;
     if (!recon_geometry(mno, K, T, &SC, &KC)) return;                   // (refused by the caller before it gets here)
-    const int n_sc = (mno + SC - 1) / SC;
-    const size_t lds = (size_t)KC * SC * rw_row_bytes(T) + (size_t)SC * rw_slot_bytes(T);
+    const int n_sc = eval_chunks(mno, SC);
+    const size_t lds = ReconLds(T, SC, KC).bytes();
     const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    hipLaunchKernelGGL(k_recon_weights, dim3((unsigned)((size_t)n_scenes * n_sc)), dim3(RW_THREADS), lds, s, Y, fut, lmask, nfut, e, w, win, val,
+    hipLaunchKernelGGL(k_recon_weights, dim3((unsigned)((size_t)n_scenes * n_sc)), dim3(EVAL_THREADS), lds, s, Y, fut, lmask, nfut, e, w, win, val,
                        n_scenes, mno, K, T, SC, n_sc, KC, vec, mode, tau, sx, sy);
 }

@@ -1,13 +1,12 @@
 // kernels_select.hip -- score-ordered non-maximum suppression of an agent's K samples (desire_select_diverse; the contract, operation by
 // operation, is in include/desire_hip.h).
 //
-//   k_select_diverse<METRIC>  one workgroup = (window, a chunk of SC slots).  For one (window, k) Y is contiguous over (slot, t), so the chunk's K
-//                  segments are streamed into LDS once with 16-byte loads, consecutive lanes on consecutive addresses (8-byte pairs where a quad
-//                  straddles a row's staged range or the buffer's end): only the frames t < t_end, only frame t_end - 1 for FINAL.  The order rows and
-//                  scores go to LDS the same way; one lane per agent range-checks its row and turns its scores into weights.  Then a group of G lanes (G = the power
-//                  of two >= K, 64 at most) runs the agent's pass out of LDS, and one lane per agent lays out order, count and mass, which leave
-//                  the workgroup with coalesced stores.  The gather of the n_top first rows re-reads them from Y (n_top / K of it, the lines
-//                  this workgroup fetched a moment ago).
+//   k_select_diverse<METRIC>  one workgroup = (window, a chunk of SC slots).  The staged range of every row of the chunk is streamed into LDS
+//                  once (the item loop of eval_tile.h's streamer, written out below): only the frames t < t_end, only frame t_end - 1 for
+//                  FINAL.  The order rows and scores go to LDS too; one lane per agent range-checks its row and turns its scores into
+//                  weights.  Then a group of G lanes (G = the power of two >= K, 64 at most) runs the agent's pass out of LDS, and one lane
+//                  per agent lays out order, count and mass, which leave the workgroup with coalesced stores.  The gather of the n_top
+//                  first rows re-reads them from Y (n_top / K of it, the lines this workgroup fetched a moment ago).
 //
 // The pass is form (b) of the two the design admits: count sequential steps.  A step finds the first candidate in processing order that is still
 // live (a min over the group's lanes, by shuffles), keeps it, and every lane tests its own live candidates against it; a candidate near it is
@@ -21,27 +20,18 @@
 // LDS rows are float2 [t], row stride (frames staged | 1) pairs: odd, so the lanes of a group -- each on its own row, the same t -- fall on
 // distinct 8-byte bank pairs (ds_read_b64 banks over a 32-lane half), and the kept sample's row is one address, a broadcast.  A candidate's
 // state has one owner lane (j mod G), so the pass needs no barrier.  No atomics, no host synchronisation: capturable, bitwise reproducible, and
-// a result depends on its agent's rows, order and scores only.
-#include "common.h"
-#include "kernels.h"
-#include "../../include/desire_hip.h"
+// a result depends on its agent's rows, order and scores only.  The LDS plan (SelLds) and the slot chunk are eval_lds.h's.
+#include "eval_tile.h"
 
-#include <cfloat>
 #include <climits>
 
-#pragma clang fp contract(off)                 // the contract rounds every operation once
+#pragma clang fp contract(off)                 // the contract rounds every operation once (after the includes: eval_tile.h says why)
 
 namespace {
 
-constexpr int SD_THREADS = 256;
-constexpr int SD_LDS_BYTES = 60 * 1024;        // dynamic LDS (below the 64 KiB a launch gets without asking for more)
 constexpr int SD_BATCH = 8;                    // 16-byte loads a lane has in flight
 constexpr int SD_LIVE = -1;                    // own[j]: not yet kept or owned
 constexpr int SD_KEPT = 1 << 30;               // own[j] = i | SD_KEPT: kept as number i; own[j] = i: owned by kept number i
-
-__host__ __device__ inline int sd_staged(int metric, int t_end) { return metric == DESIRE_DIST_FINAL ? 1 : t_end; }
-// bytes of LDS per agent: K rows of (staged | 1) float2, K x (order, state, weight, order out, mass), count and range flag
-__host__ __device__ inline size_t sd_agent_bytes(int K, int staged) { return (size_t)K * (8 * (size_t)(staged | 1) + 20) + 8; }
 
 // the predicate of (k, k') over the staged frames of two LDS rows: the contract's sequence, the same for every caller
 template <int METRIC>
@@ -70,39 +60,44 @@ __device__ inline bool sd_near(const float2* __restrict__ p, const float2* __res
 }
 
 template <int METRIC>
-__global__ __launch_bounds__(SD_THREADS) void k_select_diverse(const float* __restrict__ Y, const int32_t* __restrict__ order,
+__global__ __launch_bounds__(EVAL_THREADS) void k_select_diverse(const float* __restrict__ Y, const int32_t* __restrict__ order,
                                                                const float* __restrict__ score, int32_t* __restrict__ order_out,
                                                                int32_t* __restrict__ count, float* __restrict__ mass, float* __restrict__ top_Y,
                                                                float* __restrict__ top_score, int n_scenes, int mno, int K, int T, int t_end,
                                                                int SC, int n_sc, int G, int vec, int n_top, float radius, float ux, float uy) {
     extern __shared__ float2 sd_sm[];
-    const int nt = sd_staged(METRIC, t_end), t_lo = t_end - nt, Tp = nt | 1;
+    EVAL_LDS_TIED(sizeof(float2) == EVAL_PAIR_BYTES && sizeof(int) == 4 && sizeof(float) == 4 && SelLds::K_WORDS == 5 && SelLds::SLOT_WORDS == 2);
+    const int nt = SelLds::staged(METRIC, t_end), t_lo = t_end - nt;
+    const SelLds L(nt, SC, K);
+    const int Tp = L.Tp;
     float2* Yl = sd_sm;                                                 // [SC, K, Tp]
-    int* ordL = reinterpret_cast<int*>(Yl + (size_t)SC * K * Tp);       // [SC, K] the input order
-    int* own = ordL + SC * K;                                           // [SC, K] state of candidate j
-    float* wL = reinterpret_cast<float*>(own + SC * K);                 // [SC, K] weight of sample k
-    int* outL = reinterpret_cast<int*>(wL + SC * K);                    // [SC, K] the diverse order
-    float* massL = reinterpret_cast<float*>(outL + SC * K);             // [SC, K]
-    int* cntL = reinterpret_cast<int*>(massL + SC * K);                 // [SC]
-    int* badL = cntL + SC;                                              // [SC] the order row holds an index outside 0 .. K-1
+    int* wd = reinterpret_cast<int*>(Yl + L.pairs());                   // the words behind the pairs
+    int* ordL = wd + L.k_words(0);                                      // [SC, K] the input order
+    int* own = wd + L.k_words(1);                                       // [SC, K] state of candidate j
+    float* wL = reinterpret_cast<float*>(wd + L.k_words(2));            // [SC, K] weight of sample k
+    int* outL = wd + L.k_words(3);                                      // [SC, K] the diverse order
+    float* massL = reinterpret_cast<float*>(wd + L.k_words(4));         // [SC, K]
+    int* cntL = wd + L.slot_words(0);                                   // [SC]
+    int* badL = wd + L.slot_words(1);                                   // [SC] the order row holds an index outside 0 .. K-1
 
     const int tid = threadIdx.x;
     const int sc = blockIdx.x % n_sc, scene = blockIdx.x / n_sc;
     const int slot0 = sc * SC, ns = min(SC, mno - slot0);
     const size_t a0 = (size_t)scene * mno + slot0;                      // first agent of the chunk
 
-    // ---- stage: item = (k, slot, u): quad u of the staged range of row (k, slot).  A quad is two (row, t) pairs at an even pair index.
+    // ---- stage: item = (k, slot, u): quad u of the staged range of row (k, slot).  A quad is two (row, t) pairs at an even pair index.  This is
+    // eval_tile.h's item loop with the segment a part of one row; it stays written out here because the kernel measured 1 - 3 % slower through
+    // the shared loop (FINAL and MAX), with the same statements.
     const int nq = nt / 2 + 1;                                          // quads that cover nt pairs at either parity of their first index
-    const size_t n_pairs = (size_t)n_scenes * K * mno * T;              // (row, t) pairs of the whole buffer
     const int n_items = K * ns * nq;
-    for (int i0 = tid; i0 < n_items; i0 += SD_THREADS * SD_BATCH) {
+    for (int i0 = tid; i0 < n_items; i0 += EVAL_THREADS * SD_BATCH) {
         float4 v[SD_BATCH];
         size_t ps[SD_BATCH], qq[SD_BATCH];
         int dst[SD_BATCH];
         bool full[SD_BATCH];
 #pragma unroll
         for (int u = 0; u < SD_BATCH; ++u) {
-            const int i = i0 + u * SD_THREADS;
+            const int i = i0 + u * EVAL_THREADS;
             full[u] = false;
             if (i >= n_items) continue;
             const int rw = i / nq, uq = i - rw * nq, k = rw / ns, s = rw - k * ns;
@@ -110,12 +105,12 @@ __global__ __launch_bounds__(SD_THREADS) void k_select_diverse(const float* __re
             qq[u] = (ps[u] >> 1) + uq;
             dst[u] = (s * K + k) * Tp;
             const size_t p = 2 * qq[u];
-            full[u] = vec && p >= ps[u] && p + 1 < ps[u] + nt && p + 1 < n_pairs;
+            full[u] = vec && p >= ps[u] && p + 1 < ps[u] + nt;
             if (full[u]) v[u] = *reinterpret_cast<const float4*>(Y + 4 * qq[u]);
         }
 #pragma unroll
         for (int u = 0; u < SD_BATCH; ++u) {
-            const int i = i0 + u * SD_THREADS;
+            const int i = i0 + u * EVAL_THREADS;
             if (i >= n_items) break;
             const size_t p = 2 * qq[u];
             if (full[u]) {
@@ -131,7 +126,7 @@ __global__ __launch_bounds__(SD_THREADS) void k_select_diverse(const float* __re
         }
     }
     // ---- the chunk's order rows (contiguous: [ns, K]; read through the range check below) and scores (contiguous over the slots of one k)
-    for (int i = tid; i < ns * K; i += SD_THREADS) {
+    for (int i = tid; i < ns * K; i += EVAL_THREADS) {
         ordL[i] = order[a0 * K + i];
         if (mass) {
             const int k = i / ns, sl = i - k * ns;
@@ -140,33 +135,23 @@ __global__ __launch_bounds__(SD_THREADS) void k_select_diverse(const float* __re
         }
     }
     __syncthreads();
-    // ---- one lane per agent: the range check, and the weights (desire_kde_nll's step 1) in place of the scores
-    for (int sl = tid; sl < ns; sl += SD_THREADS) {
+    // ---- one lane per agent: the range check, and the weights (desire_kde_nll's step 1, eval_weight_stats) in place of the scores
+    for (int sl = tid; sl < ns; sl += EVAL_THREADS) {
         int bad = 0;
         for (int j = 0; j < K; ++j) bad |= (unsigned)ordL[sl * K + j] >= (unsigned)K;
         badL[sl] = bad;
         if (bad) cntL[sl] = 0;
         if (!mass) continue;
         float* w = wL + sl * K;
-        bool uniform = score == nullptr;
-        float mx = -FLT_MAX, sum = 0.f;
-        if (!uniform) {
-            for (int k = 0; k < K; ++k) {
-                const float v = w[k];
-                if (!(fabsf(v) <= FLT_MAX)) uniform = true;            // NaN, +-inf
-                mx = fmaxf(mx, v);
-            }
-        }
-        if (!uniform)
-            for (int k = 0; k < K; ++k) { const float e = expf(w[k] - mx); w[k] = e; sum += e; }
+        const EvalWeightStats ws = eval_weight_stats(score != nullptr, K, [&](int k) { return w[k]; }, [&](int k, float e) { w[k] = e; });
         const float u = 1.f / (float)K;
-        for (int k = 0; k < K; ++k) w[k] = uniform ? u : w[k] / sum;
+        for (int k = 0; k < K; ++k) w[k] = ws.uniform ? u : w[k] / ws.sum;
     }
     __syncthreads();
 
     // ---- the pass: group g of G lanes takes the agents g, g + n_groups, ...  Every lane of a wave stays in the loops (the shuffles need them all).
     const float r2 = radius * radius;
-    const int g = tid / G, lg = tid - g * G, n_groups = SD_THREADS / G;
+    const int g = tid / G, lg = tid - g * G, n_groups = EVAL_THREADS / G;
     for (int s0 = 0; s0 < ns; s0 += n_groups) {
         const int s = s0 + g;
         const bool active = s < ns && !badL[min(s, ns - 1)];
@@ -197,7 +182,7 @@ __global__ __launch_bounds__(SD_THREADS) void k_select_diverse(const float* __re
     __syncthreads();
 
     // ---- one lane per agent: kept in keeping order, then owned in processing order; the mass in processing order
-    for (int s = tid; s < ns; s += SD_THREADS) {
+    for (int s = tid; s < ns; s += EVAL_THREADS) {
         const int c = cntL[s];
         int no = c;
         for (int j = 0; j < K; ++j) {
@@ -210,19 +195,19 @@ __global__ __launch_bounds__(SD_THREADS) void k_select_diverse(const float* __re
         count[a0 + s] = c;
     }
     __syncthreads();
-    for (int i = tid; i < ns * K; i += SD_THREADS) {
+    for (int i = tid; i < ns * K; i += EVAL_THREADS) {
         order_out[a0 * K + i] = outL[i];
         if (mass) mass[a0 * K + i] = massL[i];
     }
     // ---- gather: the rows and scores of the first n_top entries, as desire_rank_samples copies them
     if (top_score)
-        for (int i = tid; i < ns * n_top; i += SD_THREADS) {
+        for (int i = tid; i < ns * n_top; i += EVAL_THREADS) {
             const int s = i / n_top, j = i - s * n_top;
             top_score[a0 * n_top + i] = score[((size_t)scene * K + outL[s * K + j]) * mno + slot0 + s];
         }
     if (top_Y) {
         const int T2 = 2 * T;
-        for (int i = tid; i < ns * n_top * T2; i += SD_THREADS) {
+        for (int i = tid; i < ns * n_top * T2; i += EVAL_THREADS) {
             const int rw = i / T2, e = i - rw * T2, s = rw / n_top, j = rw - s * n_top;
             top_Y[a0 * n_top * T2 + i] = Y[(((size_t)scene * K + outL[s * K + j]) * mno + slot0 + s) * T2 + e];
         }
@@ -231,30 +216,15 @@ __global__ __launch_bounds__(SD_THREADS) void k_select_diverse(const float* __re
 
 }  // namespace
 
-// The slot chunk: as many agents as the LDS holds, no more than 256 / G * 2 (two agents per group keep the tail short), spread evenly over the chunks.
-// false: one agent does not fit.
-bool select_geometry(int mno, int K, int metric, int t_end, int* SC, int* G) {
-    const size_t per = sd_agent_bytes(K, sd_staged(metric, t_end));
-    if (per > (size_t)SD_LDS_BYTES) return false;
-    int g = 1;
-    while (g < K && g < 64) g <<= 1;
-    int sc = (int)min((size_t)mno, (size_t)SD_LDS_BYTES / per);
-    sc = min(sc, max(1, 2 * SD_THREADS / g));
-    const int n_sc = (mno + sc - 1) / sc;
-    *SC = (mno + n_sc - 1) / n_sc;
-    *G = g;
-    return true;
-}
-
 void launch_select_diverse(const float* Y, const int32_t* order, const float* score, int32_t* order_out, int32_t* count, float* mass, float* top_Y,
                            float* top_score, int n_scenes, int mno, int K, int T, int metric, int t_end, int n_top, float radius, float ux,
                            float uy, hipStream_t s) {
     int SC = 1, G = 1;
     if (!select_geometry(mno, K, metric, t_end, &SC, &G)) return;       // (refused by the caller before it gets here)
-    const int n_sc = (mno + SC - 1) / SC;
-    size_t lds = (size_t)SC * sd_agent_bytes(K, sd_staged(metric, t_end));
+    const int n_sc = eval_chunks(mno, SC);
+    const size_t lds = SelLds(SelLds::staged(metric, t_end), SC, K).bytes();
     const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    const dim3 grid((unsigned)((size_t)n_scenes * n_sc)), block(SD_THREADS);
+    const dim3 grid((unsigned)((size_t)n_scenes * n_sc)), block(EVAL_THREADS);
 #define SD_LAUNCH(M)                                                                                                                        \
     hipLaunchKernelGGL(k_select_diverse<M>, grid, block, lds, s, Y, order, score, order_out, count, mass, top_Y, top_score, n_scenes, mno, K, T, \
                        t_end, SC, n_sc, G, vec, n_top, radius, ux, uy)

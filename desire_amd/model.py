@@ -630,6 +630,15 @@ class DESIREModel(object):
         return {"traj": traj, "score": sc, "order": order, "present": past[:, -1, :, 0] != 0, "count": count,
                 "prob": mass[:, :, :top].contiguous()}
 
+    @staticmethod
+    def _unit_scale(units, d):
+        """(ux, uy, f) of units "px", "norm" or a float: ux, uy turn a normalised difference into the unit, f turns a length in pixels into it
+        ("norm": along x)."""
+        if units == "norm":
+            return 1.0, 1.0, d.sx
+        f = 1.0 if units == "px" else float(units)
+        return f / d.sx, f / d.sy, f
+
     def evaluate_ranked(self, Y, score, fut_windows, top: Optional[int] = None, horizons=None, units="px", select: str = "score", nms_radius=None,
                         nms_metric: str = "final", nms_horizon=None, return_count: bool = False) -> np.ndarray:
         """[A, n_h, 4] = per horizon (ADE, FDE of the best-scored sample, best ADE, best FDE among the `top` best-scored samples) over the
@@ -648,11 +657,7 @@ class DESIREModel(object):
             raise ValueError("return_count needs select='nms'")
         top = default_top(d.K) if top is None else int(top)
         hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
-        if units == "norm":
-            ux, uy = 1.0, 1.0
-        else:
-            f = 1.0 if units == "px" else float(units)
-            ux, uy = f / d.sx, f / d.sy
+        ux, uy, _ = self._unit_scale(units, d)
         fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
         stream = torch.cuda.current_stream().cuda_stream
         order = torch.empty((d.A, d.K), device=self.device, dtype=torch.int32)
@@ -683,11 +688,8 @@ class DESIREModel(object):
         top = default_top(d.K) if top is None else int(top)
         hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
         r_px = 0.0 if collision_radius is None else float(collision_radius)
-        if units == "norm":
-            ux, uy, radius = 1.0, 1.0, r_px * d.sx
-        else:
-            f = 1.0 if units == "px" else float(units)
-            ux, uy, radius = f / d.sx, f / d.sy, r_px * f
+        ux, uy, f = self._unit_scale(units, d)
+        radius = r_px * f
         fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
         stream = torch.cuda.current_stream().cuda_stream
         dev, i32 = self.device, torch.int32
@@ -711,11 +713,7 @@ class DESIREModel(object):
         h = self._handles.get((n, 0, 0)) or self._handle(n, True)
         d = h.dims
         hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
-        if units == "norm":
-            ux, uy = 1.0, 1.0
-        else:
-            f = 1.0 if units == "px" else float(units)
-            ux, uy = f / d.sx, f / d.sy
+        ux, uy, _ = self._unit_scale(units, d)
         if weighted and score is None:
             raise ValueError("weighted=True needs the IOC scores")
         fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)

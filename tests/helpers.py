@@ -28,3 +28,19 @@ def small_dims(**kw):
                 nb_w=0.25, nb_h=0.3, sx=1.0 / 1400.0, sy=1.0 / 1100.0)
     base.update(kw)
     return Dims(**base)
+
+
+MISALIGNED_SHAPES = [(3, 1, 3, 7),      # (n_scenes, mno, K, T_pred): odd row length, segments of one row
+                     (2, 8, 3, 7)]      # the whole-window segment
+MISALIGNED_LONG = (2, 32, 2, 200)       # slot chunks of the error kernel, one segment per sample; the joint unit unchunked
+
+
+def at_byte_offset(t, off):
+    """The values of the float32 device tensor `t` at `off` (8 or 4) bytes past a torch allocation: a view into a flat buffer off / 4 floats larger.
+    The evaluation kernels' 16-byte loads need a 16-byte aligned buffer (desire_kde_nll's 8-byte loads an 8-byte aligned one): this is their fallback."""
+    import torch
+    flat = torch.zeros(t.numel() + off // 4, device=t.device, dtype=torch.float32)
+    v = flat[off // 4:].view(t.shape)
+    v.copy_(t)
+    assert flat.data_ptr() % 16 == 0 and v.data_ptr() % 16 == off and v.is_contiguous()
+    return v

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from desire_amd.spec import FLAG_COMPACT_IOC, FLAG_COMPACT_ROWS, init_weights
-from tests.helpers import make_case, small_dims
+from tests.helpers import MISALIGNED_LONG, MISALIGNED_SHAPES, at_byte_offset, make_case, small_dims
 from tests.joint_reference import (MARGIN, RADIUS_PX, SHAPES, chunk_centres, chunk_frames, joint_f32, joint_f64, make_inputs, planted_joint_scores)
 from tests.rank_reference import rank_order
 
@@ -121,6 +121,35 @@ def test_everything_matches_the_reference(torch_cuda, shape, unit):
     flat = _call(torch, h, d, Y_t, fut_t, None, None, hz, n_top, radius, ux, uy)
     assert (flat["jscore"] == 0).all() and (flat["order"] == np.arange(d.K)[None]).all()
     _same_bits(flat, got, keys=("first", "cnt", "jerr"))
+    h.close()
+
+
+@pytest.mark.parametrize("off", [8, 4])
+@pytest.mark.parametrize("shape", MISALIGNED_SHAPES + [MISALIGNED_LONG], ids=lambda s: "n%d_m%d_K%d_T%d" % s)
+def test_a_sample_tensor_off_16_byte_alignment(torch_cuda, shape, off):
+    """The 8-byte path of the streaming loops (the error table's and the unit's) for a whole buffer, evaluation form: the references as in the parity
+    test, and the aligned call's bits."""
+    torch = torch_cuda
+    from desire_amd import _lib
+    d = _dims(shape)
+    ux, uy, radius = _units(d)[1]
+    Y, fut, present, _ = make_inputs(d, radius, ux, uy, seed=6, centres=chunk_centres(d.mno, d.T_pred))
+    s = planted_joint_scores(d, 9)
+    hz, n_top = _hz(d.T_pred), min(d.K, 2)
+    f64 = joint_f64(Y, fut, None, s, hz, n_top, radius, ux, uy, d)
+    assert f64["margin"] > MARGIN
+    f32 = joint_f32(Y, fut, None, s, hz, n_top, radius, ux, uy, d)
+    h = _lib.Handle(d)
+    Y_t, fut_t, s_t = _t(torch, Y), _t(torch, fut), _t(torch, s)
+    got = _call(torch, h, d, at_byte_offset(Y_t, off), fut_t, None, s_t, hz, n_top, radius, ux, uy)
+    for key in ("first", "cnt", "order"):
+        np.testing.assert_array_equal(got[key], f32[key], err_msg=key)
+        np.testing.assert_array_equal(got[key], f64[key], err_msg=key)
+    m = max(ux, uy)
+    _close(got["jerr"], f32["jerr"], f64["jerr"], m, "jerr")
+    _close(got["out"], f32["out"], f64["out"], m, "out")
+    _close(got["jscore"], f32["jscore"], f64["jscore"], 1.0, "jscore")
+    _same_bits(got, _call(torch, h, d, Y_t, fut_t, None, s_t, hz, n_top, radius, ux, uy))
     h.close()
 
 

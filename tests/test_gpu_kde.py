@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from desire_amd.spec import FLAG_COMPACT_IOC, FLAG_COMPACT_ROWS, init_weights
-from tests.helpers import make_case, small_dims
+from tests.helpers import MISALIGNED_SHAPES, at_byte_offset, make_case, small_dims
 from tests.kde_reference import LOG_FLOOR, kde_nll_f32, kde_nll_f64, kde_outputs, make_samples
 from tests.rank_reference import planted_scores
 
@@ -118,6 +118,37 @@ def test_log_density_matches_scipy_in_every_unit(torch_cuda, shape):
                 np.testing.assert_allclose(out, kde_outputs(fr, fut, hz, d, dtype=np.float32), rtol=0, atol=1e-6)
                 assert not out[~counted.any(1)].any()
     print("worst |frame - f64| of the shape: %.3g" % worst)
+    h.close()
+
+
+@pytest.mark.parametrize("off", [8, 4])
+@pytest.mark.parametrize("shape", MISALIGNED_SHAPES, ids=lambda s: "n%d_m%d_K%d_T%d" % s)
+def test_a_sample_tensor_off_16_byte_alignment(torch_cuda, shape, off):
+    """The sample tensor 8 and 4 bytes past an allocation (4: the kernel's scalar loads in place of its 8-byte ones): the reference within the parity
+    test's bar, and the aligned call's bits."""
+    torch = torch_cuda
+    from desire_amd import _lib
+    from desire_amd.model import default_horizons
+    n, m, K, T = shape
+    d = small_dims(T_obs=4, n_grids=1, H=64, n_scenes=n, mno=m, K=K, T_pred=T)
+    fut, s, Y, planted, counted = _inputs(d)
+    h = _lib.Handle(d)
+    Y_t, fut_t, s_t = _t(torch, Y), _t(torch, fut), _t(torch, s)
+    Y_off = at_byte_offset(Y_t, off)
+    hz = default_horizons(T)
+    ux, uy = _units(d)[1]
+    for score, sc_t in ((None, None), (s, s_t)):
+        want = kde_nll_f64(Y, fut, score, ux, uy, LOG_FLOOR, d)
+        basis = float(np.abs(kde_nll_f32(Y, fut, score, ux, uy, LOG_FLOOR, d).astype(np.float64) - want).max())
+        bar = max(4.0 * basis, 1e-5)
+        out, fr = _call(torch, h, d, Y_off, fut_t, sc_t, hz, ux, uy)
+        err = float(np.abs(fr.astype(np.float64) - want).max())
+        print("offset %d %s: max |frame - f64| = %.3g, |f32 - f64| = %.3g, bar %.3g" % (off, "weighted" if score is not None else "uniform", err, basis, bar))
+        assert err <= bar
+        np.testing.assert_allclose(out, kde_outputs(want, fut, hz, d), rtol=0, atol=bar)
+        out_a, fr_a = _call(torch, h, d, Y_t, fut_t, sc_t, hz, ux, uy)
+        np.testing.assert_array_equal(out.view(np.uint32), out_a.view(np.uint32))
+        np.testing.assert_array_equal(fr.view(np.uint32), fr_a.view(np.uint32))
     h.close()
 
 

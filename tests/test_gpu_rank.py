@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from desire_amd.spec import init_weights
-from tests.helpers import make_case, small_dims
+from tests.helpers import MISALIGNED_LONG, MISALIGNED_SHAPES, at_byte_offset, make_case, small_dims
 from tests.rank_reference import planted_scores, rank_order, ranked_errors
 
 pytestmark = pytest.mark.gpu
@@ -152,6 +152,30 @@ def test_errors_match_the_reference_in_every_unit(torch_cuda, shape):
     np.testing.assert_array_equal(one[..., 2], one[..., 3])
     counted = (fut[..., 0] != 0).any(1).reshape(-1)
     assert not prev[~counted].any() and (prev[counted][:, -1] > 0).all()
+    h.close()
+
+
+@pytest.mark.parametrize("off", [8, 4])
+@pytest.mark.parametrize("shape", MISALIGNED_SHAPES + [MISALIGNED_LONG], ids=lambda s: "n%d_m%d_K%d_T%d" % s)
+def test_errors_of_a_sample_tensor_off_16_byte_alignment(torch_cuda, shape, off):
+    """The 8-byte path of the streaming loop for a whole buffer: the reference within the parity test's bar, and the aligned call's bits."""
+    torch = torch_cuda
+    from desire_amd import _lib
+    from desire_amd.model import default_horizons, default_top
+    n, m, K, T = shape
+    d = small_dims(T_obs=4, n_grids=1, H=64, n_scenes=n, mno=m, K=K, T_pred=T)
+    h = _lib.Handle(d)
+    _, fut, _, _, _ = _leaving(d, 7)
+    Y = np.random.default_rng(8).uniform(0.05, 0.95, (d.R, d.T_pred, 2)).astype(np.float32)
+    order = rank_order(planted_scores(d, 9), d)
+    Y_t, fut_t, order_t = _t(torch, Y), _t(torch, fut), _t(torch, order.astype(np.int32))
+    hz, n_top, ux, uy = default_horizons(T), default_top(d.K), 1.0 / d.sx, 1.0 / d.sy
+    aligned = _errors(torch, h, d, Y_t, fut_t, order_t, n_top, hz, ux, uy)
+    got = _errors(torch, h, d, at_byte_offset(Y_t, off), fut_t, order_t, n_top, hz, ux, uy)
+    want = ranked_errors(Y, fut, order, n_top, hz, ux, uy, d)
+    print("offset %d: max |diff| / unit = %.3g" % (off, float(np.abs(got - want).max()) / max(ux, uy)))
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-5 * max(ux, uy))
+    np.testing.assert_array_equal(got.view(np.uint32), aligned.view(np.uint32))
     h.close()
 
 

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from desire_amd.spec import FLAG_COMPACT_IOC, FLAG_COMPACT_ROWS, init_weights
-from tests.helpers import make_case, small_dims, to_oracle_layout
+from tests.helpers import MISALIGNED_SHAPES, at_byte_offset, make_case, small_dims, to_oracle_layout
 from tests.recon_reference import MEAN, MIN, SOFTMIN, bom_loss_and_grads, make_recon_case, recon_f32, recon_f64
 
 pytestmark = pytest.mark.gpu
@@ -146,6 +146,42 @@ def test_op_matches_the_contract(shape):
                 np.testing.assert_array_equal(part[k].view(np.uint32), full[k].view(np.uint32))
             else:
                 assert part[k] is None
+    h.close()
+
+
+@pytest.mark.parametrize("off", [8, 4])
+@pytest.mark.parametrize("shape", MISALIGNED_SHAPES, ids=lambda s: "n%d_m%d_K%d_T%d" % s)
+def test_op_on_a_sample_tensor_off_16_byte_alignment(shape, off):
+    """The 8-byte path of the streaming loop for a whole buffer: the contract as test_op_matches_the_contract holds it, and the aligned call's bits."""
+    from desire_amd import _lib
+    d = _dims(shape)
+    Y, fut, valid, _ = make_recon_case(d, seed=100 + sum(shape))
+    past = np.zeros((d.n_scenes, d.T_obs, d.mno, 3), np.float32)
+    past[..., 0] = valid.reshape(d.n_scenes, 1, d.mno)
+    past[..., 1:] = np.random.default_rng(3).uniform(200, 900, past[..., 1:].shape) * (past[..., :1] != 0)
+    h = _lib.Handle(d)
+    h.set_weights(init_weights(d, 41))
+    past_t, fut_t, Y_t = _t(past), _t(fut), _t(Y)
+    Y_off = at_byte_offset(Y_t, off)
+    h.encode(past_t.data_ptr(), fut_t.data_ptr())
+    for mode, tau in ((MIN, 0.0), (MEAN, 0.0), (SOFTMIN, TAU)):
+        f32, f64 = recon_f32(Y, fut, valid, d, mode, tau), recon_f64(Y, fut, valid, d, mode, tau)
+        got = _op(h, d, fut_t, Y_off, mode, tau)
+        np.testing.assert_array_equal(got["e"].view(np.uint32), f32["e"].view(np.uint32))
+        np.testing.assert_array_equal(got["winner"], f32["winner"])
+        np.testing.assert_array_equal(got["winner"], f64["winner"])
+        for key in ("w", "recon"):
+            if mode == SOFTMIN:
+                basis = float(np.abs(f32[key].astype(np.float64) - f64[key]).max())
+                bar = max(4.0 * basis, 1e-5)
+                err = float(np.abs(got[key].astype(np.float64) - f64[key]).max())
+                print("offset %d: max |%s - f64| = %.3g, |f32 - f64| = %.3g, bar %.3g" % (off, key, err, basis, bar))
+                assert err <= bar, (key, err, bar)
+            else:
+                np.testing.assert_array_equal(got[key].view(np.uint32), f32[key].view(np.uint32))
+        aligned = _op(h, d, fut_t, Y_t, mode, tau)
+        for key in got:
+            np.testing.assert_array_equal(got[key].view(np.uint32), aligned[key].view(np.uint32), err_msg=key)
     h.close()
 
 

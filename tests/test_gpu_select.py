@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from desire_amd.spec import FLAG_COMPACT_IOC, FLAG_COMPACT_ROWS, init_weights
-from tests.helpers import make_case, small_dims
+from tests.helpers import MISALIGNED_SHAPES, at_byte_offset, make_case, small_dims
 from tests.rank_reference import planted_scores, rank_order, ranked_errors
 from tests.select_reference import (DIST_FINAL, DIST_MAX, DIST_MEAN, MARGIN, METRICS, cases_of, make_inputs, margin_of_values, pair_values,
                                     select_f32, select_f64, weights)
@@ -123,6 +123,47 @@ def test_order_count_mass_and_gather_match_the_reference(torch_cuda, shape, unit
         bare = _call(torch, h, d, Y_t, order_t, s_t, metric, t_end, radius, ux, uy, n_top, mass=False, gather=False)
         np.testing.assert_array_equal(bare["order"], f32["order"]); np.testing.assert_array_equal(bare["count"], f32["count"])
     print("worst |mass - f64| of the shape: %.3g" % worst)
+    h.close()
+
+
+@pytest.mark.parametrize("off", [8, 4])
+@pytest.mark.parametrize("shape", MISALIGNED_SHAPES, ids=lambda s: "n%d_m%d_K%d_T%d" % s)
+def test_a_sample_tensor_off_16_byte_alignment(torch_cuda, shape, off):
+    """The 8-byte path of the streaming loop for a whole buffer (MEAN and FINAL): the reference as in the parity test, and the aligned call's bits."""
+    torch = torch_cuda
+    from desire_amd import _lib
+    d = _dims(shape)
+    ux, uy, radius = _units(d)[1]
+    s = planted_scores(d, 9)
+    Y, _ = make_inputs(d, radius, ux, uy, seed=32)
+    h = _lib.Handle(d)
+    Y_t, s_t = _t(torch, Y), _t(torch, s)
+    Y_off = at_byte_offset(Y_t, off)
+    order_t = _rank(torch, h, d, s_t)
+    order = order_t.cpu().numpy()
+    n_top = min(d.K, 3)
+    for metric in (DIST_MEAN, DIST_FINAL):
+        t_end = d.T_pred
+        v64 = pair_values(Y, metric, t_end, ux, uy, d, np.float64)
+        assert margin_of_values(v64, metric, radius) > MARGIN
+        f64 = select_f64(Y, order, s, metric, t_end, radius, ux, uy, d, values=v64)
+        f32 = select_f32(Y, order, s, metric, t_end, radius, ux, uy, d)
+        for key in ("order", "count"):
+            np.testing.assert_array_equal(f32[key], f64[key])
+        got = _call(torch, h, d, Y_off, order_t, s_t, metric, t_end, radius, ux, uy, n_top)
+        np.testing.assert_array_equal(got["order"], f32["order"])
+        np.testing.assert_array_equal(got["count"], f32["count"])
+        basis = float(np.abs(f32["mass"].astype(np.float64) - f64["mass"]).max())
+        bar = max(4.0 * basis, 1e-5)
+        err = float(np.abs(got["mass"].astype(np.float64) - f64["mass"]).max())
+        print("offset %d metric %d: max |mass - f64| = %.3g, |f32 - f64| = %.3g, bar %.3g" % (off, metric, err, basis, bar))
+        assert err <= bar
+        want_Y, want_s = _rows(Y, s, got["order"], n_top, d)
+        np.testing.assert_array_equal(got["top_Y"].view(np.uint32), want_Y.view(np.uint32))
+        np.testing.assert_array_equal(got["top_score"].view(np.uint32), want_s.view(np.uint32))
+        aligned = _call(torch, h, d, Y_t, order_t, s_t, metric, t_end, radius, ux, uy, n_top)
+        for key in got:
+            np.testing.assert_array_equal(got[key].view(np.uint32), aligned[key].view(np.uint32), err_msg=key)
     h.close()
 
 
