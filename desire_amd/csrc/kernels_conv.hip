@@ -7,10 +7,10 @@
 //   conv1   VALU   [32,32,1]  -s2 SAME->  [16,16,32]     (0.4 MF/agent)
 //   conv2   MFMA   gather, rows = output pixels, K = 25 taps x 32 ci
 //   conv3   MFMA   gather, VALID, K = 25 taps x 64 ci
-//   deconv2 MFMA   scatter: G[(sample,in-pixel), (tap,co)] = In @ W, accumulated into an
-//                  LDS output tile (gather form would waste 75% of the MFMAs on a 4->8 VALID
-//                  transposed conv); each wave owns (sample-pair, co-half) so the read-modify-
-//                  write is race-free and deterministic
+//   deconv2 MFMA   scatter: G[(sample,in-pixel), (tap,co)] = In @ W, accumulated into the lane's
+//                  64 output registers (gather form would waste 75% of the MFMAs on a 4->8 VALID
+//                  transposed conv); a half-wave owns (sample, co-half) entirely, so the
+//                  accumulation is register-local and deterministic
 //   deconv3 MFMA   stride-2 transposed conv split in its 4 output-parity classes, each a
 //                  stride-1 gather conv with 2x2 / 2x3 / 3x2 / 3x3 taps: accumulators ARE the
 //                  output, no scatter
@@ -137,88 +137,97 @@ void launch_conv3(const ConvArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// deconv2: [n,4,4,128] -> [n,8,8,64], 5x5 VALID stride 1, scatter form.
+// deconv2: [n,4,4,128] -> [n,8,8,64], 5x5 VALID stride 1, scatter form with the output tile in registers.
 // Workgroup = 4 samples; wave = (co-half hf = w&1, sample pair sp = w>>1).
-// M-tile rows = (sample s in {0,1}, input pixel p in 0..15); A (K=128) lives in 64 VGPRs.
+// M-tile rows r = ix + 4 s + 8 iy (sample s of the pair, input pixel (iy, ix)); A (K=128) lives in 64 VGPRs.
+// With these rows acc_row(i) puts sample s0 + (lane>>5) ENTIRELY into its half-wave and input pixel (i>>2, i&3) into accumulator
+// register i, so a lane keeps the whole 8 x 8 output column of one (sample, channel) in 64 registers O[oy][ox] and tap (ky, kx) is
+//     O[iy + ky][ix + kx] += acc[4 iy + ix]
+// with compile-time register indices: 16 VALU adds, no LDS read-modify-write, no zeroing pass, no cross-lane traffic.
+// (Until the rows were renumbered they were (s << 4) | p: a lane's 16 registers belonged to 8 pixels of EACH sample and the tile was
+// accumulated in LDS, 16 reads + 16 writes per lane and tap, fenced against the next tap's MFMAs.  Same sums in the same order: bit-identical.)
 // ------------------------------------------------------------------------------------------------
-// (Measured and dropped, round 5: a one-off half-tap stagger of the second workgroup of every CU -- by dispatch order or by the hardware wave slot --
-// in case the two co-resident workgroups ran their scatters in lock-step: 19.64 -> 19.64 - 20.06 ms, the phases are not aligned to begin with.)
-// (Measured and dropped, round 5: the tap's K = 128 as two interleaved chains over its halves, summed at the end -- 19.65 -> 23.3 ms: the chain consumes
-// the B fragments in the order they were requested, the interleaved form needs fragment 8 first; `-amdgpu-sched-strategy=max-ilp` for this file: 20.8 ms.)
-// (Measured and dropped: two taps interleaved into two accumulators -- the 64-deep dependent chain per tap is ~12 % of the kernel, but
-// with the LDS scatter the paired form was slower)
+// Measured on the register form (512 windows, same box, step ms; scatter form 135.1 - 135.5; history and the scatter form's own dropped
+// experiments -- workgroup stagger, K = 128 as two chains over its halves, ds_add_f32 -- in docs/DESIGN_DETAIL.md section 4):
+//   kept     taps in order, one accumulator, tile staged once through LDS for float4 stores          133.0 - 133.2
+//   dropped  epilogue straight from registers (64 dword stores per lane, a full 128-byte line each)   133.3 - 133.5 (and 200 - 370 B of scratch)
+//   dropped  the adds of tap t issued behind the first four MFMAs of tap t+1 (second accumulator)     133.2 - 133.4
+//   dropped  two taps in flight: two accumulators whose MFMAs alternate, quarter-tap fragment sets    133.1 - 133.3
+//   dropped  two workgroups per CU (what 241 registers give when nothing holds the count up)          136.3 - 136.8
+// A dependent 32x32x2 chain issues at the pipe's rate (issue interval = dependent latency = 64 cycles), so a second chain has nothing to fill.
 template <bool FWD>
 __global__ __launch_bounds__(DS_WG) void k_deconv2(ConvArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float out_s[];     // [4][64 px][64 co]
+    extern __shared__ __attribute__((aligned(16))) float out_s[];     // [4][64 px][64 co]: the finished tile on its way to the float4 stores
     const int lane = lane_id(), w = wave_id();
     const int hf = w & 1, sp = w >> 1;
+    // One wave per SIMD, as the scatter form ran (286 registers).  This form needs 241, and left at that two workgroups share a CU: step 136.3 - 136.8 ms
+    // against 133.0 - 133.2 with one (scatter form 135.1 - 135.5).  Naming the last accumulation register as clobbered puts the kernel's register count
+    // above half of the SIMD's 512.
+    asm volatile("" ::: "a255");
     // tiles bx, bx + gridDim.x, ..: one per workgroup unless the grid was sized from a count HINT (dyn_count.h: DynCount.hint) that the real count exceeds
     DYN_N(a, n, blockIdx.x * 4)
     for (int bx = blockIdx.x; bx * 4 < a.n; bx += gridDim.x) {
         const int s0 = bx * 4 + sp * 2;
         const int c = lane & 31, hi = lane >> 5;
-        float* my = out_s + (sp * 2) * 4096;
-        // zero this wave's region: 2 samples x 64 px x 32 co
-        // this wave's region = [2 samples x 64 px] x its 32 output channels; 8 lanes x float4 cover one row of it
-        const int er = lane >> 3, ec = hf * 32 + (lane & 7) * 4;
-        for (int i = 0; i < 16; ++i) *reinterpret_cast<float4*>(my + (i * 8 + er) * 64 + ec) = make_float4(0.f, 0.f, 0.f, 0.f);
-        // A fragments: row = lane&31 -> (s = row>>4, p = row&15)
+        // this lane's output: sample s0 + hi, channel hf * 32 + c, all 8 x 8 pixels -- cleared for every tile
+        float O[8][8];
+    #pragma unroll
+        for (int oy = 0; oy < 8; ++oy)
+    #pragma unroll
+            for (int ox = 0; ox < 8; ++ox) O[oy][ox] = 0.f;
+        // A fragments: row = lane&31 = ix + 4 s + 8 iy -> (s = (row>>2)&1, p = 4 iy + ix)
         float4 af[16];
         {
             const int row = lane & 31;
-            const int smp = min(s0 + (row >> 4), a.n - 1);
-            const float* src = a.in + ((size_t)smp * 16 + (row & 15)) * 128 + 4 * hi;
+            const int smp = min(s0 + ((row >> 2) & 1), a.n - 1);
+            const float* src = a.in + ((size_t)smp * 16 + (row >> 3) * 4 + (row & 3)) * 128 + 4 * hi;
     #pragma unroll
             for (int g = 0; g < 16; ++g) af[g] = *reinterpret_cast<const float4*>(src + g * 8);
         }
-        // taps: B fragments of tap t+1 are fetched while tap t contracts (two register sets, loop unrolled
-        // by 2 so the sets are addressed statically).  The scatter is a plain LDS read-add-write: this wave
-        // is the only writer of its region (deterministic), and ds_add_f32 measured 1.4x SLOWER on the whole
-        // kernel (LDS atomics retire at a fraction of the plain ds_read/ds_write rate).
-        auto load_b = [&](float4 (&b)[16], int tap) {
-            const float4* bp = a.Wp + ((size_t)(tap * 2 + hf) * 16) * 64 + lane;
+        // taps in halves of 8 k-groups: the B fragments of half q+1 are fetched while half q contracts (32 MFMAs = 2048 cycles in flight).  Two
+        // register sets of 8 float4; the 50 halves are unrolled so that the sets and the elements of O are addressed statically, with the
+        // sched_barrier fences that keep hipcc from sinking a prefetch to its use.  The offset is opaque per tile: the fragment addresses do not
+        // depend on the tile, and hoisted out of the tile loop the 400 loads live across it (3.6 KB of scratch per lane).
+        int woff = 0;
+        asm volatile("" : "+s"(woff));
+        const float4* wp = a.Wp + woff + lane;
+        auto load_b = [&](float4 (&b)[8], int q) {
+            const float4* bp = wp + ((size_t)((q >> 1) * 2 + hf) * 16 + (q & 1) * 8) * 64;
     #pragma unroll
-            for (int g = 0; g < 16; ++g) b[g] = bp[g * 64];
+            for (int g = 0; g < 8; ++g) b[g] = bp[g * 64];
         };
-        auto do_tap = [&](const float4 (&b)[16], int tap) {
-            const int ky = tap / 5, kx = tap - ky * 5;
-            f32x16 acc = zero16();
+        float4 b[2][8];
+        load_b(b[0], 0);
+        f32x16 acc = zero16();
     #pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                acc = mfma32(af[g].x, b[g].x, acc);
-                acc = mfma32(af[g].y, b[g].y, acc);
-                acc = mfma32(af[g].z, b[g].z, acc);
-                acc = mfma32(af[g].w, b[g].w, acc);
+        for (int q = 0; q < 50; ++q) {
+            if (q + 1 < 50) load_b(b[(q + 1) & 1], q + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            const float4 (&bt)[8] = b[q & 1];
+            if (!(q & 1)) acc = zero16();
+    #pragma unroll
+            for (int g = 0; g < 8; ++g) {
+                const float4 av = af[(q & 1) * 8 + g];
+                acc = mfma32(av.x, bt[g].x, acc);
+                acc = mfma32(av.y, bt[g].y, acc);
+                acc = mfma32(av.z, bt[g].z, acc);
+                acc = mfma32(av.w, bt[g].w, acc);
             }
-            // the 16 targets of a lane are distinct (different input pixels, same tap) and no other lane touches its column:
-            // read all, then add and write all -- written as one dependent chain the compiler serialises 16 LDS round trips
-            float* dst[16]; float old[16];
+            if (q & 1) {
+                // accumulator register i = input pixel (iy, ix) = (i >> 2, i & 3) of this lane's own sample and channel: the tap is 16 adds.
+                // Every output element receives 0 + G_tap0 + G_tap1 + .. in ascending tap order, as in the scatter form: the same bits
+                const int tap = q >> 1, ky = tap / 5, kx = tap - ky * 5;
     #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int rr = acc_row(i);
-                const int s = rr >> 4, p = rr & 15;
-                const int o = ((p >> 2) + ky) * 8 + (p & 3) + kx;
-                dst[i] = my + (s * 64 + o) * 64 + hf * 32 + c;
+                for (int i = 0; i < 16; ++i) O[(i >> 2) + ky][(i & 3) + kx] = O[(i >> 2) + ky][(i & 3) + kx] + acc[i];
             }
-    #pragma unroll
-            for (int i = 0; i < 16; ++i) old[i] = *dst[i];
-    #pragma unroll
-            for (int i = 0; i < 16; ++i) *dst[i] = old[i] + acc[i];
-        };
-        float4 b0[16], b1[16];
-        load_b(b0, 0);
-    #pragma clang loop unroll(disable)
-        for (int tap = 0; tap < 24; tap += 2) {
-            load_b(b1, tap + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            do_tap(b0, tap);
-            __builtin_amdgcn_sched_barrier(0);
-            load_b(b0, tap + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            do_tap(b1, tap + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
-        do_tap(b0, 24);
+        // the finished tile goes through LDS once, so that 8 lanes x float4 store one 128-byte row of (pixel, 32 channels).  This wave's region =
+        // [2 samples x 64 px] x its 32 output channels; it is the only reader and writer of it (no barrier)
+        float* my = out_s + (sp * 2) * 4096;
+    #pragma unroll
+        for (int o = 0; o < 64; ++o) my[(hi * 64 + o) * 64 + hf * 32 + c] = O[o >> 3][o & 7];
+        const int er = lane >> 3, ec = hf * 32 + (lane & 7) * 4;
         const float4 sc4 = *reinterpret_cast<const float4*>(a.scale + ec), sh4 = *reinterpret_cast<const float4*>(a.shift + ec);
         for (int i = 0; i < 16; ++i) {
             const int sp_px = i * 8 + er;                                  // 0..127 = (sample, pixel)
