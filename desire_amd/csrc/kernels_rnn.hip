@@ -395,6 +395,40 @@ template <> struct MaskT<32> { typedef unsigned type; };
 __device__ __forceinline__ int ffs_(unsigned m) { return __ffs((int)m); }
 __device__ __forceinline__ int ffs_(unsigned long long m) { return __ffsll((long long)m); }
 typedef float f32x4v __attribute__((ext_vector_type(4)));
+// The pooling chain of one bin (k_ioc, the dense form): acc += A[32 rows][8 G] W_b, G = H / 8 groups = whole pairs of chunks, first chunk `b0`
+// requested by the caller (load_b4, ahead of the build of the next operand).  The products and their order are mma_run<1>'s; the chunks are
+// unrolled over the two fragment sets so that no set is carried around a loop (every wait is a whole chunk behind its loads), and the A
+// fragment of group g + 1 is read before the MFMAs of group g, fenced per group.  Why: docs/DESIGN_DETAIL.md section 4.
+template <int G>
+__device__ __forceinline__ void ioc_bin_chain(f32x16& acc, const float* a_lane, const float4* __restrict__ b_lane, float4 (&b0)[4]) {
+    static_assert(G % 8 == 0, "whole pairs of chunks");
+    float4 b1[4];
+    float4 an = *reinterpret_cast<const float4*>(a_lane);
+    auto chunk = [&](int g0, const float4 (&b)[4]) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float4 av = an;
+            if (g0 + j + 1 < G) an = *reinterpret_cast<const float4*>(a_lane + (g0 + j + 1) * 8);
+            __builtin_amdgcn_sched_barrier(0);
+            acc = mfma32(av.x, b[j].x, acc);
+            acc = mfma32(av.y, b[j].y, acc);
+            acc = mfma32(av.z, b[j].z, acc);
+            acc = mfma32(av.w, b[j].w, acc);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+#pragma unroll
+    for (int c = 0; c < G / 4; c += 2) {
+        load_b4(b1, b_lane, 4 * c + 4);
+        __builtin_amdgcn_sched_barrier(0);
+        chunk(4 * c, b0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (c + 2 < G / 4) load_b4(b0, b_lane, 4 * c + 8);
+        __builtin_amdgcn_sched_barrier(0);
+        chunk(4 * c + 4, b1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
 // CP ("compact pooling", opt-in: DESIRE_IOC_VARIANT=8, TM = 32): only the rows that have a neighbour in bin b are built,
 // packed into the first rows of the operand tile, contracted as 16-row v_mfma_f32_16x16x4_f32 tiles and added into the rows
 // they belong to -- at the bench's density (about a quarter of the rows per bin) that halves the pooling MFMAs and builds a
@@ -697,16 +731,11 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
                     const int b = ffs_(om) - 1;
                     om &= om - 1;
                     const float4* wb = a.Wsoc + ((size_t)(b * NT + cb) * GH) * 64 + lane;
-                    MmaHead hd;
-                    if (active) mma_begin(hd, wb, GH);             // this bin's first weight fragments travel while the next operand is built
+                    float4 wb0[4];
+                    if (active) load_b4(wb0, wb, 0);               // this bin's first weight fragments travel while the next operand is built
                     if (om) build(ffs_(om) - 1, buf ^ 1);
                     IOC_TICK(3)
-                    if (active) {
-                        f32x16 t1[1] = {soc};
-                        const float* ap1[1] = {AB + buf * TM * LDB + (mt * 32 + (lane & 31)) * LDB + 4 * (lane >> 5)};
-                        mma_run<1>(t1, ap1, wb, GH, hd);
-                        soc = t1[0];
-                    }
+                    if (active) ioc_bin_chain<GH>(soc, AB + buf * TM * LDB + (mt * 32 + (lane & 31)) * LDB + 4 * (lane >> 5), wb, wb0);
                     IOC_TICK(4)
                     __syncthreads();
                     IOC_TICK(5)
