@@ -27,8 +27,10 @@ EXPORTS = [
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
     "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse", "desire_joint_metrics",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
-    "desire_set_recon_loss", "desire_recon_weights",
+    "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy",
 ]
+OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
+OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
 RNG_BITS, RNG_NORMAL, RNG_LATENT, RNG_ROLLOUT = 0, 1, 2, 3          # desire_rng_fill kinds (DESIRE_RNG_*)
 DIST_FINAL, DIST_MEAN, DIST_MAX = 0, 1, 2                           # desire_select_diverse metrics (DESIRE_DIST_*)
 RECON_MEAN, RECON_MIN, RECON_SOFTMIN = 0, 1, 2                      # desire_set_recon_loss / desire_recon_weights modes (DESIRE_RECON_*)
@@ -105,6 +107,7 @@ def load() -> C.CDLL:
     lib.desire_select_diverse.argtypes = [vp, f32p, vp, f32p, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, vp, f32p, f32p, f32p, vp]
     lib.desire_joint_metrics.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, f32p, f32p,
                                          vp, f32p, vp]
+    lib.desire_occupancy.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, i32, i32, vp, vp, f32p, f32p, f32p, f32p, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
     lib.desire_rollout_samples.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
@@ -329,6 +332,21 @@ class Handle:
                                            hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, int(n_top), C.c_float(radius), C.c_float(unit_x),
                                            C.c_float(unit_y), first_ptr or None, cnt_ptr or None, jerr_ptr or None, jscore_ptr or None,
                                            jorder_ptr or None, out_ptr or None, stream or None))
+
+    def occupancy(self, yhat_ptr: int, fut_ptr: int, present_ptr: int, score_ptr: int, horizons, mode: int, Oh: int, Ow: int, occ_ptr: int,
+                  exp_ptr: int = 0, hit_ptr: int = 0, viol_ptr: int = 0, off_ptr: int = 0, mask_ptr: int = 0, mask_of_scene_ptr: int = 0,
+                  stream: int = 0) -> None:
+        """Predicted occupancy maps of the K weighted samples on an Oh x Ow grid over the normalised frame: occ [n, n_h, Oh, Ow] = the probability
+        that at least one agent is in the cell at frame h - 1 (OCC_AT) or at any counted frame before h (OCC_UNTIL), exp (same shape) = the
+        expected number of agents; per agent [A, n_h]: off = the weight of its samples that are off frame, viol = the weight on cells whose byte
+        of mask [n_masks, Oh, Ow] uint8 is 0 (mask_of_scene [n] int32 on the device, negative: none), hit = the weight on the ground truth's cell
+        (fut_ptr and OCC_AT only).  Exactly one of fut_ptr (evaluation) and present_ptr ([A] uint8, prediction time); score_ptr = 0: equal
+        weights, else softmax(score) as in kde_nll."""
+        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+        _chk(self.lib.desire_occupancy(self._h, yhat_ptr or None, fut_ptr or None, present_ptr or None, score_ptr or None,
+                                       hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, int(mode), int(Oh), int(Ow), mask_ptr or None,
+                                       mask_of_scene_ptr or None, occ_ptr or None, exp_ptr or None, hit_ptr or None, viol_ptr or None,
+                                       off_ptr or None, stream or None))
 
     def set_training(self, on: bool) -> None:
         _chk(self.lib.desire_set_training(self._h, int(on)))

@@ -366,6 +366,40 @@ extern "C" int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, con
     return DESIRE_OK;
 }
 
+// ---- predicted occupancy maps of the K weighted samples (kernels_occ.hip): the contract is stated in include/desire_hip.h ----
+extern "C" int desire_occupancy(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present, const float* dev_score,
+                                const int32_t* host_horizons, int32_t n_h, int32_t mode, int32_t Oh, int32_t Ow, const uint8_t* dev_mask,
+                                const int32_t* dev_mask_of_scene, float* dev_occ, float* dev_exp, float* dev_hit, float* dev_viol, float* dev_off,
+                                void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_occ) return fail(DESIRE_ERR_ARG, "dev_occ is NULL");
+    if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (mode != DESIRE_OCC_AT && mode != DESIRE_OCC_UNTIL) return fail(DESIRE_ERR_ARG, "mode must be DESIRE_OCC_AT or DESIRE_OCC_UNTIL (0, 1)");
+    if (Oh < 1 || Oh > DESIRE_OCC_MAX_SIDE) return fail(DESIRE_ERR_ARG, "Oh must be 1.." + std::to_string(DESIRE_OCC_MAX_SIDE));
+    if (Ow < 1 || Ow > DESIRE_OCC_MAX_SIDE) return fail(DESIRE_ERR_ARG, "Ow must be 1.." + std::to_string(DESIRE_OCC_MAX_SIDE));
+    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
+    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    if (dev_hit && !dev_fut) return fail(DESIRE_ERR_ARG, "dev_hit needs dev_fut (the cell of the ground truth)");
+    if (dev_hit && mode != DESIRE_OCC_AT) return fail(DESIRE_ERR_ARG, "dev_hit is defined in mode DESIRE_OCC_AT only");
+    if (dev_viol && (!dev_mask || !dev_mask_of_scene)) return fail(DESIRE_ERR_ARG, "dev_viol needs dev_mask and dev_mask_of_scene");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read occupancy from");
+    RankHz hz{};
+    if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
+    if ((uint64_t)d.mno * (uint64_t)d.K >= (1ull << 32)) return fail(DESIRE_ERR_ARG, "mno * K must be below 2^32 (the stamps of the occupancy kernel)");
+    int kc = 0, fc = 0, rows = 0;
+    const int until = mode == DESIRE_OCC_UNTIL;
+    if (!occupancy_geometry(d.K, until ? hz.h[hz.n - 1] : 1, Oh, Ow, until, &kc, &fc, &rows))
+        return fail(DESIRE_ERR_ARG, "one grid row does not fit the occupancy kernel's LDS");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    launch_kde_weights(dev_score, W(h, "kde_w"), W(h, "kde_st"), d.n_scenes, d.mno, d.K, s);
+    launch_occupancy(dev_Yhat, dev_fut, dev_present, W(h, "kde_w"), dev_viol ? dev_mask : nullptr, dev_viol ? dev_mask_of_scene : nullptr, dev_occ,
+                     dev_exp, dev_hit, dev_viol, dev_off, d.n_scenes, d.mno, d.K, d.T_pred, Oh, Ow, mode, hz, d.sx, d.sy, s);
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- the device generator (philox.h, kernels_rng.hip): the packing of its counters is stated in include/desire_hip.h ------------------------
 namespace {
 int rng_check_packing(const desire_ctx* h, uint32_t slot_base) {

@@ -1,7 +1,7 @@
 // eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
-// _recon.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// _recon / _occ.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
 // that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
-// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp compiles it with g++ (tests/test_eval_lds.py).
+// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp and occ_lds_driver.cpp compile it with g++ (tests/test_eval_lds.py, test_occ_lds.py).
 #pragma once
 #include <stddef.h>
 
@@ -129,4 +129,39 @@ struct JointLds {
 inline int joint_chunk_frames(int mno, int T) {
     const size_t fixed = JointLds(mno, 0).bytes(), per = JointLds(mno, 1).bytes() - fixed, fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;
     return (int)((size_t)T < fit ? (size_t)T : fit);
+}
+
+// ---- k_occupancy: 32-bit words.  Over the `cells` of a band of grid rows: E, q, P floats (expected count, product of the complements, one
+// agent's marginal) and, in mode UNTIL, S uint32 (the stamp of the last (agent, k) that reached the cell: `at most once per sample`).  Each is
+// an array of its own, so the lanes of a wave that walk consecutive cells walk consecutive banks in every one of them, and E, q, P of one cell
+// are never read by one instruction.  Behind them the staging of one chunk of an agent, `ent` = KC samples x FC frames: id int32 [ent] (the
+// cell of a position, or a marker), then w float, off int, viol int [ent] (per sample of the chunk: its weight, `was off frame`, `visited a
+// masked cell`; KC <= ent) and cm int [ent] (per frame of the chunk: counted; FC <= ent).
+struct OccLds {
+    enum { ENTRIES = 512, CHUNK_REGIONS = 5 };
+    int cells, ent, until;
+    EVAL_HD constexpr OccLds(int cells_, int ent_, int until_) : cells(cells_), ent(ent_), until(until_ ? 1 : 0) {}
+    EVAL_HD static constexpr int cell_words(int until_) { return until_ ? 4 : 3; }
+    EVAL_HD constexpr size_t E() const { return 0; }
+    EVAL_HD constexpr size_t q() const { return (size_t)cells; }
+    EVAL_HD constexpr size_t P() const { return (size_t)2 * cells; }
+    EVAL_HD constexpr size_t S() const { return (size_t)3 * cells; }                        // (mode UNTIL only)
+    EVAL_HD constexpr size_t chunk(int r) const { return (size_t)cell_words(until) * cells + (size_t)r * ent; }     // region r: id, w, off, viol, cm
+    EVAL_HD constexpr size_t bytes() const { return 4 * chunk(CHUNK_REGIONS); }
+};
+// frames = the frames of a sample that one workgroup walks at most: 1 in mode AT, the largest horizon in mode UNTIL.  The chunk: all frames of
+// as many samples as ENTRIES positions hold (spread evenly over the chunks), or part of one sample's frames when they are more than that.  The
+// band: as many whole grid rows as the rest of the budget holds, spread evenly over the bands.  Ow <= 1024: one row always fits.
+inline bool occupancy_geometry(int K, int frames, int Oh, int Ow, int until, int* KC, int* FC, int* rows) {
+    if (K < 1 || frames < 1 || Oh < 1 || Ow < 1) return false;
+    const int fc = eval_min(frames, (int)OccLds::ENTRIES);
+    int kc = eval_min(K, eval_max(1, (int)OccLds::ENTRIES / fc));
+    kc = eval_chunks(K, eval_chunks(K, kc));
+    const size_t left = (size_t)EVAL_LDS_BYTES - OccLds(0, kc * fc, until).bytes();
+    const size_t fit = left / (4 * (size_t)OccLds::cell_words(until)) / (size_t)Ow;
+    if (fit < 1) return false;
+    const int r = (size_t)Oh < fit ? Oh : (int)fit;
+    *KC = kc; *FC = fc;
+    *rows = eval_chunks(Oh, eval_chunks(Oh, r));
+    return true;
 }

@@ -19,6 +19,7 @@
 //   k_sample_errors   the segment's first row in the error region (sg * rows per segment)
 //   k_joint_unit      sg: the slot when the unit is walked in frame chunks (one segment per slot, EVAL_ONE_ROW), 0 for the whole unit
 //   k_recon_weights   sg: the sample of the pass
+//   k_occupancy       sg: the sample of the chunk (one segment per sample: a run of one row's frames, EVAL_ONE_ROW)
 // An item is (segment, quad): a quad is two pairs at an even pair index of the buffer, and seg_len / 2 + 1 quads cover a segment at either
 // parity of its first index.  A lane issues the BATCH 16-byte loads of its items before it consumes any; a quad that straddles its segment's
 // ends, and every quad of a buffer off 16-byte alignment (vec == 0), takes 8-byte loads of the pairs that are inside.  With one segment its

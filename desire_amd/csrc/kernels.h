@@ -279,6 +279,14 @@ void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* prese
                           int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
                           const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
 
+// ---- predicted occupancy maps of the K weighted samples (kernels_occ.hip) ----
+// step 1 of launch_kde_nll alone: w [R] (the score layout) and st [A, 2], the handle's "kde_w" / "kde_st"; score may be nullptr (kernels_kde.hip)
+void launch_kde_weights(const float* score, float* w, float* st, int n_scenes, int mno, int K, hipStream_t s);
+// exactly one of fut / present; w = the filled "kde_w"; mask + mask_of_scene (with viol), expv, hit (fut and mode AT only), viol and off may be nullptr
+void launch_occupancy(const float* Y, const float* fut, const uint8_t* present, const float* w, const uint8_t* mask, const int32_t* mask_of_scene,
+                      float* occ, float* expv, float* hit, float* viol, float* off, int n_scenes, int mno, int K, int T, int Oh, int Ow, int mode,
+                      const RankHz& hz, float sx, float sy, hipStream_t s);
+
 // ---- per-sample reconstruction errors and the best-of-many / soft-min weights (kernels_recon.hip) ----
 // lmask / nfut: launch_loss_mask's; e, w [A, K], win [A], val [A] are all written (none may be nullptr); mode = DESIRE_RECON_*; no scratch
 void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,

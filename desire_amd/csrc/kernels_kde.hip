@@ -157,6 +157,12 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_kde_nll(const float* __restric
 
 }  // namespace
 
+// step 1 alone, for a caller that weighs the samples itself (desire_occupancy): the same kernel into the same scratch
+void launch_kde_weights(const float* score, float* w, float* st, int n_scenes, int mno, int K, hipStream_t s) {
+    const int A = n_scenes * mno;
+    hipLaunchKernelGGL(k_kde_weights, dim3((A + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, s, score, w, st, A, mno, K);
+}
+
 void launch_kde_nll(const float* Y, const float* fut, const float* score, float* w, float* st, float* out, float* frame, int n_scenes, int mno,
                     int K, int T, const RankHz& hz, float sx, float sy, float ux, float uy, float log_floor, hipStream_t s) {
     int SA = 1;

@@ -4,7 +4,7 @@ device, errors per horizon of the best-scored sample (top-1), of the best among 
     python -m desire_amd.evaluate --checkpoint save/social_model-400.npz --data_dir data/ --max_num_obj 32 --d_dim 128 \\
         --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json] \\
         [--generator cvae|rollout] [--nll] [--select nms --nms_radius 20 [--nms_metric final|mean|max] [--nms_horizon 12]] \\
-        [--joint [--collision_radius 10]]
+        [--joint [--collision_radius 10]] [--occupancy 64x64 [--occupancy_mode at|until]]
 
 The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
@@ -49,6 +49,13 @@ def build_parser() -> argparse.ArgumentParser:
                         "next to the ground truth's under the same rule, see --collision_radius")
     p.add_argument("--collision_radius", type=float, default=None,
                    help="--joint: two agents closer than this many pixels in a frame touch (default: 0, nothing touches)")
+    p.add_argument("--occupancy", type=str, default=None, metavar="OHxOW",
+                   help="also report the predicted occupancy maps of the score-weighted samples on a grid of OH x OW cells over the frame "
+                        "(desire_occupancy): per horizon the mean of -log(max(mass on the ground truth's cell, 1e-6)), the mean mass off the frame and "
+                        "the mean expected number of agents in the frame per window")
+    p.add_argument("--occupancy_mode", type=str, default="at", choices=("at", "until"),
+                   help="--occupancy: the maps at the frame of the horizon (at) or swept over every frame before it (until); the mass on the ground "
+                        "truth's cell is always the frame's")
     p.add_argument("--out", type=str, default=None, help="write the result JSON here (default: standard output only)")
     return p
 
@@ -106,6 +113,10 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     joint = bool(getattr(args, "joint", False))
     j_sums, j_windows = np.zeros((len(hz), 4), np.float64), np.zeros(len(hz), np.int64)
     j_cnt = {k: np.zeros((len(hz), 2), np.int64) for k in ("top1", "all_K", "ground_truth")}      # (touching, taking part)
+    occ_grid = parse_grid(getattr(args, "occupancy", None))
+    occ_mode = str(getattr(args, "occupancy_mode", "at") or "at")
+    o_nll, o_off, o_exp = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64)
+    o_at = np.zeros(len(hz), np.int64)                                                           # agents counted at the horizon's own frame
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
@@ -130,6 +141,10 @@ def evaluate(args, data_loader=None, model=None) -> dict:
             j_cnt["top1"] += cnt[np.arange(cnt.shape[0]), jm["order"][:, 0]].sum(0)
             j_cnt["all_K"] += cnt[:, :K].sum((0, 1))
             j_cnt["ground_truth"] += cnt[:, K].sum(0)
+        if occ_grid:
+            om = model.evaluate_occupancy(Y, score, fut, occ_grid, horizons=hz, mode=occ_mode)
+            o_hit = om["hit"] if occ_mode == "at" else model.evaluate_occupancy(Y, score, fut, occ_grid, horizons=hz, mode="at")["hit"]
+            o_exp += om["expected"].astype(np.float64).sum((0, 2, 3))
         pw, fw = np.stack(past), np.stack(fut)
         mno = ranked.shape[0] // pw.shape[0]
         valid = np.zeros((pw.shape[0], mno), bool)
@@ -144,6 +159,11 @@ def evaluate(args, data_loader=None, model=None) -> dict:
             sums["best_of_K"][i] += best[c, i, 2:4].sum(0)
             if nms:
                 nms_sums[i] += distinct[c, i, 2:4].sum(0)
+            if occ_grid:
+                at = (valid & seen[:, h - 1]).reshape(-1)
+                o_at[i] += int(at.sum())
+                o_nll[i] += float(-np.log(np.maximum(o_hit.reshape(-1, len(hz))[at, i].astype(np.float64), 1e-6)).sum())
+                o_off[i] += float(om["off"].reshape(-1, len(hz))[c, i].astype(np.float64).sum())
             if nll:
                 nll_sums["uniform"][i] += nll_u[c, i].astype(np.float64).sum(0)
                 nll_sums["score_weighted"][i] += nll_w[c, i].astype(np.float64).sum(0)
@@ -184,7 +204,23 @@ def evaluate(args, data_loader=None, model=None) -> dict:
                         "top1": {"jade": [float(v) for v in m[:, 0]], "jfde": [float(v) for v in m[:, 1]]},
                         "best_of_top": {"jade": [float(v) for v in m[:, 2]], "jfde": [float(v) for v in m[:, 3]]},
                         "collision_rate": rate, "slots": [int(v) for v in j_cnt["ground_truth"][:, 1]]}
+    if occ_grid:
+        res["occupancy"] = {"grid": [int(occ_grid[0]), int(occ_grid[1])], "mode": occ_mode, "weights": "score", "hit_floor": 1e-6,
+                            "agents_at_frame": [int(v) for v in o_at],
+                            "hit_nll": [float(o_nll[i] / max(int(o_at[i]), 1)) for i in range(len(hz))],
+                            "off_mass": [float(o_off[i] / max(int(agents[i]), 1)) for i in range(len(hz))],
+                            "expected_in_frame": [float(o_exp[i] / max(n_windows, 1)) for i in range(len(hz))]}
     return res
+
+
+def parse_grid(text) -> Optional[Tuple[int, int]]:
+    """--occupancy OHxOW -> (OH, OW); None without the flag."""
+    if not text:
+        return None
+    parts = str(text).lower().split("x")
+    if len(parts) != 2 or not all(p.isdigit() for p in parts) or not all(1 <= int(p) <= 1024 for p in parts):
+        raise ValueError("--occupancy takes OHxOW with both sides in 1..1024, e.g. 64x64, got %r" % (text,))
+    return int(parts[0]), int(parts[1])
 
 
 def main(argv: Optional[List[str]] = None) -> None:

@@ -700,6 +700,81 @@ class DESIREModel(object):
                         res["order"].data_ptr(), res["first"].data_ptr(), res["jerr"].data_ptr(), res["jscore"].data_ptr(), res["out"].data_ptr(), stream)
         return {k: v.cpu().numpy() for k, v in res.items()}
 
+    def _occupancy_args(self, d, grid, horizons, mode, weights, mask, mask_of_window, n):
+        """(Oh, Ow, horizons, mode id, mask tensor or None, mask_of_window tensor or None) of the occupancy calls, refused here where they are bad."""
+        torch = self.torch
+        Oh, Ow = (int(x) for x in grid)
+        if mode not in _lib.OCC_MODES:
+            raise ValueError("mode must be 'at' (the frame h - 1) or 'until' (any frame before h), got %r" % (mode,))
+        if weights not in ("score", "uniform"):
+            raise ValueError("weights must be 'score' (softmax of the IOC scores) or 'uniform', got %r" % (weights,))
+        hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
+        if mask is None:
+            if mask_of_window is not None:
+                raise ValueError("mask_of_window needs mask")
+            return Oh, Ow, hz, _lib.OCC_MODES[mode], None, None
+        mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+        if mask.dim() == 2:
+            mask = mask[None]
+        if mask.dim() != 3 or tuple(mask.shape[1:]) != (Oh, Ow):
+            raise ValueError("mask must be [n_masks, Oh, Ow] (or [Oh, Ow]) on the occupancy grid, got %s" % (tuple(mask.shape),))
+        mow = np.zeros(n, np.int32) if mask_of_window is None else np.asarray(mask_of_window, np.int64).reshape(-1)
+        if mow.size != n or (mow >= int(mask.shape[0])).any():
+            raise ValueError("mask_of_window must hold one index below n_masks (negative: no mask) per window")
+        return Oh, Ow, hz, _lib.OCC_MODES[mode], mask, torch.as_tensor(mow.astype(np.int32), device=self.device)
+
+    def _occupancy(self, h, Y, fut, present, score, args, want_hit):
+        torch = self.torch
+        d = h.dims
+        Oh, Ow, hz, mode, mask, mow = args
+        n, nh = d.n_scenes, len(hz)
+        res = {"occ": torch.empty((n, nh, Oh, Ow), device=self.device), "expected": torch.empty((n, nh, Oh, Ow), device=self.device),
+               "off": torch.empty((n, d.mno, nh), device=self.device)}
+        if mask is not None:
+            res["violation"] = torch.empty((n, d.mno, nh), device=self.device)
+        if want_hit:
+            res["hit"] = torch.empty((n, d.mno, nh), device=self.device)
+        ptr = lambda x: 0 if x is None else x.data_ptr()
+        h.occupancy(Y.data_ptr(), ptr(fut), ptr(present), ptr(score), hz, mode, Oh, Ow, res["occ"].data_ptr(), res["expected"].data_ptr(),
+                    ptr(res.get("hit")), ptr(res.get("violation")), res["off"].data_ptr(), ptr(mask), ptr(mow), torch.cuda.current_stream().cuda_stream)
+        return res
+
+    def predict_occupancy(self, past, grid, horizons=None, mode: str = "at", weights: str = "score", mask=None, mask_of_window=None, eps=None,
+                          seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0) -> dict:
+        """Predicted occupancy maps of windows already in HBM (predict_device's `past`): the forward as predict_device runs it, then one
+        desire_occupancy call in its prediction form (an agent counts when its id is != 0 at the last observed frame).  grid = (Oh, Ow) cells over
+        the normalised frame.  Returns device tensors: "occ" [n, n_h, Oh, Ow] = the probability that at least one agent is in the cell at frame
+        h - 1 (mode "at") or at any frame before h ("until"), "expected" (same shape) = the expected number of agents there, "off" [n, mno, n_h] =
+        the weight of an agent's samples that are off the frame, "present" [n, mno] bool and, with mask [n_masks, Oh, Ow] (nonzero: traversable;
+        mask_of_window [n]: its mask per window, negative: none; default mask 0 for every window), "violation" [n, mno, n_h] = the weight of the
+        samples that enter a cell the mask forbids.  weights "score": softmax of the IOC scores per agent; "uniform": 1 / K.  horizons in frames
+        (default default_horizons(T_pred)).  All K samples and scores stay available as self.final_output / self.final_states."""
+        n = int(past.shape[0])
+        args = self._occupancy_args(self._handle(n, False).dims, grid, horizons, mode, weights, mask, mask_of_window, n)      # refused before the forward runs
+        Y, score = self.forward_device(past, None, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
+        h = self._handle(n, False)
+        present = past[:, -1, :, 0] != 0
+        res = self._occupancy(h, Y, None, present.to(self.torch.uint8).contiguous(), score if weights == "score" else None, args, False)
+        res["present"] = present
+        return res
+
+    def evaluate_occupancy(self, Y, score, fut_windows, grid, horizons=None, mode: str = "at", weights: str = "score", mask=None,
+                           mask_of_window=None) -> dict:
+        """The occupancy maps of samples Y [n, K, mno, T_pred, 2] (and scores) against their futures: desire_occupancy in its evaluation form (a frame
+        counts when the object is in it).  Returns numpy arrays: "occ", "expected", "off" and "violation" as predict_occupancy, and in mode "at"
+        "hit" [n, mno, n_h] = the weight of the agent's samples in the cell the ground truth is in at frame h - 1 (0 where it is not counted or off
+        the frame).  `fut_windows`, horizons as in evaluate_ranked; weights "score" needs `score`."""
+        torch = self.torch
+        n = int(Y.shape[0])
+        h = self._handles.get((n, 0, 0)) or self._handle(n, True)
+        d = h.dims
+        args = self._occupancy_args(d, grid, horizons, mode, weights, mask, mask_of_window, n)
+        if weights == "score" and score is None:
+            raise ValueError("weights='score' needs the IOC scores")
+        fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
+        res = self._occupancy(h, Y, fut, None, score if weights == "score" else None, args, mode == "at")
+        return {k: v.cpu().numpy() for k, v in res.items()}
+
     def evaluate_nll(self, Y, score, fut_windows, horizons=None, units="px", weighted: bool = False, log_floor: float = _lib.KDE_LOG_FLOOR,
                      return_frames: bool = False):
         """[A, n_h, 2] = per horizon (mean, final) KDE negative log-likelihood of the ground truth under the agent's K samples: at every counted

@@ -461,6 +461,53 @@ int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, const float* d
                          int32_t* dev_first, int32_t* dev_cnt, float* dev_jerr, float* dev_jscore, int32_t* dev_jorder,
                          float* dev_out, void* stream);
 
+/* ---- predicted occupancy maps: how likely is it that somebody stands in this cell of the frame at horizon h, or at any time before it.  The K
+ * samples of every agent, weighted, are rasterised onto an Oh x Ow grid over the normalised frame [0, 1) x [0, 1).  Layouts are the evaluation
+ * calls': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot, dev_fut [n_scenes, T_pred, mno, 3], host_horizons as in
+ * desire_ranked_errors (strictly increasing, 1 .. T_pred, n_h <= 8, read at call time, by value).  All arithmetic is fp32, every operation is
+ * rounded once (no fused multiply-add); no float atomics.
+ *   1 counted     exactly one of dev_fut and dev_present is non-NULL, as in desire_joint_metrics.  With dev_fut: c(a, t) =
+ *                 dev_fut[scene, t, slot, 0] != 0 (evaluation).  With dev_present [A] uint8: c(a, t) = dev_present[a] != 0 for every t (prediction).
+ *   2 weights     w_k of agent a is desire_kde_nll's step 1 exactly: NULL dev_score: 1.f / K; else m = max_j s_j, e_k = expf(s_k - m), w_k =
+ *                 e_k / sum_j e_j, once per agent; 1.f / K for an agent with a non-finite score.  The same kernel fills the same scratch, so the
+ *                 two calls are ordered by the stream like any two calls on one handle.
+ *   3 cell        for a position (x, y): fx = floorf(x * (float)Ow), fy = floorf(y * (float)Oh), one rounded multiply each.  The position is IN
+ *                 FRAME iff 0 <= fx <= Ow - 1 and 0 <= fy <= Oh - 1; every other position is OFF FRAME: a NaN, x = 1.0 exactly, negatives.  There
+ *                 is no clamp (unlike the scene lookup: mass must not pile up on the border).  cell = (int)fy * Ow + (int)fx.
+ *   4 visits      sample k of agent a VISITS cell c for horizon h -- DESIRE_OCC_AT: frame h - 1 is counted, its position is in frame and its
+ *                 cell is c.  DESIRE_OCC_UNTIL: some counted frame t < h has an in-frame position in cell c.  Either way a sample contributes
+ *                 to a cell at most once, however often it returns to it.
+ *   5 marginal    p_a(h, c) = sum_k w_k * [k visits c], in increasing k from 0.f.
+ *   6 window maps the agents are walked in increasing slot.  dev_exp [n_scenes, n_h, Oh, Ow] (may be NULL) = E, the sum of p_a from 0.f: the expected
+ *                 number of agents.  dev_occ [n_scenes, n_h, Oh, Ow] (required) = 1.f - q, q starting at 1.f and q = q * (1.f - p_a) per agent: the
+ *                 probability that at least one agent is there, agents being independent given the window.  An agent with p_a(h, c) = 0 leaves
+ *                 both unchanged (adding 0.f and multiplying by 1.f are exact).
+ *   7 columns     per agent, each [A, n_h], each may be NULL, each a sum over k in increasing k from 0.f; zeros for an agent with no counted frame.
+ *                 dev_off  = the weight of the samples that are off frame -- AT: at frame h - 1, when it is counted; UNTIL: at any counted t < h.
+ *                 dev_viol = the weight of the samples that visit a cell whose byte of the window's mask is 0 ("not traversable").  Needs
+ *                            dev_mask [n_masks, Oh, Ow] uint8 and dev_mask_of_scene [n_scenes] int32 on the device (entries < n_masks: the
+ *                            caller's promise); a scene whose entry is negative gets zeros.
+ *                 dev_hit  = p_a(h, cell of g(a, h - 1)), g = (fut_x * sx, fut_y * sy) rounded once, the scaled target of desire_ranked_errors:
+ *                            the mass on the ground truth's cell.  With dev_fut and DESIRE_OCC_AT only; 0 when frame h - 1 is not counted or g is
+ *                            off frame.
+ *   8 A window's results depend on that window's rows, scores and targets only -- not on the grid of workgroups, the batch or
+ *     DESIRE_FLAG_COMPACT_*.  Bitwise reproducible, stream-ordered, capturable, no host wait, no allocation (the weights' scratch is desire_create's).
+ * LDS plan: one workgroup owns one (window, horizon, band of grid rows): three floats per cell of the band (E, q, one agent's marginal), in
+ * UNTIL a fourth word (the last sample that reached the cell), next to 20 bytes per position of a chunk of at most 512 positions of one agent,
+ * 61440 bytes in all.  A grid beyond that -- 4266 cells in AT, 3200 in UNTIL at a full chunk -- is cut into bands of whole rows, each band a
+ * workgroup that reads the window's rows again; a cell's sequence of operations is the same in every cut.  Every Oh, Ow <= 1024 and every
+ * (mno, K, T_pred) of a handle is served.
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing launched or written: a NULL handle / dev_Yhat / dev_occ / host_horizons; bad
+ * horizons; a mode other than the two; Oh or Ow outside 1 .. 1024; both or neither of dev_fut / dev_present; dev_hit without dev_fut or in
+ * UNTIL; dev_viol without both mask arguments; a ref_compat handle. */
+#define DESIRE_OCC_AT 0       /* the frame h - 1 */
+#define DESIRE_OCC_UNTIL 1    /* swept: any counted frame t < h */
+#define DESIRE_OCC_MAX_SIDE 1024
+int desire_occupancy(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present,
+                     const float* dev_score, const int32_t* host_horizons, int32_t n_h, int32_t mode,
+                     int32_t Oh, int32_t Ow, const uint8_t* dev_mask, const int32_t* dev_mask_of_scene,
+                     float* dev_occ, float* dev_exp, float* dev_hit, float* dev_viol, float* dev_off, void* stream);
+
 /* ---- hipGraph capture: desire_graph_begin(h, stream); any stream-ordered desire_* calls on that stream (desire_forward,
  * desire_backward, desire_clip_grads, desire_ioc_step ...) ; desire_graph_end -> graph id; desire_graph_launch replays them with
  * the SAME device pointers.  For launch-bound shapes (small batches, the training step, the agent-sharded IOC loop).  Calls
