@@ -17,6 +17,8 @@
 //   deconv4 VALU   one output channel: 32-wide dot per tap, parity class per wave (+sigmoid)
 #include "common.h"
 #include "kernels.h"
+#include <type_traits>
+#include <utility>
 
 // ------------------------------------------------------------------------------------------------
 // conv1 (VALU): one workgroup per agent
@@ -262,6 +264,33 @@ void launch_deconv2(const ConvArgs& a, hipStream_t s) {
 // input shift d = (p + 1 - k)/2, i = q + d for o = 2q + p.  One wave per sample, MT = 2 covers the
 // 64 outputs of a class.
 // ------------------------------------------------------------------------------------------------
+// A tile is one statically unrolled sequence of 25 (class, tap) chains.  The eight B-fragment loads of chain s + 1 and its LDS row pointers are
+// issued before the MFMAs of chain s (two named fragment sets; across class boundaries, so ahead of the class epilogue's stores; chain 0's ahead
+// of the staging loop and its barrier), and a row outside the image is a select between the image row and its zero_row slot, not a divergent
+// region.  Until then each chain was one mma_groups_ptr<2, true> call: about 45 instructions of address set-up with four s_and_saveexec
+// regions, eight loads, and `s_waitcnt vmcnt(7)` on the first of them, 25 times per tile and wave.  Same products in the same order per
+// accumulator, same stores: bit-identical (tests/test_gpu_gen_chain_bits.py).  Measured (512 windows, same box, step ms, three alternating runs
+// each; the rule and the tables: profiles/README.md, gen_heads):
+//   parent   rolled chains, B fragments requested at the head of each chain                         130.83 - 130.93   (118 + 32 registers)
+//   kept     weights and row pointers a chain ahead                                                 129.17 - 129.34   (162 + 32, no scratch)
+//   dropped  ... + the A fragment of unit (g, m) + 1 read before the MFMAs of unit (g, m)           129.33 - 129.40   (166 + 32): the other M-tile's
+//            four MFMAs already cover the LDS read -- the two accumulators alternate, which k_ioc's single chain does not have
+//   not built  a second accumulator pair, so that a class's ELU and stores issue between the first MFMAs of the next class
+// Kernel time 17.50 -> 15.94 ms, MfmaUtil 0.79 -> 0.88, the same SQ_VALU_MFMA_BUSY_CYCLES.
+// The 25 (class, tap) chains of a tile, 64 MFMAs per M-tile each, in the order of the nest  py, px, ky = 1 - py (+2) .., kx = 1 - px (+2) .. :
+// chains 0-3 class (0,0), 4-9 (0,1), 10-15 (1,0), 16-24 (1,1).  first / last: the chain that opens / closes its class's accumulators.
+struct D3Chain { int py, px, ky, kx; bool first, last; };
+__host__ __device__ constexpr D3Chain d3_chain(int s) {
+    const int c = s < 4 ? 0 : s < 10 ? 1 : s < 16 ? 2 : 3, s0 = c == 0 ? 0 : c == 1 ? 4 : c == 2 ? 10 : 16;
+    const int py = c >> 1, px = c & 1, nkx = px ? 3 : 2, n = (py ? 3 : 2) * nkx, i = s - s0;
+    return D3Chain{py, px, 1 - py + 2 * (i / nkx), 1 - px + 2 * (i % nkx), i == 0, i == n - 1};
+}
+// f(integral_constant<int, 0>), .., f(integral_constant<int, N - 1>) in order: a loop whose index is a constant in the body by construction (the
+// epilogue of the training-mode form is large enough for `#pragma unroll` to give up on 25 chains, and a rolled loop indexes the fragment sets at run time)
+template <class F, int... S>
+__device__ __forceinline__ void static_for_(F&& f, std::integer_sequence<int, S...>) { (f(std::integral_constant<int, S>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_(f, std::make_integer_sequence<int, N>{}); }
 // NS = samples (= waves) per workgroup (4; NS = 2 -- four small workgroups per CU instead of two -- measured 15 % slower).
 template <bool FWD, int NS>
 __global__ __launch_bounds__(NS * 64) void k_deconv3(ConvArgs a) {
@@ -278,6 +307,20 @@ __global__ __launch_bounds__(NS * 64) void k_deconv3(ConvArgs a) {
     DYN_N(a, n, blockIdx.x * NS)
     for (int bx = blockIdx.x; bx * NS < a.n; bx += gridDim.x) {
         const int s0 = bx * NS;
+        // B fragments (the packed weights of a tap: 8 k-groups) in two statically named sets: the eight loads of chain s + 1 are issued before the
+        // MFMAs of chain s, across class boundaries, and chain 0's before the staging below.  The offset is opaque per tile, as in k_deconv2: the
+        // fragment addresses do not depend on the tile, and hoisted out of the tile loop the 200 loads would live across it.
+        int woff = 0;
+        asm volatile("" : "+s"(woff));
+        const float4* wp = a.Wp + woff + lane;
+        auto load_b = [&](float4 (&f)[8], const D3Chain ch) __attribute__((always_inline)) {
+            const float4* bp = wp + ((size_t)(ch.ky * 5 + ch.kx) * 8) * 64;
+    #pragma unroll
+            for (int g = 0; g < 8; ++g) f[g] = bp[g * 64];
+        };
+        float4 b[2][8];
+        load_b(b[0], d3_chain(0));
+        __builtin_amdgcn_sched_barrier(0);
         for (int i = tid; i < 128; i += NS * 64) zero_row[i] = 0.f;
         for (int i = tid; i < NS * 64 * 16; i += NS * 64) {
             const int pix = i >> 4, c4 = i & 15;
@@ -288,8 +331,7 @@ __global__ __launch_bounds__(NS * 64) void k_deconv3(ConvArgs a) {
         }
         __syncthreads();
         const int smp = s0 + w;
-        const float* mine = in_s + w * 64 * LDP;
-        const int c = lane & 31, hi = lane >> 5;
+        const int hi = lane >> 5;
         // transposed contraction (weights as the A operand): the accumulators hold D[co][pixel] with lane = pixel and the 16
         // registers = output channels in runs of four, so the epilogue stores float4 (4x fewer store instructions)
         float4 sc[4], sh[4];
@@ -301,21 +343,41 @@ __global__ __launch_bounds__(NS * 64) void k_deconv3(ConvArgs a) {
         int qy[2], qx[2];
     #pragma unroll
         for (int m = 0; m < 2; ++m) { const int q = m * 32 + (lane & 31); qy[m] = q >> 3; qx[m] = q & 7; }
-        for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px) {
-                f32x16 acc[2] = {zero16(), zero16()};
-                for (int ky = 1 - py; ky < 5; ky += 2)
-                    for (int kx = 1 - px; kx < 5; kx += 2) {
-                        const int dy = (py + 1 - ky) / 2, dx = (px + 1 - kx) / 2;   // exact: numerators even
-                        const float* ap[2];
+        // LDS rows of chain s: the pixel's row of this wave's image, or its slot of zero_row outside the image -- one select per M-tile, no divergence
+        auto rows = [&](const D3Chain ch, const float* (&ap)[2]) __attribute__((always_inline)) {
+            const int dy = (ch.py + 1 - ch.ky) / 2, dx = (ch.px + 1 - ch.kx) / 2;   // exact: numerators even
     #pragma unroll
-                        for (int m = 0; m < 2; ++m) {
-                            const int iy = qy[m] + dy, ix = qx[m] + dx;
-                            const bool ok = iy >= 0 && iy < 8 && ix >= 0 && ix < 8;
-                            ap[m] = (ok ? mine + (iy * 8 + ix) * LDP : zero_row + ((((w * 64 + iy * 8 + ix + 64) * LDP + 128) & 63))) + 4 * hi;
-                        }
-                        mma_groups_ptr<2, true>(acc, ap, a.Wp + ((size_t)(ky * 5 + kx) * 8) * 64 + lane, 8);
-                    }
+            for (int m = 0; m < 2; ++m) {
+                const int iy = qy[m] + dy, ix = qx[m] + dx;
+                const bool ok = iy >= 0 && iy < 8 && ix >= 0 && ix < 8;
+                const int in_off = 128 + (w * 64 + iy * 8 + ix) * LDP, zero_off = ((w * 64 + iy * 8 + ix + 64) * LDP + 128) & 63;
+                ap[m] = smem + (ok ? in_off : zero_off) + 4 * hi;
+            }
+        };
+        const float* ap[2][2];
+        rows(d3_chain(0), ap[0]);
+        f32x16 acc[2];
+        static_for<25>([&](auto chain_no) __attribute__((always_inline)) {
+            constexpr int s = decltype(chain_no)::value;
+            constexpr D3Chain ch = d3_chain(s);
+            constexpr int py = ch.py, px = ch.px;
+            if constexpr (s + 1 < 25) { load_b(b[(s + 1) & 1], d3_chain(s + 1)); rows(d3_chain(s + 1), ap[(s + 1) & 1]); }
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (ch.first) { acc[0] = zero16(); acc[1] = zero16(); }
+            const float4 (&bt)[8] = b[s & 1];
+            // unit (g, m) = k-group g on M-tile m, in mma_chunk's order, fenced per unit
+    #pragma unroll
+            for (int g = 0; g < 8; ++g)
+    #pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const float4 av = *reinterpret_cast<const float4*>(ap[s & 1][m] + g * 8);
+                    acc[m] = mfma32(bt[g].x, av.x, acc[m]);
+                    acc[m] = mfma32(bt[g].y, av.y, acc[m]);
+                    acc[m] = mfma32(bt[g].z, av.z, acc[m]);
+                    acc[m] = mfma32(bt[g].w, av.w, acc[m]);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            if constexpr (ch.last) {
                 if (smp < a.n) {
     #pragma unroll
                     for (int m = 0; m < 2; ++m) {
@@ -339,6 +401,7 @@ __global__ __launch_bounds__(NS * 64) void k_deconv3(ConvArgs a) {
                     }
                 }
             }
+        });
         __syncthreads();                                   // (the next tile of this workgroup restages the LDS tiles)
     }
 }

@@ -227,6 +227,25 @@ void launch_encoder(const EncArgs& a, hipStream_t s) {
 // Decoder: tile = 64 rows; constant input x_z => its contribution (and the biases) is computed once
 // and kept in 48 accumulator-layout registers per wave; per step only the h-part contracts (K = H).
 // ------------------------------------------------------------------------------------------------
+// Every contraction is one ioc_bin_chain<G> (below, with k_ioc): the products and their order are mma_run<1>'s (what mma1 ran here before), the
+// chunks are unrolled over two statically named fragment sets and the A fragment of group g + 1 is read before the MFMAs of group g.
+// Same products in the same order, same stores: bit-identical (tests/test_gpu_gen_chain_bits.py).  Measured (512 windows, same box, step ms, three
+// alternating runs each; the rule and the tables: profiles/README.md, gen_heads):
+//   parent   mma1: rolled mma_begin / mma_run, A read and waited for in front of its MFMAs          130.83 - 130.93   (<128,32,false>: 202 registers)
+//   kept     ioc_bin_chain, first chunk requested in front of its chain                             130.07 - 130.33   (192, no scratch in any form)
+//   dropped  ... + first chunks requested early (u's before the r chain, the candidate's before the gate epilogue and its barrier, the next
+//            step's r before the barrier in front of the head phase; a third named set)             130.09 - 130.35   (198)
+// Kernel time 11.32 -> 10.79 ms, MfmaUtil 0.77 -> 0.81, the same SQ_VALU_MFMA_BUSY_CYCLES.  The training-mode (SAVE) forms address their
+// saves from a uniform base and 32-bit offsets (below) and no longer spill: 256 registers + 20 - 424 B of scratch -> 213 - 221 and none.
+template <int G>
+__device__ __forceinline__ void ioc_bin_chain(f32x16& acc, const float* a_lane, const float4* __restrict__ b_lane, float4 (&b0)[4]);
+template <int G>
+__device__ __forceinline__ void dec_chain(f32x16& acc, const float* a_lane, const float4* __restrict__ b_lane) {
+    float4 b0[4];
+    load_b4(b0, b_lane, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    ioc_bin_chain<G>(acc, a_lane, b_lane, b0);
+}
 template <int H, int TM, bool SAVE>       // SAVE: training-mode forward (gates / candidate / hidden states kept for BPTT)
 __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, 2) void k_decoder(DecArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -278,9 +297,9 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, 2) void k_decoder(DecArg
     f32x16 xr, xu, xc, h;
     if (active) {
         xr = splat16(a.b_g[col]); xu = splat16(a.b_g[H + col]); xc = splat16(a.b_c[col]);
-        mma1(xr, x_lane, a.Wxg + ((size_t)cb * G) * 64 + lane, G);
-        mma1(xu, x_lane, a.Wxg + ((size_t)(cb + NT) * G) * 64 + lane, G);
-        mma1(xc, x_lane, a.Wxc + ((size_t)cb * G) * 64 + lane, G);
+        dec_chain<G>(xr, x_lane, a.Wxg + ((size_t)cb * G) * 64 + lane);
+        dec_chain<G>(xu, x_lane, a.Wxg + ((size_t)(cb + NT) * G) * 64 + lane);
+        dec_chain<G>(xc, x_lane, a.Wxc + ((size_t)cb * G) * 64 + lane);
 #pragma unroll
         for (int i = 0; i < 16; ++i) h[i] = my_h[((i & 3) + 8 * (i >> 2)) * LDH];
     }
@@ -288,12 +307,23 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, 2) void k_decoder(DecArg
     const float bh0 = a.b_head[0], bh1 = a.b_head[1];
     // two barriers per step: h and r*h live in separate tiles, so the gates read h while nobody writes it, the candidate
     // reads r*h while nobody writes it, and h_t is published (for the head and the next step) after the first barrier
+    // training-mode saves, [R][T][H] streams: element (row0 + rl, t, col) = a base that is uniform over the tile and the step + a 32-bit offset per
+    // lane and accumulator row that is opaque per step, so the stores of all four streams share 16 offsets worked out in the step (hoisted out of
+    // the time loop as 64-bit addresses per stream and row, they were spilled and reloaded in it)
+    const unsigned sv_row = (unsigned)a.T * H, sv_lane0 = (unsigned)(mt * 32 + 4 * (lane >> 5)) * sv_row + col;
     for (int t = 0; t < a.T; ++t) {
         f32x16 rh, u;
+        const size_t sv_t = ((size_t)row0 * a.T + t) * H;
+        unsigned sv_lane = sv_lane0;
+        if (SAVE) asm volatile("" : "+v"(sv_lane));
+        // the weights through an offset that is opaque per step: the unrolled chains address every chunk from these pointers, and hoisted out of the
+        // time loop the chunk addresses of three chains live across it -- spilled, and reloaded at the top of every step
+        int woff = 0;
+        asm volatile("" : "+s"(woff));
         if (active) {
             rh = xr; u = xu;
-            mma1(rh, a_lane, a.Whg + ((size_t)cb * G) * 64 + lane, G);
-            mma1(u, a_lane, a.Whg + ((size_t)(cb + NT) * G) * 64 + lane, G);
+            dec_chain<G>(rh, a_lane, a.Whg + woff + ((size_t)cb * G) * 64 + lane);
+            dec_chain<G>(u, a_lane, a.Whg + woff + ((size_t)(cb + NT) * G) * 64 + lane);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const float r = sigmoidf_(rh[i]);
@@ -301,8 +331,8 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, 2) void k_decoder(DecArg
                 if (SAVE && a.sv_r) {                           // training: keep the gates for BPTT
                     const int rl = mt * 32 + acc_row(i);
                     if (row0 + rl < a.R) {
-                        const size_t ix = ((size_t)(row0 + rl) * a.T + t) * H + col;
-                        a.sv_r[ix] = r; a.sv_u[ix] = u[i];
+                        const unsigned ix = sv_lane + ((i & 3) + 8 * (i >> 2)) * sv_row;
+                        a.sv_r[sv_t + ix] = r; a.sv_u[sv_t + ix] = u[i];
                     }
                 }
             }
@@ -312,21 +342,21 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, 2) void k_decoder(DecArg
         __syncthreads();
         if (active) {
             f32x16 ac = xc;
-            mma1(ac, r_lane, a.Whc + ((size_t)cb * G) * 64 + lane, G);
+            dec_chain<G>(ac, r_lane, a.Whc + woff + ((size_t)cb * G) * 64 + lane);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 const float c = tanhf_(ac[i]);
                 h[i] = gru_blend(u[i], h[i], c);
                 if (SAVE && a.sv_c) {
                     const int rl = mt * 32 + acc_row(i);
-                    if (row0 + rl < a.R) a.sv_c[((size_t)(row0 + rl) * a.T + t) * H + col] = c;
+                    if (row0 + rl < a.R) a.sv_c[sv_t + (sv_lane + ((i & 3) + 8 * (i >> 2)) * sv_row)] = c;
                 }
             }
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
                 my_h[((i & 3) + 8 * (i >> 2)) * LDH] = h[i];
                 const int rl = mt * 32 + acc_row(i);
-                if (SAVE && a.hdump && row0 + rl < a.R) a.hdump[((size_t)(row0 + rl) * a.T + t) * H + col] = h[i];
+                if (SAVE && a.hdump && row0 + rl < a.R) a.hdump[sv_t + (sv_lane + ((i & 3) + 8 * (i >> 2)) * sv_row)] = h[i];
             }
         }
         __syncthreads();
