@@ -24,6 +24,15 @@ struct IocLdsRegions {
 #define IOC_LDS_TIED(cond) static_assert(cond, "hand carve-up and ioc_lds.h plan disagree: " #cond)
 IOC_HD constexpr int ioc_kx(int H, int EV, int C) { return EV + C + 2 * H; }      // columns of [e_v | e_s | e_r | h]
 
+// k_ioc, the dense pooling with rows read in place: between the position phase and the candidate the AB region holds no operand tile but
+// the sums of the (row, bin) pairs with two or more neighbours, one slot of H + 4 floats each, and behind them the row-source table
+// [TM][bins] of one byte per pair (ioc_tile.h: ioc_row_code; bins <= 64, the occupancy word).  The slots are what fits in front of the
+// table; a tile-step with more such pairs runs the build loop, so the count is a performance choice only (tests/test_ioc_pool_plan.py)
+constexpr int IOC_POOL_MAX_BINS = 64;
+IOC_HD constexpr int ioc_pool_slots(int H, int TM) {
+    return 2 * TM - (TM * IOC_POOL_MAX_BINS + (H + 4) * 4 - 1) / ((H + 4) * 4);
+}
+
 // fp32 operand tiles XH [rows][KX + 4] and AB [2][TM][H + 4]: k_ioc, k_ioc_cl, k_ioc_step, k_ioc_step_x2
 struct IocLds : IocLdsRegions<12> {
     enum { XH, AB, MASKS, PC, PP, WV, RED, VLD, OCC, ROWBITS, ROWLIST, SPARE };         // PC = pg (the whole group's positions) in the cluster form

@@ -459,6 +459,12 @@ __device__ __forceinline__ void ioc_bin_chain(f32x16& acc, const float* a_lane, 
         __builtin_amdgcn_sched_barrier(0);
     }
 }
+// k_ioc, the dense pooling (every form but CP): per step and populated bin, e_r += P_b W_b with P_b[row] = the sum of the h rows of the row's
+// neighbours in bin b.  P_b is not built: a pre-pass per step (pool_rows) gives every (row, bin) a row source -- the zero row, the one
+// neighbour's h row where it lies in XH, or a slot holding the sum of two or more -- and the bin loop is one ioc_bin_chain per populated bin
+// whose lanes read their A fragments from those rows, with no operand copy and no barrier between the bins (one barrier in front of the loop,
+// one behind it).  A tile-step with more multi-neighbour pairs than sum slots (ioc_lds.h: ioc_pool_slots) builds P_b in AB per bin between two
+// barriers, as every tile-step did before; same bits either way.  tests/test_gpu_ioc_pool_rows.py, profiles/README.md (ioc_pool).
 // CP ("compact pooling", opt-in: DESIRE_IOC_VARIANT=8, TM = 32): only the rows that have a neighbour in bin b are built,
 // packed into the first rows of the operand tile, contracted as 16-row v_mfma_f32_16x16x4_f32 tiles and added into the rows
 // they belong to -- at the bench's density (about a quarter of the rows per bin) that halves the pooling MFMAs and builds a
@@ -500,6 +506,15 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
     IOC_LDS_TIED(P0.sz[P0.MASKS] == 0 && P1.sz[P1.MASKS] == TM * (int)sizeof(mask_t));
     IOC_LDS_TIED(P0.off(P0.ROWLIST) - P0.off(P0.PC) == (TM * 2 * 2 + 3 * EV + NT * TM) * 4 + TM + (2 + 36) * 4);
     IOC_LDS_TIED(P0.sz[P0.ROWLIST] == 2 * (TM / 4) * 4);
+    // the dense pooling with the rows read in place (P2/P3 below): the sum slots are AB's rows, the row-source table [TM][B] lies behind them,
+    // the slot counter is the first word of rowbits (the CP form's, unused here)
+    // (two 64-row forms keep the build loop: in place, hipcc reloads one more spilled register inside their time loop than before)
+    constexpr bool INPLACE = !CP && !(TM == 64 && ((H == 128 && TRAIN) || (H == 64 && !TRAIN)));
+    constexpr int NSLOT = ioc_pool_slots(H, TM);
+    unsigned char* rsrc = reinterpret_cast<unsigned char*>(AB + NSLOT * LDB);     // (ioc_tile.h: ioc_row_offset for the codes)
+    unsigned* nsum = rowbits;
+    IOC_LDS_TIED(NSLOT > 0 && (2 * TM - NSLOT) * LDB * 4 >= TM * IOC_POOL_MAX_BINS && 3 * TM < 256 && P0.sz[P0.ROWBITS] >= 4);
+    static_assert(LDX % 4 == 0 && LDB % 4 == 0 && E % 4 == 0 && 4 * 15 + 4 + 8 * (GH - 1) + 4 <= LDX, "16-byte units; the zero row holds a slot per lane");
 
     const int lane = lane_id(), w = wave_id(), tid = threadIdx.x;
     const int cb = w % NT, mt = w / NT;
@@ -573,6 +588,59 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
 #pragma unroll
         for (int c = 0; c < NCH; ++c) *reinterpret_cast<float4*>(ab + q8 * 4 + c * 4 * TPR) = s[c];
     };
+    // Rows read in place (INPLACE: every dense form but two, above).  At the bench's density 87 % of the rows build() writes are zeros and 12 % a copy of
+    // one h row (h_j + 0), so the MFMAs of a lane read their A fragment from where the row already lies: pool_rows() classifies every (row,
+    // bin) once per step (ioc_tile.h: ioc_row_source) into the table rsrc -- the zero row TM (read at a slot per lane: one shared address would
+    // sit on the bank slot of some other lane of every 16-lane group, k_deconv3), the h columns of the neighbour's row of XH, or a sum slot --
+    // and only the pairs with two or more neighbours are summed, in build()'s order (h_j0 + h_j1, then += ascending), into slots handed
+    // out by an LDS counter.  The bin loop is then chain behind chain with no build and no barrier.  A tile-step with more such pairs than
+    // slots runs the build loop (wave-uniform: the counter); both give the same bits -- a copied row differs from build()'s only where
+    // h_j = -0, a zero product's sign, and an accumulator that started at +0 never holds -0.  profiles/README.md, section ioc_pool.
+    auto pool_rows = [&](unsigned long long om) {
+        int r = r8, q = q8, gb = grp_base;           // opaque per step: what is derived from them is not hoisted out of the time loop and spilled
+        asm volatile("" : "+v"(r), "+v"(q), "+v"(gb));
+        unsigned mlo = 0u, mhi = 0u;
+        for (int b = q; b < B; b += TPR) {
+            const int src = ioc_row_source(masks[r * B + b]);
+            if (src == IOC_ROW_SUM) { if (b < 32) mlo |= 1u << b; else mhi |= 1u << (b - 32); }
+            else rsrc[r * B + b] = (unsigned char)(src == IOC_ROW_ZERO ? TM : gb + src);
+        }
+#pragma unroll
+        for (int d = 1; d < TPR; d <<= 1) { mlo |= __shfl_xor(mlo, d); if (B > 32) mhi |= __shfl_xor(mhi, d); }
+        unsigned long long multi = (((unsigned long long)mhi << 32) | mlo) & om;          // the same in the TPR lanes of a row
+        while (multi) {
+            const int b = ffs_(multi) - 1;
+            multi &= multi - 1;
+            int slot = 0;
+            if (q == 0) slot = (int)atomicAdd(nsum, 1u);
+            slot = __shfl(slot, lane & ~(TPR - 1));
+            if (slot >= NSLOT) continue;                               // (more pairs than slots: this tile-step runs the build loop)
+            mask_t m2 = masks[r * B + b];
+            const float* s0 = XH + (gb + ffs_(m2) - 1) * LDX + E + q * 4;
+            m2 &= m2 - 1;
+            const float* s1 = XH + (gb + ffs_(m2) - 1) * LDX + E + q * 4;
+            m2 &= m2 - 1;
+            float4 s[NCH];
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const float4 v0 = *reinterpret_cast<const float4*>(s0 + c * 4 * TPR);
+                const float4 v1 = *reinterpret_cast<const float4*>(s1 + c * 4 * TPR);
+                s[c].x = v0.x + v1.x; s[c].y = v0.y + v1.y; s[c].z = v0.z + v1.z; s[c].w = v0.w + v1.w;
+            }
+            while (m2) {
+                const float* src = XH + (gb + ffs_(m2) - 1) * LDX + E + q * 4;
+                m2 &= m2 - 1;
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) {
+                    const float4 v = *reinterpret_cast<const float4*>(src + c * 4 * TPR);
+                    s[c].x += v.x; s[c].y += v.y; s[c].z += v.z; s[c].w += v.w;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) *reinterpret_cast<float4*>(AB + slot * LDB + q * 4 + c * 4 * TPR) = s[c];
+            if (q == 0) rsrc[r * B + b] = (unsigned char)(TM + 1 + slot);
+        }
+    };
 
     for (int it = 0; it < a.iters; ++it) {
         // h_0 = Hx[agent]
@@ -602,6 +670,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
         }
         for (int i = tid; i < TM * B; i += NTHR) masks[i] = 0;
         if (tid < 2) occ[tid] = 0;
+        if (INPLACE && tid == 2) *nsum = 0;
         if (CP && tid < B) rowbits[tid] = 0;
         __syncthreads();
         const float* rh_lane = AB + (mt * 32 + (lane & 31)) * LDB + 4 * (lane >> 5);     // r*h operand (AB buffer 0)
@@ -742,21 +811,58 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
             } else
             // ---- P2/P3: social pooling -> e_r, over the bins that hold a neighbour somewhere in this tile only
             //      (an empty bin's pooled operand is all zeros: skipping it drops exact-zero products, and on real
-            //      tracks most of the window is empty).  build(next) and the contraction of the current bin sit between
-            //      the same two barriers, so waves that finish building early start their MFMAs while others build
+            //      tracks most of the window is empty).  Rows are read in place (pool_rows above); in the build loop that a crowded
+            //      tile-step falls back to, build(next) and the contraction of the current bin sit between the same two barriers,
+            //      so waves that finish building early start their MFMAs while others build
             {
                 f32x16 soc = zero16();          // biases join after the contraction (a splat start value would pin 16 registers)
                 unsigned long long om = ioc_occ64(occ);
                 if (NSPL > 1) om &= my_bins;
                 int buf = 0;
-                if (om) build(ffs_(om) - 1, 0);
-                __syncthreads();
+                bool in_place = false;
+                if constexpr (INPLACE) {
+                    if (om) pool_rows(om);
+                    __syncthreads();
+                    in_place = __builtin_amdgcn_readfirstlane((int)*nsum) <= NSLOT;
+                } else {
+                    if (om) build(ffs_(om) - 1, 0);
+                    __syncthreads();
+                }
                 IOC_TICK(2)
+                if (INPLACE && !in_place) {                        // more multi-neighbour pairs than sum slots: the build loop, as it was
+                    if (om) build(ffs_(om) - 1, 0);
+                    __syncthreads();
+                }
                 // wave priority by phase (round 6): two workgroups per CU = two waves per SIMD; a wave inside its bin loop (3) or its gate / candidate
                 // contraction (2) wins the issue arbitration against one that builds operands or sits in the position phase (0).  Same-box ABAB on the
                 // headline: k_ioc 78.77 - 79.10 ms without, 78.55 - 78.65 with (the reverse order, 1 / 3: 79.1 - 79.25).  Where it pays properly is the
                 // bf16 cluster kernel (kernels_bf16_cl.hip: -6.5 %); k_ioc_bf16 and k_ioc_x3 measured neutral and carry none.
                 __builtin_amdgcn_s_setprio(3);
+                if (INPLACE && in_place) {
+                    // chain behind chain.  The row code of the NEXT populated bin is read before this bin's MFMAs and turned into a pointer
+                    // behind them, so no chain waits for its LDS read.  (Its first weight chunk requested a chunk ahead, into the set the last
+                    // chunk leaves free, measured slower: profiles/README.md, ioc_pool.)
+                    int ln = lane;                                   // (opaque per step, as in pool_rows)
+                    asm volatile("" : "+v"(ln));
+                    const unsigned char* my_src = rsrc + (mt * 32 + (ln & 31)) * B;
+                    const float* a0 = smem + 4 * (ln >> 5);
+                    if (om && active) {
+                        int code = my_src[ffs_(om) - 1];
+                        while (om) {
+                            const int b = ffs_(om) - 1;
+                            om &= om - 1;
+                            const float4* wb = a.Wsoc + ((size_t)(b * NT + cb) * GH) * 64 + lane;
+                            float4 wb0[4];
+                            load_b4(wb0, wb, 0);
+                            const float* ap = a0 + ioc_row_offset(code, TM, LDX, E, LDB, ln & 15);
+                            code = my_src[om ? ffs_(om) - 1 : b];
+                            __builtin_amdgcn_sched_barrier(0);
+                            ioc_bin_chain<GH>(soc, ap, wb, wb0);
+                        }
+                    }
+                    IOC_TICK(4)
+                    om = 0;
+                }
                 while (om) {
                     const int b = ffs_(om) - 1;
                     om &= om - 1;
@@ -860,6 +966,7 @@ __global__ __launch_bounds__((H / 32) * (TM / 32) * 64, ((H / 32) * (TM / 32) <=
             }
             for (int i = tid; i < TM * B; i += NTHR) masks[i] = 0;
             if (tid < 2) occ[tid] = 0;
+            if (INPLACE && tid == 2) *nsum = 0;
             if (CP && tid < B) rowbits[tid] = 0;
             __syncthreads();
             IOC_TICK(8)

@@ -117,6 +117,14 @@ class Dims:
         return dataclasses.replace(self, **kw)
 
 
+def ioc_pool_slots(H: int, TM: int) -> int:
+    """Mirror of ioc_pool_slots (desire_amd/csrc/ioc_lds.h): the sum slots of k_ioc's dense pooling with rows read in place -- the rows of H + 4
+    floats of the AB region [2 TM] in front of the row-source table [TM][64 bins] of one byte per pair.  A (32- or 64-row) tile-step with more (row, bin)
+    pairs of two or more neighbours runs the build loop.  tests/test_ioc_pool_plan.py holds it equal to the header."""
+    row = (H + 4) * 4
+    return 2 * TM - (TM * 64 + row - 1) // row
+
+
 def flops_per_sample(d: Dims) -> float:
     """Algorithmic FLOPs per agent-trajectory-sample (multiply-add = 2),
     re-derived for this spec's dims.  Used by bench.py for the MFMA roofline."""
