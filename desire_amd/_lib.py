@@ -27,7 +27,7 @@ EXPORTS = [
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
     "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse", "desire_joint_metrics",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
-    "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy",
+    "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy", "desire_plan_risk",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
@@ -108,6 +108,7 @@ def load() -> C.CDLL:
     lib.desire_joint_metrics.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, f32p, f32p,
                                          vp, f32p, vp]
     lib.desire_occupancy.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, i32, i32, vp, vp, f32p, f32p, f32p, f32p, f32p, vp]
+    lib.desire_plan_risk.argtypes = [vp, f32p, f32p, vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, vp, f32p, f32p, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
     lib.desire_rollout_samples.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
@@ -332,6 +333,21 @@ class Handle:
                                            hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, int(n_top), C.c_float(radius), C.c_float(unit_x),
                                            C.c_float(unit_y), first_ptr or None, cnt_ptr or None, jerr_ptr or None, jscore_ptr or None,
                                            jorder_ptr or None, out_ptr or None, stream or None))
+
+    def plan_risk(self, yhat_ptr: int, fut_ptr: int, present_ptr: int, score_ptr: int, plans_ptr: int, ego_ptr: int, M: int, horizons,
+                  radius: float, unit_x: float, unit_y: float, risk_ptr: int, first_ptr: int = 0, clear_ptr: int = 0, blame_ptr: int = 0,
+                  stream: int = 0) -> None:
+        """M candidate ego plans per window (plans [n, M, T_pred, 2], normalised; ego [n, M] int32 = the slot a plan replaces, negative or
+        ego_ptr = 0: none) against the K joint futures: risk [n, M, n_h] = the weight of the joint futures in which the plan comes within `radius`
+        of a slot before each horizon (softmax of the joint scores; score_ptr = 0: equal weights), first [n, M, K + 1] int32 = the frame of that
+        first contact (T_pred: never; row K: the ground truth), clear [n, M, K + 1, n_h] = the smallest SQUARED distance to any slot before each
+        horizon (+inf: nobody counted), blame [n, M, n_h, mno] = the risk split by the slot touched.  Exactly one of fut_ptr (evaluation) and
+        present_ptr ([A] uint8, prediction time); distances are scaled by (unit_x, unit_y) as in joint_metrics."""
+        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+        _chk(self.lib.desire_plan_risk(self._h, yhat_ptr or None, fut_ptr or None, present_ptr or None, score_ptr or None, plans_ptr or None,
+                                       ego_ptr or None, int(M), hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, C.c_float(radius),
+                                       C.c_float(unit_x), C.c_float(unit_y), first_ptr or None, clear_ptr or None, risk_ptr or None,
+                                       blame_ptr or None, stream or None))
 
     def occupancy(self, yhat_ptr: int, fut_ptr: int, present_ptr: int, score_ptr: int, horizons, mode: int, Oh: int, Ow: int, occ_ptr: int,
                   exp_ptr: int = 0, hit_ptr: int = 0, viol_ptr: int = 0, off_ptr: int = 0, mask_ptr: int = 0, mask_of_scene_ptr: int = 0,

@@ -366,6 +366,34 @@ extern "C" int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, con
     return DESIRE_OK;
 }
 
+// ---- candidate ego plans against the K joint futures (kernels_plan.hip): the contract is stated in include/desire_hip.h ----
+extern "C" int desire_plan_risk(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present, const float* dev_score,
+                                const float* dev_plans, const int32_t* dev_ego, int32_t M, const int32_t* host_horizons, int32_t n_h, float radius,
+                                float unit_x, float unit_y, int32_t* dev_first, float* dev_clear, float* dev_risk, float* dev_blame, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_plans) return fail(DESIRE_ERR_ARG, "dev_plans is NULL");
+    if (!dev_risk) return fail(DESIRE_ERR_ARG, "dev_risk is NULL");
+    if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
+    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    if (M < 1) return fail(DESIRE_ERR_ARG, "M must be at least 1 (the candidate plans per window)");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read joint futures from");
+    RankHz hz{};
+    if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
+    if (int rc = check_radius(radius)) return rc;
+    if (int rc = check_units(unit_x, unit_y)) return rc;
+    int pc = 0, tc = 0;
+    plan_geometry(d.mno, d.T_pred, M, &pc, &tc);
+    if (tc < 1) return fail(DESIRE_ERR_ARG, "one frame of the window does not fit the plan kernel's LDS");      // (not reachable at mno <= 256)
+    if ((uint64_t)d.n_scenes * (uint64_t)((M + pc - 1) / pc) >= (1ull << 31)) return fail(DESIRE_ERR_ARG, "n_scenes * plan chunks must be below 2^31");
+    launch_plan_risk(dev_Yhat, dev_fut, dev_present, dev_score, dev_plans, dev_ego, W(h, "joint_js"), dev_first, dev_clear, dev_risk, dev_blame,
+                     d.n_scenes, d.mno, d.K, d.T_pred, M, hz, d.sx, d.sy, unit_x, unit_y, radius, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- predicted occupancy maps of the K weighted samples (kernels_occ.hip): the contract is stated in include/desire_hip.h ----
 extern "C" int desire_occupancy(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present, const float* dev_score,
                                 const int32_t* host_horizons, int32_t n_h, int32_t mode, int32_t Oh, int32_t Ow, const uint8_t* dev_mask,

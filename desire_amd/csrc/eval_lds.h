@@ -1,5 +1,5 @@
 // eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
-// _recon / _occ.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// _recon / _occ / _plan.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
 // that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
 // Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp and occ_lds_driver.cpp compile it with g++ (tests/test_eval_lds.py, test_occ_lds.py).
 #pragma once
@@ -129,6 +129,32 @@ struct JointLds {
 inline int joint_chunk_frames(int mno, int T) {
     const size_t fixed = JointLds(mno, 0).bytes(), per = JointLds(mno, 1).bytes() - fixed, fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;
     return (int)((size_t)T < fit ? (size_t)T : fit);
+}
+
+// ---- k_plan_risk: PL float2 [PC][eval_odd(TC)] (the frames of a pass of a chunk of PC candidate plans), P float2 [TC][mp] (the unit's positions,
+// JointLds' layout and frame stride), then two sets -- one per parity of k -- of PC ints (first contact of the plan with any slot) and PC * HZ
+// words (its clearance per horizon: the bits of a non-negative float, which order as unsigned integers)
+struct PlanLds {
+    enum { HZ = 8, MAX_PC = EVAL_THREADS / HZ, SETS = 2 };                 // one lane per (plan, horizon) keeps the risk: PC * HZ <= EVAL_THREADS
+    int mno, PC, TC;
+    EVAL_HD constexpr PlanLds(int mno_, int PC_, int TC_) : mno(mno_), PC(PC_), TC(TC_) {}
+    EVAL_HD constexpr int plan_stride() const { return eval_odd(TC); }
+    EVAL_HD constexpr size_t plans() const { return (size_t)PC * plan_stride(); }           // float2 in front of the positions
+    EVAL_HD constexpr size_t pos() const { return (size_t)TC * JointLds::stride(mno); }     // float2 in front of the words
+    EVAL_HD constexpr int first(int set) const { return set * PC * (1 + HZ); }              // word offsets behind the pairs
+    EVAL_HD constexpr int clear(int set) const { return first(set) + PC; }
+    EVAL_HD constexpr size_t bytes() const { return (plans() + pos()) * EVAL_PAIR_BYTES + (size_t)4 * first(SETS); }
+};
+// The plan chunk: as many plans as EVAL_THREADS (plan, slot) items hold -- every lane owns one item for the whole call -- MAX_PC at most, spread
+// evenly over the chunks of the M plans.  Frames per pass: the whole horizon when the chunk's plans and the unit's positions fit, else as many
+// frames of both as do (eval_odd(TC) <= TC + 1).  One frame of 256 slots and one plan is 2 KB, so every (mno, T_pred, M) is served.
+inline void plan_geometry(int mno, int T, int M, int* PC, int* TC) {
+    const int cap = eval_min(eval_min(M, (int)PlanLds::MAX_PC), eval_max(1, EVAL_THREADS / mno));
+    const int pc = eval_chunks(M, eval_chunks(M, cap));
+    const size_t fixed = PlanLds(mno, pc, 0).bytes(), per = (size_t)EVAL_PAIR_BYTES * ((size_t)pc + JointLds::stride(mno));
+    const size_t fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;            // (PlanLds(.., 0) already holds the one pair per plan of the odd stride)
+    *PC = pc;
+    *TC = (int)((size_t)T < fit ? (size_t)T : fit);
 }
 
 // ---- k_occupancy: 32-bit words.  Over the `cells` of a band of grid rows: E, q, P floats (expected count, product of the complements, one

@@ -279,6 +279,13 @@ void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* prese
                           int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
                           const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
 
+// ---- candidate ego plans against the K joint futures (kernels_plan.hip) ----
+// exactly one of fut / present; plans [n_scenes, M, T, 2]; w [n_scenes, K] is scratch of the call (the handle's "joint_js": the joint scores, then
+// their weights); score, ego, first, clear and blame may be nullptr
+void launch_plan_risk(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* plans, const int32_t* ego,
+                      float* w, int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
+                      const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
+
 // ---- predicted occupancy maps of the K weighted samples (kernels_occ.hip) ----
 // step 1 of launch_kde_nll alone: w [R] (the score layout) and st [A, 2], the handle's "kde_w" / "kde_st"; score may be nullptr (kernels_kde.hip)
 void launch_kde_weights(const float* score, float* w, float* st, int n_scenes, int mno, int K, hipStream_t s);

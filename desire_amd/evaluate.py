@@ -4,7 +4,7 @@ device, errors per horizon of the best-scored sample (top-1), of the best among 
     python -m desire_amd.evaluate --checkpoint save/social_model-400.npz --data_dir data/ --max_num_obj 32 --d_dim 128 \\
         --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json] \\
         [--generator cvae|rollout] [--nll] [--select nms --nms_radius 20 [--nms_metric final|mean|max] [--nms_horizon 12]] \\
-        [--joint [--collision_radius 10]] [--occupancy 64x64 [--occupancy_mode at|until]]
+        [--joint [--collision_radius 10]] [--occupancy 64x64 [--occupancy_mode at|until]] [--plan_risk [--collision_radius 10]]
 
 The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
@@ -48,7 +48,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "joint sample with the best summed score and of the best among the top N, and the collision rate of the predicted joint futures "
                         "next to the ground truth's under the same rule, see --collision_radius")
     p.add_argument("--collision_radius", type=float, default=None,
-                   help="--joint: two agents closer than this many pixels in a frame touch (default: 0, nothing touches)")
+                   help="--joint, --plan_risk: two agents closer than this many pixels in a frame touch (default: 0, nothing touches)")
+    p.add_argument("--plan_risk", action="store_true",
+                   help="also report the leave-one-out plan risk (desire_plan_risk): per horizon the mean predicted risk of what each agent actually "
+                        "did, held against the K joint futures of the others, next to the rate at which it actually came within --collision_radius of "
+                        "somebody; a predictor that is calibrated about interactions brings the two close")
     p.add_argument("--occupancy", type=str, default=None, metavar="OHxOW",
                    help="also report the predicted occupancy maps of the score-weighted samples on a grid of OH x OW cells over the frame "
                         "(desire_occupancy): per horizon the mean of -log(max(mass on the ground truth's cell, 1e-6)), the mean mass off the frame and "
@@ -117,6 +121,8 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     occ_mode = str(getattr(args, "occupancy_mode", "at") or "at")
     o_nll, o_off, o_exp = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64)
     o_at = np.zeros(len(hz), np.int64)                                                           # agents counted at the horizon's own frame
+    plan_risk = bool(getattr(args, "plan_risk", False))
+    p_pred, p_act, p_agents = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.int64)
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
@@ -141,6 +147,11 @@ def evaluate(args, data_loader=None, model=None) -> dict:
             j_cnt["top1"] += cnt[np.arange(cnt.shape[0]), jm["order"][:, 0]].sum(0)
             j_cnt["all_K"] += cnt[:, :K].sum((0, 1))
             j_cnt["ground_truth"] += cnt[:, K].sum(0)
+        if plan_risk:                                # sums over the agents taking part, so that the batches weigh as their agents do
+            pm = model.evaluate_plan_risk(Y, score, fut, float(getattr(args, "collision_radius", None) or 0.0), horizons=hz)
+            p_pred += pm["predicted"] * pm["agents"]
+            p_act += pm["actual"] * pm["agents"]
+            p_agents += pm["agents"]
         if occ_grid:
             om = model.evaluate_occupancy(Y, score, fut, occ_grid, horizons=hz, mode=occ_mode)
             o_hit = om["hit"] if occ_mode == "at" else model.evaluate_occupancy(Y, score, fut, occ_grid, horizons=hz, mode="at")["hit"]
@@ -204,6 +215,10 @@ def evaluate(args, data_loader=None, model=None) -> dict:
                         "top1": {"jade": [float(v) for v in m[:, 0]], "jfde": [float(v) for v in m[:, 1]]},
                         "best_of_top": {"jade": [float(v) for v in m[:, 2]], "jfde": [float(v) for v in m[:, 3]]},
                         "collision_rate": rate, "slots": [int(v) for v in j_cnt["ground_truth"][:, 1]]}
+    if plan_risk:
+        res["plan_risk"] = {"collision_radius_px": float(getattr(args, "collision_radius", None) or 0.0), "agents": [int(v) for v in p_agents],
+                            "predicted_risk": [float(p_pred[i] / max(int(p_agents[i]), 1)) for i in range(len(hz))],
+                            "actual_rate": [float(p_act[i] / max(int(p_agents[i]), 1)) for i in range(len(hz))]}
     if occ_grid:
         res["occupancy"] = {"grid": [int(occ_grid[0]), int(occ_grid[1])], "mode": occ_mode, "weights": "score", "hit_floor": 1e-6,
                             "agents_at_frame": [int(v) for v in o_at],

@@ -700,6 +700,95 @@ class DESIREModel(object):
                         res["order"].data_ptr(), res["first"].data_ptr(), res["jerr"].data_ptr(), res["jscore"].data_ptr(), res["out"].data_ptr(), stream)
         return {k: v.cpu().numpy() for k, v in res.items()}
 
+    def _plan_risk(self, h, Y, fut, present, score, plans, ego, hz, radius, ux, uy):
+        """One desire_plan_risk call on device tensors: plans [n, M, T_pred, 2] normalised, ego [n, M] int32 or None.  Device tensors back."""
+        torch = self.torch
+        d = h.dims
+        n, M, nh = d.n_scenes, int(plans.shape[1]), len(hz)
+        dev, i32 = self.device, torch.int32
+        res = {"risk": torch.empty((n, M, nh), device=dev), "first": torch.empty((n, M, d.K + 1), device=dev, dtype=i32),
+               "clear": torch.empty((n, M, d.K + 1, nh), device=dev), "blame": torch.empty((n, M, nh, d.mno), device=dev)}
+        ptr = lambda x: 0 if x is None else x.data_ptr()
+        h.plan_risk(Y.data_ptr(), ptr(fut), ptr(present), ptr(score), plans.data_ptr(), ptr(ego), M, hz, radius, ux, uy, res["risk"].data_ptr(),
+                    res["first"].data_ptr(), res["clear"].data_ptr(), res["blame"].data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return res
+
+    def score_plans(self, past, plans, collision_radius, horizons=None, ego_slot=None, weights: str = "score", **predict_kwargs) -> dict:
+        """M candidate trajectories of the planner's own vehicle per window against the K joint futures the model predicts: the forward as
+        predict_device runs it (predict_kwargs: eps, seed, grid_of_scene, device_rng, window_base), then one desire_plan_risk call in its
+        prediction form (an agent counts when its id is != 0 at the last observed frame).  `past`: loader windows [T_obs, MNO, 3] or
+        predict_device's tensor; plans [n, M, T_pred, 2] IN PIXELS (scaled like the observed positions; a NaN frame: the plan is not defined
+        there); collision_radius in pixels, finite and >= 0; ego_slot [n, M] (or [n]: one slot for every plan of the window) = the slot the plan
+        replaces, negative or None: nobody.  Returns device tensors: "risk" [n, M, n_h] = the weight of the joint futures in which the plan comes
+        within the radius of somebody before the horizon (weights "score": softmax of the joint scores; "uniform": 1 / K), "clearance"
+        [n, M, K, n_h] = the smallest distance in pixels to anybody before the horizon (inf: nobody there), "first" [n, M, K] int32 = the frame
+        of the first contact (T_pred: none), "blame" [n, M, n_h, mno] = the risk by the agent touched, "present" [n, mno] and "best" [n, n_h] =
+        per horizon the plan of least risk, ties to the greater clearance (its smallest over the K futures), then to the lower index."""
+        torch = self.torch
+        if weights not in ("score", "uniform"):
+            raise ValueError("weights must be 'score' (softmax of the joint scores) or 'uniform', got %r" % (weights,))
+        if not (np.isfinite(float(collision_radius)) and float(collision_radius) >= 0):
+            raise ValueError("collision_radius must be finite and >= 0 (pixels), got %r" % (collision_radius,))
+        if not torch.is_tensor(past):
+            past = self._pad_windows(past, self._handle(len(past), False).dims.mno)
+        n = int(past.shape[0])
+        d = self._handle(n, False).dims
+        hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
+        P = torch.as_tensor(plans, device=self.device).to(torch.float32)
+        if P.dim() != 4 or int(P.shape[0]) != n or int(P.shape[1]) < 1 or tuple(P.shape[2:]) != (d.T_pred, 2):
+            raise ValueError("plans must be [n, M, T_pred, 2] in pixels with M >= 1, got %s" % (tuple(P.shape),))
+        M = int(P.shape[1])
+        P = (P * torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)).contiguous()
+        ego = None
+        if ego_slot is not None:
+            ego = torch.as_tensor(ego_slot, device=self.device).to(torch.int32)
+            ego = (ego[:, None].expand(n, M) if ego.dim() == 1 else ego).contiguous()
+            if tuple(ego.shape) != (n, M):
+                raise ValueError("ego_slot must be [n, M] or [n], got %s" % (tuple(ego.shape),))
+        Y, score = self.forward_device(past, None, **predict_kwargs)
+        h = self._handle(n, False)
+        present = past[:, -1, :, 0] != 0
+        res = self._plan_risk(h, Y, None, present.to(torch.uint8).contiguous(), score if weights == "score" else None, P, ego, hz,
+                              float(collision_radius), 1.0 / d.sx, 1.0 / d.sy)
+        clearance = res["clear"][:, :, :d.K].sqrt()
+        worst = clearance.min(2).values                                        # [n, M, n_h]
+        least = res["risk"] == res["risk"].min(1, keepdim=True).values
+        room = torch.where(least, worst, torch.full_like(worst, -1.0))
+        pick = least & (room == room.max(1, keepdim=True).values)
+        idx = torch.arange(M, device=self.device)[None, :, None].expand_as(pick)
+        best = torch.where(pick, idx, torch.full_like(idx, M)).min(1).values
+        return {"risk": res["risk"], "clearance": clearance, "first": res["first"][:, :, :d.K].contiguous(), "blame": res["blame"],
+                "present": present, "best": best}
+
+    def evaluate_plan_risk(self, Y, score, fut_windows, collision_radius, horizons=None, weights: str = "score") -> dict:
+        """Leave-one-out check of the predicted interactions that needs no planner: plan m of a window is what agent m actually did (its
+        recorded future, undefined where it is not counted), replacing slot m, held against the K joint futures of the others.  Returns numpy
+        arrays: "risk" [n, mno, n_h] = the predicted risk of what each agent did, "first" [n, mno, K + 1] int32 (row K: against the recorded
+        futures of the others), "takes_part" [n, mno, n_h] bool, and per horizon over the agents taking part before it "predicted" [n_h] = the
+        mean predicted risk, "actual" [n_h] = the rate at which they actually came within collision_radius (pixels) of somebody, "agents" [n_h].
+        A predictor that is calibrated about interactions brings the two columns close."""
+        torch = self.torch
+        if weights not in ("score", "uniform"):
+            raise ValueError("weights must be 'score' (softmax of the joint scores) or 'uniform', got %r" % (weights,))
+        n = int(Y.shape[0])
+        h = self._handles.get((n, 0, 0)) or self._handle(n, True)
+        d = h.dims
+        hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
+        fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
+        counted = (fut[..., 0] != 0).permute(0, 2, 1)                          # [n, mno, T_pred]
+        g = (fut[..., 1:] * torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)).permute(0, 2, 1, 3)
+        plans = torch.where(counted[..., None], g, torch.full_like(g, float("nan"))).contiguous()
+        ego = torch.arange(d.mno, device=self.device, dtype=torch.int32)[None].expand(n, d.mno).contiguous()
+        res = self._plan_risk(h, Y, fut, None, score if weights == "score" else None, plans, ego, hz, float(collision_radius), 1.0 / d.sx, 1.0 / d.sy)
+        takes = torch.stack([counted[:, :, :x].any(-1) for x in hz], -1)       # [n, mno, n_h]
+        hit = res["first"][:, :, d.K, None] < torch.tensor(hz, device=self.device, dtype=torch.int32)[None, None]
+        agents = takes.sum((0, 1)).to(torch.float64)
+        predicted = torch.where(takes, res["risk"], torch.zeros_like(res["risk"])).to(torch.float64).sum((0, 1))
+        actual = (takes & hit).sum((0, 1)).to(torch.float64)
+        den = agents.clamp(min=1)
+        return {"risk": res["risk"].cpu().numpy(), "first": res["first"].cpu().numpy(), "takes_part": takes.cpu().numpy(),
+                "predicted": (predicted / den).cpu().numpy(), "actual": (actual / den).cpu().numpy(), "agents": agents.cpu().numpy().astype(np.int64)}
+
     def _occupancy_args(self, d, grid, horizons, mode, weights, mask, mask_of_window, n):
         """(Oh, Ow, horizons, mode id, mask tensor or None, mask_of_window tensor or None) of the occupancy calls, refused here where they are bad."""
         torch = self.torch

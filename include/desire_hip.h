@@ -461,6 +461,46 @@ int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, const float* d
                          int32_t* dev_first, int32_t* dev_cnt, float* dev_jerr, float* dev_jscore, int32_t* dev_jorder,
                          float* dev_out, void* stream);
 
+/* ---- candidate ego plans against the K joint futures: a planner holds M candidate trajectories for its own vehicle per window and asks of each:
+ * how likely do I hit somebody before each horizon, how close do I get, when is the first contact, and which agent is the threat.  Layouts, the
+ * counting rule c(a, t), g, host_horizons, radius and unit_x / unit_y are desire_joint_metrics' exactly; a slot TAKES PART BEFORE h when it has a
+ * counted frame t < h.  All arithmetic is fp32, every operation rounded once (no fused multiply-add); no float atomics.
+ *   1 plans       dev_plans [n_scenes, M, T_pred, 2] fp32, normalised coordinates: M >= 1 candidate ego trajectories per window.  dev_ego
+ *                 [n_scenes, M] int32 (may be NULL) = the slot of the window that plan m replaces, or a negative value for none: that slot is left
+ *                 out of every rule below for that plan (contact, clearance, blame); it stays in the joint score.  NULL: no plan replaces anybody.
+ *                 An entry >= mno behaves as a negative one.  Exactly one of dev_fut and dev_present is non-NULL.
+ *   2 distance    for plan m, slot i, joint future k and frame t: a = (P[m, t, 0] - Y[r_i, t, 0]) * unit_x; b = (P[m, t, 1] - Y[r_i, t, 1]) * unit_y;
+ *                 q = a * a + b * b; r2 = radius * radius.  The plan TOUCHES slot i at t iff c(i, t) && q < r2: strict, false for a NaN (a NaN plan
+ *                 frame means `the plan is not defined here` and needs no rule of its own); radius 0: nothing touches.
+ *   3 truth       with dev_fut the same rule runs on the positions g(a, t) as a pseudo-sample k = K: would this plan have hit the recorded future.
+ *   4 first       dev_first [n_scenes, M, K + 1] int32 (may be NULL) = the smallest t at which the plan touches any slot, T_pred when there is none.
+ *                 With dev_present row K is filled with T_pred.
+ *   5 clearance   dev_clear [n_scenes, M, K + 1, n_h] (may be NULL) = the minimum of q over the slots i other than the ego slot and the counted
+ *                 frames t < h, starting from +inf; a NaN q never replaces the minimum, so the result does not depend on the order of the
+ *                 reduction.  Squared units: the caller takes the root.  With dev_present row K is +inf.
+ *   6 weights     js_k = desire_joint_metrics' step 7 (the sum of dev_score[r] over the slots taking part before T_pred, in increasing slot from
+ *                 0.f: the bits of dev_jscore).  W_k is desire_kde_nll's step 1 on the K joint scores: m = max_k js_k, e_k = expf(js_k - m),
+ *                 W_k = e_k / sum_k e_k, the sum in increasing k from 0.f.  W_k = 1.f / K for every k when dev_score is NULL or any js_k is not finite.
+ *   7 risk        dev_risk [n_scenes, M, n_h] (required) = sum_k W_k * [first(m, k) < h] over k < K, in increasing k from 0.f.
+ *   8 blame       dev_blame [n_scenes, M, n_h, mno] (may be NULL) = sum_k W_k * [plan m touches slot i at some t < h], in the same order; 0 for
+ *                 the ego slot and for a slot that is never counted.
+ *   9 A window's results depend on that window's rows, scores, targets and plans only -- not on the grid of workgroups, the batch, the chunks M
+ *     is cut into or DESIRE_FLAG_COMPACT_*.  Bitwise reproducible (first and clearance are order-free minima, every float sum one fixed
+ *     sequence), stream-ordered, capturable, no host wait, no allocation: the K weights of a window live in desire_joint_metrics' scratch of joint
+ *     scores, so the two calls are ordered by the stream like any two calls on one handle.
+ * LDS plan: one workgroup owns (window, chunk of PC plans), PC = as many plans as 256 (plan, slot) items hold, 32 at most, spread evenly over
+ * the chunks of M.  It stages the chunk's plans as float2 [PC][frames | 1] and each unit's positions as desire_joint_metrics does, next to
+ * 72 PC bytes of minima, 61440 bytes in all; when that does not fit it walks the frames in passes of (61440 - 80 PC) / (8 (PC + stride)) frames --
+ * 29 at 256 slots -- carrying first and the running minimum across them, with the bits of an unchunked walk.  Every (mno, K, T_pred) of a
+ * handle and every M is served.
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing is launched or written: a NULL handle / dev_Yhat / dev_plans / dev_risk /
+ * host_horizons; bad horizons; M < 1; a radius that is negative or not finite; a unit that is not finite and > 0; both or neither of dev_fut /
+ * dev_present; a ref_compat handle. */
+int desire_plan_risk(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present,
+                     const float* dev_score, const float* dev_plans, const int32_t* dev_ego, int32_t M,
+                     const int32_t* host_horizons, int32_t n_h, float radius, float unit_x, float unit_y,
+                     int32_t* dev_first, float* dev_clear, float* dev_risk, float* dev_blame, void* stream);
+
 /* ---- predicted occupancy maps: how likely is it that somebody stands in this cell of the frame at horizon h, or at any time before it.  The K
  * samples of every agent, weighted, are rasterised onto an Oh x Ow grid over the normalised frame [0, 1) x [0, 1).  Layouts are the evaluation
  * calls': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot, dev_fut [n_scenes, T_pred, mno, 3], host_horizons as in
