@@ -27,7 +27,7 @@ EXPORTS = [
     "desire_peer_export", "desire_peer_open", "desire_ioc_peer_pass", "desire_peer_close", "desire_peer_region", "desire_peer_open_ptr", "desire_peer_status",
     "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse", "desire_joint_metrics",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
-    "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy", "desire_plan_risk",
+    "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy", "desire_plan_risk", "desire_fit_modes",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
@@ -35,6 +35,7 @@ RNG_BITS, RNG_NORMAL, RNG_LATENT, RNG_ROLLOUT = 0, 1, 2, 3          # desire_rng
 DIST_FINAL, DIST_MEAN, DIST_MAX = 0, 1, 2                           # desire_select_diverse metrics (DESIRE_DIST_*)
 RECON_MEAN, RECON_MIN, RECON_SOFTMIN = 0, 1, 2                      # desire_set_recon_loss / desire_recon_weights modes (DESIRE_RECON_*)
 RECON_MODES = {"mean": RECON_MEAN, "min": RECON_MIN, "softmin": RECON_SOFTMIN}      # their names on the Python surface (args.recon_loss, --recon_loss)
+MODES_MAX, MODES_MAX_ITERS = 16, 32                                 # desire_fit_modes: the most modes and passes (DESIRE_MODES_MAX, _MAX_ITERS)
 KDE_LOG_FLOOR = -20.0                                               # desire_kde_nll: the clip of a frame's log-density (Trajectron++'s)
 
 
@@ -109,6 +110,8 @@ def load() -> C.CDLL:
                                          vp, f32p, vp]
     lib.desire_occupancy.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, i32, i32, vp, vp, f32p, f32p, f32p, f32p, f32p, vp]
     lib.desire_plan_risk.argtypes = [vp, f32p, f32p, vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, vp, f32p, f32p, f32p, vp]
+    lib.desire_fit_modes.argtypes = [vp, f32p, vp, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32), i32, C.c_float,
+                                     vp, vp, f32p, f32p, f32p, vp, f32p, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
     lib.desire_rollout_samples.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
@@ -348,6 +351,22 @@ class Handle:
                                        ego_ptr or None, int(M), hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, C.c_float(radius),
                                        C.c_float(unit_x), C.c_float(unit_y), first_ptr or None, clear_ptr or None, risk_ptr or None,
                                        blame_ptr or None, stream or None))
+
+    def fit_modes(self, yhat_ptr: int, order_ptr: int, score_ptr: int, n_modes: int, t_end: int, iters: int, unit_x: float, unit_y: float,
+                  var_floor: float, count_ptr: int, prob_ptr: int, label_ptr: int = 0, mean_ptr: int = 0, cov_ptr: int = 0, passes_ptr: int = 0,
+                  fut_ptr: int = 0, horizons=None, log_floor: float = KDE_LOG_FLOOR, out_ptr: int = 0, frame_ptr: int = 0, stream: int = 0) -> None:
+        """n_modes modes per agent fitted to its K weighted samples by a weighted Lloyd iteration seeded with the first n_modes entries of order
+        [A, K] (rank_samples' or select_diverse's), at most `iters` passes, the assignment distance over the frames t < t_end scaled by
+        (unit_x, unit_y): count [A, n_modes] int32 = the members of each mode, prob [A, n_modes] = their weight (softmax(score); score_ptr = 0:
+        1 / K), label [A, K] int32, mean [A, n_modes, T_pred, 2] in Y's coordinates, cov [A, n_modes, T_pred, 3] = (Cxx, Cyy, Cxy) in unit^2 with
+        var_floor added to the diagonal, passes [A] int32.  With fut_ptr (and horizons): out [A, n_h, 2] = (mean, final) negative log-density of
+        the ground truth under that mixture, clipped below at log_floor, as kde_nll reports it; frame [A, T_pred] the per-frame log-densities."""
+        hz = np.ascontiguousarray([] if horizons is None else horizons, dtype=np.int32).reshape(-1)
+        hzp = hz.ctypes.data_as(C.POINTER(C.c_int32)) if horizons is not None else None
+        _chk(self.lib.desire_fit_modes(self._h, yhat_ptr or None, order_ptr or None, score_ptr or None, fut_ptr or None, int(n_modes), int(t_end),
+                                       int(iters), C.c_float(unit_x), C.c_float(unit_y), C.c_float(var_floor), hzp, hz.size, C.c_float(log_floor),
+                                       label_ptr or None, count_ptr or None, prob_ptr or None, mean_ptr or None, cov_ptr or None,
+                                       passes_ptr or None, out_ptr or None, frame_ptr or None, stream or None))
 
     def occupancy(self, yhat_ptr: int, fut_ptr: int, present_ptr: int, score_ptr: int, horizons, mode: int, Oh: int, Ow: int, occ_ptr: int,
                   exp_ptr: int = 0, hit_ptr: int = 0, viol_ptr: int = 0, off_ptr: int = 0, mask_ptr: int = 0, mask_of_scene_ptr: int = 0,

@@ -394,6 +394,49 @@ extern "C" int desire_plan_risk(desire_handle* h, const float* dev_Yhat, const f
     return DESIRE_OK;
 }
 
+// ---- n modes with covariances fitted to the K samples (kernels_modes.hip): the contract is stated in include/desire_hip.h.  As in
+// desire_select_diverse the checks that need no handle come first. ----
+extern "C" int desire_fit_modes(desire_handle* h, const float* dev_Yhat, const int32_t* dev_order, const float* dev_score, const float* dev_fut,
+                                int32_t n_modes, int32_t t_end, int32_t iters, float unit_x, float unit_y, float var_floor,
+                                const int32_t* host_horizons, int32_t n_h, float log_floor, int32_t* dev_label, int32_t* dev_count, float* dev_prob,
+                                float* dev_mean, float* dev_cov, int32_t* dev_passes, float* dev_out, float* dev_frame, void* stream) {
+    if (n_modes < 1 || n_modes > DESIRE_MODES_MAX) return fail(DESIRE_ERR_ARG, "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")");
+    if (t_end < 1) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    if (iters < 0 || iters > DESIRE_MODES_MAX_ITERS) return fail(DESIRE_ERR_ARG, "iters must be 0.." + std::to_string(DESIRE_MODES_MAX_ITERS));
+    if (int rc = check_units(unit_x, unit_y)) return rc;
+    if (!std::isfinite(var_floor) || var_floor < 0.f) return fail(DESIRE_ERR_ARG, "var_floor must be finite and >= 0");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_order) return fail(DESIRE_ERR_ARG, "dev_order is NULL");
+    if (!dev_count) return fail(DESIRE_ERR_ARG, "dev_count is NULL");
+    if (!dev_prob) return fail(DESIRE_ERR_ARG, "dev_prob is NULL");
+    if (!dev_fut && dev_out) return fail(DESIRE_ERR_ARG, "dev_out needs dev_fut (the likelihood is that of the ground truth)");
+    if (!dev_fut && dev_frame) return fail(DESIRE_ERR_ARG, "dev_frame needs dev_fut (the likelihood is that of the ground truth)");
+    if (dev_fut && !dev_out) return fail(DESIRE_ERR_ARG, "dev_out is NULL (dev_fut asks for the likelihood)");
+    if (dev_fut && !host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (dev_fut && !std::isfinite(log_floor)) return fail(DESIRE_ERR_ARG, "log_floor must be finite");
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to fit modes to");
+    if (n_modes > d.K) return fail(DESIRE_ERR_ARG, "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")");
+    if (t_end > d.T_pred) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    RankHz hz{};
+    if (dev_fut)
+        if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
+    int sc = 0, g = 0;
+    if (!modes_geometry(d.mno, d.K, d.T_pred, n_modes, &sc, &g))
+        return fail(DESIRE_ERR_ARG, "K samples and n_modes means of T_pred frames do not fit the mode kernel's LDS: " + std::to_string(EVAL_PAIR_BYTES) +
+                                        " * (K + n_modes) * (T_pred | 1) + 12 * n_modes * T_pred + " + std::to_string(4 * ModesLds::FRAME_WORDS) +
+                                        " * (T_pred | 1) + " + std::to_string(4 * ModesLds::K_WORDS) + " * K + " +
+                                        std::to_string(4 * ModesLds::MODE_WORDS) + " * n_modes + " + std::to_string(4 * ModesLds::SLOT_WORDS) +
+                                        " must be <= " + std::to_string(EVAL_LDS_BYTES));
+    if ((uint64_t)d.n_scenes * (uint64_t)((d.mno + sc - 1) / sc) >= (1ull << 31)) return fail(DESIRE_ERR_ARG, "n_scenes * slot chunks must be below 2^31");
+    launch_fit_modes(dev_Yhat, dev_order, dev_score, dev_fut, dev_label, dev_count, dev_prob, dev_mean, dev_cov, dev_passes, dev_out, dev_frame,
+                     d.n_scenes, d.mno, d.K, d.T_pred, n_modes, t_end, iters, hz, d.sx, d.sy, unit_x, unit_y, var_floor, log_floor,
+                     static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- predicted occupancy maps of the K weighted samples (kernels_occ.hip): the contract is stated in include/desire_hip.h ----
 extern "C" int desire_occupancy(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present, const float* dev_score,
                                 const int32_t* host_horizons, int32_t n_h, int32_t mode, int32_t Oh, int32_t Ow, const uint8_t* dev_mask,

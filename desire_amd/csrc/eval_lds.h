@@ -1,5 +1,5 @@
 // eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
-// _recon / _occ / _plan.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// _recon / _occ / _plan / _modes.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
 // that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
 // Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp and occ_lds_driver.cpp compile it with g++ (tests/test_eval_lds.py, test_occ_lds.py).
 #pragma once
@@ -155,6 +155,42 @@ inline void plan_geometry(int mno, int T, int M, int* PC, int* TC) {
     const size_t fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;            // (PlanLds(.., 0) already holds the one pair per plan of the odd stride)
     *PC = pc;
     *TC = (int)((size_t)T < fit ? (size_t)T : fit);
+}
+
+// ---- k_fit_modes: float2 rows Yl [SC][K][Tp] (all T frames of the K samples of SC agents, Tp = T | 1), then the running means ml [SC][n][Tp] with
+// the same stride; behind the pairs, in 32-bit words: cov float [SC][n][T][3] (Cxx, Cyy, Cxy: the layout of the output, so it leaves by a linear
+// copy), val and cm float [SC][Tp] each (frame value and counted mask: KdeLds' pair), three [SC][K] words (weight, label, previous label), two
+// [SC][n] words (mass, member count) and four [SC] words (bad order row, passes, and the two parities of `a label changed in the last assign`).
+// The limit this gives is stated in desire_hip.h and in desire_fit_modes' message.
+struct ModesLds {
+    enum { FRAME_WORDS = 2, K_WORDS = 3, MODE_WORDS = 2, SLOT_WORDS = 4 };
+    int T, Tp, SC, K, n;
+    EVAL_HD constexpr ModesLds(int T_, int SC_, int K_, int n_) : T(T_), Tp(eval_odd(T_)), SC(SC_), K(K_), n(n_) {}
+    EVAL_HD constexpr size_t rows() const { return (size_t)SC * K * Tp; }                   // float2 in front of the means
+    EVAL_HD constexpr size_t pairs() const { return (size_t)SC * (K + n) * Tp; }            // float2 in front of the words
+    EVAL_HD constexpr size_t cov() const { return 0; }                                      // word offsets behind the pairs
+    EVAL_HD constexpr size_t frame_words(int r) const { return (size_t)3 * SC * n * T + (size_t)r * SC * Tp; }
+    EVAL_HD constexpr size_t k_words(int r) const { return frame_words(FRAME_WORDS) + (size_t)r * SC * K; }
+    EVAL_HD constexpr size_t mode_words(int r) const { return k_words(K_WORDS) + (size_t)r * SC * n; }
+    EVAL_HD constexpr size_t slot_words(int r) const { return mode_words(MODE_WORDS) + (size_t)r * SC; }
+    EVAL_HD static constexpr size_t agent_bytes(int K, int T, int n) {
+        return EVAL_PAIR_BYTES * (size_t)(K + n) * eval_odd(T) + 4 * ((size_t)3 * n * T + (size_t)FRAME_WORDS * eval_odd(T) + (size_t)K_WORDS * K +
+                                                                      (size_t)MODE_WORDS * n + SLOT_WORDS);
+    }
+    EVAL_HD constexpr size_t bytes() const { return (size_t)SC * agent_bytes(K, T, n); }
+};
+// The slot chunk: as many agents as the LDS holds, no more than one per group of G lanes (G = the power of two >= K, 64 at most, as in
+// select_geometry; beyond 64 samples a group's lanes loop), spread evenly over the chunks.  false: one agent does not fit.
+inline bool modes_geometry(int mno, int K, int T, int n, int* SC, int* G) {
+    const size_t per = ModesLds::agent_bytes(K, T, n);
+    if (per > (size_t)EVAL_LDS_BYTES) return false;
+    int g = 1;
+    while (g < K && g < 64) g <<= 1;
+    int sc = (int)((size_t)mno < (size_t)EVAL_LDS_BYTES / per ? (size_t)mno : (size_t)EVAL_LDS_BYTES / per);
+    sc = eval_min(sc, eval_max(1, EVAL_THREADS / g));
+    *SC = eval_chunks(mno, eval_chunks(mno, sc));
+    *G = g;
+    return true;
 }
 
 // ---- k_occupancy: 32-bit words.  Over the `cells` of a band of grid rows: E, q, P floats (expected count, product of the complements, one

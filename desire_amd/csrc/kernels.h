@@ -279,6 +279,13 @@ void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* prese
                           int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
                           const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
 
+// ---- n modes with covariances fitted to the K samples, and the mixture's likelihood (kernels_modes.hip) ----
+// score, fut, label, mean, cov and passes may be nullptr; out (required with fut) and frame only with fut; no scratch
+void launch_fit_modes(const float* Y, const int32_t* order, const float* score, const float* fut, int32_t* label, int32_t* count, float* prob,
+                      float* mean, float* cov, int32_t* passes, float* out, float* frame, int n_scenes, int mno, int K, int T, int n_modes,
+                      int t_end, int iters, const RankHz& hz, float sx, float sy, float ux, float uy, float var_floor, float log_floor,
+                      hipStream_t s);
+
 // ---- candidate ego plans against the K joint futures (kernels_plan.hip) ----
 // exactly one of fut / present; plans [n_scenes, M, T, 2]; w [n_scenes, K] is scratch of the call (the handle's "joint_js": the joint scores, then
 // their weights); score, ego, first, clear and blame may be nullptr

@@ -4,7 +4,8 @@ device, errors per horizon of the best-scored sample (top-1), of the best among 
     python -m desire_amd.evaluate --checkpoint save/social_model-400.npz --data_dir data/ --max_num_obj 32 --d_dim 128 \\
         --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json] \\
         [--generator cvae|rollout] [--nll] [--select nms --nms_radius 20 [--nms_metric final|mean|max] [--nms_horizon 12]] \\
-        [--joint [--collision_radius 10]] [--occupancy 64x64 [--occupancy_mode at|until]] [--plan_risk [--collision_radius 10]]
+        [--joint [--collision_radius 10]] [--occupancy 64x64 [--occupancy_mode at|until]] [--plan_risk [--collision_radius 10]] \\
+        [--modes 6 [--modes_iters 8] [--modes_min_std 1.0] [--modes_seeds nms|score]]
 
 The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
@@ -60,6 +61,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--occupancy_mode", type=str, default="at", choices=("at", "until"),
                    help="--occupancy: the maps at the frame of the horizon (at) or swept over every frame before it (until); the mass on the ground "
                         "truth's cell is always the frame's")
+    p.add_argument("--modes", type=int, default=0, metavar="N",
+                   help="also report the mixture of N modes per agent that predict_modes hands out (desire_fit_modes): per horizon its negative "
+                        "log-likelihood of the ground truth (mean over the frames and final frame; density per unit^2 of --units, log clipped at -20) and "
+                        "the ADE / FDE of the most probable mode's mean and of the best mode's mean")
+    p.add_argument("--modes_iters", type=int, default=8, help="--modes: the most Lloyd passes (0..32)")
+    p.add_argument("--modes_min_std", type=float, default=1.0, help="--modes: the standard deviation in pixels whose square is added to every variance")
+    p.add_argument("--modes_seeds", type=str, default="nms", choices=("nms", "score"),
+                   help="--modes: the seeds -- nms: the mutually distinct samples first (needs --nms_radius; --nms_metric applies), score: the best-scored")
     p.add_argument("--out", type=str, default=None, help="write the result JSON here (default: standard output only)")
     return p
 
@@ -123,6 +132,11 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     o_at = np.zeros(len(hz), np.int64)                                                           # agents counted at the horizon's own frame
     plan_risk = bool(getattr(args, "plan_risk", False))
     p_pred, p_act, p_agents = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.int64)
+    n_modes = int(getattr(args, "modes", 0) or 0)
+    if n_modes and str(getattr(args, "modes_seeds", "nms")) == "nms" and getattr(args, "nms_radius", None) is None:
+        raise ValueError("--modes with --modes_seeds nms needs --nms_radius (pixels)")
+    m_sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("nll", "top1", "best")}
+    m_passes, m_present = 0, 0
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
@@ -156,6 +170,10 @@ def evaluate(args, data_loader=None, model=None) -> dict:
             om = model.evaluate_occupancy(Y, score, fut, occ_grid, horizons=hz, mode=occ_mode)
             o_hit = om["hit"] if occ_mode == "at" else model.evaluate_occupancy(Y, score, fut, occ_grid, horizons=hz, mode="at")["hit"]
             o_exp += om["expected"].astype(np.float64).sum((0, 2, 3))
+        if n_modes:
+            mm = model.evaluate_modes(Y, score, fut, modes=n_modes, seeds=str(getattr(args, "modes_seeds", "nms")), nms_radius=getattr(args, "nms_radius", None),
+                                      nms_metric=str(getattr(args, "nms_metric", "final")), iters=int(getattr(args, "modes_iters", 8)),
+                                      min_std=float(getattr(args, "modes_min_std", 1.0)), horizons=hz, units=units, log_floor=KDE_LOG_FLOOR)
         pw, fw = np.stack(past), np.stack(fut)
         mno = ranked.shape[0] // pw.shape[0]
         valid = np.zeros((pw.shape[0], mno), bool)
@@ -175,6 +193,9 @@ def evaluate(args, data_loader=None, model=None) -> dict:
                 o_at[i] += int(at.sum())
                 o_nll[i] += float(-np.log(np.maximum(o_hit.reshape(-1, len(hz))[at, i].astype(np.float64), 1e-6)).sum())
                 o_off[i] += float(om["off"].reshape(-1, len(hz))[c, i].astype(np.float64).sum())
+            if n_modes:
+                for k in m_sums:
+                    m_sums[k][i] += mm[k][c, i].astype(np.float64).sum(0)
             if nll:
                 nll_sums["uniform"][i] += nll_u[c, i].astype(np.float64).sum(0)
                 nll_sums["score_weighted"][i] += nll_w[c, i].astype(np.float64).sum(0)
@@ -184,6 +205,9 @@ def evaluate(args, data_loader=None, model=None) -> dict:
             nms_count += int(kept[valid.reshape(-1)].sum())
             nms_present += int(valid.sum())
         n_all += int(c.sum())
+        if n_modes:                                  # passes per agent present at the last observed frame
+            m_passes += int(mm["passes"][valid.reshape(-1)].sum())
+            m_present += int(valid.sum())
         if nll:                                      # the counted frames of those agents, and how many of them sit on the floor (equal weights)
             cf = (valid[:, None, :] & seen).transpose(0, 2, 1).reshape(fr.shape)
             nll_frames += int(cf.sum())
@@ -225,6 +249,14 @@ def evaluate(args, data_loader=None, model=None) -> dict:
                             "hit_nll": [float(o_nll[i] / max(int(o_at[i]), 1)) for i in range(len(hz))],
                             "off_mass": [float(o_off[i] / max(int(agents[i]), 1)) for i in range(len(hz))],
                             "expected_in_frame": [float(o_exp[i] / max(n_windows, 1)) for i in range(len(hz))]}
+    if n_modes:
+        m = {k: v / np.maximum(agents, 1)[:, None] for k, v in m_sums.items()}
+        res["modes"] = {"n": n_modes, "seeds": str(getattr(args, "modes_seeds", "nms")), "iters": int(getattr(args, "modes_iters", 8)),
+                        "min_std_px": float(getattr(args, "modes_min_std", 1.0)), "log_floor": KDE_LOG_FLOOR,
+                        "mean_passes": float(m_passes / max(m_present, 1)),
+                        "nll": {"mean": [float(v) for v in m["nll"][:, 0]], "final": [float(v) for v in m["nll"][:, 1]]},
+                        "top1": {"ade": [float(v) for v in m["top1"][:, 0]], "fde": [float(v) for v in m["top1"][:, 1]]},
+                        "best": {"ade": [float(v) for v in m["best"][:, 0]], "fde": [float(v) for v in m["best"][:, 1]]}}
     return res
 
 

@@ -789,6 +789,123 @@ class DESIREModel(object):
         return {"risk": res["risk"].cpu().numpy(), "first": res["first"].cpu().numpy(), "takes_part": takes.cpu().numpy(),
                 "predicted": (predicted / den).cpu().numpy(), "actual": (actual / den).cpu().numpy(), "agents": agents.cpu().numpy().astype(np.int64)}
 
+    @staticmethod
+    def _modes_args(d, modes, seeds, nms_radius, iters, min_std, weights):
+        """(n_modes, iters) of the mode calls, refused here where they are bad (before a forward runs)."""
+        n = int(modes)
+        if not 1 <= n <= min(d.K, _lib.MODES_MAX):
+            raise ValueError("modes must be 1..min(num_samples, %d), got %d" % (_lib.MODES_MAX, n))
+        if seeds not in ("nms", "score"):
+            raise ValueError("seeds must be 'nms' (the mutually distinct samples first) or 'score' (the best-scored samples), got %r" % (seeds,))
+        if seeds == "nms" and nms_radius is None:
+            raise ValueError("seeds='nms' needs nms_radius (pixels)")
+        if not 0 <= int(iters) <= _lib.MODES_MAX_ITERS:
+            raise ValueError("iters must be 0..%d, got %r" % (_lib.MODES_MAX_ITERS, iters))
+        if not (np.isfinite(float(min_std)) and float(min_std) >= 0):
+            raise ValueError("min_std must be finite and >= 0 (pixels), got %r" % (min_std,))
+        if weights not in ("score", "uniform"):
+            raise ValueError("weights must be 'score' (softmax of the IOC scores) or 'uniform', got %r" % (weights,))
+        return n, int(iters)
+
+    def _fit_modes(self, h, Y, score, fut, n, seeds, nms, iters, t_end, ux, uy, var_floor, weighted, hz=None, log_floor=_lib.KDE_LOG_FLOOR):
+        """Rank (and the non-maximum suppression with seeds "nms"), then one desire_fit_modes call, on device tensors.  Device tensors back, shaped
+        per window and slot."""
+        torch = self.torch
+        d = h.dims
+        dev, i32 = self.device, torch.int32
+        N, m = d.n_scenes, d.mno
+        stream = torch.cuda.current_stream().cuda_stream
+        order = torch.empty((d.A, d.K), device=dev, dtype=i32)
+        h.rank_samples(score.data_ptr(), 0, n, order.data_ptr(), 0, 0, stream)
+        if seeds == "nms":
+            diverse, kept = torch.empty_like(order), torch.empty((d.A,), device=dev, dtype=i32)
+            h.select_diverse(Y.data_ptr(), order.data_ptr(), score.data_ptr(), nms[0], nms[1], nms[2], 1.0 / d.sx, 1.0 / d.sy, n, diverse.data_ptr(),
+                             kept.data_ptr(), 0, 0, 0, stream)
+            order = diverse
+        res = {"mean": torch.empty((N, m, n, d.T_pred, 2), device=dev), "cov": torch.empty((N, m, n, d.T_pred, 3), device=dev),
+               "prob": torch.empty((N, m, n), device=dev), "label": torch.empty((N, m, d.K), device=dev, dtype=i32),
+               "count": torch.empty((N, m, n), device=dev, dtype=i32), "passes": torch.empty((N, m), device=dev, dtype=i32)}
+        if fut is not None:
+            res["nll"] = torch.empty((N, m, len(hz), 2), device=dev)
+        h.fit_modes(Y.data_ptr(), order.data_ptr(), score.data_ptr() if weighted else 0, n, t_end, iters, ux, uy, var_floor, res["count"].data_ptr(),
+                    res["prob"].data_ptr(), res["label"].data_ptr(), res["mean"].data_ptr(), res["cov"].data_ptr(), res["passes"].data_ptr(),
+                    0 if fut is None else fut.data_ptr(), hz, float(log_floor), res["nll"].data_ptr() if fut is not None else 0, 0, stream)
+        return res
+
+    def predict_modes(self, past, modes: int = 6, seeds: str = "nms", nms_radius=None, nms_metric: str = "final", iters: int = 8,
+                      min_std: float = 1.0, horizon=None, weights: str = "score", **predict_kwargs) -> dict:
+        """A small mixture per agent, the form trackers, planners and the benchmark formats take: the forward as predict_device runs it
+        (predict_kwargs: eps, seed, grid_of_scene, device_rng, window_base), the ranking by IOC score (and, with seeds "nms", the score-ordered
+        non-maximum suppression at nms_radius pixels by nms_metric, so that the seeds are mutually distinct samples), then one desire_fit_modes
+        call: a weighted Lloyd iteration of at most `iters` passes from the first `modes` samples of that order, the assignment looking at the
+        first `horizon` frames (None: all).  `past`: loader windows [T_obs, MNO, 3] or predict_device's tensor.  Returns device tensors: "mean"
+        [n, mno, modes, T_pred, 2] IN PIXELS, "cov" [n, mno, modes, T_pred, 3] = (Cxx, Cyy, Cxy) in px^2 with min_std^2 (pixels) added to the
+        diagonal, "prob" [n, mno, modes] = the weight of a mode's members (weights "score": softmax of the IOC scores; "uniform": 1 / K), "label"
+        [n, mno, K] int32 = the mode of every sample, "count" [n, mno, modes] int32, "passes" [n, mno] int32 and "present" [n, mno] bool.  All K
+        samples and scores stay available as self.final_output / self.final_states."""
+        torch = self.torch
+        if not torch.is_tensor(past):
+            past = self._pad_windows(past, self._handle(len(past), False).dims.mno)
+        n_w = int(past.shape[0])
+        d = self._handle(n_w, False).dims
+        n, iters = self._modes_args(d, modes, seeds, nms_radius, iters, min_std, weights)     # refused before the forward runs
+        nms = self._nms_args("nms", nms_radius, nms_metric, horizon, d.T_pred) if seeds == "nms" else None
+        t_end = d.T_pred if horizon is None else int(horizon)
+        if not 1 <= t_end <= d.T_pred:
+            raise ValueError("horizon must be 1..pred_length (%d), got %d" % (d.T_pred, t_end))
+        Y, score = self.forward_device(past, None, **predict_kwargs)
+        h = self._handle(n_w, False)
+        res = self._fit_modes(h, Y, score, None, n, seeds, nms, iters, t_end, 1.0 / d.sx, 1.0 / d.sy, float(min_std) ** 2, weights == "score")
+        res["mean"] /= torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)
+        res["present"] = past[:, -1, :, 0] != 0
+        return res
+
+    def evaluate_modes(self, Y, score, fut_windows, modes: int = 6, seeds: str = "nms", nms_radius=None, nms_metric: str = "final", iters: int = 8,
+                       min_std: float = 1.0, horizon=None, weights: str = "score", horizons=None, units="px",
+                       log_floor: float = _lib.KDE_LOG_FLOOR) -> dict:
+        """The mixture predict_modes hands out, held against the ground truth.  Returns numpy arrays per agent a = window * mno + slot: "nll"
+        [A, n_h, 2] = per horizon the (mean, final-frame) negative log-likelihood of the ground truth under the agent's mixture (density per
+        unit^2, the log clipped below at log_floor, as evaluate_nll reports the KDE's), "top1" [A, n_h, 2] = (ADE, FDE) of the most probable
+        mode's mean, "best" [A, n_h, 2] = the minimum over the modes with mass of their means' ADE, and of their FDE; zeros where the agent has no
+        counted frame before the horizon; and "prob" [A, modes], "count" [A, modes], "passes" [A].  units, horizons and `fut_windows` as in
+        evaluate_ranked; min_std and nms_radius in pixels."""
+        torch = self.torch
+        N = int(Y.shape[0])
+        h = self._handles.get((N, 0, 0)) or self._handle(N, True)
+        d = h.dims
+        n, iters = self._modes_args(d, modes, seeds, nms_radius, iters, min_std, weights)
+        nms = self._nms_args("nms", nms_radius, nms_metric, horizon, d.T_pred) if seeds == "nms" else None
+        t_end = d.T_pred if horizon is None else int(horizon)
+        hz = default_horizons(d.T_pred) if horizons is None else [int(x) for x in horizons]
+        ux, uy, f = self._unit_scale(units, d)
+        fut = fut_windows if torch.is_tensor(fut_windows) else self._pad_windows(fut_windows, d.mno)
+        res = self._fit_modes(h, Y, score, fut, n, seeds, nms, iters, t_end, ux, uy, (float(min_std) * f) ** 2, weights == "score", hz, log_floor)
+        # the errors of the means: torch on the small [A, n, T, 2] tensor
+        mean = res["mean"].reshape(d.A, n, d.T_pred, 2)
+        prob = res["prob"].reshape(d.A, n)
+        counted = (fut[..., 0] != 0).permute(0, 2, 1).reshape(d.A, d.T_pred)
+        g = (fut[..., 1:] * torch.tensor([d.sx, d.sy], device=self.device, dtype=torch.float32)).permute(0, 2, 1, 3).reshape(d.A, 1, d.T_pred, 2)
+        e = (((mean - g) * torch.tensor([ux, uy], device=self.device, dtype=torch.float32)) ** 2).sum(-1).sqrt()      # [A, n, T]
+        e = torch.where(counted[:, None], e, torch.zeros_like(e))
+        top = prob.argmax(1)
+        alive = prob > 0
+        inf = torch.full((), float("inf"), device=self.device)
+        top1, best = torch.zeros((d.A, len(hz), 2), device=self.device), torch.zeros((d.A, len(hz), 2), device=self.device)
+        ar = torch.arange(d.A, device=self.device)
+        for i, x in enumerate(hz):
+            c = counted[:, :x]
+            np_ = c.sum(1)
+            last = (c * torch.arange(1, x + 1, device=self.device)).argmax(1)                                         # the last counted frame < x
+            ade = e[:, :, :x].sum(2) / np_.clamp(min=1)[:, None]
+            fde = e[ar, :, last]
+            has = (np_ > 0) & alive.any(1)
+            both = torch.stack([ade, fde], -1)                                                                        # [A, n, 2]
+            top1[:, i] = torch.where(has[:, None], both[ar, top], torch.zeros_like(top1[:, i]))
+            low = torch.where(alive[:, :, None], both, inf).min(1).values
+            best[:, i] = torch.where(has[:, None], low, torch.zeros_like(low))
+        return {"nll": res["nll"].reshape(d.A, len(hz), 2).cpu().numpy(), "top1": top1.cpu().numpy(), "best": best.cpu().numpy(),
+                "prob": prob.cpu().numpy(), "count": res["count"].reshape(d.A, n).cpu().numpy(), "passes": res["passes"].reshape(d.A).cpu().numpy()}
+
     def _occupancy_args(self, d, grid, horizons, mode, weights, mask, mask_of_window, n):
         """(Oh, Ow, horizons, mode id, mask tensor or None, mask_of_window tensor or None) of the occupancy calls, refused here where they are bad."""
         torch = self.torch

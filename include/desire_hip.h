@@ -501,6 +501,64 @@ int desire_plan_risk(desire_handle* h, const float* dev_Yhat, const float* dev_f
                      const int32_t* host_horizons, int32_t n_h, float radius, float unit_x, float unit_y,
                      int32_t* dev_first, float* dev_clear, float* dev_risk, float* dev_blame, void* stream);
 
+/* ---- n modes with covariances per agent: what trackers, planners and the benchmark formats take -- a small mixture per agent: n modes, a
+ * probability for each, a mean trajectory and a 2 x 2 covariance per frame -- fitted to the agent's K weighted samples by a weighted Lloyd
+ * iteration from given seeds, and the likelihood of the ground truth under exactly that mixture.  Layouts are desire_select_diverse's: agent
+ * a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot; dev_order [A, K] int32 = the seed order (desire_rank_samples' output, or
+ * desire_select_diverse's, which puts mutually distinct samples first); dev_score [R] or NULL; dev_fut [n_scenes, T_pred, mno, 3] or NULL (only
+ * the likelihood needs it).  All arithmetic is fp32, every operation rounded once (no fused multiply-add), every sum over k or t runs in increasing
+ * index from 0.f; no float atomics.
+ *   1 weights     w_k = desire_kde_nll's step 1: NULL dev_score or any non-finite score of the agent: 1.f / K; else m = max_j s_j, e_k =
+ *                 expf(s_k - m), w_k = e_k / sum_j e_j.
+ *   2 seeds       c_i = dev_order[a, i] for i < n_modes; mean_i[t] = Y[r_{c_i}, t, :] for every t < T_pred.  Only these n_modes entries of the row
+ *                 are read.  The agent is BAD when one of them lies outside 0 .. K-1 or repeats an earlier one: it gets labels -1, counts 0, prob,
+ *                 mean and cov 0.f, passes 0 and log_floor at every counted frame.  No case reads outside dev_Yhat.
+ *   3 distance    D(k, i) = sum over t < t_end, from 0.f in increasing t, of (a * a + b * b), with a = (Y[r_k, t, 0] - mean_i[t, 0]) * unit_x and
+ *                 b = (Y[r_k, t, 1] - mean_i[t, 1]) * unit_y.
+ *   4 assign      label_k: walking i = 0 .. n_modes-1, mode i is taken when D(k, i) is not a NaN and either nothing is taken yet or D(k, i) < the
+ *                 distance taken (strict: ties go to the lower i; a NaN is never chosen).  Every D(k, i) a NaN: label_k = -1, and sample k is
+ *                 left out of everything below.
+ *   5 update      W_i = the sum of w_k over the samples with label_k = i, in increasing k from 0.f.  When W_i > 0: mean_i[t, c] = (the sum of
+ *                 w_k * Y[r_k, t, c] over the same samples in the same order) / W_i for every t < T_pred.  A mode without members, or with
+ *                 W_i == 0 (its members' weights underflowed), keeps the mean it has.
+ *   6 iteration   labels = assign(seed means).  For p = 1 .. iters: update, assign, and stop when no label differs from the pass before.  The stop
+ *                 is exact: equal labels reproduce the means bit for bit.  The reported means are update(final labels) in every case, so
+ *                 iters = 0 gives the weighted means of the seeds' Voronoi cells.  dev_passes [A] int32 (may be NULL) = the p reached (iters
+ *                 when the labels never stood still).
+ *   7 outputs     dev_label [A, K] int32 (may be NULL); dev_count [A, n_modes] int32 = the members of mode i; dev_prob [A, n_modes] = W_i -- the
+ *                 mass of the samples with label -1 is simply missing from the sum, the probabilities are NOT renormalised; dev_mean
+ *                 [A, n_modes, T_pred, 2] (may be NULL), in Y's own coordinates (a mode that never had mass reports its seed row); dev_cov
+ *                 [A, n_modes, T_pred, 3] (may be NULL) = (Cxx, Cyy, Cxy): with c_k = ((Y[r_k, t, 0] - mean_i[t, 0]) * unit_x, (Y[r_k, t, 1] -
+ *                 mean_i[t, 1]) * unit_y) over the members of mode i in increasing k, Cxx = (sum w_k * (c_kx * c_kx)) / W_i + var_floor, Cyy
+ *                 alike, Cxy = (sum w_k * (c_kx * c_ky)) / W_i; three zeros (no floor) for a mode with W_i == 0.  var_floor is in the caller's
+ *                 units squared.
+ *   8 likelihood  only with dev_fut: dev_out [A, n_h, 2] (then required) and dev_frame [A, T_pred] (may be NULL).  The counting rule, g, the
+ *                 floor, the per-horizon mean and last-frame reduction and the zeros when nothing is counted are desire_kde_nll's steps 7 - 8.
+ *                 For a counted (a, t) mode i is USABLE when prob_i > 0 and det > DESIRE_KDE_MIN_DET_RATIO * Cxx * Cyy, det = Cxx * Cyy - Cxy * Cxy.
+ *                 d = ((mean_i[t, 0] - g_x) * unit_x, (mean_i[t, 1] - g_y) * unit_y); l_i = logf(prob_i) + (-0.5f * ((Cyy * (d_x * d_x) -
+ *                 (2.f * Cxy) * (d_x * d_y)) + Cxx * (d_y * d_y))) / det - logf(2 pi) - 0.5f * logf(det), left to right; M = the maximum of the
+ *                 l_i (fmaxf, from -inf); l = M + logf(sum of expf(l_i - M) over the usable modes in increasing i, from 0.f).  The frame's value is
+ *                 l where l > log_floor, else log_floor (a NaN among them, and a frame without a usable mode).
+ * A result depends on its agent's rows, order, scores and targets only -- not on the grid, the rest of the batch, DESIRE_FLAG_COMPACT_* or the
+ * last desire_encode.  An absent slot's zero rows coincide: it reports count (K, 0, ...), zero spread plus var_floor, and needs no validity input.
+ * One launch, stream-ordered, capturable, no host wait, no allocation, no scratch; bitwise reproducible.  host_horizons, n_h and log_floor are
+ * read (and checked) only with dev_fut.
+ * LDS plan: one workgroup stages all T_pred frames of all K samples of a chunk of slots next to the n_modes running means, the covariances and the
+ * per-sample words; one agent must fit: 8 * (K + n_modes) * (T_pred | 1) + 12 * n_modes * T_pred + 8 * (T_pred | 1) + 12 * K + 8 * n_modes + 16
+ * <= 61440 bytes -- e.g. (K 20, T_pred 40, n 6), (K 130, T_pred 9, n 4), (K 64, T_pred 9, n 16), (K 3, T_pred 200, n 3).  K beyond 64 is served
+ * (a group's lanes loop), not refused.
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing is launched or written: n_modes outside 1 .. min(K, DESIRE_MODES_MAX); t_end outside
+ * 1 .. T_pred; iters outside 0 .. DESIRE_MODES_MAX_ITERS; a unit that is not finite and > 0; a var_floor that is negative or not finite; a NULL
+ * dev_Yhat / dev_order / dev_count / dev_prob; dev_out or dev_frame without dev_fut; dev_fut without dev_out or host_horizons; with dev_fut bad
+ * horizons or a non-finite log_floor; a NULL handle; a ref_compat handle; a (K, T_pred, n_modes) beyond the LDS plan. */
+#define DESIRE_MODES_MAX 16
+#define DESIRE_MODES_MAX_ITERS 32
+int desire_fit_modes(desire_handle* h, const float* dev_Yhat, const int32_t* dev_order, const float* dev_score, const float* dev_fut,
+                     int32_t n_modes, int32_t t_end, int32_t iters, float unit_x, float unit_y, float var_floor,
+                     const int32_t* host_horizons, int32_t n_h, float log_floor,
+                     int32_t* dev_label, int32_t* dev_count, float* dev_prob, float* dev_mean, float* dev_cov, int32_t* dev_passes,
+                     float* dev_out, float* dev_frame, void* stream);
+
 /* ---- predicted occupancy maps: how likely is it that somebody stands in this cell of the frame at horizon h, or at any time before it.  The K
  * samples of every agent, weighted, are rasterised onto an Oh x Ow grid over the normalised frame [0, 1) x [0, 1).  Layouts are the evaluation
  * calls': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot, dev_fut [n_scenes, T_pred, mno, 3], host_horizons as in
