@@ -162,6 +162,14 @@ def _chk(rc: int) -> None:
         raise DesireError("libdesire_hip error %d: %s" % (rc, load().desire_last_error().decode()))
 
 
+def _horizons(horizons, optional: bool = False):
+    """(the horizons as a flat int32 array, its const int32_t* for a call); with optional, None gives an empty array and a NULL pointer."""
+    if optional and horizons is None:
+        return np.zeros(0, np.int32), None
+    hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+    return hz, hz.ctypes.data_as(C.POINTER(C.c_int32))
+
+
 class Handle:
     """Thin owner of one desire_handle*.  All device pointers are raw integers (torch .data_ptr())."""
 
@@ -297,8 +305,8 @@ class Handle:
                       stream: int = 0) -> None:
         """out [A, len(horizons), 4] = (ADE_h, FDE_h of the best-scored sample, best ADE_h, FDE_h among the n_top best-scored); errors are
         scaled by (unit_x, unit_y) per axis: (1, 1) normalised units, (1/sx, 1/sy) pixels."""
-        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
-        _chk(self.lib.desire_ranked_errors(self._h, yhat_ptr, fut_ptr, order_ptr, int(n_top), hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size,
+        hz, hzp = _horizons(horizons)
+        _chk(self.lib.desire_ranked_errors(self._h, yhat_ptr, fut_ptr, order_ptr, int(n_top), hzp, hz.size,
                                            C.c_float(unit_x), C.c_float(unit_y), out_ptr, stream or None))
 
     def kde_nll(self, yhat_ptr: int, fut_ptr: int, score_ptr: int, horizons, unit_x: float, unit_y: float, log_floor: float, out_ptr: int,
@@ -306,8 +314,8 @@ class Handle:
         """out [A, len(horizons), 2] = (mean, final) negative log-density of the ground truth under a Gaussian KDE of the agent's K samples, per
         frame, clipped below at log_floor, over the counted frames before each horizon; score_ptr = 0: equal weights, else softmax(score).  The
         density is per unit^2 of (unit_x, unit_y), as in ranked_errors.  frame [A, T_pred] (optional): the per-frame log-densities."""
-        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
-        _chk(self.lib.desire_kde_nll(self._h, yhat_ptr or None, fut_ptr or None, score_ptr or None, hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size,
+        hz, hzp = _horizons(horizons)
+        _chk(self.lib.desire_kde_nll(self._h, yhat_ptr or None, fut_ptr or None, score_ptr or None, hzp, hz.size,
                                      C.c_float(unit_x), C.c_float(unit_y), C.c_float(log_floor), out_ptr or None, frame_ptr or None, stream or None))
 
     def select_diverse(self, yhat_ptr: int, order_ptr: int, score_ptr: int, metric: int, t_end: int, radius: float, unit_x: float, unit_y: float,
@@ -331,9 +339,9 @@ class Handle:
         (rank_samples' rule), out [n, n_h, 4] = (JADE, JFDE of the best-scored joint sample, best JADE, best JFDE among the n_top best-scored).
         Exactly one of fut_ptr (evaluation) and present_ptr ([A] uint8, prediction time: no jerr / out); distances are scaled by (unit_x, unit_y)
         as in ranked_errors."""
-        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+        hz, hzp = _horizons(horizons)
         _chk(self.lib.desire_joint_metrics(self._h, yhat_ptr or None, fut_ptr or None, present_ptr or None, score_ptr or None,
-                                           hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, int(n_top), C.c_float(radius), C.c_float(unit_x),
+                                           hzp, hz.size, int(n_top), C.c_float(radius), C.c_float(unit_x),
                                            C.c_float(unit_y), first_ptr or None, cnt_ptr or None, jerr_ptr or None, jscore_ptr or None,
                                            jorder_ptr or None, out_ptr or None, stream or None))
 
@@ -346,9 +354,9 @@ class Handle:
         first contact (T_pred: never; row K: the ground truth), clear [n, M, K + 1, n_h] = the smallest SQUARED distance to any slot before each
         horizon (+inf: nobody counted), blame [n, M, n_h, mno] = the risk split by the slot touched.  Exactly one of fut_ptr (evaluation) and
         present_ptr ([A] uint8, prediction time); distances are scaled by (unit_x, unit_y) as in joint_metrics."""
-        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+        hz, hzp = _horizons(horizons)
         _chk(self.lib.desire_plan_risk(self._h, yhat_ptr or None, fut_ptr or None, present_ptr or None, score_ptr or None, plans_ptr or None,
-                                       ego_ptr or None, int(M), hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, C.c_float(radius),
+                                       ego_ptr or None, int(M), hzp, hz.size, C.c_float(radius),
                                        C.c_float(unit_x), C.c_float(unit_y), first_ptr or None, clear_ptr or None, risk_ptr or None,
                                        blame_ptr or None, stream or None))
 
@@ -361,8 +369,7 @@ class Handle:
         1 / K), label [A, K] int32, mean [A, n_modes, T_pred, 2] in Y's coordinates, cov [A, n_modes, T_pred, 3] = (Cxx, Cyy, Cxy) in unit^2 with
         var_floor added to the diagonal, passes [A] int32.  With fut_ptr (and horizons): out [A, n_h, 2] = (mean, final) negative log-density of
         the ground truth under that mixture, clipped below at log_floor, as kde_nll reports it; frame [A, T_pred] the per-frame log-densities."""
-        hz = np.ascontiguousarray([] if horizons is None else horizons, dtype=np.int32).reshape(-1)
-        hzp = hz.ctypes.data_as(C.POINTER(C.c_int32)) if horizons is not None else None
+        hz, hzp = _horizons(horizons, optional=True)
         _chk(self.lib.desire_fit_modes(self._h, yhat_ptr or None, order_ptr or None, score_ptr or None, fut_ptr or None, int(n_modes), int(t_end),
                                        int(iters), C.c_float(unit_x), C.c_float(unit_y), C.c_float(var_floor), hzp, hz.size, C.c_float(log_floor),
                                        label_ptr or None, count_ptr or None, prob_ptr or None, mean_ptr or None, cov_ptr or None,
@@ -377,9 +384,9 @@ class Handle:
         of mask [n_masks, Oh, Ow] uint8 is 0 (mask_of_scene [n] int32 on the device, negative: none), hit = the weight on the ground truth's cell
         (fut_ptr and OCC_AT only).  Exactly one of fut_ptr (evaluation) and present_ptr ([A] uint8, prediction time); score_ptr = 0: equal
         weights, else softmax(score) as in kde_nll."""
-        hz = np.ascontiguousarray(horizons, dtype=np.int32).reshape(-1)
+        hz, hzp = _horizons(horizons)
         _chk(self.lib.desire_occupancy(self._h, yhat_ptr or None, fut_ptr or None, present_ptr or None, score_ptr or None,
-                                       hz.ctypes.data_as(C.POINTER(C.c_int32)), hz.size, int(mode), int(Oh), int(Ow), mask_ptr or None,
+                                       hzp, hz.size, int(mode), int(Oh), int(Ow), mask_ptr or None,
                                        mask_of_scene_ptr or None, occ_ptr or None, exp_ptr or None, hit_ptr or None, viol_ptr or None,
                                        off_ptr or None, stream or None))
 

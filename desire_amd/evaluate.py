@@ -11,16 +11,22 @@ The model flags are train.py's and must be the ones the checkpoint was trained w
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
 float64 on the host over the agents the loss counts (present at the last observed frame and in at least one target frame); a horizon's
 mean runs over those of them with a target frame before it, so every horizon carries its own agent count.
+
+Every report is one block below (_Ranked and one class per optional flag): __init__(args, hz, run) reads its flags, update(model, Y, score, fut,
+masks) makes its model calls for a batch and adds to its float64 / int64 sums, result() returns its part of the result.  evaluate() only walks the
+batches, computes the agent masks they share (_masks) and asks the enabled blocks in the order of the result's keys.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import sys
+from types import SimpleNamespace
 from typing import Iterator, List, Optional, Tuple
 
 import numpy as np
 
+from ._lib import KDE_LOG_FLOOR
 from .train import build_parser as _train_parser, parse_horizons, split_windows
 
 
@@ -93,11 +99,248 @@ def iter_batches(data_loader, batch_size: int, max_windows: int = 0) -> Iterator
         yield xs, ds
 
 
+def _per_horizon(m, a: str, b: str) -> dict:
+    """{a: column 0, b: column 1} of a [n_h, >= 2] array of means, as the result's lists of floats."""
+    return {a: [float(v) for v in m[:, 0]], b: [float(v) for v in m[:, 1]]}
+
+
+class _Run:
+    """The settings every block reads and the counts they divide by: windows walked, and per horizon the agents the loss counts (present at the
+    last observed frame and in a target frame before the horizon).  Its result is the head of the result dict."""
+
+    def __init__(self, args, hz, generator: str, K: int, top: int, t_pred: int):
+        self.args, self.hz, self.generator, self.K, self.top, self.t_pred = args, hz, generator, K, top, t_pred
+        self.units = args.units if args.units in ("px", "norm") else float(args.units)
+        self.agents, self.windows = np.zeros(len(hz), np.int64), 0
+
+    def update(self, model, Y, score, fut, masks):
+        for i, c in enumerate(masks.c):
+            self.agents[i] += int(c.sum())
+        self.windows += masks.valid.shape[0]
+
+    def mean(self, sums):
+        """Per-horizon sums [n_h, ...] over the counted agents -> their means."""
+        return sums / np.maximum(self.agents, 1)[:, None]
+
+    def result(self) -> dict:
+        return {"checkpoint": self.args.checkpoint, "generator": self.generator, "units": self.args.units, "seed": int(self.args.seed), "K": self.K,
+                "top": self.top, "horizons": self.hz, "windows": self.windows, "agents": [int(a) for a in self.agents]}
+
+
+class _Ranked:
+    """top1 / best_of_top / best_of_K: the errors of the best-scored sample, of the best among the top N by score and of the best of all K; and
+    mean_of_K from the ADE / FDE harness (normalised units, the whole prediction)."""
+    on = True
+
+    def __init__(self, args, hz, run):
+        self.run = run
+        self.sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("top1", "best_of_top", "best_of_K")}
+        self.mean_k, self.n_all = np.zeros(2, np.float64), 0
+
+    def update(self, model, Y, score, fut, masks):
+        r = self.run
+        ranked = model.evaluate_ranked(Y, score, fut, top=r.top, horizons=r.hz, units=r.units).astype(np.float64)
+        best = model.evaluate_ranked(Y, score, fut, top=r.K, horizons=r.hz, units=r.units).astype(np.float64)
+        ev = model.evaluate(Y, fut).astype(np.float64)
+        for i, c in enumerate(masks.c):
+            self.sums["top1"][i] += ranked[c, i, 0:2].sum(0)
+            self.sums["best_of_top"][i] += ranked[c, i, 2:4].sum(0)
+            self.sums["best_of_K"][i] += best[c, i, 2:4].sum(0)
+        self.mean_k += ev[masks.all, 0:2].sum(0)
+        self.n_all += int(masks.all.sum())
+
+    def result(self) -> dict:
+        res = {k: _per_horizon(self.run.mean(v), "ade", "fde") for k, v in self.sums.items()}
+        res["mean_of_K"] = {"ade": float(self.mean_k[0] / max(self.n_all, 1)), "fde": float(self.mean_k[1] / max(self.n_all, 1)), "units": "norm",
+                            "horizon": self.run.t_pred, "agents": self.n_all}
+        return res
+
+
+class _Select:
+    """--select nms: the best of the N most plausible mutually distinct futures, and the samples kept per agent present at the last observed frame."""
+
+    def __init__(self, args, hz, run):
+        self.on = str(getattr(args, "select", "score") or "score") == "nms"
+        if self.on and getattr(args, "nms_radius", None) is None:
+            raise ValueError("--select nms needs --nms_radius (pixels)")
+        self.args, self.run = args, run
+        self.sums, self.count, self.present = np.zeros((len(hz), 2), np.float64), 0, 0
+
+    def update(self, model, Y, score, fut, masks):
+        a, r = self.args, self.run
+        distinct, kept = model.evaluate_ranked(Y, score, fut, top=r.top, horizons=r.hz, units=r.units, return_count=True, select="nms",
+                                               nms_radius=a.nms_radius, nms_metric=a.nms_metric, nms_horizon=a.nms_horizon)
+        distinct = distinct.astype(np.float64)
+        for i, c in enumerate(masks.c):
+            self.sums[i] += distinct[c, i, 2:4].sum(0)
+        self.count += int(kept[masks.valid.reshape(-1)].sum())
+        self.present += int(masks.valid.sum())
+
+    def result(self) -> dict:
+        a = self.args
+        return {"select": {"mode": "nms", "radius_px": float(a.nms_radius), "metric": str(a.nms_metric), "horizon": int(a.nms_horizon or self.run.t_pred),
+                           "mean_count": float(self.count / max(self.present, 1)), "present_agents": self.present,
+                           "best_of_top_distinct": _per_horizon(self.run.mean(self.sums), "ade", "fde")}}
+
+
+class _KdeNll:
+    """--nll: the KDE negative log-likelihood of the ground truth with equal weights and with weights softmax(score), and of the counted frames of
+    the counted agents how many sit on the floor (equal weights)."""
+
+    def __init__(self, args, hz, run):
+        self.on = bool(getattr(args, "nll", False))
+        self.run = run
+        self.sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("uniform", "score_weighted")}
+        self.floored, self.frames = 0, 0
+
+    def update(self, model, Y, score, fut, masks):
+        r = self.run
+        by = {}
+        by["uniform"], fr = model.evaluate_nll(Y, score, fut, horizons=r.hz, units=r.units, log_floor=KDE_LOG_FLOOR, return_frames=True)
+        by["score_weighted"] = model.evaluate_nll(Y, score, fut, horizons=r.hz, units=r.units, weighted=True, log_floor=KDE_LOG_FLOOR)
+        for i, c in enumerate(masks.c):
+            for k, v in by.items():
+                self.sums[k][i] += v[c, i].astype(np.float64).sum(0)
+        cf = (masks.valid[:, None, :] & masks.seen).transpose(0, 2, 1).reshape(fr.shape)
+        self.frames += int(cf.sum())
+        self.floored += int((cf & (fr <= np.float32(KDE_LOG_FLOOR))).sum())
+
+    def result(self) -> dict:
+        res = {"log_floor": KDE_LOG_FLOOR}
+        for k, v in self.sums.items():
+            res[k] = _per_horizon(self.run.mean(v), "mean", "final")
+        res.update({"floored_frames": self.floored, "frames": self.frames})
+        return {"kde_nll": res}
+
+
+class _Joint:
+    """--joint: the K samples of a window as K joint futures -- JADE / JFDE over the windows with an agent taking part, and the collision rates.
+    Per window: the call counts by the targets' ids alone."""
+
+    def __init__(self, args, hz, run):
+        self.on = bool(getattr(args, "joint", False))
+        self.radius, self.run = getattr(args, "collision_radius", None), run
+        self.sums, self.windows = np.zeros((len(hz), 4), np.float64), np.zeros(len(hz), np.int64)
+        self.cnt = {k: np.zeros((len(hz), 2), np.int64) for k in ("top1", "all_K", "ground_truth")}      # (touching, taking part)
+
+    def update(self, model, Y, score, fut, masks):
+        r = self.run
+        jm = model.evaluate_joint(Y, score, fut, top=r.top, horizons=r.hz, units=r.units, collision_radius=self.radius)
+        cnt = jm["cnt"].astype(np.int64)
+        takes = cnt[:, 0, :, 1] > 0                                                              # [n, n_h]
+        self.sums += np.where(takes[:, :, None], jm["out"].astype(np.float64), 0.0).sum(0)
+        self.windows += takes.sum(0)
+        self.cnt["top1"] += cnt[np.arange(cnt.shape[0]), jm["order"][:, 0]].sum(0)
+        self.cnt["all_K"] += cnt[:, :r.K].sum((0, 1))
+        self.cnt["ground_truth"] += cnt[:, r.K].sum(0)
+
+    def result(self) -> dict:
+        m = self.sums / np.maximum(self.windows, 1)[:, None]
+        rate = {k: [float(v[i, 0] / max(int(v[i, 1]), 1)) for i in range(len(self.run.hz))] for k, v in self.cnt.items()}
+        return {"joint": {"collision_radius_px": float(self.radius or 0.0), "windows": [int(v) for v in self.windows],
+                          "top1": _per_horizon(m[:, 0:2], "jade", "jfde"), "best_of_top": _per_horizon(m[:, 2:4], "jade", "jfde"),
+                          "collision_rate": rate, "slots": [int(v) for v in self.cnt["ground_truth"][:, 1]]}}
+
+
+class _PlanRisk:
+    """--plan_risk: the leave-one-out plan risk, summed over the agents taking part so that the batches weigh as their agents do."""
+
+    def __init__(self, args, hz, run):
+        self.on = bool(getattr(args, "plan_risk", False))
+        self.radius, self.run = float(getattr(args, "collision_radius", None) or 0.0), run
+        self.pred, self.act, self.agents = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.int64)
+
+    def update(self, model, Y, score, fut, masks):
+        pm = model.evaluate_plan_risk(Y, score, fut, self.radius, horizons=self.run.hz)
+        self.pred += pm["predicted"] * pm["agents"]
+        self.act += pm["actual"] * pm["agents"]
+        self.agents += pm["agents"]
+
+    def result(self) -> dict:
+        rate = lambda s: [float(s[i] / max(int(self.agents[i]), 1)) for i in range(len(self.run.hz))]
+        return {"plan_risk": {"collision_radius_px": self.radius, "agents": [int(v) for v in self.agents], "predicted_risk": rate(self.pred),
+                              "actual_rate": rate(self.act)}}
+
+
+class _Occupancy:
+    """--occupancy OHxOW: the occupancy maps of the score-weighted samples.  The mass on the ground truth's cell is always the frame's (mode "at"),
+    over the agents counted at the horizon's own frame; --occupancy_mode until asks for it in a second call."""
+
+    def __init__(self, args, hz, run):
+        self.grid = parse_grid(getattr(args, "occupancy", None))
+        self.on = bool(self.grid)
+        self.mode, self.run = str(getattr(args, "occupancy_mode", "at") or "at"), run
+        self.nll, self.off, self.exp = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64)
+        self.at = np.zeros(len(hz), np.int64)
+
+    def update(self, model, Y, score, fut, masks):
+        hz = self.run.hz
+        om = model.evaluate_occupancy(Y, score, fut, self.grid, horizons=hz, mode=self.mode)
+        hit = om["hit"] if self.mode == "at" else model.evaluate_occupancy(Y, score, fut, self.grid, horizons=hz, mode="at")["hit"]
+        self.exp += om["expected"].astype(np.float64).sum((0, 2, 3))
+        for i, (c, at) in enumerate(zip(masks.c, masks.at)):
+            self.at[i] += int(at.sum())
+            self.nll[i] += float(-np.log(np.maximum(hit.reshape(-1, len(hz))[at, i].astype(np.float64), 1e-6)).sum())
+            self.off[i] += float(om["off"].reshape(-1, len(hz))[c, i].astype(np.float64).sum())
+
+    def result(self) -> dict:
+        r, nh = self.run, len(self.run.hz)
+        return {"occupancy": {"grid": [int(self.grid[0]), int(self.grid[1])], "mode": self.mode, "weights": "score", "hit_floor": 1e-6,
+                              "agents_at_frame": [int(v) for v in self.at],
+                              "hit_nll": [float(self.nll[i] / max(int(self.at[i]), 1)) for i in range(nh)],
+                              "off_mass": [float(self.off[i] / max(int(r.agents[i]), 1)) for i in range(nh)],
+                              "expected_in_frame": [float(self.exp[i] / max(r.windows, 1)) for i in range(nh)]}}
+
+
+class _Modes:
+    """--modes N: the mixture of N modes per agent -- its likelihood of the ground truth, the errors of the most probable and of the best mode's
+    mean, and the Lloyd passes per agent present at the last observed frame."""
+
+    def __init__(self, args, hz, run):
+        self.n = int(getattr(args, "modes", 0) or 0)
+        self.on = bool(self.n)
+        self.seeds, self.radius = str(getattr(args, "modes_seeds", "nms")), getattr(args, "nms_radius", None)
+        if self.on and self.seeds == "nms" and self.radius is None:
+            raise ValueError("--modes with --modes_seeds nms needs --nms_radius (pixels)")
+        self.metric, self.iters = str(getattr(args, "nms_metric", "final")), int(getattr(args, "modes_iters", 8))
+        self.min_std, self.run = float(getattr(args, "modes_min_std", 1.0)), run
+        self.sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("nll", "top1", "best")}
+        self.passes, self.present = 0, 0
+
+    def update(self, model, Y, score, fut, masks):
+        r = self.run
+        mm = model.evaluate_modes(Y, score, fut, modes=self.n, seeds=self.seeds, nms_radius=self.radius, nms_metric=self.metric, iters=self.iters,
+                                  min_std=self.min_std, horizons=r.hz, units=r.units, log_floor=KDE_LOG_FLOOR)
+        for i, c in enumerate(masks.c):
+            for k in self.sums:
+                self.sums[k][i] += mm[k][c, i].astype(np.float64).sum(0)
+        self.passes += int(mm["passes"][masks.valid.reshape(-1)].sum())
+        self.present += int(masks.valid.sum())
+
+    def result(self) -> dict:
+        m = {k: self.run.mean(v) for k, v in self.sums.items()}
+        return {"modes": {"n": self.n, "seeds": self.seeds, "iters": self.iters, "min_std_px": self.min_std, "log_floor": KDE_LOG_FLOOR,
+                          "mean_passes": float(self.passes / max(self.present, 1)), "nll": _per_horizon(m["nll"], "mean", "final"),
+                          "top1": _per_horizon(m["top1"], "ade", "fde"), "best": _per_horizon(m["best"], "ade", "fde")}}
+
+
+def _masks(past, fut, hz, mno: int) -> SimpleNamespace:
+    """The agent masks of a batch, computed once for every block, on the model's slot axis (mno >= the loader's, the padding never counted):
+    valid [n, mno] = present at the last observed frame; seen [n, T_pred, mno] = in that target frame; per horizon h, flat over (window, slot),
+    c = valid and seen before h and at = valid and seen at frame h - 1; all = valid and seen at all."""
+    pw, fw = np.stack(past), np.stack(fut)
+    valid = np.zeros((pw.shape[0], mno), bool)
+    valid[:, :pw.shape[2]] = pw[:, -1, :, 0] != 0
+    seen = np.zeros((pw.shape[0], fw.shape[1], mno), bool)
+    seen[:, :, :pw.shape[2]] = fw[:, :, :, 0] != 0
+    return SimpleNamespace(valid=valid, seen=seen, c=[(valid & seen[:, :h].any(1)).reshape(-1) for h in hz],
+                           at=[(valid & seen[:, h - 1]).reshape(-1) for h in hz], all=(valid & seen.any(1)).reshape(-1))
+
+
 def evaluate(args, data_loader=None, model=None) -> dict:
     """Runs the walk; returns the result dict main() prints.  `data_loader` / `model` may be injected (tests)."""
     from .data_loader import DataLoader
-    from .model import DESIREModel, default_top
-    from ._lib import KDE_LOG_FLOOR
+    from .model import DESIREModel, default_top, dims_from_args
     if args.pred_length is None:
         args.pred_length = args.seq_length
     t_obs, t_pred = int(args.seq_length), int(args.pred_length)
@@ -108,155 +351,22 @@ def evaluate(args, data_loader=None, model=None) -> dict:
         model = DESIREModel.restore(args, args.checkpoint)
     K = int(args.num_samples)
     generator = str(getattr(args, "generator", "cvae") or "cvae")
-    top = int(args.eval_top or default_top(K))
     hz = parse_horizons(args.eval_horizons, t_pred)
-    units = args.units if args.units in ("px", "norm") else float(args.units)
-    names = ("top1", "best_of_top", "best_of_K")
-    sums = {k: np.zeros((len(hz), 2), np.float64) for k in names}
-    agents = np.zeros(len(hz), np.int64)
-    mean_k, n_all, n_windows = np.zeros(2, np.float64), 0, 0
-    nll = bool(getattr(args, "nll", False))
-    nll_sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("uniform", "score_weighted")}
-    nll_floored, nll_frames = 0, 0
-    nms = str(getattr(args, "select", "score") or "score") == "nms"
-    if nms and getattr(args, "nms_radius", None) is None:
-        raise ValueError("--select nms needs --nms_radius (pixels)")
-    nms_kw = dict(select="nms", nms_radius=args.nms_radius, nms_metric=args.nms_metric, nms_horizon=args.nms_horizon) if nms else {}
-    nms_sums, nms_count, nms_present = np.zeros((len(hz), 2), np.float64), 0, 0
-    joint = bool(getattr(args, "joint", False))
-    j_sums, j_windows = np.zeros((len(hz), 4), np.float64), np.zeros(len(hz), np.int64)
-    j_cnt = {k: np.zeros((len(hz), 2), np.int64) for k in ("top1", "all_K", "ground_truth")}      # (touching, taking part)
-    occ_grid = parse_grid(getattr(args, "occupancy", None))
-    occ_mode = str(getattr(args, "occupancy_mode", "at") or "at")
-    o_nll, o_off, o_exp = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64)
-    o_at = np.zeros(len(hz), np.int64)                                                           # agents counted at the horizon's own frame
-    plan_risk = bool(getattr(args, "plan_risk", False))
-    p_pred, p_act, p_agents = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.int64)
-    n_modes = int(getattr(args, "modes", 0) or 0)
-    if n_modes and str(getattr(args, "modes_seeds", "nms")) == "nms" and getattr(args, "nms_radius", None) is None:
-        raise ValueError("--modes with --modes_seeds nms needs --nms_radius (pixels)")
-    m_sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("nll", "top1", "best")}
-    m_passes, m_present = 0, 0
+    run = _Run(args, hz, generator, K, int(args.eval_top or default_top(K)), t_pred)
+    # every block reads its flags here -- a bad one is refused before a window is touched --, the enabled ones report in this order
+    blocks = [run] + [b for b in [B(args, hz, run) for B in (_Ranked, _Select, _KdeNll, _Joint, _PlanRisk, _Occupancy, _Modes)] if b.on]
+    mno = dims_from_args(args, 1, False).mno                             # the model's slot axis: max_num_obj padded up
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
         gen = {} if generator == "cvae" else {"generator": generator}
-        model.predict(past, top=top, seed=args.seed, device_rng=bool(getattr(args, "device_rng", False)), window_base=n_windows, **gen)
-        Y, score = model.final_output, model.final_states
-        ranked = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units=units).astype(np.float64)
-        best = model.evaluate_ranked(Y, score, fut, top=K, horizons=hz, units=units).astype(np.float64)
-        ev = model.evaluate(Y, fut).astype(np.float64)
-        if nms:
-            distinct, kept = model.evaluate_ranked(Y, score, fut, top=top, horizons=hz, units=units, return_count=True, **nms_kw)
-            distinct = distinct.astype(np.float64)
-        if nll:
-            nll_u, fr = model.evaluate_nll(Y, score, fut, horizons=hz, units=units, log_floor=KDE_LOG_FLOOR, return_frames=True)
-            nll_w = model.evaluate_nll(Y, score, fut, horizons=hz, units=units, weighted=True, log_floor=KDE_LOG_FLOOR)
-        if joint:                                    # per window: the call counts by the targets' ids alone
-            jm = model.evaluate_joint(Y, score, fut, top=top, horizons=hz, units=units, collision_radius=getattr(args, "collision_radius", None))
-            cnt = jm["cnt"].astype(np.int64)
-            takes = cnt[:, 0, :, 1] > 0                                                          # [n, n_h]
-            j_sums += np.where(takes[:, :, None], jm["out"].astype(np.float64), 0.0).sum(0)
-            j_windows += takes.sum(0)
-            j_cnt["top1"] += cnt[np.arange(cnt.shape[0]), jm["order"][:, 0]].sum(0)
-            j_cnt["all_K"] += cnt[:, :K].sum((0, 1))
-            j_cnt["ground_truth"] += cnt[:, K].sum(0)
-        if plan_risk:                                # sums over the agents taking part, so that the batches weigh as their agents do
-            pm = model.evaluate_plan_risk(Y, score, fut, float(getattr(args, "collision_radius", None) or 0.0), horizons=hz)
-            p_pred += pm["predicted"] * pm["agents"]
-            p_act += pm["actual"] * pm["agents"]
-            p_agents += pm["agents"]
-        if occ_grid:
-            om = model.evaluate_occupancy(Y, score, fut, occ_grid, horizons=hz, mode=occ_mode)
-            o_hit = om["hit"] if occ_mode == "at" else model.evaluate_occupancy(Y, score, fut, occ_grid, horizons=hz, mode="at")["hit"]
-            o_exp += om["expected"].astype(np.float64).sum((0, 2, 3))
-        if n_modes:
-            mm = model.evaluate_modes(Y, score, fut, modes=n_modes, seeds=str(getattr(args, "modes_seeds", "nms")), nms_radius=getattr(args, "nms_radius", None),
-                                      nms_metric=str(getattr(args, "nms_metric", "final")), iters=int(getattr(args, "modes_iters", 8)),
-                                      min_std=float(getattr(args, "modes_min_std", 1.0)), horizons=hz, units=units, log_floor=KDE_LOG_FLOOR)
-        pw, fw = np.stack(past), np.stack(fut)
-        mno = ranked.shape[0] // pw.shape[0]
-        valid = np.zeros((pw.shape[0], mno), bool)
-        valid[:, :pw.shape[2]] = pw[:, -1, :, 0] != 0
-        seen = np.zeros((pw.shape[0], t_pred, mno), bool)
-        seen[:, :, :pw.shape[2]] = fw[:, :, :, 0] != 0
-        for i, h in enumerate(hz):
-            c = (valid & seen[:, :h].any(1)).reshape(-1)
-            agents[i] += int(c.sum())
-            sums["top1"][i] += ranked[c, i, 0:2].sum(0)
-            sums["best_of_top"][i] += ranked[c, i, 2:4].sum(0)
-            sums["best_of_K"][i] += best[c, i, 2:4].sum(0)
-            if nms:
-                nms_sums[i] += distinct[c, i, 2:4].sum(0)
-            if occ_grid:
-                at = (valid & seen[:, h - 1]).reshape(-1)
-                o_at[i] += int(at.sum())
-                o_nll[i] += float(-np.log(np.maximum(o_hit.reshape(-1, len(hz))[at, i].astype(np.float64), 1e-6)).sum())
-                o_off[i] += float(om["off"].reshape(-1, len(hz))[c, i].astype(np.float64).sum())
-            if n_modes:
-                for k in m_sums:
-                    m_sums[k][i] += mm[k][c, i].astype(np.float64).sum(0)
-            if nll:
-                nll_sums["uniform"][i] += nll_u[c, i].astype(np.float64).sum(0)
-                nll_sums["score_weighted"][i] += nll_w[c, i].astype(np.float64).sum(0)
-        c = (valid & seen.any(1)).reshape(-1)
-        mean_k += ev[c, 0:2].sum(0)
-        if nms:                                      # samples kept per agent present at the last observed frame
-            nms_count += int(kept[valid.reshape(-1)].sum())
-            nms_present += int(valid.sum())
-        n_all += int(c.sum())
-        if n_modes:                                  # passes per agent present at the last observed frame
-            m_passes += int(mm["passes"][valid.reshape(-1)].sum())
-            m_present += int(valid.sum())
-        if nll:                                      # the counted frames of those agents, and how many of them sit on the floor (equal weights)
-            cf = (valid[:, None, :] & seen).transpose(0, 2, 1).reshape(fr.shape)
-            nll_frames += int(cf.sum())
-            nll_floored += int((cf & (fr <= np.float32(KDE_LOG_FLOOR))).sum())
-        n_windows += len(xs)
-    res = {"checkpoint": args.checkpoint, "generator": generator, "units": args.units, "seed": int(args.seed), "K": K, "top": top, "horizons": hz,
-           "windows": n_windows, "agents": [int(a) for a in agents]}
-    for k in names:
-        m = sums[k] / np.maximum(agents, 1)[:, None]
-        res[k] = {"ade": [float(v) for v in m[:, 0]], "fde": [float(v) for v in m[:, 1]]}
-    # mean-of-K comes from the ADE / FDE harness: normalised units, the whole prediction
-    res["mean_of_K"] = {"ade": float(mean_k[0] / max(n_all, 1)), "fde": float(mean_k[1] / max(n_all, 1)), "units": "norm", "horizon": t_pred,
-                        "agents": n_all}
-    if nms:
-        m = nms_sums / np.maximum(agents, 1)[:, None]
-        res["select"] = {"mode": "nms", "radius_px": float(args.nms_radius), "metric": str(args.nms_metric),
-                         "horizon": int(args.nms_horizon or t_pred), "mean_count": float(nms_count / max(nms_present, 1)), "present_agents": nms_present,
-                         "best_of_top_distinct": {"ade": [float(v) for v in m[:, 0]], "fde": [float(v) for v in m[:, 1]]}}
-    if nll:
-        res["kde_nll"] = {"log_floor": KDE_LOG_FLOOR}
-        for k in ("uniform", "score_weighted"):
-            m = nll_sums[k] / np.maximum(agents, 1)[:, None]
-            res["kde_nll"][k] = {"mean": [float(v) for v in m[:, 0]], "final": [float(v) for v in m[:, 1]]}
-        res["kde_nll"].update({"floored_frames": nll_floored, "frames": nll_frames})
-    if joint:
-        m = j_sums / np.maximum(j_windows, 1)[:, None]
-        rate = {k: [float(v[i, 0] / max(int(v[i, 1]), 1)) for i in range(len(hz))] for k, v in j_cnt.items()}
-        res["joint"] = {"collision_radius_px": float(getattr(args, "collision_radius", None) or 0.0), "windows": [int(v) for v in j_windows],
-                        "top1": {"jade": [float(v) for v in m[:, 0]], "jfde": [float(v) for v in m[:, 1]]},
-                        "best_of_top": {"jade": [float(v) for v in m[:, 2]], "jfde": [float(v) for v in m[:, 3]]},
-                        "collision_rate": rate, "slots": [int(v) for v in j_cnt["ground_truth"][:, 1]]}
-    if plan_risk:
-        res["plan_risk"] = {"collision_radius_px": float(getattr(args, "collision_radius", None) or 0.0), "agents": [int(v) for v in p_agents],
-                            "predicted_risk": [float(p_pred[i] / max(int(p_agents[i]), 1)) for i in range(len(hz))],
-                            "actual_rate": [float(p_act[i] / max(int(p_agents[i]), 1)) for i in range(len(hz))]}
-    if occ_grid:
-        res["occupancy"] = {"grid": [int(occ_grid[0]), int(occ_grid[1])], "mode": occ_mode, "weights": "score", "hit_floor": 1e-6,
-                            "agents_at_frame": [int(v) for v in o_at],
-                            "hit_nll": [float(o_nll[i] / max(int(o_at[i]), 1)) for i in range(len(hz))],
-                            "off_mass": [float(o_off[i] / max(int(agents[i]), 1)) for i in range(len(hz))],
-                            "expected_in_frame": [float(o_exp[i] / max(n_windows, 1)) for i in range(len(hz))]}
-    if n_modes:
-        m = {k: v / np.maximum(agents, 1)[:, None] for k, v in m_sums.items()}
-        res["modes"] = {"n": n_modes, "seeds": str(getattr(args, "modes_seeds", "nms")), "iters": int(getattr(args, "modes_iters", 8)),
-                        "min_std_px": float(getattr(args, "modes_min_std", 1.0)), "log_floor": KDE_LOG_FLOOR,
-                        "mean_passes": float(m_passes / max(m_present, 1)),
-                        "nll": {"mean": [float(v) for v in m["nll"][:, 0]], "final": [float(v) for v in m["nll"][:, 1]]},
-                        "top1": {"ade": [float(v) for v in m["top1"][:, 0]], "fde": [float(v) for v in m["top1"][:, 1]]},
-                        "best": {"ade": [float(v) for v in m["best"][:, 0]], "fde": [float(v) for v in m["best"][:, 1]]}}
+        model.predict(past, top=run.top, seed=args.seed, device_rng=bool(getattr(args, "device_rng", False)), window_base=run.windows, **gen)
+        masks = _masks(past, fut, hz, mno)
+        for b in blocks:
+            b.update(model, model.final_output, model.final_states, fut, masks)
+    res = {}
+    for b in blocks:
+        res.update(b.result())
     return res
 
 

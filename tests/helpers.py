@@ -44,3 +44,22 @@ def at_byte_offset(t, off):
     v.copy_(t)
     assert flat.data_ptr() % 16 == 0 and v.data_ptr() % 16 == off and v.is_contiguous()
     return v
+
+
+# the command line of the small model the evaluation tests share (8 slots, 5 samples, 6 target frames), the keys of the evaluation's result
+# without an optional report, and the video they walk
+EVAL_FLAGS = ["--batch_size", "2", "--seq_length", "4", "--pred_length", "6", "--max_num_obj", "8", "--d_dim", "64", "--latent_size", "64",
+              "--num_samples", "5", "--neighborhood_size", "256", "--max_windows", "4", "--device_rng", "--seed", "3", "--checkpoint", "none.npz",
+              "--units", "norm"]
+PLAIN_KEYS = ["checkpoint", "generator", "units", "seed", "K", "top", "horizons", "windows", "agents", "top1", "best_of_top", "best_of_K", "mean_of_K"]
+
+
+def walking_video():
+    t = np.arange(60, dtype=np.float32)
+    video = np.zeros((60, 8, 3), np.float32)                          # five objects walking straight lines, the last one leaves half way
+    for i in range(5):
+        video[:, i, 0] = i + 1
+        video[:, i, 1] = 200 + 150 * i + 3 * t
+        video[:, i, 2] = 150 + 100 * i + 2 * t
+    video[30:, 4] = 0
+    return video

@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 from desire_amd.spec import FLAG_COMPACT_IOC, FLAG_COMPACT_ROWS, init_weights
-from tests.helpers import at_byte_offset, make_case, small_dims
+from tests.helpers import PLAIN_KEYS as _PLAIN_KEYS, at_byte_offset, make_case, small_dims
 from tests.occupancy_reference import AT, SEEDS, SHAPES, UNTIL, band_rows, constant_ids, make_inputs, occupancy_f32, occupancy_f64
 
 pytestmark = pytest.mark.gpu
@@ -367,7 +367,6 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch_cuda):
 
 _FLAGS = ["--batch_size", "2", "--seq_length", "8", "--pred_length", "12", "--max_num_obj", "32", "--d_dim", "64", "--latent_size", "64",
           "--num_samples", "5", "--neighborhood_size", "200", "--max_windows", "2", "--device_rng", "--seed", "3", "--checkpoint", "none.npz", "--units", "norm"]
-_PLAIN_KEYS = ["checkpoint", "generator", "units", "seed", "K", "top", "horizons", "windows", "agents", "top1", "best_of_top", "best_of_K", "mean_of_K"]
 _GRID = (9, 12)
 
 

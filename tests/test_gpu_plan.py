@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 from desire_amd.spec import FLAG_COMPACT_IOC, FLAG_COMPACT_ROWS, init_weights
-from tests.helpers import at_byte_offset, make_case, small_dims
+from tests.helpers import (EVAL_FLAGS as _FLAGS, PLAIN_KEYS as _PLAIN_KEYS, walking_video as _video,
+                           at_byte_offset, make_case, small_dims)
 from tests.plan_reference import (MARGIN, RADIUS_PX, SHAPES, equal_joint_scores, brute_force_first, make_inputs, plan_centres, plan_f32, plan_f64,
                                   plan_geometry, planted_joint_scores, risk_bound)
 
@@ -426,22 +427,6 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch_cuda):
     assert bool((risk == 0).all()) and bool((outs["first_ptr"] == IFILL).all()) and bool((outs["blame_ptr"] == FILL).all())
     for x in (h, rc):
         x.close()
-
-
-_FLAGS = ["--batch_size", "2", "--seq_length", "4", "--pred_length", "6", "--max_num_obj", "8", "--d_dim", "64", "--latent_size", "64",
-          "--num_samples", "5", "--neighborhood_size", "256", "--max_windows", "4", "--device_rng", "--seed", "3", "--checkpoint", "none.npz", "--units", "norm"]
-_PLAIN_KEYS = ["checkpoint", "generator", "units", "seed", "K", "top", "horizons", "windows", "agents", "top1", "best_of_top", "best_of_K", "mean_of_K"]
-
-
-def _video():
-    t = np.arange(60, dtype=np.float32)
-    video = np.zeros((60, 8, 3), np.float32)                          # five objects walking straight lines, the last one leaves half way
-    for i in range(5):
-        video[:, i, 0] = i + 1
-        video[:, i, 1] = 200 + 150 * i + 3 * t
-        video[:, i, 2] = 150 + 100 * i + 2 * t
-    video[30:, 4] = 0
-    return video
 
 
 def test_score_plans_prefers_the_far_plan(torch_cuda):

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from desire_amd.spec import FLAG_COMPACT_IOC, FLAG_COMPACT_ROWS, init_weights
-from tests.helpers import MISALIGNED_SHAPES, at_byte_offset, make_case, small_dims
+from tests.helpers import (EVAL_FLAGS as _FLAGS, PLAIN_KEYS as _PLAIN_KEYS, walking_video as _video,
+                           MISALIGNED_SHAPES, at_byte_offset, make_case, small_dims)
 from tests.rank_reference import planted_scores, rank_order, ranked_errors
 from tests.select_reference import (DIST_FINAL, DIST_MAX, DIST_MEAN, MARGIN, METRICS, cases_of, make_inputs, margin_of_values, pair_values,
                                     select_f32, select_f64, weights)
@@ -379,23 +380,6 @@ def test_bad_arguments_are_refused_and_nothing_is_written(torch_cuda):
     assert bool((outs["count_ptr"] == d.K).all()) and bool((outs["order_out_ptr"] == 0).all()) and bool((outs["mass_ptr"] == FILL).all())
     for x in (h, big, rc):
         x.close()
-
-
-_FLAGS = ["--batch_size", "2", "--seq_length", "4", "--pred_length", "6", "--max_num_obj", "8", "--d_dim", "64", "--latent_size", "64",
-          "--num_samples", "5", "--neighborhood_size", "256", "--max_windows", "4", "--device_rng", "--seed", "3", "--checkpoint", "none.npz", "--units", "norm"]
-# the keys of the evaluation's result without --select: what the command line printed before the selection existed
-_PLAIN_KEYS = ["checkpoint", "generator", "units", "seed", "K", "top", "horizons", "windows", "agents", "top1", "best_of_top", "best_of_K", "mean_of_K"]
-
-
-def _video():
-    t = np.arange(60, dtype=np.float32)
-    video = np.zeros((60, 8, 3), np.float32)                          # five objects walking straight lines, the last one leaves half way
-    for i in range(5):
-        video[:, i, 0] = i + 1
-        video[:, i, 1] = 200 + 150 * i + 3 * t
-        video[:, i, 2] = 150 + 100 * i + 2 * t
-    video[30:, 4] = 0
-    return video
 
 
 def _radius_with_a_margin(Y, metric, t_end, ux, uy, d, present):

@@ -4,7 +4,7 @@ without --joint its result keeps the key list it has always had."""
 import numpy as np
 import pytest
 
-from tests.helpers import small_dims
+from tests.helpers import EVAL_FLAGS, PLAIN_KEYS as _PLAIN_KEYS, small_dims
 from tests.joint_reference import (MARGIN, RADIUS_PX, SHAPES, brute_force_first, chunk_centres, chunk_frames, float_bound, joint_f32, joint_f64,
                                    make_inputs, planted_joint_scores)
 
@@ -146,9 +146,7 @@ class _Stub:
                 "jscore": np.zeros((n, K), np.float32), "cnt": cnt, "first": np.zeros((n, K + 1, m), np.int32)}
 
 
-_PLAIN_KEYS = ["checkpoint", "generator", "units", "seed", "K", "top", "horizons", "windows", "agents", "top1", "best_of_top", "best_of_K", "mean_of_K"]
-_FLAGS = ["--batch_size", "2", "--seq_length", "4", "--pred_length", "6", "--max_num_obj", "8", "--d_dim", "64", "--latent_size", "64",
-          "--num_samples", "5", "--neighborhood_size", "256", "--max_windows", "4", "--seed", "3", "--checkpoint", "none.npz", "--units", "norm"]
+_FLAGS = [f for f in EVAL_FLAGS if f != "--device_rng"]
 
 
 def test_the_command_line_keeps_its_keys_without_the_flag():
