@@ -28,11 +28,13 @@ EXPORTS = [
     "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse", "desire_joint_metrics",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
     "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy", "desire_plan_risk", "desire_fit_modes",
+    "desire_select_worlds",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
 RNG_BITS, RNG_NORMAL, RNG_LATENT, RNG_ROLLOUT = 0, 1, 2, 3          # desire_rng_fill kinds (DESIRE_RNG_*)
 DIST_FINAL, DIST_MEAN, DIST_MAX = 0, 1, 2                           # desire_select_diverse metrics (DESIRE_DIST_*)
+WORLD_ALL, WORLD_MEAN = 0, 1                                        # desire_select_worlds reduces over the slots (DESIRE_WORLD_*)
 RECON_MEAN, RECON_MIN, RECON_SOFTMIN = 0, 1, 2                      # desire_set_recon_loss / desire_recon_weights modes (DESIRE_RECON_*)
 RECON_MODES = {"mean": RECON_MEAN, "min": RECON_MIN, "softmin": RECON_SOFTMIN}      # their names on the Python surface (args.recon_loss, --recon_loss)
 MODES_MAX, MODES_MAX_ITERS = 16, 32                                 # desire_fit_modes: the most modes and passes (DESIRE_MODES_MAX, _MAX_ITERS)
@@ -108,6 +110,7 @@ def load() -> C.CDLL:
     lib.desire_select_diverse.argtypes = [vp, f32p, vp, f32p, i32, i32, C.c_float, C.c_float, C.c_float, i32, vp, vp, f32p, f32p, f32p, vp]
     lib.desire_joint_metrics.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, f32p, f32p,
                                          vp, f32p, vp]
+    lib.desire_select_worlds.argtypes = [vp, f32p, vp, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, f32p, vp, vp]
     lib.desire_occupancy.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, i32, i32, vp, vp, f32p, f32p, f32p, f32p, f32p, vp]
     lib.desire_plan_risk.argtypes = [vp, f32p, f32p, vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, vp, f32p, f32p, f32p, vp]
     lib.desire_fit_modes.argtypes = [vp, f32p, vp, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32), i32, C.c_float,
@@ -344,6 +347,18 @@ class Handle:
                                            hzp, hz.size, int(n_top), C.c_float(radius), C.c_float(unit_x),
                                            C.c_float(unit_y), first_ptr or None, cnt_ptr or None, jerr_ptr or None, jscore_ptr or None,
                                            jorder_ptr or None, out_ptr or None, stream or None))
+
+    def select_worlds(self, yhat_ptr: int, present_ptr: int, wscore_ptr: int, metric: int, reduce: int, t_end: int, radius: float, unit_x: float,
+                      unit_y: float, worder_ptr: int, wcount_ptr: int, wmass_ptr: int = 0, wlabel_ptr: int = 0, stream: int = 0) -> None:
+        """Score-ordered non-maximum suppression of a window's K joint futures (world k = sample k of every slot): walking the worlds by
+        descending wscore [n, K] (ranked by the call; wscore_ptr = 0: the identity order), a world is kept unless it is near one already kept --
+        WORLD_ALL: every taking-part slot (present [A] uint8, present_ptr = 0: all) is within `radius` by `metric` (DIST_* over the frames
+        t < t_end, as in select_diverse); WORLD_MEAN: the mean over those slots of the distance is below `radius`.  worder [n, K] int32 = the
+        kept worlds, then the suppressed ones; wcount [n] int32 = the number kept; optionally wmass [n, K] = the softmax(wscore) weight each
+        kept world absorbed and wlabel [n, K] int32 = for every world the keeping position of the world that owns it."""
+        _chk(self.lib.desire_select_worlds(self._h, yhat_ptr or None, present_ptr or None, wscore_ptr or None, int(metric), int(reduce), int(t_end),
+                                           C.c_float(radius), C.c_float(unit_x), C.c_float(unit_y), worder_ptr or None, wcount_ptr or None,
+                                           wmass_ptr or None, wlabel_ptr or None, stream or None))
 
     def plan_risk(self, yhat_ptr: int, fut_ptr: int, present_ptr: int, score_ptr: int, plans_ptr: int, ego_ptr: int, M: int, horizons,
                   radius: float, unit_x: float, unit_y: float, risk_ptr: int, first_ptr: int = 0, clear_ptr: int = 0, blame_ptr: int = 0,

@@ -366,6 +366,34 @@ extern "C" int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, con
     return DESIRE_OK;
 }
 
+// ---- score-ordered non-maximum suppression of a window's K joint futures (kernels_worlds.hip): the contract is stated in include/desire_hip.h.
+// As in desire_select_diverse the checks that need no handle come first. ----
+extern "C" int desire_select_worlds(desire_handle* h, const float* dev_Yhat, const uint8_t* dev_present, const float* dev_wscore, int32_t metric,
+                                    int32_t reduce, int32_t t_end, float radius, float unit_x, float unit_y, int32_t* dev_worder,
+                                    int32_t* dev_wcount, float* dev_wmass, int32_t* dev_wlabel, void* stream) {
+    if (metric < DESIRE_DIST_FINAL || metric > DESIRE_DIST_MAX) return fail(DESIRE_ERR_ARG, "metric must be DESIRE_DIST_FINAL, _MEAN or _MAX (0..2)");
+    if (reduce != DESIRE_WORLD_ALL && reduce != DESIRE_WORLD_MEAN) return fail(DESIRE_ERR_ARG, "reduce must be DESIRE_WORLD_ALL or DESIRE_WORLD_MEAN (0, 1)");
+    if (int rc = check_radius(radius)) return rc;
+    if (int rc = check_units(unit_x, unit_y)) return rc;
+    if (t_end < 1) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_worder) return fail(DESIRE_ERR_ARG, "dev_worder is NULL");
+    if (!dev_wcount) return fail(DESIRE_ERR_ARG, "dev_wcount is NULL");
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read joint futures from");
+    if (t_end > d.T_pred) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    int sc = 0;
+    if (!worlds_geometry(d.mno, d.K, metric, t_end, &sc))
+        return fail(DESIRE_ERR_ARG, "K worlds of mno slots and t_end frames do not fit the world-selection kernel's LDS: " +
+                                        std::to_string(4 * (WorldsLds::K_WORDS + 2)) + " * K + 4 * mno + " + std::to_string(EVAL_PAIR_BYTES) +
+                                        " * (frames | 1) must be <= " + std::to_string(EVAL_LDS_BYTES));
+    launch_select_worlds(dev_Yhat, dev_present, dev_wscore, dev_worder, dev_wcount, dev_wmass, dev_wlabel, d.n_scenes, d.mno, d.K, d.T_pred, metric,
+                         reduce, t_end, radius, unit_x, unit_y, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- candidate ego plans against the K joint futures (kernels_plan.hip): the contract is stated in include/desire_hip.h ----
 extern "C" int desire_plan_risk(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present, const float* dev_score,
                                 const float* dev_plans, const int32_t* dev_ego, int32_t M, const int32_t* host_horizons, int32_t n_h, float radius,

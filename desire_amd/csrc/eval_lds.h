@@ -1,5 +1,5 @@
 // eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
-// _recon / _occ / _plan / _modes.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// _recon / _occ / _plan / _modes / _worlds.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
 // that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
 // Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp and occ_lds_driver.cpp compile it with g++ (tests/test_eval_lds.py, test_occ_lds.py).
 #pragma once
@@ -225,5 +225,37 @@ inline bool occupancy_geometry(int K, int frames, int Oh, int Ow, int until, int
     const int r = (size_t)Oh < fit ? Oh : (int)fit;
     *KC = kc; *FC = fc;
     *rows = eval_chunks(Oh, eval_chunks(Oh, r));
+    return true;
+}
+
+// ---- k_select_worlds: Yk float2 [SC][Fp] (the staged frames of one kept world's rows of a chunk of SC taking-part slots, Fp = staged frames | 1,
+// SelLds::staged's), then dv [K][SC | 1] words (candidate x slot of the chunk: the linear distance d_i, or the predicate near_i as an integer;
+// the odd stride keeps the lanes that each reduce one candidate's slots on distinct banks), then nine [K] words (processing order, candidate
+// state, weight, order out, mass, label, running sum D, running conjunction, the live list) and one [mno] word (the taking-part slots in
+// increasing slot).  The chunks run over the SLOTS, never over the frames: a slot's value is finished inside its chunk and only the per-world
+// reduction over the slots -- a sum in increasing slot, a conjunction -- is carried from chunk to chunk, so a chunked window has the bits of
+// an unchunked one by construction.  The limit this gives is stated in desire_hip.h and in desire_select_worlds' message.
+struct WorldsLds {
+    enum { K_WORDS = 9 };
+    int Fp, SC, K, mno;
+    EVAL_HD constexpr WorldsLds(int staged_, int SC_, int K_, int mno_) : Fp(eval_odd(staged_)), SC(SC_), K(K_), mno(mno_) {}
+    EVAL_HD constexpr size_t pairs() const { return (size_t)SC * Fp; }                      // float2 in front of the words
+    EVAL_HD constexpr int dv_stride() const { return eval_odd(SC); }
+    EVAL_HD constexpr size_t dv() const { return 0; }                                       // word offsets behind the pairs
+    EVAL_HD constexpr size_t k_words(int r) const { return (size_t)K * (SC + 1) + (size_t)r * K; }
+    EVAL_HD constexpr size_t slots() const { return k_words(K_WORDS); }
+    EVAL_HD static constexpr size_t fixed_bytes(int K, int mno) { return 4 * ((size_t)(K_WORDS + 1) * K + (size_t)mno); }
+    EVAL_HD static constexpr size_t slot_bytes(int K, int staged_) { return EVAL_PAIR_BYTES * (size_t)eval_odd(staged_) + 4 * (size_t)K; }
+    EVAL_HD constexpr size_t bytes() const { return fixed_bytes(K, mno) + (size_t)SC * slot_bytes(K, Fp); }     // (Fp | 1 == Fp)
+};
+// The slot chunk: as many slots as the LDS holds next to the per-world words, spread evenly over the chunks of mno.  false: the per-world words
+// and one slot do not fit: 40 K + 4 mno + 8 (F | 1) + 4 K > 61440.  At (mno 256, t_end 200, K 176) a chunk is 22 slots.
+inline bool worlds_geometry(int mno, int K, int metric, int t_end, int* SC) {
+    if (mno < 1 || K < 1 || t_end < 1) return false;
+    const size_t fixed = WorldsLds::fixed_bytes(K, mno), per = WorldsLds::slot_bytes(K, SelLds::staged(metric, t_end));
+    if (fixed + per > (size_t)EVAL_LDS_BYTES) return false;
+    const size_t fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;
+    const int sc = (int)((size_t)mno < fit ? (size_t)mno : fit);
+    *SC = eval_chunks(mno, eval_chunks(mno, sc));
     return true;
 }

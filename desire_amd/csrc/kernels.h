@@ -279,6 +279,12 @@ void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* prese
                           int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
                           const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
 
+// ---- score-ordered non-maximum suppression of a window's K joint futures (kernels_worlds.hip) ----
+// present, wscore, wmass and wlabel may be nullptr; no scratch
+void launch_select_worlds(const float* Y, const uint8_t* present, const float* wscore, int32_t* worder, int32_t* wcount, float* wmass,
+                          int32_t* wlabel, int n_scenes, int mno, int K, int T, int metric, int reduce, int t_end, float radius, float ux, float uy,
+                          hipStream_t s);
+
 // ---- n modes with covariances fitted to the K samples, and the mixture's likelihood (kernels_modes.hip) ----
 // score, fut, label, mean, cov and passes may be nullptr; out (required with fut) and frame only with fut; no scratch
 void launch_fit_modes(const float* Y, const int32_t* order, const float* score, const float* fut, int32_t* label, int32_t* count, float* prob,

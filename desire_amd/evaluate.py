@@ -56,6 +56,19 @@ def build_parser() -> argparse.ArgumentParser:
                         "next to the ground truth's under the same rule, see --collision_radius")
     p.add_argument("--collision_radius", type=float, default=None,
                    help="--joint, --plan_risk: two agents closer than this many pixels in a frame touch (default: 0, nothing touches)")
+    p.add_argument("--joint_select", type=str, default=None, choices=("nms",),
+                   help="--joint: also report the best of the N most plausible MUTUALLY DISTINCT joint futures -- score-ordered non-maximum suppression "
+                        "of the K joint samples of a window on the device (desire_select_worlds), see --joint_radius")
+    p.add_argument("--joint_radius", type=float, default=None, help="--joint_select nms: two joint futures closer than this many pixels are one (required then)")
+    p.add_argument("--joint_metric", type=str, default="final", choices=("final", "mean", "max"),
+                   help="--joint_select nms: the distance of an agent's two futures, as --nms_metric")
+    p.add_argument("--joint_reduce", type=str, default="mean", choices=("mean", "all"),
+                   help="--joint_select nms: two joint futures are one when the mean over the agents of that distance is below the radius (mean), or when "
+                        "every agent's is (all)")
+    p.add_argument("--joint_horizon", type=int, default=None, help="--joint_select nms: frames the distance looks at (default: all of --pred_length)")
+    p.add_argument("--collision_penalty", type=float, default=0.0,
+                   help="--joint_select nms: rank the joint futures by joint score minus this much per agent that collides (--collision_radius) before "
+                        "the last horizon")
     p.add_argument("--plan_risk", action="store_true",
                    help="also report the leave-one-out plan risk (desire_plan_risk): per horizon the mean predicted risk of what each agent actually "
                         "did, held against the K joint futures of the others, next to the rate at which it actually came within --collision_radius of "
@@ -215,19 +228,32 @@ class _KdeNll:
 
 class _Joint:
     """--joint: the K samples of a window as K joint futures -- JADE / JFDE over the windows with an agent taking part, and the collision rates.
-    Per window: the call counts by the targets' ids alone."""
+    Per window: the call counts by the targets' ids alone.  --joint_select nms: the same call also puts the joint samples through the
+    non-maximum suppression of worlds, and the block gains its parameters, the worlds kept per window and the best of the top N distinct ones."""
 
     def __init__(self, args, hz, run):
         self.on = bool(getattr(args, "joint", False))
         self.radius, self.run = getattr(args, "collision_radius", None), run
+        self.nms = getattr(args, "joint_select", None) == "nms"
+        if self.on and self.nms and getattr(args, "joint_radius", None) is None:
+            raise ValueError("--joint_select nms needs --joint_radius (pixels)")
+        self.worlds = {}
+        if self.nms:
+            self.worlds = dict(select="worlds", worlds_radius=args.joint_radius, worlds_metric=str(getattr(args, "joint_metric", "final")),
+                               worlds_reduce=str(getattr(args, "joint_reduce", "mean")), worlds_horizon=getattr(args, "joint_horizon", None),
+                               collision_penalty=float(getattr(args, "collision_penalty", 0.0) or 0.0))
+        self.distinct, self.kept = np.zeros((len(hz), 2), np.float64), 0
         self.sums, self.windows = np.zeros((len(hz), 4), np.float64), np.zeros(len(hz), np.int64)
         self.cnt = {k: np.zeros((len(hz), 2), np.int64) for k in ("top1", "all_K", "ground_truth")}      # (touching, taking part)
 
     def update(self, model, Y, score, fut, masks):
         r = self.run
-        jm = model.evaluate_joint(Y, score, fut, top=r.top, horizons=r.hz, units=r.units, collision_radius=self.radius)
+        jm = model.evaluate_joint(Y, score, fut, top=r.top, horizons=r.hz, units=r.units, collision_radius=self.radius, **self.worlds)
         cnt = jm["cnt"].astype(np.int64)
         takes = cnt[:, 0, :, 1] > 0                                                              # [n, n_h]
+        if self.nms:
+            self.distinct += np.where(takes[:, :, None], jm["out_distinct"].astype(np.float64), 0.0).sum(0)
+            self.kept += int(jm["wcount"][takes[:, -1]].sum())
         self.sums += np.where(takes[:, :, None], jm["out"].astype(np.float64), 0.0).sum(0)
         self.windows += takes.sum(0)
         self.cnt["top1"] += cnt[np.arange(cnt.shape[0]), jm["order"][:, 0]].sum(0)
@@ -237,9 +263,16 @@ class _Joint:
     def result(self) -> dict:
         m = self.sums / np.maximum(self.windows, 1)[:, None]
         rate = {k: [float(v[i, 0] / max(int(v[i, 1]), 1)) for i in range(len(self.run.hz))] for k, v in self.cnt.items()}
-        return {"joint": {"collision_radius_px": float(self.radius or 0.0), "windows": [int(v) for v in self.windows],
-                          "top1": _per_horizon(m[:, 0:2], "jade", "jfde"), "best_of_top": _per_horizon(m[:, 2:4], "jade", "jfde"),
-                          "collision_rate": rate, "slots": [int(v) for v in self.cnt["ground_truth"][:, 1]]}}
+        res = {"collision_radius_px": float(self.radius or 0.0), "windows": [int(v) for v in self.windows],
+               "top1": _per_horizon(m[:, 0:2], "jade", "jfde"), "best_of_top": _per_horizon(m[:, 2:4], "jade", "jfde"),
+               "collision_rate": rate, "slots": [int(v) for v in self.cnt["ground_truth"][:, 1]]}
+        if self.nms:
+            w = self.worlds
+            res["select"] = {"mode": "nms", "radius_px": float(w["worlds_radius"]), "metric": w["worlds_metric"], "reduce": w["worlds_reduce"],
+                             "horizon": int(w["worlds_horizon"] or self.run.t_pred), "collision_penalty": w["collision_penalty"],
+                             "mean_count": float(self.kept / max(int(self.windows[-1]), 1)),
+                             "best_of_top_distinct": _per_horizon(self.distinct / np.maximum(self.windows, 1)[:, None], "jade", "jfde")}
+        return {"joint": res}
 
 
 class _PlanRisk:

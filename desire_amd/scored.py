@@ -93,7 +93,7 @@ class ScoredSamples(object):
             return None
         if select != "nms":
             raise ValueError("select must be 'score' (the best-scored samples), 'nms' (score-ordered non-maximum suppression) or 'joint' (the best-scored "
-                             "joint samples of the window), got %r" % (select,))
+                             "joint samples of the window) or 'worlds' (the distinct joint samples of the window), got %r" % (select,))
         if nms_radius is None:
             raise ValueError("select='nms' needs nms_radius (pixels)")
         metrics = {"final": _lib.DIST_FINAL, "mean": _lib.DIST_MEAN, "max": _lib.DIST_MAX}
@@ -104,21 +104,62 @@ class ScoredSamples(object):
             raise ValueError("nms_horizon must be 1..pred_length (%d), got %d" % (T_pred, t_end))
         return metrics[nms_metric], t_end, float(nms_radius)
 
+    @staticmethod
+    def _worlds_args(select: str, worlds_radius, worlds_metric: str, worlds_reduce: str, worlds_horizon, collision_penalty, T_pred: int):
+        """None unless select == "worlds" (the world keywords are then refused); else (metric, reduce, t_end, radius in pixels, penalty)."""
+        if select != "worlds":
+            if worlds_radius is not None or worlds_metric != "final" or worlds_reduce != "mean" or worlds_horizon is not None or collision_penalty != 0.0:
+                raise ValueError("worlds_radius, worlds_metric, worlds_reduce, worlds_horizon and collision_penalty belong to select='worlds'")
+            return None
+        if worlds_radius is None:
+            raise ValueError("select='worlds' needs worlds_radius (pixels)")
+        if not (np.isfinite(float(worlds_radius)) and float(worlds_radius) >= 0):
+            raise ValueError("worlds_radius must be finite and >= 0 (pixels), got %r" % (worlds_radius,))
+        metrics = {"final": _lib.DIST_FINAL, "mean": _lib.DIST_MEAN, "max": _lib.DIST_MAX}
+        if worlds_metric not in metrics:
+            raise ValueError("worlds_metric must be 'final', 'mean' or 'max', got %r" % (worlds_metric,))
+        reduces = {"all": _lib.WORLD_ALL, "mean": _lib.WORLD_MEAN}
+        if worlds_reduce not in reduces:
+            raise ValueError("worlds_reduce must be 'mean' (the mean distance over the agents) or 'all' (every agent), got %r" % (worlds_reduce,))
+        t_end = T_pred if worlds_horizon is None else int(worlds_horizon)
+        if not 1 <= t_end <= T_pred:
+            raise ValueError("worlds_horizon must be 1..pred_length (%d), got %d" % (T_pred, t_end))
+        if not np.isfinite(float(collision_penalty)):
+            raise ValueError("collision_penalty must be finite, got %r" % (collision_penalty,))
+        return metrics[worlds_metric], reduces[worlds_reduce], t_end, float(worlds_radius), float(collision_penalty)
+
+    def _select_worlds(self, h, Y, pres8, jscore, collided, wargs, radius: float, ux: float, uy: float):
+        """One desire_select_worlds call on device tensors: the world score is jscore [n, K], minus penalty times the collisions of the world
+        (collided [n, K] int32) when the penalty is not 0 -- two fp32 operations.  Returns (worder [n, K], wcount [n], wmass [n, K], wlabel [n, K])."""
+        torch = self.torch
+        d = h.dims
+        metric, reduce, t_end, _, penalty = wargs
+        wscore = jscore if penalty == 0.0 else (jscore - collided.to(torch.float32) * penalty).contiguous()
+        worder = torch.empty((d.n_scenes, d.K), device=self.device, dtype=torch.int32)
+        wlabel, wcount = torch.empty_like(worder), torch.empty((d.n_scenes,), device=self.device, dtype=torch.int32)
+        wmass = torch.empty((d.n_scenes, d.K), device=self.device, dtype=torch.float32)
+        h.select_worlds(Y.data_ptr(), _ptr(pres8), wscore.data_ptr(), metric, reduce, t_end, radius, ux, uy, worder.data_ptr(), wcount.data_ptr(),
+                        wmass.data_ptr(), wlabel.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        return worder, wcount, wmass, wlabel
+
     def predict(self, x_batch: Sequence[np.ndarray], top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False,
                 window_base: int = 0, generator: str = "cvae", normals=None, select: str = "score", nms_radius=None, nms_metric: str = "final",
-                nms_horizon=None, collision_radius=None):
+                nms_horizon=None, collision_radius=None, worlds_radius=None, worlds_metric: str = "final", worlds_reduce: str = "mean", worlds_horizon=None,
+                collision_penalty: float = 0.0):
         """The `top` most plausible futures of every agent of a batch of observed loader windows [T_obs, MNO, 3], ranked by IOC score
         (prior sampling: no future given).  See predict_device for the result."""
         d = self._handle(len(x_batch), False).dims
         out = self.predict_device(self._pad_windows(x_batch, d.mno), top, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng,
                                   window_base=window_base, generator=generator, normals=normals, select=select, nms_radius=nms_radius,
-                                  nms_metric=nms_metric, nms_horizon=nms_horizon, collision_radius=collision_radius)
+                                  nms_metric=nms_metric, nms_horizon=nms_horizon, collision_radius=collision_radius, worlds_radius=worlds_radius,
+                                  worlds_metric=worlds_metric, worlds_reduce=worlds_reduce, worlds_horizon=worlds_horizon, collision_penalty=collision_penalty)
         self.input_data, self.target_data = x_batch, None
         return out
 
     def predict_device(self, past, top: Optional[int] = None, eps=None, seed: int = 0, grid_of_scene=None, device_rng: bool = False, window_base: int = 0,
                        generator: str = "cvae", normals=None, select: str = "score", nms_radius=None, nms_metric: str = "final", nms_horizon=None,
-                       collision_radius=None):
+                       collision_radius=None, worlds_radius=None, worlds_metric: str = "final", worlds_reduce: str = "mean", worlds_horizon=None,
+                       collision_penalty: float = 0.0):
         """predict() on windows already in HBM (forward_device's layout).  Returns a dict of device tensors: "traj" [n, mno, top, T_pred, 2]
         IN PIXELS, best-scored first; "score" [n, mno, top]; "order" [n, mno, K] int32 (sample indices by descending score, ties to the
         lower index); "present" [n, mno] bool (id != 0 at the last observed frame -- the rows of absent agents are whatever the forward
@@ -137,14 +178,25 @@ class ScoredSamples(object):
         entry j of EVERY agent of a window is then joint sample jorder[j] -- the order of the scores summed over the present agents
         (desire_joint_metrics, prediction form) -- instead of each agent's own best.  "traj", "score" and "order" keep their shapes ("order" is the
         window's joint order repeated for every slot), and the dict gains "joint_score" [n, top] and "collisions" [n, top] int32: the present agents
-        of that joint sample that come within collision_radius pixels (None: 0, nothing touches) of another one at some frame."""
+        of that joint sample that come within collision_radius pixels (None: 0, nothing touches) of another one at some frame.
+        select "worlds": as "joint", but the `top` most plausible MUTUALLY DISTINCT joint futures (desire_select_worlds): walking the joint samples
+        best-scored first, one is kept unless it lies within worlds_radius pixels (required) of one already kept -- worlds_reduce "mean": the mean
+        over the present agents of their distance (worlds_metric "final", "mean" or "max" over the first worlds_horizon frames, as nms_metric);
+        "all": every present agent within the radius.  collision_penalty P != 0 ranks the joint samples by joint score - P * (present agents that
+        collide), so a world that runs its agents through each other falls behind a clean one.  The dict is "joint"'s, following the distinct
+        order (the kept worlds, then the suppressed ones best-scored first), and gains "count" [n] int32 (worlds kept) and "prob" [n, top] (the
+        softmax mass of the world scores each returned world absorbed; 0 for a suppressed one)."""
         torch = self.torch
-        joint = select == "joint"
+        worlds = select == "worlds"
+        joint = select == "joint" or worlds
         if collision_radius is not None and not joint:
-            raise ValueError("collision_radius belongs to select='joint'")
+            raise ValueError("collision_radius belongs to select='joint' and select='worlds'")
         if collision_radius is not None:
             _check_radius(collision_radius)
-        nms = None if joint else self._nms_args(select, nms_radius, nms_metric, None, 1)      # refuse a bad selection before the forward runs (the horizon: below)
+        # refuse a bad selection before the forward runs (the nms horizon: below)
+        wargs = self._worlds_args(select, worlds_radius, worlds_metric, worlds_reduce, worlds_horizon, collision_penalty,
+                                  self._prediction(past)[1].dims.T_pred if worlds else 1)
+        nms = None if joint else self._nms_args(select, nms_radius, nms_metric, None, 1)
         if generator == "cvae":
             if normals is not None:
                 raise ValueError("`normals` are the head rollout's draws: pass generator='rollout' with them")
@@ -170,11 +222,16 @@ class ScoredSamples(object):
             jorder = torch.empty((n, d.K), device=self.device, dtype=torch.int32)
             h.joint_metrics(Y.data_ptr(), 0, pres8.data_ptr(), score.data_ptr(), [d.T_pred], top, float(collision_radius or 0.0), 1.0 / d.sx, 1.0 / d.sy,
                             cnt.data_ptr(), jorder.data_ptr(), 0, 0, jscore.data_ptr(), 0, stream)
+            if worlds:
+                jorder, wcount, wmass, _ = self._select_worlds(h, Y, pres8, jscore, cnt[:, :d.K, 0, 0], wargs, wargs[3], 1.0 / d.sx, 1.0 / d.sy)
             idx = jorder[:, :top].long()                                     # [n, top]: the joint samples, best first
             w = torch.arange(n, device=self.device)[:, None]
             traj = (Y[w, idx].permute(0, 2, 1, 3, 4) / self._scale(d)).contiguous()
-            return {"traj": traj, "score": score[w, idx].permute(0, 2, 1).contiguous(), "order": jorder[:, None, :].expand(n, d.mno, d.K).contiguous(),
-                    "present": present, "joint_score": jscore[w, idx], "collisions": cnt[:, :d.K, 0, 0][w, idx]}
+            out = {"traj": traj, "score": score[w, idx].permute(0, 2, 1).contiguous(), "order": jorder[:, None, :].expand(n, d.mno, d.K).contiguous(),
+                   "present": present, "joint_score": jscore[w, idx], "collisions": cnt[:, :d.K, 0, 0][w, idx]}
+            if worlds:
+                out.update({"count": wcount, "prob": wmass[:, :top].contiguous()})
+            return out
         if nms is None:
             h.rank_samples(score.data_ptr(), Y.data_ptr(), top, order.data_ptr(), traj.data_ptr(), sc.data_ptr(), stream)
             traj /= self._scale(d)
@@ -216,7 +273,9 @@ class ScoredSamples(object):
         h.ranked_errors(Y.data_ptr(), fut.data_ptr(), order.data_ptr(), top, hz, ux, uy, out.data_ptr(), stream)
         return (out.cpu().numpy(), count.cpu().numpy()) if return_count else out.cpu().numpy()
 
-    def evaluate_joint(self, Y, score, fut_windows, top: Optional[int] = None, horizons=None, units="px", collision_radius=None) -> dict:
+    def evaluate_joint(self, Y, score, fut_windows, top: Optional[int] = None, horizons=None, units="px", collision_radius=None, select: str = "score",
+                       worlds_radius=None, worlds_metric: str = "final", worlds_reduce: str = "mean", worlds_horizon=None,
+                       collision_penalty: float = 0.0) -> dict:
         """The K samples of every window as K JOINT futures of the scene (desire_joint_metrics).  Returns numpy arrays: "jerr" [n, K, n_h, 2] =
         (JADE_h, JFDE_h): the mean over the agents that take part before the horizon of each agent's ADE_h / FDE_h under sample k; "jscore" [n, K] the
         scores summed over the agents that take part; "order" [n, K] the joint samples by descending joint score; "out" [n, n_h, 4] = (JADE, JFDE
@@ -224,9 +283,17 @@ class ScoredSamples(object):
         agent comes within collision_radius of another agent of the same joint sample (T_pred: never), row K being the ground truth under the same
         rule; "cnt" [n, K + 1, n_h, 2] int32 = (agents touching, agents taking part) before each horizon -- the collision rate is cnt[..., 0] /
         cnt[..., 1].  units, horizons, top and `fut_windows` as in evaluate_ranked; collision_radius in pixels, converted to the call's unit (units
-        "norm": along x); None: radius 0, nothing touches."""
+        "norm": along x); None: radius 0, nothing touches.
+        select="worlds" (worlds_radius in pixels, worlds_metric, worlds_reduce, worlds_horizon, collision_penalty as in predict_device; an agent takes
+        part when it has a counted frame; the penalty counts the collisions before the last horizon): the joint samples also go through
+        desire_select_worlds, and the dict gains "worder" [n, K] (the kept worlds, then the suppressed ones), "wcount" [n], "wprob" [n, K] (the mass
+        each kept world absorbed), "wlabel" [n, K] (the keeping position of every world's owner) and "out_distinct" [n, n_h, 2] = the best JADE, and
+        the best JFDE, among the `top` first worlds of "worder" (a NaN is kept, as in "out")."""
         torch = self.torch
+        if select not in ("score", "worlds"):
+            raise ValueError("select must be 'score' (the best-scored joint samples) or 'worlds' (the distinct ones too), got %r" % (select,))
         h, d, hz, (ux, uy, f), fut, stream = self._evaluation(Y, fut_windows, horizons, units)
+        wargs = self._worlds_args(select, worlds_radius, worlds_metric, worlds_reduce, worlds_horizon, collision_penalty, d.T_pred)
         n = d.n_scenes
         top = default_top(d.K) if top is None else int(top)
         radius = (0.0 if collision_radius is None else float(collision_radius)) * f
@@ -236,6 +303,14 @@ class ScoredSamples(object):
                "cnt": torch.empty((n, d.K + 1, len(hz), 2), device=dev, dtype=i32), "first": torch.empty((n, d.K + 1, d.mno), device=dev, dtype=i32)}
         h.joint_metrics(Y.data_ptr(), fut.data_ptr(), 0, _ptr(score), hz, top, radius, ux, uy, res["cnt"].data_ptr(),
                         res["order"].data_ptr(), res["first"].data_ptr(), res["jerr"].data_ptr(), res["jscore"].data_ptr(), res["out"].data_ptr(), stream)
+        if wargs is not None:
+            part8 = (fut[..., 0] != 0).any(1).to(torch.uint8).contiguous()    # [n, mno]: a counted frame before T_pred
+            res["worder"], res["wcount"], res["wprob"], res["wlabel"] = self._select_worlds(h, Y, part8, res["jscore"], res["cnt"][:, :d.K, -1, 0], wargs,
+                                                                                            wargs[3] * f, ux, uy)
+            idx = res["worder"][:, :top].long()
+            je = res["jerr"][torch.arange(n, device=dev)[:, None], idx]      # [n, top, n_h, 2]
+            low = je.min(1).values
+            res["out_distinct"] = torch.where(torch.isnan(je).any(1), torch.full_like(low, float("nan")), low)
         return {k: v.cpu().numpy() for k, v in res.items()}
 
     def _plan_risk(self, h, Y, fut, present, score, plans, ego, hz, radius, ux, uy):

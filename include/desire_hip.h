@@ -461,6 +461,46 @@ int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, const float* d
                          int32_t* dev_first, int32_t* dev_cnt, float* dev_jerr, float* dev_jscore, int32_t* dev_jorder,
                          float* dev_out, void* stream);
 
+/* ---- n distinct joint futures per window: score-ordered non-maximum suppression of the K WORLDS of a window, world k being sample k of every
+ * slot together (what desire_joint_metrics ranks and desire_plan_risk weights).  Layouts are desire_joint_metrics': agent a = scene * mno + slot,
+ * row r_k = (scene * K + k) * mno + slot.  All arithmetic is fp32; every operation is rounded once (no fused multiply-add); no float atomics.
+ *   1 taking part dev_present [A] uint8 (may be NULL: every slot takes part).  Slot i takes part iff dev_present[a] != 0.  The rows of a slot that
+ *                 does not take part are never read.
+ *   2 per agent   for worlds k, k' of a window and a slot i: q_t, m and s are desire_select_diverse's steps 1 - 2 on the rows r_k, r_k' of slot i
+ *                 (the same operation sequence, symmetric in k, k' bit for bit), near_i that call's predicate for `metric` (DESIRE_DIST_*), and
+ *                 d_i the linear distance: DESIRE_DIST_FINAL sqrtf(q_{t_end - 1}); DESIRE_DIST_MAX sqrtf(m); DESIRE_DIST_MEAN s / (float)t_end.
+ *   3 world       r2 = radius * radius.  DESIRE_WORLD_ALL: k and k' are NEAR iff near_i holds for every taking-part slot (a conjunction: order-
+ *                 free; a NaN is never near).  DESIRE_WORLD_MEAN: D = (the sum of d_i over the taking-part slots, in increasing slot from 0.f) /
+ *                 (float)(their number); NEAR iff D < radius, strict and false for a NaN.  No taking-part slot: the worlds are near whenever
+ *                 radius > 0.  radius == 0: nothing is near.
+ *   4 order in    the processing order of the window is the order of dev_wscore [n_scenes, K] under desire_rank_samples' rule exactly (IEEE >,
+ *                 ties to the lower k, NaNs last by index), ranked by the call itself.  dev_wscore may be NULL: the identity order, uniform
+ *                 weights.  Any caller-made score will do (desire_joint_metrics' dev_jscore; that minus a penalty per collision; ...).
+ *   5 greedy pass desire_select_diverse's steps 3 - 4 with `sample of an agent` read as `world of a window`: dev_worder [n_scenes, K] = the kept
+ *                 worlds in keeping order, then the owned ones in processing order; dev_wcount [n_scenes] = the number kept, >= 1.
+ *   6 mass        dev_wmass [n_scenes, K] (may be NULL).  The weights W_k are desire_plan_risk's step 6 on dev_wscore (m = max_k, e_k =
+ *                 expf(s_k - m), W_k = e_k / sum_k e_k in increasing k from 0.f; 1.f / K when dev_wscore is NULL or any score is not finite).
+ *                 dev_wmass[w, i], i < count = the sum of W over kept world i and the worlds it owns, in processing order from 0.f; 0.f beyond.
+ *   7 label       dev_wlabel [n_scenes, K] int32 (may be NULL): for world k the position in keeping order of the kept world that owns it, its own
+ *                 position when it is kept.
+ *   8 A window's result depends on that window's taking-part rows, scores and presence only -- not on the grid, the batch, DESIRE_FLAG_COMPACT_*
+ *     or the last desire_encode.  Bitwise reproducible, one launch, stream-ordered, capturable, no host wait, no allocation and no scratch.
+ * At mno = 1 with the slot present and DESIRE_WORLD_ALL, dev_worder / dev_wcount / dev_wmass are the bits of desire_select_diverse given
+ * desire_rank_samples' order and the same scores.  With radius 0 and dev_wscore = desire_joint_metrics' dev_jscore, dev_worder is its dev_jorder.
+ * LDS plan: one workgroup owns one window.  Per kept world it stages the frames it walks (F = 1 for DESIRE_DIST_FINAL, else t_end) of that world's
+ * rows of a chunk of taking-part slots, next to K words per slot of the chunk, 40 K bytes of per-world words and 4 mno bytes; the candidates' rows
+ * are read from dev_Yhat.  The chunks run over the slots, a world's reduction over the slots is carried across them in increasing slot: the bits
+ * of an unchunked walk.  One slot must fit: 44 K + 4 mno + 8 (F | 1) <= 61440 bytes -- every (mno <= 256, T_pred <= 200) at any K <= 1300, e.g.
+ * 22 slots per chunk at (mno 256, t_end 200, K 176).
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing is launched or written: a NULL handle / dev_Yhat / dev_worder / dev_wcount; a metric
+ * outside 0 .. 2; a reduce outside 0 .. 1; t_end outside 1 .. T_pred; a radius that is negative or not finite; a unit that is not finite and > 0;
+ * a ref_compat handle; a (K, mno, t_end) beyond the LDS plan. */
+#define DESIRE_WORLD_ALL  0   /* near iff every taking-part slot is near */
+#define DESIRE_WORLD_MEAN 1   /* near iff the mean over the taking-part slots of the linear distance is below the radius */
+int desire_select_worlds(desire_handle* h, const float* dev_Yhat, const uint8_t* dev_present, const float* dev_wscore,
+                         int32_t metric, int32_t reduce, int32_t t_end, float radius, float unit_x, float unit_y,
+                         int32_t* dev_worder, int32_t* dev_wcount, float* dev_wmass, int32_t* dev_wlabel, void* stream);
+
 /* ---- candidate ego plans against the K joint futures: a planner holds M candidate trajectories for its own vehicle per window and asks of each:
  * how likely do I hit somebody before each horizon, how close do I get, when is the first contact, and which agent is the threat.  Layouts, the
  * counting rule c(a, t), g, host_horizons, radius and unit_x / unit_y are desire_joint_metrics' exactly; a slot TAKES PART BEFORE h when it has a
