@@ -28,7 +28,7 @@ EXPORTS = [
     "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse", "desire_joint_metrics",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
     "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy", "desire_plan_risk", "desire_fit_modes",
-    "desire_select_worlds",
+    "desire_select_worlds", "desire_fit_scene_modes",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
@@ -115,6 +115,8 @@ def load() -> C.CDLL:
     lib.desire_plan_risk.argtypes = [vp, f32p, f32p, vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, vp, f32p, f32p, f32p, vp]
     lib.desire_fit_modes.argtypes = [vp, f32p, vp, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32), i32, C.c_float,
                                      vp, vp, f32p, f32p, f32p, vp, f32p, f32p, vp]
+    lib.desire_fit_scene_modes.argtypes = [vp, f32p, vp, vp, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32), i32,
+                                           C.c_float, vp, vp, f32p, f32p, f32p, vp, f32p, f32p, vp]
     lib.desire_rollout.argtypes = [vp, f32p, f32p, i32, f32p, vp]
     lib.desire_rollout_samples.argtypes = [vp, f32p, f32p, f32p, vp]
     lib.desire_set_training.argtypes = [vp, C.c_int]
@@ -197,7 +199,7 @@ class Handle:
 
     def set_option(self, name: str, value: int) -> None:
         """One of the behavioural switches of desire_dims ("ioc_form", "ioc_split", "train_fp32_mask", "flags") or a handle option
-        ("compact_min_rows", "compact_host_counts", "scene_grad") on the live handle."""
+        ("compact_min_rows", "compact_host_counts", "scene_grad", "scene_modes_chunk") on the live handle."""
         _chk(self.lib.desire_set_option(self._h, name.encode(), int(value)))
         if hasattr(self.dims, name):                      # ("compact_min_rows" is a handle option, not a desire_dims field)
             self.dims = self.dims.replace(**{name: int(value)})
@@ -389,6 +391,24 @@ class Handle:
                                        int(iters), C.c_float(unit_x), C.c_float(unit_y), C.c_float(var_floor), hzp, hz.size, C.c_float(log_floor),
                                        label_ptr or None, count_ptr or None, prob_ptr or None, mean_ptr or None, cov_ptr or None,
                                        passes_ptr or None, out_ptr or None, frame_ptr or None, stream or None))
+
+    def fit_scene_modes(self, yhat_ptr: int, present_ptr: int, worder_ptr: int, wscore_ptr: int, n_modes: int, t_end: int, iters: int, unit_x: float,
+                        unit_y: float, var_floor: float, count_ptr: int, prob_ptr: int, label_ptr: int = 0, mean_ptr: int = 0, cov_ptr: int = 0,
+                        passes_ptr: int = 0, fut_ptr: int = 0, horizons=None, log_floor: float = KDE_LOG_FLOOR, out_ptr: int = 0, frame_ptr: int = 0,
+                        stream: int = 0) -> None:
+        """n_modes scene modes per window fitted to its K weighted joint futures (world k = sample k of every slot) by fit_modes' weighted Lloyd
+        iteration on whole worlds, seeded with the first n_modes entries of worder [n, K] (joint_metrics' jorder or select_worlds' worder), at most
+        `iters` passes; the distance of a world to a mode is the sum over the taking-part slots (present [A] uint8, present_ptr = 0: all) of
+        fit_modes' distance over the frames t < t_end: count [n, n_modes] int32 = the member worlds of each mode, prob [n, n_modes] = their weight
+        (softmax(wscore [n, K]); wscore_ptr = 0: 1 / K), label [n, K] int32, mean [n, n_modes, mno, T_pred, 2] in Y's coordinates, cov
+        [n, n_modes, mno, T_pred, 3] = (Cxx, Cyy, Cxy) per agent in unit^2 with var_floor added to the diagonal (zeros for a slot that does not
+        take part), passes [n] int32.  With fut_ptr (and horizons): out [n, n_h, 2] = (mean, final) negative joint log-density of the ground
+        truth under that mixture PER AGENT counted in the frame, clipped below at log_floor; frame [n, T_pred] the per-frame values."""
+        hz, hzp = _horizons(horizons, optional=True)
+        _chk(self.lib.desire_fit_scene_modes(self._h, yhat_ptr or None, present_ptr or None, worder_ptr or None, wscore_ptr or None, fut_ptr or None,
+                                             int(n_modes), int(t_end), int(iters), C.c_float(unit_x), C.c_float(unit_y), C.c_float(var_floor), hzp,
+                                             hz.size, C.c_float(log_floor), label_ptr or None, count_ptr or None, prob_ptr or None, mean_ptr or None,
+                                             cov_ptr or None, passes_ptr or None, out_ptr or None, frame_ptr or None, stream or None))
 
     def occupancy(self, yhat_ptr: int, fut_ptr: int, present_ptr: int, score_ptr: int, horizons, mode: int, Oh: int, Ow: int, occ_ptr: int,
                   exp_ptr: int = 0, hit_ptr: int = 0, viol_ptr: int = 0, off_ptr: int = 0, mask_ptr: int = 0, mask_of_scene_ptr: int = 0,

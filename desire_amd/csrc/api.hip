@@ -157,7 +157,12 @@ extern "C" int desire_set_option(desire_handle* h, const char* name, int32_t val
         h->ci_min_rows = value;
         return DESIRE_OK;
     }
-    else return fail(DESIRE_ERR_ARG, "unknown option: " + nm + " (ioc_form, ioc_split, train_fp32_mask, flags, compact_min_rows, compact_host_counts, scene_grad)");
+    else if (nm == "scene_modes_chunk") {      // desire_fit_scene_modes: at most this many slots per chunk (0, the default: as many as the LDS plan holds); the bits do not depend on it
+        if (value < 0) return fail(DESIRE_ERR_ARG, "scene_modes_chunk must be >= 0");
+        h->scene_modes_chunk = value;
+        return DESIRE_OK;
+    }
+    else return fail(DESIRE_ERR_ARG, "unknown option: " + nm + " (ioc_form, ioc_split, train_fp32_mask, flags, compact_min_rows, compact_host_counts, scene_grad, scene_modes_chunk)");
     if (int rc = check_options(d)) return rc;
     // the maps of the last desire_encode were built for the other setting, or for the other slot-class set (ioc_form and train_fp32_mask decide
     // whether class 10 exists): a new desire_encode comes first

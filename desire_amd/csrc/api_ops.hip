@@ -465,6 +465,50 @@ extern "C" int desire_fit_modes(desire_handle* h, const float* dev_Yhat, const i
     return DESIRE_OK;
 }
 
+// ---- n scene modes with covariances fitted to a window's K joint futures (kernels_scene_modes.hip): the contract is stated in
+// include/desire_hip.h.  As in desire_fit_modes the checks that need no handle come first. ----
+extern "C" int desire_fit_scene_modes(desire_handle* h, const float* dev_Yhat, const uint8_t* dev_present, const int32_t* dev_worder,
+                                      const float* dev_wscore, const float* dev_fut, int32_t n_modes, int32_t t_end, int32_t iters, float unit_x,
+                                      float unit_y, float var_floor, const int32_t* host_horizons, int32_t n_h, float log_floor, int32_t* dev_label,
+                                      int32_t* dev_count, float* dev_prob, float* dev_mean, float* dev_cov, int32_t* dev_passes, float* dev_out,
+                                      float* dev_frame, void* stream) {
+    if (n_modes < 1 || n_modes > DESIRE_MODES_MAX) return fail(DESIRE_ERR_ARG, "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")");
+    if (t_end < 1) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    if (iters < 0 || iters > DESIRE_MODES_MAX_ITERS) return fail(DESIRE_ERR_ARG, "iters must be 0.." + std::to_string(DESIRE_MODES_MAX_ITERS));
+    if (int rc = check_units(unit_x, unit_y)) return rc;
+    if (!std::isfinite(var_floor) || var_floor < 0.f) return fail(DESIRE_ERR_ARG, "var_floor must be finite and >= 0");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_worder) return fail(DESIRE_ERR_ARG, "dev_worder is NULL");
+    if (!dev_count) return fail(DESIRE_ERR_ARG, "dev_count is NULL");
+    if (!dev_prob) return fail(DESIRE_ERR_ARG, "dev_prob is NULL");
+    if (!dev_fut && dev_out) return fail(DESIRE_ERR_ARG, "dev_out needs dev_fut (the likelihood is that of the ground truth)");
+    if (!dev_fut && dev_frame) return fail(DESIRE_ERR_ARG, "dev_frame needs dev_fut (the likelihood is that of the ground truth)");
+    if (dev_fut && !dev_out) return fail(DESIRE_ERR_ARG, "dev_out is NULL (dev_fut asks for the likelihood)");
+    if (dev_fut && !host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (dev_fut && !std::isfinite(log_floor)) return fail(DESIRE_ERR_ARG, "log_floor must be finite");
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to fit scene modes to");
+    if (n_modes > d.K) return fail(DESIRE_ERR_ARG, "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")");
+    if (t_end > d.T_pred) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    RankHz hz{};
+    if (dev_fut)
+        if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
+    int sc = 0;
+    if (!scene_modes_geometry(d.mno, d.K, d.T_pred, n_modes, &sc))
+        return fail(DESIRE_ERR_ARG, "K worlds and n_modes means of one slot's T_pred frames do not fit the scene-mode kernel's LDS: " +
+                                        std::to_string(EVAL_PAIR_BYTES) + " * (K + n_modes) * (T_pred | 1) + " +
+                                        std::to_string(4 * (SceneModesLds::TERM_WORDS + SceneModesLds::FRAME_WORDS)) + " * n_modes * T_pred + 12 * K * n_modes + " +
+                                        std::to_string(4 * SceneModesLds::K_WORDS) + " * K + " + std::to_string(4 * SceneModesLds::MODE_WORDS) +
+                                        " * n_modes + 4 * n_modes * ceil(K / 32) + " + std::to_string(4 * SceneModesLds::T_WORDS) +
+                                        " * T_pred + 4 * mno must be <= " + std::to_string(EVAL_LDS_BYTES));
+    launch_fit_scene_modes(dev_Yhat, dev_present, dev_worder, dev_wscore, dev_fut, dev_label, dev_count, dev_prob, dev_mean, dev_cov, dev_passes,
+                           dev_out, dev_frame, d.n_scenes, d.mno, d.K, d.T_pred, n_modes, t_end, iters, hz, d.sx, d.sy, unit_x, unit_y, var_floor,
+                           log_floor, h->scene_modes_chunk, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- predicted occupancy maps of the K weighted samples (kernels_occ.hip): the contract is stated in include/desire_hip.h ----
 extern "C" int desire_occupancy(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present, const float* dev_score,
                                 const int32_t* host_horizons, int32_t n_h, int32_t mode, int32_t Oh, int32_t Ow, const uint8_t* dev_mask,

@@ -70,6 +70,7 @@ struct desire_ctx {
     bool cp_enc = false;                                     // the last desire_encode ran its stack on the present agents only (saves in compact agent order)
     bool cp_host_counts = false;                             // desire_set_option("compact_host_counts", 1): inference reads the counts back like training does (A/B)
     bool cp_last = false;                                    // the last desire_sample ran compacted (desire_backward follows it, not the flag)
+    int scene_modes_chunk = 0;                               // desire_set_option("scene_modes_chunk", c): desire_fit_scene_modes walks at most c slots per chunk (0: what the LDS holds; the tests' lever)
     // desire_build_windows*: plain pointers, cached at creation -- a feeder thread may run the builder while the owner thread runs a forward or a backward on
     // the same handle (desire_amd/prefetch.py: DeviceWindowFeeder), and those allocate workspace entries lazily (allocation inserts; reads do not): the
     // builder must not walk the map

@@ -1,7 +1,8 @@
 // eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
-// _recon / _occ / _plan / _modes / _worlds.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// _recon / _occ / _plan / _modes / _worlds / _scene_modes.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
 // that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
-// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp and occ_lds_driver.cpp compile it with g++ (tests/test_eval_lds.py, test_occ_lds.py).
+// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp, occ_lds_driver.cpp and scene_modes_lds_driver.cpp compile it with g++ (tests/test_eval_lds.py, test_occ_lds.py,
+// test_scene_modes_cpu.py).
 #pragma once
 #include <stddef.h>
 
@@ -190,6 +191,56 @@ inline bool modes_geometry(int mno, int K, int T, int n, int* SC, int* G) {
     sc = eval_min(sc, eval_max(1, EVAL_THREADS / g));
     *SC = eval_chunks(mno, eval_chunks(mno, sc));
     *G = g;
+    return true;
+}
+
+// ---- k_fit_scene_modes: one workgroup owns a window and walks its taking-part slots in chunks of SC.  Per chunk, float2 rows Yl [SC][K][Tp] (all T
+// frames of the K worlds' rows of the chunk's slots, Tp = T | 1) and the modes' means ml [SC][n][Tp] with the same stride; behind the pairs, in
+// 32-bit words: three [SC][n][T] words of the last pass (a slot's quadratic term over its determinant, half the log of the determinant, and the
+// state of (slot, mode, t): not counted / usable / not usable), ds [K * n][SC | 1] (the chunk's distances d_s; the odd stride keeps the lanes
+// that each reduce one (world, mode) on distinct banks) and, kept across the chunks, D [K][n] (the running sum of d_s in increasing slot), three
+// [K] words (weight, label, previous label), five [n] words (mass, the mass the mean was divided by, members, seed, `the mode has had mass`),
+// member [n][ceil(K / 32)] (bit k: world k is one of the worlds the mode's mean is formed from), two [n][T] words (the running log-likelihood
+// L_i of a frame and `usable so far`), three [T] words (slots counted, the frame's value, counted) and one [mno] word (the taking-part slots in
+// increasing slot).  As in WorldsLds the chunks run over the SLOTS, never over the frames: what crosses a chunk border is a per-(world, mode)
+// sum in increasing slot and a per-(mode, t) chain in increasing slot, so a chunked window has the bits of an unchunked one by construction.  A
+// chunk's means are formed anew from the member words in every pass (a mode that lost its mass keeps the members its mean came from), so
+// nothing per slot outlives its chunk.  The limit this gives is stated in desire_hip.h and in desire_fit_scene_modes' message.
+struct SceneModesLds {
+    enum { TERM_WORDS = 3, K_WORDS = 3, MODE_WORDS = 5, FRAME_WORDS = 2, T_WORDS = 3 };
+    int T, Tp, SC, K, n, mno;
+    EVAL_HD constexpr SceneModesLds(int T_, int SC_, int K_, int n_, int mno_) : T(T_), Tp(eval_odd(T_)), SC(SC_), K(K_), n(n_), mno(mno_) {}
+    EVAL_HD static constexpr int member_words(int K) { return (K + 31) / 32; }
+    EVAL_HD constexpr size_t rows() const { return (size_t)SC * K * Tp; }                   // float2 in front of the means
+    EVAL_HD constexpr size_t pairs() const { return (size_t)SC * (K + n) * Tp; }            // float2 in front of the words
+    EVAL_HD constexpr int ds_stride() const { return eval_odd(SC); }
+    EVAL_HD constexpr size_t term(int r) const { return (size_t)r * SC * n * T; }           // word offsets behind the pairs
+    EVAL_HD constexpr size_t ds() const { return term(TERM_WORDS); }
+    EVAL_HD constexpr size_t dist() const { return ds() + (size_t)K * n * (SC + 1); }
+    EVAL_HD constexpr size_t k_words(int r) const { return dist() + (size_t)K * n + (size_t)r * K; }
+    EVAL_HD constexpr size_t mode_words(int r) const { return k_words(K_WORDS) + (size_t)r * n; }
+    EVAL_HD constexpr size_t member() const { return mode_words(MODE_WORDS); }
+    EVAL_HD constexpr size_t frame_words(int r) const { return member() + (size_t)n * member_words(K) + (size_t)r * n * T; }
+    EVAL_HD constexpr size_t t_words(int r) const { return frame_words(FRAME_WORDS) + (size_t)r * T; }
+    EVAL_HD constexpr size_t slots() const { return t_words(T_WORDS); }
+    EVAL_HD static constexpr size_t fixed_bytes(int K, int T, int n, int mno) {
+        return 4 * ((size_t)2 * K * n + (size_t)K_WORDS * K + (size_t)MODE_WORDS * n + (size_t)n * member_words(K) + (size_t)FRAME_WORDS * n * T +
+                    (size_t)T_WORDS * T + (size_t)mno);
+    }
+    EVAL_HD static constexpr size_t slot_bytes(int K, int T, int n) {
+        return EVAL_PAIR_BYTES * (size_t)(K + n) * eval_odd(T) + 4 * ((size_t)TERM_WORDS * n * T + (size_t)K * n);
+    }
+    EVAL_HD constexpr size_t bytes() const { return fixed_bytes(K, T, n, mno) + (size_t)SC * slot_bytes(K, T, n); }
+};
+// The slot chunk: as many slots as the LDS holds next to the per-window words, spread evenly over the chunks of mno.  false: the per-window words
+// and one slot do not fit.  At (mno 32, K 20, T_pred 40, n 6) a chunk is 4 slots, at (256, 20, 40, 6) too.
+inline bool scene_modes_geometry(int mno, int K, int T, int n, int* SC) {
+    if (mno < 1 || K < 1 || T < 1 || n < 1) return false;
+    const size_t fixed = SceneModesLds::fixed_bytes(K, T, n, mno), per = SceneModesLds::slot_bytes(K, T, n);
+    if (fixed + per > (size_t)EVAL_LDS_BYTES) return false;
+    const size_t fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;
+    const int sc = (int)((size_t)mno < fit ? (size_t)mno : fit);
+    *SC = eval_chunks(mno, eval_chunks(mno, sc));
     return true;
 }
 

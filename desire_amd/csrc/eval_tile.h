@@ -1,5 +1,5 @@
 // eval_tile.h -- the device pieces that the evaluation kernels over the sample tensor Y [R, T_pred, 2] share, each stated once: the streaming
-// loop over Y, the order rule of the scores, the pick through an order, the horizon list and its walk, the weight statistics of the scores.
+// loop over Y, the order rule of the scores, the pick through an order, the horizon list and its walk, the weight statistics of the scores, the compaction of a predicate.
 // The sinks and everything that is arithmetic on positions stay in the kernels.
 //
 // RULE: no floating-point multiply that feeds an add in this header.  kernels_rank.hip is compiled with the compiler's default contraction,
@@ -77,6 +77,22 @@ __device__ __forceinline__ void eval_stream(const float* __restrict__ Y, int vec
 __device__ __forceinline__ bool eval_before(float sj, int j, float sk, int k) {
     const bool nk = sk != sk;
     return (sj != sj) ? (nk && j < k) : (nk || sj > sk || (sj == sk && j < k));
+}
+
+// ---- the compaction of a predicate: called by wave 0 alone (lanes 0 .. 63 of the workgroup); out[0 .. n) = the i < N with pred(i), in increasing
+// i; n comes back in every lane of the wave.
+template <class Pred>
+__device__ __forceinline__ int eval_compact(int N, int* out, Pred pred) {
+    const int lane = threadIdx.x;
+    int n = 0;
+    for (int b = 0; b < N; b += 64) {
+        const int i = b + lane;
+        const bool p = i < N && pred(i);
+        const unsigned long long m = __ballot(p);
+        if (p) out[n + __popcll(m & ((1ull << lane) - 1ull))] = i;
+        n += __popcll(m);
+    }
+    return n;
 }
 
 // ---- the pick through an order row: (ADE, FDE of the first entry; min over the n_top first entries of ADE, of FDE), tab(k) being the

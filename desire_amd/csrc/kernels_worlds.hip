@@ -29,21 +29,6 @@ namespace {
 constexpr int SW_LIVE = -1;                    // st[j]: not yet kept or owned
 constexpr int SW_KEPT = 1 << 30;               // st[j] = i | SW_KEPT: kept as number i; st[j] = i: owned by kept number i
 
-// Wave 0 alone: out[0 .. n) = the i < N with pred(i), in increasing i; n comes back in every lane of the wave.
-template <class Pred>
-__device__ __forceinline__ int sw_compact(int N, int* out, Pred pred) {
-    const int lane = threadIdx.x;
-    int n = 0;
-    for (int b = 0; b < N; b += 64) {
-        const int i = b + lane;
-        const bool p = i < N && pred(i);
-        const unsigned long long m = __ballot(p);
-        if (p) out[n + __popcll(m & ((1ull << lane) - 1ull))] = i;
-        n += __popcll(m);
-    }
-    return n;
-}
-
 // desire_select_diverse's steps 1 - 2 on one slot of (candidate, kept): the candidate's row from Y (p0 = its first staged pair), the kept row
 // from LDS.  FINAL: q; MAX: m; MEAN: s -- the contract's sequence, symmetric in the two rows bit for bit (a, b only change sign).
 template <int METRIC>
@@ -112,7 +97,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_select_worlds(const float* __r
     }
     if (tid < 64) {
         const uint8_t* pr = present ? present + scene * mno : nullptr;
-        const int n = sw_compact(mno, slotL, [&](int i) { return !pr || pr[i] != 0; });
+        const int n = eval_compact(mno, slotL, [&](int i) { return !pr || pr[i] != 0; });
         if (tid == 0) npS = n;
     }
     __syncthreads();
@@ -139,7 +124,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_select_worlds(const float* __r
     for (;;) {
         __syncthreads();                                                // the states of the last step
         if (tid < 64) {
-            const int n = sw_compact(K, live, [&](int j) { return st[j] == SW_LIVE; });
+            const int n = eval_compact(K, live, [&](int j) { return st[j] == SW_LIVE; });
             if (tid == 0) nlS = n;
         }
         __syncthreads();

@@ -5,7 +5,8 @@ device, errors per horizon of the best-scored sample (top-1), of the best among 
         --pred_length 12 [--eval_top 2] [--eval_horizons 3,6,9,12] [--units px|norm|0.2] [--max_windows 500] [--out result.json] \\
         [--generator cvae|rollout] [--nll] [--select nms --nms_radius 20 [--nms_metric final|mean|max] [--nms_horizon 12]] \\
         [--joint [--collision_radius 10]] [--occupancy 64x64 [--occupancy_mode at|until]] [--plan_risk [--collision_radius 10]] \\
-        [--modes 6 [--modes_iters 8] [--modes_min_std 1.0] [--modes_seeds nms|score]]
+        [--modes 6 [--modes_iters 8] [--modes_min_std 1.0] [--modes_seeds nms|score]] \\
+        [--joint_modes 6 [--joint_modes_iters 8] [--joint_modes_min_std 1.0] [--joint_modes_seeds nms|score] [--joint_radius 20]]
 
 The model flags are train.py's and must be the ones the checkpoint was trained with.  Every video is walked once from its first frame in
 steps of one window (no random pointer jumps); the windows are cut and slot-assigned like DataLoader.next_batch does.  Means are taken in
@@ -88,6 +89,16 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--modes_min_std", type=float, default=1.0, help="--modes: the standard deviation in pixels whose square is added to every variance")
     p.add_argument("--modes_seeds", type=str, default="nms", choices=("nms", "score"),
                    help="--modes: the seeds -- nms: the mutually distinct samples first (needs --nms_radius; --nms_metric applies), score: the best-scored")
+    p.add_argument("--joint_modes", type=int, default=0, metavar="N",
+                   help="also report the mixture of N SCENE modes per window that predict_scene_modes hands out (desire_fit_scene_modes): per horizon "
+                        "its negative joint log-likelihood of the ground truth per agent (mean over the frames and final frame; density per unit^2 of "
+                        "--units, log clipped at -20) and the JADE / JFDE of the most probable mode's means and of the best mode's means")
+    p.add_argument("--joint_modes_iters", type=int, default=8, help="--joint_modes: the most Lloyd passes (0..32)")
+    p.add_argument("--joint_modes_min_std", type=float, default=1.0,
+                   help="--joint_modes: the standard deviation in pixels whose square is added to every variance")
+    p.add_argument("--joint_modes_seeds", type=str, default="nms", choices=("nms", "score"),
+                   help="--joint_modes: the seeds -- nms: the mutually distinct joint futures first (needs --joint_radius; --joint_metric, --joint_reduce, "
+                        "--joint_horizon, --collision_radius and --collision_penalty apply), score: the joint futures with the best summed score")
     p.add_argument("--out", type=str, default=None, help="write the result JSON here (default: standard output only)")
     return p
 
@@ -357,6 +368,45 @@ class _Modes:
                           "top1": _per_horizon(m["top1"], "ade", "fde"), "best": _per_horizon(m["best"], "ade", "fde")}}
 
 
+class _JointModes:
+    """--joint_modes N: the mixture of N scene modes per window -- its joint likelihood of the ground truth per agent, the joint errors of the most
+    probable and of the best mode's means, over the windows with an agent taking part (by the targets' ids alone, as --joint counts), and the Lloyd
+    passes per such window."""
+
+    def __init__(self, args, hz, run):
+        self.n = int(getattr(args, "joint_modes", 0) or 0)
+        self.on = bool(self.n)
+        self.seeds = str(getattr(args, "joint_modes_seeds", "nms"))
+        if self.on and self.seeds == "nms" and getattr(args, "joint_radius", None) is None:
+            raise ValueError("--joint_modes with --joint_modes_seeds nms needs --joint_radius (pixels)")
+        self.iters, self.min_std, self.run = int(getattr(args, "joint_modes_iters", 8)), float(getattr(args, "joint_modes_min_std", 1.0)), run
+        self.worlds = {"seeds": "score"}
+        if self.seeds == "nms":
+            self.worlds = dict(seeds="worlds", worlds_radius=getattr(args, "joint_radius", None), worlds_metric=str(getattr(args, "joint_metric", "final")),
+                               worlds_reduce=str(getattr(args, "joint_reduce", "mean")), horizon=getattr(args, "joint_horizon", None),
+                               collision_radius=getattr(args, "collision_radius", None),
+                               collision_penalty=float(getattr(args, "collision_penalty", 0.0) or 0.0))
+        self.sums = {k: np.zeros((len(hz), 2), np.float64) for k in ("nll", "top1", "best")}
+        self.windows, self.passes = np.zeros(len(hz), np.int64), 0
+
+    def update(self, model, Y, score, fut, masks):
+        r = self.run
+        mm = model.evaluate_scene_modes(Y, score, fut, modes=self.n, iters=self.iters, min_std=self.min_std, horizons=r.hz, units=r.units,
+                                        log_floor=KDE_LOG_FLOOR, **self.worlds)
+        takes = np.stack([masks.seen[:, :h].any((1, 2)) for h in r.hz], 1)                       # [n, n_h]
+        for k in self.sums:
+            self.sums[k] += np.where(takes[:, :, None], mm[k].astype(np.float64), 0.0).sum(0)
+        self.windows += takes.sum(0)
+        self.passes += int(mm["passes"][takes[:, -1]].sum())
+
+    def result(self) -> dict:
+        m = {k: v / np.maximum(self.windows, 1)[:, None] for k, v in self.sums.items()}
+        return {"joint_modes": {"n": self.n, "seeds": self.seeds, "iters": self.iters, "min_std_px": self.min_std, "log_floor": KDE_LOG_FLOOR,
+                                "windows": [int(v) for v in self.windows], "mean_passes": float(self.passes / max(int(self.windows[-1]), 1)),
+                                "nll": _per_horizon(m["nll"], "mean", "final"), "top1": _per_horizon(m["top1"], "jade", "jfde"),
+                                "best": _per_horizon(m["best"], "jade", "jfde")}}
+
+
 def _masks(past, fut, hz, mno: int) -> SimpleNamespace:
     """The agent masks of a batch, computed once for every block, on the model's slot axis (mno >= the loader's, the padding never counted):
     valid [n, mno] = present at the last observed frame; seen [n, T_pred, mno] = in that target frame; per horizon h, flat over (window, slot),
@@ -387,7 +437,7 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     hz = parse_horizons(args.eval_horizons, t_pred)
     run = _Run(args, hz, generator, K, int(args.eval_top or default_top(K)), t_pred)
     # every block reads its flags here -- a bad one is refused before a window is touched --, the enabled ones report in this order
-    blocks = [run] + [b for b in [B(args, hz, run) for B in (_Ranked, _Select, _KdeNll, _Joint, _PlanRisk, _Occupancy, _Modes)] if b.on]
+    blocks = [run] + [b for b in [B(args, hz, run) for B in (_Ranked, _Select, _KdeNll, _Joint, _PlanRisk, _Occupancy, _Modes, _JointModes)] if b.on]
     mno = dims_from_args(args, 1, False).mno                             # the model's slot axis: max_num_obj padded up
     for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)

@@ -1,5 +1,5 @@
 """The scored-sample methods of DESIREModel: everything that looks at the K samples of an agent together with their IOC scores -- ranking,
-non-maximum suppression, joint metrics, plan risk, mode fitting, occupancy maps, KDE likelihood -- in their prediction form (predict_* /
+non-maximum suppression, joint metrics, plan risk, mode fitting per agent and per window, occupancy maps, KDE likelihood -- in their prediction form (predict_* /
 score_plans: the prior forward first) and their evaluation form (evaluate_*: samples and scores given, held against the futures).
 
 ScoredSamples is a mixin of DESIREModel (desire_amd/model.py) and uses its torch, device, _handle, _handles, _pad_windows and forward_device.  What
@@ -489,6 +489,133 @@ class ScoredSamples(object):
             best[:, i] = torch.where(has[:, None], low, torch.zeros_like(low))
         return {"nll": res["nll"].reshape(d.A, len(hz), 2).cpu().numpy(), "top1": top1.cpu().numpy(), "best": best.cpu().numpy(),
                 "prob": prob.cpu().numpy(), "count": res["count"].reshape(d.A, n).cpu().numpy(), "passes": res["passes"].reshape(d.A).cpu().numpy()}
+
+    def _scene_modes_args(self, d, modes, seeds, worlds_radius, worlds_metric, worlds_reduce, iters, min_std, horizon, weights, collision_radius,
+                          collision_penalty):
+        """(n_modes, iters, t_end, _worlds_args' tuple or None) of the scene-mode calls, refused here where they are bad (before a forward runs)."""
+        n = int(modes)
+        if not 1 <= n <= min(d.K, _lib.MODES_MAX):
+            raise ValueError("modes must be 1..min(num_samples, %d), got %d" % (_lib.MODES_MAX, n))
+        if seeds not in ("worlds", "score"):
+            raise ValueError("seeds must be 'worlds' (the mutually distinct joint samples first) or 'score' (the best-scored joint samples), got %r"
+                             % (seeds,))
+        if not 0 <= int(iters) <= _lib.MODES_MAX_ITERS:
+            raise ValueError("iters must be 0..%d, got %r" % (_lib.MODES_MAX_ITERS, iters))
+        if not (np.isfinite(float(min_std)) and float(min_std) >= 0):
+            raise ValueError("min_std must be finite and >= 0 (pixels), got %r" % (min_std,))
+        _check_weights(weights, "joint")
+        t_end = d.T_pred if horizon is None else int(horizon)
+        if not 1 <= t_end <= d.T_pred:
+            raise ValueError("horizon must be 1..pred_length (%d), got %d" % (d.T_pred, t_end))
+        if collision_radius is not None:
+            _check_radius(collision_radius)
+        if seeds == "score":
+            if worlds_radius is not None or worlds_metric != "final" or worlds_reduce != "mean" or collision_penalty != 0.0:
+                raise ValueError("worlds_radius, worlds_metric, worlds_reduce and collision_penalty belong to seeds='worlds'")
+            return n, int(iters), t_end, None
+        if worlds_radius is None:
+            raise ValueError("seeds='worlds' needs worlds_radius (pixels)")
+        return n, int(iters), t_end, self._worlds_args("worlds", worlds_radius, worlds_metric, worlds_reduce, horizon, collision_penalty, d.T_pred)
+
+    def _fit_scene_modes(self, h, Y, score, fut, part8, n, wargs, iters, t_end, ux, uy, f, var_floor, weighted, collision_radius, hz=None,
+                         log_floor=_lib.KDE_LOG_FLOOR):
+        """The joint scores and their order (desire_joint_metrics), with wargs the non-maximum suppression of the worlds (desire_select_worlds), then
+        one desire_fit_scene_modes call, on device tensors; f turns a length in pixels into the call's unit.  Device tensors back, per window."""
+        torch = self.torch
+        d = h.dims
+        dev, i32 = self.device, torch.int32
+        N, stream = d.n_scenes, torch.cuda.current_stream().cuda_stream
+        nh = 1 if fut is None else len(hz)
+        cnt = torch.empty((N, d.K + 1, nh, 2), device=dev, dtype=i32)
+        wscore, order = torch.empty((N, d.K), device=dev), torch.empty((N, d.K), device=dev, dtype=i32)
+        h.joint_metrics(Y.data_ptr(), _ptr(fut), 0 if fut is not None else part8.data_ptr(), score.data_ptr(), [d.T_pred] if fut is None else hz, n,
+                        float(collision_radius or 0.0) * f, ux, uy, cnt.data_ptr(), order.data_ptr(), 0, 0, wscore.data_ptr(), 0, stream)
+        if wargs is not None:
+            if wargs[4] != 0.0:                                             # the penalty per colliding agent, as _select_worlds forms it
+                wscore = (wscore - cnt[:, :d.K, -1, 0].to(torch.float32) * wargs[4]).contiguous()
+            order = self._select_worlds(h, Y, part8, wscore, None, wargs[:4] + (0.0,), wargs[3] * f, ux, uy)[0]
+        res = {"mean": torch.empty((N, n, d.mno, d.T_pred, 2), device=dev), "cov": torch.empty((N, n, d.mno, d.T_pred, 3), device=dev),
+               "prob": torch.empty((N, n), device=dev), "label": torch.empty((N, d.K), device=dev, dtype=i32),
+               "count": torch.empty((N, n), device=dev, dtype=i32), "passes": torch.empty((N,), device=dev, dtype=i32)}
+        if fut is not None:
+            res["nll"] = torch.empty((N, nh, 2), device=dev)
+        h.fit_scene_modes(Y.data_ptr(), part8.data_ptr(), order.data_ptr(), wscore.data_ptr() if weighted else 0, n, t_end, iters, ux, uy, var_floor,
+                          res["count"].data_ptr(), res["prob"].data_ptr(), res["label"].data_ptr(), res["mean"].data_ptr(), res["cov"].data_ptr(),
+                          res["passes"].data_ptr(), _ptr(fut), hz, float(log_floor), _ptr(res.get("nll")), 0, stream)
+        return res
+
+    def predict_scene_modes(self, past, modes: int = 6, seeds: str = "worlds", worlds_radius=None, worlds_metric: str = "final",
+                            worlds_reduce: str = "mean", iters: int = 8, min_std: float = 1.0, horizon=None, weights: str = "score",
+                            collision_radius=None, collision_penalty: float = 0.0, **predict_kwargs) -> dict:
+        """A small mixture per WINDOW, the form joint consumers take: `modes` scene modes, one probability per mode and, for every agent of that
+        mode, a mean trajectory and a covariance per frame, consistent across the agents -- a mode is a set of joint samples (sample k of every
+        agent together), never agent A's left turn next to agent B's incompatible one.  The forward as predict_device runs it (predict_kwargs:
+        eps, seed, grid_of_scene, device_rng, window_base), the joint scores and their order (desire_joint_metrics), with seeds "worlds" the
+        score-ordered non-maximum suppression of the joint samples (desire_select_worlds at worlds_radius pixels by worlds_metric / worlds_reduce,
+        as predict_device's select="worlds"; collision_penalty P ranks by joint score - P * agents that collide within collision_radius pixels),
+        then one desire_fit_scene_modes call: a weighted Lloyd iteration on whole joint samples of at most `iters` passes from the first `modes`
+        of that order, the assignment looking at the first `horizon` frames (None: all) of the agents present at the last observed frame.
+        Returns device tensors: "mean" [n, modes, mno, T_pred, 2] IN PIXELS, "cov" [n, modes, mno, T_pred, 3] = (Cxx, Cyy, Cxy) in px^2 with
+        min_std^2 added to the diagonal (zeros for an absent agent), "prob" [n, modes] = the weight of a mode's joint samples (weights "score":
+        softmax of the joint scores; "uniform": 1 / K), "label" [n, K] int32 = the mode of every joint sample, "count" [n, modes] int32, "passes"
+        [n] int32 and "present" [n, mno] bool.  All K samples and scores stay available as self.final_output / self.final_states."""
+        past, h, present, pres8 = self._prediction(past, u8=True)
+        d = h.dims
+        n, iters, t_end, wargs = self._scene_modes_args(d, modes, seeds, worlds_radius, worlds_metric, worlds_reduce, iters, min_std, horizon, weights,
+                                                        collision_radius, collision_penalty)       # refused before the forward runs
+        Y, score = self.forward_device(past, None, **predict_kwargs)
+        res = self._fit_scene_modes(h, Y, score, None, pres8, n, wargs, iters, t_end, 1.0 / d.sx, 1.0 / d.sy, 1.0, float(min_std) ** 2,
+                                    weights == "score", collision_radius)
+        res["mean"] /= self._scale(d)
+        res["present"] = present
+        return res
+
+    def evaluate_scene_modes(self, Y, score, fut_windows, modes: int = 6, seeds: str = "worlds", worlds_radius=None, worlds_metric: str = "final",
+                             worlds_reduce: str = "mean", iters: int = 8, min_std: float = 1.0, horizon=None, weights: str = "score",
+                             collision_radius=None, collision_penalty: float = 0.0, horizons=None, units="px",
+                             log_floor: float = _lib.KDE_LOG_FLOOR) -> dict:
+        """The mixture predict_scene_modes hands out, held against the ground truth (an agent takes part when it has a counted frame).  Returns
+        numpy arrays per window: "nll" [n, n_h, 2] = per horizon the (mean over the frames, final-frame) negative JOINT log-likelihood of the
+        ground truth under the window's mixture -- log sum_modes p_m prod_agents N(g | mean, cov) -- PER AGENT counted in the frame (density per
+        unit^2, the per-agent log clipped below at log_floor): comparable with evaluate_modes' "nll", and below the agents' mean of it exactly
+        when the mixture captures their interaction; "top1" [n, n_h, 2] = (JADE, JFDE) of the most probable mode's means (the mean over the
+        agents taking part before the horizon of each agent's ADE / FDE, as evaluate_joint's), "best" [n, n_h, 2] = the minimum over the modes
+        with mass of their JADE, and of their JFDE; zeros where nobody takes part before the horizon; and "prob" [n, modes], "count" [n, modes],
+        "passes" [n].  units, horizons and `fut_windows` as in evaluate_ranked; min_std, worlds_radius and collision_radius in pixels."""
+        torch = self.torch
+        h, d, hz, (ux, uy, f), fut, _ = self._evaluation(Y, fut_windows, horizons, units)
+        n, iters, t_end, wargs = self._scene_modes_args(d, modes, seeds, worlds_radius, worlds_metric, worlds_reduce, iters, min_std, horizon, weights,
+                                                        collision_radius, collision_penalty)
+        counted = (fut[..., 0] != 0).permute(0, 2, 1)                          # [n, mno, T_pred]
+        part8 = counted.any(2).to(torch.uint8).contiguous()
+        res = self._fit_scene_modes(h, Y, score, fut, part8, n, wargs, iters, t_end, ux, uy, f, (float(min_std) * f) ** 2, weights == "score",
+                                    collision_radius, hz, log_floor)
+        # the errors of the means: torch on the small [n, modes, mno, T, 2] tensor
+        N, dev = d.n_scenes, self.device
+        g = (fut[..., 1:] * self._scale(d)).permute(0, 2, 1, 3)[:, None]       # [n, 1, mno, T, 2]
+        e = (((res["mean"] - g) * torch.tensor([ux, uy], device=dev, dtype=torch.float32)) ** 2).sum(-1).sqrt()      # [n, modes, mno, T]
+        e = torch.where(counted[:, None], e, torch.zeros_like(e))
+        top = res["prob"].argmax(1)
+        alive = res["prob"] > 0
+        inf = torch.full((), float("inf"), device=dev)
+        top1, best = torch.zeros((N, len(hz), 2), device=dev), torch.zeros((N, len(hz), 2), device=dev)
+        ar = torch.arange(N, device=dev)
+        for i, x in enumerate(hz):
+            c = counted[:, :, :x]
+            np_ = c.sum(2)                                                      # [n, mno] counted frames before the horizon
+            takes = np_ > 0
+            last = (c * torch.arange(1, x + 1, device=dev)).argmax(2)           # the last counted frame < x
+            ade = e[..., :x].sum(3) / np_.clamp(min=1)[:, None]                 # [n, modes, mno]
+            fde = e.gather(3, last[:, None, :, None].expand(N, n, d.mno, 1))[..., 0]
+            agents = takes.sum(1).clamp(min=1)[:, None]
+            both = torch.stack([torch.where(takes[:, None], ade, torch.zeros_like(ade)).sum(2) / agents,
+                                torch.where(takes[:, None], fde, torch.zeros_like(fde)).sum(2) / agents], -1)      # [n, modes, 2] = (JADE, JFDE)
+            has = takes.any(1) & alive.any(1)
+            top1[:, i] = torch.where(has[:, None], both[ar, top], torch.zeros_like(top1[:, i]))
+            low = torch.where(alive[:, :, None], both, inf).min(1).values
+            best[:, i] = torch.where(has[:, None], low, torch.zeros_like(low))
+        return {"nll": res["nll"].cpu().numpy(), "top1": top1.cpu().numpy(), "best": best.cpu().numpy(), "prob": res["prob"].cpu().numpy(),
+                "count": res["count"].cpu().numpy(), "passes": res["passes"].cpu().numpy()}
 
     def _occupancy_args(self, d, grid, horizons, mode, weights, mask, mask_of_window, n):
         """(Oh, Ow, horizons, mode id, mask tensor or None, mask_of_window tensor or None) of the occupancy calls, refused here where they are bad."""

@@ -599,6 +599,70 @@ int desire_fit_modes(desire_handle* h, const float* dev_Yhat, const int32_t* dev
                      int32_t* dev_label, int32_t* dev_count, float* dev_prob, float* dev_mean, float* dev_cov, int32_t* dev_passes,
                      float* dev_out, float* dev_frame, void* stream);
 
+/* ---- n scene modes with covariances per window: what joint consumers take -- n scene modes, one probability per mode for the window and, for
+ * every agent of that mode, a mean trajectory and a 2 x 2 covariance per frame, consistent across the agents -- fitted to the window's K weighted
+ * WORLDS (world k = sample k of every slot together) by desire_fit_modes' weighted Lloyd iteration with `sample of an agent` read as `world of a
+ * window`, and the joint likelihood of the ground truth under exactly that mixture: log sum_modes p_m prod_agents N(g | mean, cov).  Layouts are
+ * desire_select_worlds': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot.  All arithmetic is fp32, every operation rounded
+ * once (no fused multiply-add), every sum runs in one fixed sequence (over k, t or the slots in increasing index from 0.f); no float atomics.
+ *   1 taking part dev_present [A] uint8 (may be NULL: every slot takes part).  Slot s takes part iff dev_present[a] != 0.  The rows of a slot that
+ *                 does not take part are never read (under DESIRE_FLAG_COMPACT_* they may hold anything).
+ *   2 weights     W_k = desire_select_worlds' step 6 on dev_wscore [n_scenes, K]: m = max_k s_k, e_k = expf(s_k - m), W_k = e_k / sum_k e_k in
+ *                 increasing k from 0.f; 1.f / K when dev_wscore is NULL or any score of the window is not finite.
+ *   3 seeds       c_i = dev_worder[scene, i] for i < n_modes (desire_joint_metrics' dev_jorder, or desire_select_worlds' dev_worder, which puts
+ *                 mutually distinct worlds first); mean_i[s, t] = Y[r_{c_i}, t, :] for every taking-part slot s and t < T_pred.  Only these
+ *                 n_modes entries of the row are read, through desire_fit_modes' check: the window is BAD when one of them lies outside 0 .. K-1 or
+ *                 repeats an earlier one.  A BAD window gets labels -1, counts 0, prob, mean and cov 0.f, passes 0 and log_floor at every counted
+ *                 frame.  No case reads outside dev_Yhat.
+ *   4 distance    d_s(k, i) = desire_fit_modes' step 3 on slot s: the sum over t < t_end, from 0.f in increasing t, of (a * a + b * b), a =
+ *                 (Y[r_k, t, 0] - mean_i[s, t, 0]) * unit_x, b = (Y[r_k, t, 1] - mean_i[s, t, 1]) * unit_y.  D(k, i) = the sum of d_s(k, i) over
+ *                 the taking-part slots, in increasing slot from 0.f.
+ *   5 assign      desire_fit_modes' step 4 on D(k, i): walking i = 0 .. n_modes-1, strict <, ties to the lower i, a NaN is never chosen; every
+ *                 D(k, i) a NaN: label_k = -1, and world k is left out of everything below.
+ *   6 update      W_i = the sum of W_k over the worlds with label_k = i, in increasing k from 0.f.  When W_i > 0: mean_i[s, t, c] = (the sum of
+ *                 W_k * Y[r_k, t, c] over the same worlds in the same order) / W_i for every taking-part slot s and every t < T_pred.  A mode
+ *                 without members, or with W_i == 0, keeps the means it has.
+ *   7 iteration   desire_fit_modes' step 6: labels = assign(seed means); for p = 1 .. iters: update, assign, stop when no label differs from the
+ *                 pass before.  The stop is exact; the reported means are update(final labels) in every case.  dev_passes [n_scenes] int32 (may
+ *                 be NULL) = the p reached.  There is no special case: a window with nobody taking part runs the same sequence (every D is 0.f,
+ *                 every world gets label 0, the fit stops at p = 1); a world with a NaN among the frames t < t_end of a taking-part row gets label
+ *                 -1, and as a seed it is a mode nobody joins.
+ *   8 outputs     dev_label [n_scenes, K] int32 (may be NULL); dev_count, dev_prob [n_scenes, n_modes] (required) = the members and W_i of mode
+ *                 i, NOT renormalised; dev_mean [n_scenes, n_modes, mno, T_pred, 2] (may be NULL), in Y's own coordinates (a mode that never had
+ *                 mass reports its seed's rows); dev_cov [n_scenes, n_modes, mno, T_pred, 3] (may be NULL) = (Cxx, Cyy, Cxy) by desire_fit_modes'
+ *                 formula per slot over the mode's member worlds in increasing k, with W_k and W_i: three zeros (no floor) for a mode with
+ *                 W_i == 0.  The slots that do not take part get zeros in dev_mean and dev_cov.
+ *   9 likelihood  only with dev_fut [n_scenes, T_pred, mno, 3]: dev_out [n_scenes, n_h, 2] (then required) and dev_frame [n_scenes, T_pred] (may
+ *                 be NULL).  c(a, t) and g are desire_kde_nll's.  C_t = the taking-part slots counted at t, c_t their number; frame t counts iff
+ *                 c_t >= 1.  Mode i is USABLE at t when prob_i > 0 and every slot of C_t has det_s > DESIRE_KDE_MIN_DET_RATIO * Cxx * Cyy, det_s =
+ *                 Cxx * Cyy - Cxy * Cxy.  L_i starts as logf(prob_i); for every slot of C_t in increasing slot, L_i = ((L_i + quad_s / det_s) -
+ *                 logf(2 pi)) - 0.5f * logf(det_s), left to right, with d = ((mean_i[s, t, 0] - g_x) * unit_x, (mean_i[s, t, 1] - g_y) * unit_y) and
+ *                 quad_s = -0.5f * ((Cyy * (d_x * d_x) - (2.f * Cxy) * (d_x * d_y)) + Cxx * (d_y * d_y)): desire_fit_modes' expressions.  M = the
+ *                 maximum of the L_i (fmaxf, from -inf); l = M + logf(sum of expf(L_i - M) over the usable modes in increasing i, from 0.f).  The
+ *                 frame's value is v = l / (float)c_t -- nats per agent, comparable with the per-agent calls -- where v > log_floor, else
+ *                 log_floor (a NaN among them, and a frame without a usable mode); 0.f for a frame that does not count.  The per-horizon mean and
+ *                 last-frame reduction and the zeros when nothing is counted are desire_kde_nll's steps 7 - 8 with `agent` read as `window`.
+ * ANCHOR: at mno = 1 with the slot present, every output has the bits of desire_fit_modes given the same order row, dev_wscore holding that
+ * agent's scores and the same dev_fut (0.f + x is exact, x / 1.f is exact).
+ * A window's result depends on that window's taking-part rows, order row, scores and targets only -- not on the grid, the batch, the chunks the
+ * slots are cut into, DESIRE_FLAG_COMPACT_* or the last desire_encode.  One launch, stream-ordered, capturable, no host wait, no allocation, no
+ * scratch; bitwise reproducible.  host_horizons, n_h and log_floor are read (and checked) only with dev_fut.
+ * LDS plan: one workgroup owns one window and walks its taking-part slots in chunks, once per pass: per chunk all T_pred frames of the K worlds'
+ * rows next to the n_modes means, the chunk's distances and the likelihood's terms; what crosses a chunk border is the sum of d_s and the chain
+ * of L_i, both in increasing slot: the bits of an unchunked walk.  One slot must fit next to the per-window words: 8 * (K + n_modes) * (T_pred | 1)
+ * + 20 * n_modes * T_pred + 12 * K * n_modes + 12 * K + 20 * n_modes + 4 * n_modes * ceil(K / 32) + 12 * T_pred + 4 * mno <= 61440 bytes -- e.g.
+ * (mno 256, K 20, T_pred 40, n 6): 4 slots per chunk; (K 70, T_pred 6, n 4), (K 3, T_pred 200, n 3).
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing is launched or written: n_modes outside 1 .. min(K, DESIRE_MODES_MAX); t_end outside
+ * 1 .. T_pred; iters outside 0 .. DESIRE_MODES_MAX_ITERS; a unit that is not finite and > 0; a var_floor that is negative or not finite; a NULL
+ * dev_Yhat / dev_worder / dev_count / dev_prob; dev_out or dev_frame without dev_fut; dev_fut without dev_out or host_horizons; with dev_fut bad
+ * horizons or a non-finite log_floor; a NULL handle; a ref_compat handle; a (K, mno, T_pred, n_modes) beyond the LDS plan. */
+int desire_fit_scene_modes(desire_handle* h, const float* dev_Yhat, const uint8_t* dev_present, const int32_t* dev_worder,
+                           const float* dev_wscore, const float* dev_fut,
+                           int32_t n_modes, int32_t t_end, int32_t iters, float unit_x, float unit_y, float var_floor,
+                           const int32_t* host_horizons, int32_t n_h, float log_floor,
+                           int32_t* dev_label, int32_t* dev_count, float* dev_prob, float* dev_mean, float* dev_cov,
+                           int32_t* dev_passes, float* dev_out, float* dev_frame, void* stream);
+
 /* ---- predicted occupancy maps: how likely is it that somebody stands in this cell of the frame at horizon h, or at any time before it.  The K
  * samples of every agent, weighted, are rasterised onto an Oh x Ow grid over the normalised frame [0, 1) x [0, 1).  Layouts are the evaluation
  * calls': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot, dev_fut [n_scenes, T_pred, mno, 3], host_horizons as in
