@@ -28,7 +28,7 @@ EXPORTS = [
     "desire_rank_samples", "desire_ranked_errors", "desire_kde_nll", "desire_select_diverse", "desire_joint_metrics",
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
     "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy", "desire_plan_risk", "desire_fit_modes",
-    "desire_select_worlds", "desire_fit_scene_modes",
+    "desire_select_worlds", "desire_fit_scene_modes", "desire_plan_risk_cond",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
@@ -113,6 +113,8 @@ def load() -> C.CDLL:
     lib.desire_select_worlds.argtypes = [vp, f32p, vp, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp, f32p, vp, vp]
     lib.desire_occupancy.argtypes = [vp, f32p, f32p, vp, f32p, C.POINTER(C.c_int32), i32, i32, i32, i32, vp, vp, f32p, f32p, f32p, f32p, f32p, vp]
     lib.desire_plan_risk.argtypes = [vp, f32p, f32p, vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, vp, f32p, f32p, f32p, vp]
+    lib.desire_plan_risk_cond.argtypes = [vp, f32p, f32p, vp, f32p, f32p, vp, i32, C.POINTER(C.c_int32), i32, C.c_float, C.c_float, C.c_float, C.c_float, i32,
+                                          vp, f32p, f32p, f32p, f32p, f32p, f32p, f32p, vp, vp]
     lib.desire_fit_modes.argtypes = [vp, f32p, vp, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32), i32, C.c_float,
                                      vp, vp, f32p, f32p, f32p, vp, f32p, f32p, vp]
     lib.desire_fit_scene_modes.argtypes = [vp, f32p, vp, vp, f32p, f32p, i32, i32, i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int32), i32,
@@ -376,6 +378,24 @@ class Handle:
                                        ego_ptr or None, int(M), hzp, hz.size, C.c_float(radius),
                                        C.c_float(unit_x), C.c_float(unit_y), first_ptr or None, clear_ptr or None, risk_ptr or None,
                                        blame_ptr or None, stream or None))
+
+    def plan_risk_cond(self, yhat_ptr: int, fut_ptr: int, present_ptr: int, score_ptr: int, plans_ptr: int, ego_ptr: int, M: int, horizons,
+                       radius: float, unit_x: float, unit_y: float, sigma: float, t_cond: int, risk_ptr: int, cw_ptr: int, first_ptr: int = 0,
+                       clear_ptr: int = 0, blame_ptr: int = 0, dist_ptr: int = 0, ess_ptr: int = 0, support_ptr: int = 0, cond_ptr: int = 0,
+                       stream: int = 0) -> None:
+        """plan_risk given that the ego drives the plan: the K joint futures of a window are reweighted per plan by how well their own sample of
+        the slot the plan replaces (ego) agrees with it -- a Gaussian kernel of bandwidth `sigma` (the unit of the radius: the RMS deviation per
+        frame) on the mean squared distance over the counted frames t < t_cond -- times the prior weight.  cw [n, M, K] (required) = those
+        weights, the prior's for a plan without an ego slot or a compared frame; risk, first, clear and blame as in plan_risk with cw in place of
+        the prior; optionally dist [n, M, K] = the mean squared distances, ess [n, M] = the effective number of worlds 1 / sum cw^2, support
+        [n, M] = the kernel density of the plan under the predicted ego in (0, 1], cond [n, M] int32 = the compared frames of a conditioned
+        plan, 0 otherwise."""
+        hz, hzp = _horizons(horizons)
+        _chk(self.lib.desire_plan_risk_cond(self._h, yhat_ptr or None, fut_ptr or None, present_ptr or None, score_ptr or None, plans_ptr or None,
+                                            ego_ptr or None, int(M), hzp, hz.size, C.c_float(radius), C.c_float(unit_x), C.c_float(unit_y),
+                                            C.c_float(sigma), int(t_cond), first_ptr or None, clear_ptr or None, risk_ptr or None,
+                                            blame_ptr or None, cw_ptr or None, dist_ptr or None, ess_ptr or None, support_ptr or None,
+                                            cond_ptr or None, stream or None))
 
     def fit_modes(self, yhat_ptr: int, order_ptr: int, score_ptr: int, n_modes: int, t_end: int, iters: int, unit_x: float, unit_y: float,
                   var_floor: float, count_ptr: int, prob_ptr: int, label_ptr: int = 0, mean_ptr: int = 0, cov_ptr: int = 0, passes_ptr: int = 0,

@@ -422,6 +422,49 @@ extern "C" int desire_plan_risk(desire_handle* h, const float* dev_Yhat, const f
     return DESIRE_OK;
 }
 
+// ---- the same against the K joint futures reweighted by their agreement with each plan (kernels_plan_cond.hip, then kernels_plan.hip's walk
+// reading dev_cw): the contract is stated in include/desire_hip.h.  The window's weights live in "joint_js" as in desire_plan_risk, its logits
+// p_k in the first n_scenes * K floats of "joint_je"; nothing grows with M but the caller's own dev_cw. ----
+extern "C" int desire_plan_risk_cond(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present,
+                                     const float* dev_score, const float* dev_plans, const int32_t* dev_ego, int32_t M,
+                                     const int32_t* host_horizons, int32_t n_h, float radius, float unit_x, float unit_y, float sigma, int32_t t_cond,
+                                     int32_t* dev_first, float* dev_clear, float* dev_risk, float* dev_blame, float* dev_cw, float* dev_dist,
+                                     float* dev_ess, float* dev_support, int32_t* dev_cond, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_plans) return fail(DESIRE_ERR_ARG, "dev_plans is NULL");
+    if (!dev_risk) return fail(DESIRE_ERR_ARG, "dev_risk is NULL");
+    if (!dev_cw) return fail(DESIRE_ERR_ARG, "dev_cw is NULL (the [n_scenes, M, K] weight table the risk is summed from)");
+    if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
+    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    if (M < 1) return fail(DESIRE_ERR_ARG, "M must be at least 1 (the candidate plans per window)");
+    if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(DESIRE_ERR_ARG, "sigma must be finite and > 0");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read joint futures from");
+    if (t_cond < 1 || t_cond > d.T_pred) return fail(DESIRE_ERR_ARG, "t_cond must be 1..T_pred");
+    RankHz hz{};
+    if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
+    if (int rc = check_radius(radius)) return rc;
+    if (int rc = check_units(unit_x, unit_y)) return rc;
+    int pc = 0, tc = 0, cpc = 0, ctc = 0, rows = 0;
+    plan_geometry(d.mno, d.T_pred, M, &pc, &tc);
+    plan_cond_geometry(d.K, t_cond, M, &cpc, &ctc, &rows);
+    if (tc < 1 || ctc < 1) return fail(DESIRE_ERR_ARG, "one frame of the window does not fit the plan kernels' LDS");      // (not reachable)
+    const int least = pc < cpc ? pc : cpc;
+    if ((uint64_t)d.n_scenes * (uint64_t)((M + least - 1) / least) >= (1ull << 31)) return fail(DESIRE_ERR_ARG, "n_scenes * plan chunks must be below 2^31");
+    const volatile float two_s = 2.f * sigma, two_s2 = two_s * sigma;  // fp32, every operation rounded once (2 * sigma is exact)
+    const float inv = 1.f / two_s2;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    launch_plan_prior(dev_fut, dev_present, dev_score, W(h, "joint_js"), W(h, "joint_je"), d.n_scenes, d.mno, d.K, d.T_pred, s);
+    launch_plan_cond_weights(dev_Yhat, dev_fut, dev_present, dev_plans, dev_ego, W(h, "joint_js"), W(h, "joint_je"), dev_cw, dev_dist, dev_ess,
+                             dev_support, dev_cond, d.n_scenes, d.mno, d.K, d.T_pred, M, t_cond, unit_x, unit_y, inv, s);
+    launch_plan_risk_per_plan(dev_Yhat, dev_fut, dev_present, dev_plans, dev_ego, dev_cw, dev_first, dev_clear, dev_risk, dev_blame, d.n_scenes,
+                              d.mno, d.K, d.T_pred, M, hz, d.sx, d.sy, unit_x, unit_y, radius, s);
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 // ---- n modes with covariances fitted to the K samples (kernels_modes.hip): the contract is stated in include/desire_hip.h.  As in
 // desire_select_diverse the checks that need no handle come first. ----
 extern "C" int desire_fit_modes(desire_handle* h, const float* dev_Yhat, const int32_t* dev_order, const float* dev_score, const float* dev_fut,

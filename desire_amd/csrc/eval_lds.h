@@ -1,8 +1,8 @@
 // eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
-// _recon / _occ / _plan / _modes / _worlds / _scene_modes.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// _recon / _occ / _plan / _plan_cond / _modes / _worlds / _scene_modes.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
 // that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
-// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp, occ_lds_driver.cpp and scene_modes_lds_driver.cpp compile it with g++ (tests/test_eval_lds.py, test_occ_lds.py,
-// test_scene_modes_cpu.py).
+// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp, occ_lds_driver.cpp, scene_modes_lds_driver.cpp and plan_cond_lds_driver.cpp compile it with g++
+// (tests/test_eval_lds.py, test_occ_lds.py, test_scene_modes_cpu.py, test_plan_cond_cpu.py).
 #pragma once
 #include <stddef.h>
 
@@ -156,6 +156,36 @@ inline void plan_geometry(int mno, int T, int M, int* PC, int* TC) {
     const size_t fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;            // (PlanLds(.., 0) already holds the one pair per plan of the odd stride)
     *PC = pc;
     *TC = (int)((size_t)T < fit ? (size_t)T : fit);
+}
+
+// ---- k_plan_cond_weights: PL float2 [PC][eval_odd(TC)] (the compared frames of a pass of a chunk of PC candidate plans, PlanLds' row stride),
+// then, when rows_in_lds, E float2 [K][eval_odd(TC)] (the K rows of the ONE ego slot the chunk's plans name), then two [PC] ints (the ego slot of
+// a plan or -1, its compared frames so far).  Nothing else grows with K: the K distances and weight numerators of a plan are parked in the
+// call's own output dev_cw, so every K is served.
+struct PlanCondLds {
+    enum { MAX_PC = 64, ITEMS = 4 * EVAL_THREADS, PLAN_WORDS = 2 };       // a lane owns ITEMS / EVAL_THREADS (plan, k) items at most where M allows
+    int K, PC, TC, rows_in_lds;
+    EVAL_HD constexpr PlanCondLds(int K_, int PC_, int TC_, int rows_) : K(K_), PC(PC_), TC(TC_), rows_in_lds(rows_ ? 1 : 0) {}
+    EVAL_HD constexpr int stride() const { return eval_odd(TC); }
+    EVAL_HD constexpr size_t plans() const { return (size_t)PC * stride(); }                // float2 in front of the ego rows
+    EVAL_HD constexpr size_t rows() const { return rows_in_lds ? (size_t)K * stride() : 0; }     // float2 in front of the words
+    EVAL_HD constexpr int ego() const { return 0; }                                         // word offsets behind the pairs
+    EVAL_HD constexpr int count() const { return PC; }
+    EVAL_HD constexpr size_t bytes() const { return (plans() + rows()) * EVAL_PAIR_BYTES + (size_t)4 * PLAN_WORDS * PC; }
+};
+// The plan chunk: as many plans as ITEMS (plan, k) items hold, MAX_PC at most, spread evenly over the chunks of the M plans.  The frames are the
+// t_cond compared ones.  When the chunk's plans and the K ego rows fit, both are staged whole (rows = 1).  Else the rows stay in global memory
+// (rows = 0) and the plans are staged whole, or -- beyond ~7600 frames of one plan -- in passes of TC frames: 16 PC bytes are fixed and a frame
+// of the chunk is 8 PC <= 512 bytes, so every (K, t_cond, M) is served.
+inline void plan_cond_geometry(int K, int t_cond, int M, int* PC, int* TC, int* rows) {
+    const int cap = eval_min(eval_min(M, (int)PlanCondLds::MAX_PC), eval_max(1, (int)PlanCondLds::ITEMS / K));
+    const int pc = eval_chunks(M, eval_chunks(M, cap));
+    *PC = pc;
+    if (PlanCondLds(K, pc, t_cond, 1).bytes() <= (size_t)EVAL_LDS_BYTES) { *TC = t_cond; *rows = 1; return; }
+    const size_t fixed = PlanCondLds(K, pc, 0, 0).bytes(), per = (size_t)EVAL_PAIR_BYTES * pc;
+    const size_t fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;            // (PlanCondLds(.., 0, 0) already holds the one pair per plan of the odd stride)
+    *TC = (int)((size_t)t_cond < fit ? (size_t)t_cond : fit);
+    *rows = 0;
 }
 
 // ---- k_fit_modes: float2 rows Yl [SC][K][Tp] (all T frames of the K samples of SC agents, Tp = T | 1), then the running means ml [SC][n][Tp] with

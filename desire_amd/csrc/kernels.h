@@ -306,6 +306,18 @@ void launch_fit_scene_modes(const float* Y, const uint8_t* present, const int32_
 void launch_plan_risk(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* plans, const int32_t* ego,
                       float* w, int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
                       const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
+// desire_plan_risk_cond's three steps.  launch_plan_prior: launch_plan_risk's weight kernel alone, which also keeps prior [n_scenes, K] = the
+// logits p_k (the joint scores where a window's are all finite, else 0.f; the handle's "joint_je").  launch_plan_cond_weights
+// (kernels_plan_cond.hip): cw [n_scenes, M, K] from w and prior; dist, ess, support and cond may be nullptr; inv = 1 / (2 sigma^2).
+// launch_plan_risk_per_plan: launch_plan_risk's walk reading plan m's weights from cw[(scene * M + m) * K + k]
+void launch_plan_prior(const float* fut, const uint8_t* present, const float* score, float* w, float* prior, int n_scenes, int mno, int K, int T,
+                       hipStream_t s);
+void launch_plan_cond_weights(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* w,
+                              const float* prior, float* cw, float* dist, float* ess, float* support, int32_t* cond, int n_scenes, int mno, int K,
+                              int T, int M, int t_cond, float ux, float uy, float inv, hipStream_t s);
+void launch_plan_risk_per_plan(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* cw,
+                               int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
+                               const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
 
 // ---- predicted occupancy maps of the K weighted samples (kernels_occ.hip) ----
 // step 1 of launch_kde_nll alone: w [R] (the score layout) and st [A, 2], the handle's "kde_w" / "kde_st"; score may be nullptr (kernels_kde.hip)

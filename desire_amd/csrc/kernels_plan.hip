@@ -4,12 +4,14 @@
 //
 //   k_plan_weights  one workgroup per window: which slots take part, the K joint scores (desire_joint_metrics' step 7: one lane per k walks the
 //                   slots in increasing order), their weight statistics (eval_weight_stats, one lane) and the K weights, into the handle's scratch.
+//                   For desire_plan_risk_cond (launch_plan_prior) it also keeps the K logits p_k that kernels_plan_cond.hip conditions.
 //   k_plan_risk     one workgroup = (window, chunk of PC plans).  It walks k = 0 .. K (K = the ground truth) and stages each unit's positions as
 //                   k_joint_unit does; a lane owns ONE (plan, slot) item for the whole call and walks the frames in increasing t, keeping its
 //                   first contact and a running minimum of q in registers.  Over the slots of a plan both are reduced by order-free minima
 //                   (a shuffle over 32 lanes or fewer, then an LDS atomic: integers, and the bits of non-negative floats as unsigned integers).
 //                   The lane of item (plan, slot) adds W_k into its blame registers, one fixed lane per (plan, horizon) adds W_k into its risk
-//                   register: the k order is the loop's, and both are written once at the end.
+//                   register: the k order is the loop's, and both are written once at the end.  Its second instantiation (PER_PLAN_W,
+//                   launch_plan_risk_per_plan) reads the weight of (plan, k) from desire_plan_risk_cond's table instead of the window's W_k.
 //
 // The streaming loop over Y, the horizon list and the weight statistics are eval_tile.h's; the LDS plan (PlanLds) and its geometry are eval_lds.h's.
 //
@@ -46,8 +48,11 @@ __device__ __forceinline__ unsigned plan_group_min(unsigned v, int width) {
     return v;
 }
 
+// KEEP_PRIOR: desire_plan_risk_cond's launch also keeps prior [n_scenes, K] = the logits p_k
+template <bool KEEP_PRIOR>
 __global__ __launch_bounds__(EVAL_THREADS) void k_plan_weights(const float* __restrict__ fut, const uint8_t* __restrict__ present,
-                                                             const float* __restrict__ score, float* w, int mno, int K, int T) {
+                                                             const float* __restrict__ score, float* w, float* __restrict__ prior, int mno,
+                                                             int K, int T) {
     __shared__ int part[EVAL_THREADS];                                  // mno <= 256: the slot takes part before T_pred
     __shared__ float stL[2];
     __shared__ int uniL;
@@ -78,9 +83,15 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_plan_weights(const float* __re
     __syncthreads();
     const bool uni = uniL != 0;
     const float mx = stL[0], sum = stL[1];
-    for (int k = tid; k < K; k += EVAL_THREADS) ws[k] = uni ? 1.f / (float)K : expf(ws[k] - mx) / sum;
+    for (int k = tid; k < K; k += EVAL_THREADS) {
+        if (KEEP_PRIOR) prior[(size_t)scene * K + k] = uni ? 0.f : ws[k];  // p_k: the joint score where every one of the window is finite
+        ws[k] = uni ? 1.f / (float)K : expf(ws[k] - mx) / sum;
+    }
 }
 
+// PER_PLAN_W: w is desire_plan_risk_cond's table [n_scenes, M, K] -- the blame lane reads its plan's row, the risk lane its own -- instead of the
+// window's K weights
+template <bool PER_PLAN_W>
 __global__ __launch_bounds__(EVAL_THREADS) void k_plan_risk(const float* __restrict__ Y, const float* __restrict__ fut,
                                                           const uint8_t* __restrict__ present, const float* __restrict__ plans,
                                                           const int32_t* __restrict__ ego, const float* __restrict__ w,
@@ -189,7 +200,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_plan_risk(const float* __restr
             const int v = (int)plan_group_min((unsigned)fi, width);     // 0 .. T: ordered alike as unsigned
             if (lead && v < T) atomicMin(&firstL[pp], v);
         }
-        const float wk = gt ? 0.f : w[(size_t)scene * K + k];
+        const float wk = gt ? 0.f : w[PER_PLAN_W ? (plan0 + pp) * K + k : (size_t)scene * K + k];
         if (!gt) {
 #pragma unroll
             for (int h = 0; h < PlanLds::HZ; ++h)
@@ -198,7 +209,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_plan_risk(const float* __restr
         __syncthreads();
         if (rlane) {
             const int f = firstL[rp];
-            if (!gt && f < hzs[rh]) rk += wk;
+            if (!gt && f < hzs[rh]) rk += PER_PLAN_W ? w[(plan0 + rp) * K + k] : wk;
             const size_t row = (plan0 + rp) * (K + 1) + k;
             if (first_out && rh == 0) first_out[row] = f;
             if (clear_out) clear_out[row * n_h + rh] = __uint_as_float(clrL[rp * PlanLds::HZ + rh]);
@@ -226,15 +237,33 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_plan_risk(const float* __restr
 
 }  // namespace
 
-void launch_plan_risk(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* plans, const int32_t* ego,
-                      float* w, int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
-                      const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
+template <bool PER_PLAN_W>
+static void plan_risk_launch(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* w,
+                             int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M, const RankHz& hz,
+                             float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
     int PC = 0, TC = 0;
     plan_geometry(mno, T, M, &PC, &TC);
     const size_t lds = PlanLds(mno, PC, TC).bytes();
     const int vecY = (reinterpret_cast<uintptr_t>(Y) & 15) == 0, vecP = (reinterpret_cast<uintptr_t>(plans) & 15) == 0;
     const size_t n_ch = (size_t)((M + PC - 1) / PC);
-    hipLaunchKernelGGL(k_plan_weights, dim3(n_scenes), dim3(EVAL_THREADS), 0, s, fut, present, score, w, mno, K, T);
-    hipLaunchKernelGGL(k_plan_risk, dim3((unsigned)((size_t)n_scenes * n_ch)), dim3(EVAL_THREADS), lds, s, Y, fut, present, plans, ego, w, first, clear,
-                       risk, blame, M, mno, K, T, PC, TC, vecY, vecP, sx, sy, ux, uy, radius * radius, hz);
+    hipLaunchKernelGGL(k_plan_risk<PER_PLAN_W>, dim3((unsigned)((size_t)n_scenes * n_ch)), dim3(EVAL_THREADS), lds, s, Y, fut, present, plans, ego, w,
+                       first, clear, risk, blame, M, mno, K, T, PC, TC, vecY, vecP, sx, sy, ux, uy, radius * radius, hz);
+}
+
+void launch_plan_risk(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* plans, const int32_t* ego,
+                      float* w, int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
+                      const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
+    hipLaunchKernelGGL(k_plan_weights<false>, dim3(n_scenes), dim3(EVAL_THREADS), 0, s, fut, present, score, w, static_cast<float*>(nullptr), mno, K, T);
+    plan_risk_launch<false>(Y, fut, present, plans, ego, w, first, clear, risk, blame, n_scenes, mno, K, T, M, hz, sx, sy, ux, uy, radius, s);
+}
+
+void launch_plan_prior(const float* fut, const uint8_t* present, const float* score, float* w, float* prior, int n_scenes, int mno, int K, int T,
+                       hipStream_t s) {
+    hipLaunchKernelGGL(k_plan_weights<true>, dim3(n_scenes), dim3(EVAL_THREADS), 0, s, fut, present, score, w, prior, mno, K, T);
+}
+
+void launch_plan_risk_per_plan(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* cw,
+                               int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
+                               const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
+    plan_risk_launch<true>(Y, fut, present, plans, ego, cw, first, clear, risk, blame, n_scenes, mno, K, T, M, hz, sx, sy, ux, uy, radius, s);
 }

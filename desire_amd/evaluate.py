@@ -74,6 +74,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also report the leave-one-out plan risk (desire_plan_risk): per horizon the mean predicted risk of what each agent actually "
                         "did, held against the K joint futures of the others, next to the rate at which it actually came within --collision_radius of "
                         "somebody; a predictor that is calibrated about interactions brings the two close")
+    p.add_argument("--plan_risk_sigma", type=float, default=None, metavar="PX",
+                   help="--plan_risk: also report the risk GIVEN what the agent did (desire_plan_risk_cond): the K joint futures reweighted by how close "
+                        "their own sample of the agent came to its recorded future, a Gaussian kernel of this many pixels RMS per frame; next to it the "
+                        "mean effective number of joint futures that carry the answer")
+    p.add_argument("--plan_risk_cond_horizon", type=int, default=None, metavar="T",
+                   help="--plan_risk_sigma: frames the reweighting compares (default: all of --pred_length)")
     p.add_argument("--occupancy", type=str, default=None, metavar="OHxOW",
                    help="also report the predicted occupancy maps of the score-weighted samples on a grid of OH x OW cells over the frame "
                         "(desire_occupancy): per horizon the mean of -log(max(mass on the ground truth's cell, 1e-6)), the mean mass off the frame and "
@@ -293,17 +299,27 @@ class _PlanRisk:
         self.on = bool(getattr(args, "plan_risk", False))
         self.radius, self.run = float(getattr(args, "collision_radius", None) or 0.0), run
         self.pred, self.act, self.agents = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64), np.zeros(len(hz), np.int64)
+        self.sigma, self.t_cond = getattr(args, "plan_risk_sigma", None), getattr(args, "plan_risk_cond_horizon", None)
+        self.given, self.ess = np.zeros(len(hz), np.float64), np.zeros(len(hz), np.float64)
 
     def update(self, model, Y, score, fut, masks):
-        pm = model.evaluate_plan_risk(Y, score, fut, self.radius, horizons=self.run.hz)
+        if self.sigma is None:
+            pm = model.evaluate_plan_risk(Y, score, fut, self.radius, horizons=self.run.hz)
+        else:
+            pm = model.evaluate_plan_risk(Y, score, fut, self.radius, horizons=self.run.hz, condition=True, condition_sigma=self.sigma,
+                                          condition_horizon=self.t_cond)
+            self.given += pm["predicted_given"] * pm["agents"]
+            self.ess += pm["ess_mean"] * pm["agents"]
         self.pred += pm["predicted"] * pm["agents"]
         self.act += pm["actual"] * pm["agents"]
         self.agents += pm["agents"]
 
     def result(self) -> dict:
         rate = lambda s: [float(s[i] / max(int(self.agents[i]), 1)) for i in range(len(self.run.hz))]
-        return {"plan_risk": {"collision_radius_px": self.radius, "agents": [int(v) for v in self.agents], "predicted_risk": rate(self.pred),
-                              "actual_rate": rate(self.act)}}
+        res = {"collision_radius_px": self.radius, "agents": [int(v) for v in self.agents], "predicted_risk": rate(self.pred), "actual_rate": rate(self.act)}
+        if self.sigma is not None:
+            res.update({"predicted_risk_given": rate(self.given), "ess": rate(self.ess)})
+        return {"plan_risk": res}
 
 
 class _Occupancy:

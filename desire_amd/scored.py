@@ -325,7 +325,49 @@ class ScoredSamples(object):
                     res["first"].data_ptr(), res["clear"].data_ptr(), res["blame"].data_ptr(), torch.cuda.current_stream().cuda_stream)
         return res
 
-    def score_plans(self, past, plans, collision_radius, horizons=None, ego_slot=None, weights: str = "score", **predict_kwargs) -> dict:
+    def _plan_risk_cond(self, h, Y, fut, present, score, plans, ego, hz, radius, ux, uy, sigma, t_cond):
+        """One desire_plan_risk_cond call on device tensors (_plan_risk's arguments; sigma in the unit of the radius): _plan_risk's tensors, then
+        "cw" and "dist" [n, M, K], "ess" and "support" [n, M] and "cond" [n, M] int32."""
+        torch = self.torch
+        d = h.dims
+        n, M, nh = d.n_scenes, int(plans.shape[1]), len(hz)
+        dev, i32 = self.device, torch.int32
+        res = {"risk": torch.empty((n, M, nh), device=dev), "first": torch.empty((n, M, d.K + 1), device=dev, dtype=i32),
+               "clear": torch.empty((n, M, d.K + 1, nh), device=dev), "blame": torch.empty((n, M, nh, d.mno), device=dev),
+               "cw": torch.empty((n, M, d.K), device=dev), "dist": torch.empty((n, M, d.K), device=dev), "ess": torch.empty((n, M), device=dev),
+               "support": torch.empty((n, M), device=dev), "cond": torch.empty((n, M), device=dev, dtype=i32)}
+        h.plan_risk_cond(Y.data_ptr(), _ptr(fut), _ptr(present), _ptr(score), plans.data_ptr(), _ptr(ego), M, hz, radius, ux, uy, sigma, t_cond,
+                         res["risk"].data_ptr(), res["cw"].data_ptr(), res["first"].data_ptr(), res["clear"].data_ptr(), res["blame"].data_ptr(),
+                         res["dist"].data_ptr(), res["ess"].data_ptr(), res["support"].data_ptr(), res["cond"].data_ptr(),
+                         torch.cuda.current_stream().cuda_stream)
+        return res
+
+    @staticmethod
+    def _condition_args(d, condition_sigma, condition_horizon):
+        """(sigma in pixels, t_cond) of a conditioned call, refused here where they are bad (before a forward runs)."""
+        if condition_sigma is None or not (np.isfinite(float(condition_sigma)) and float(condition_sigma) > 0):
+            raise ValueError("condition=True needs condition_sigma: pixels, finite and > 0 (the RMS deviation per frame), got %r" % (condition_sigma,))
+        t_cond = d.T_pred if condition_horizon is None else int(condition_horizon)
+        if not 1 <= t_cond <= d.T_pred:
+            raise ValueError("condition_horizon must be 1..pred_length, got %r" % (condition_horizon,))
+        return float(condition_sigma), t_cond
+
+    def _prior_risk(self, d, first, score, part, hz):
+        """desire_plan_risk's risk stated in torch on the small tensors: first [n, M, >= K] int32, score [R] or None, part [n, mno] bool (the slots
+        taking part).  [n, M, n_h]."""
+        torch = self.torch
+        n = d.n_scenes
+        W = torch.full((n, d.K), 1.0 / d.K, device=self.device)
+        if score is not None:
+            s = score.reshape(n, d.K, d.mno)
+            js = torch.where(part[:, None, :], s, torch.zeros_like(s)).sum(-1)
+            fin = torch.isfinite(js).all(-1, keepdim=True)
+            W = torch.where(fin, torch.softmax(torch.where(fin, js, torch.zeros_like(js)), -1), W)
+        hit = first[:, :, :d.K, None] < torch.tensor(hz, device=self.device, dtype=torch.int32)[None, None, None]
+        return (hit.to(torch.float32) * W[:, None, :, None]).sum(2)
+
+    def score_plans(self, past, plans, collision_radius, horizons=None, ego_slot=None, weights: str = "score", condition: bool = False,
+                    condition_sigma=None, condition_horizon=None, **predict_kwargs) -> dict:
         """M candidate trajectories of the planner's own vehicle per window against the K joint futures the model predicts: the forward as
         predict_device runs it (predict_kwargs: eps, seed, grid_of_scene, device_rng, window_base), then one desire_plan_risk call in its
         prediction form (an agent counts when its id is != 0 at the last observed frame).  `past`: loader windows [T_obs, MNO, 3] or
@@ -335,13 +377,23 @@ class ScoredSamples(object):
         within the radius of somebody before the horizon (weights "score": softmax of the joint scores; "uniform": 1 / K), "clearance"
         [n, M, K, n_h] = the smallest distance in pixels to anybody before the horizon (inf: nobody there), "first" [n, M, K] int32 = the frame
         of the first contact (T_pred: none), "blame" [n, M, n_h, mno] = the risk by the agent touched, "present" [n, mno] and "best" [n, n_h] =
-        per horizon the plan of least risk, ties to the greater clearance (its smallest over the K futures), then to the lower index."""
+        per horizon the plan of least risk, ties to the greater clearance (its smallest over the K futures), then to the lower index.
+        condition=True (needs ego_slot and condition_sigma, pixels: the RMS deviation per frame a joint future's own sample of the ego may have
+        from the plan; condition_horizon: the frames compared, default all): one desire_plan_risk_cond call instead -- "risk", "blame" and
+        "best" are then GIVEN that the ego drives the plan (the joint futures reweighted by how well their ego sample agrees with it), and the
+        dict also holds "cond_weights" [n, M, K], "plan_distance" [n, M, K] (pixels RMS), "ess" [n, M] (the effective number of joint futures
+        behind the answer), "support" [n, M] (how well the predicted ego supports the plan, in (0, 1]), "conditioned" [n, M] bool and
+        "risk_prior" [n, M, n_h], the unconditioned risk."""
         torch = self.torch
         _check_weights(weights, "joint")
         _check_radius(collision_radius)
         past, h, present, pres8 = self._prediction(past, u8=True)
         n, d = int(past.shape[0]), h.dims
         hz = self._horizons(d, horizons)
+        if condition:
+            if ego_slot is None:
+                raise ValueError("condition=True needs ego_slot (the slot whose predicted samples are compared with the plan)")
+            sigma, t_cond = self._condition_args(d, condition_sigma, condition_horizon)
         P = torch.as_tensor(plans, device=self.device).to(torch.float32)
         if P.dim() != 4 or int(P.shape[0]) != n or int(P.shape[1]) < 1 or tuple(P.shape[2:]) != (d.T_pred, 2):
             raise ValueError("plans must be [n, M, T_pred, 2] in pixels with M >= 1, got %s" % (tuple(P.shape),))
@@ -354,7 +406,11 @@ class ScoredSamples(object):
             if tuple(ego.shape) != (n, M):
                 raise ValueError("ego_slot must be [n, M] or [n], got %s" % (tuple(ego.shape),))
         Y, score = self.forward_device(past, None, **predict_kwargs)
-        res = self._plan_risk(h, Y, None, pres8, score if weights == "score" else None, P, ego, hz, float(collision_radius), 1.0 / d.sx, 1.0 / d.sy)
+        sc = score if weights == "score" else None
+        if condition:
+            res = self._plan_risk_cond(h, Y, None, pres8, sc, P, ego, hz, float(collision_radius), 1.0 / d.sx, 1.0 / d.sy, sigma, t_cond)
+        else:
+            res = self._plan_risk(h, Y, None, pres8, sc, P, ego, hz, float(collision_radius), 1.0 / d.sx, 1.0 / d.sy)
         clearance = res["clear"][:, :, :d.K].sqrt()
         worst = clearance.min(2).values                                        # [n, M, n_h]
         least = res["risk"] == res["risk"].min(1, keepdim=True).values
@@ -362,20 +418,31 @@ class ScoredSamples(object):
         pick = least & (room == room.max(1, keepdim=True).values)
         idx = torch.arange(M, device=self.device)[None, :, None].expand_as(pick)
         best = torch.where(pick, idx, torch.full_like(idx, M)).min(1).values
-        return {"risk": res["risk"], "clearance": clearance, "first": res["first"][:, :, :d.K].contiguous(), "blame": res["blame"],
-                "present": present, "best": best}
+        out = {"risk": res["risk"], "clearance": clearance, "first": res["first"][:, :, :d.K].contiguous(), "blame": res["blame"],
+               "present": present, "best": best}
+        if condition:
+            out.update({"cond_weights": res["cw"], "plan_distance": res["dist"].sqrt(), "ess": res["ess"], "support": res["support"],
+                        "conditioned": res["cond"] > 0, "risk_prior": self._prior_risk(d, res["first"], sc, pres8.reshape(n, d.mno) != 0, hz)})
+        return out
 
-    def evaluate_plan_risk(self, Y, score, fut_windows, collision_radius, horizons=None, weights: str = "score") -> dict:
+    def evaluate_plan_risk(self, Y, score, fut_windows, collision_radius, horizons=None, weights: str = "score", condition: bool = False,
+                           condition_sigma=None, condition_horizon=None) -> dict:
         """Leave-one-out check of the predicted interactions that needs no planner: plan m of a window is what agent m actually did (its
         recorded future, undefined where it is not counted), replacing slot m, held against the K joint futures of the others.  Returns numpy
         arrays: "risk" [n, mno, n_h] = the predicted risk of what each agent did, "first" [n, mno, K + 1] int32 (row K: against the recorded
         futures of the others), "takes_part" [n, mno, n_h] bool, and per horizon over the agents taking part before it "predicted" [n_h] = the
         mean predicted risk, "actual" [n_h] = the rate at which they actually came within collision_radius (pixels) of somebody, "agents" [n_h].
-        A predictor that is calibrated about interactions brings the two columns close."""
+        A predictor that is calibrated about interactions brings the two columns close.  condition=True (condition_sigma in pixels;
+        condition_horizon: the frames compared, default all) adds a desire_plan_risk_cond call: "risk_given" [n, mno, n_h] = the risk GIVEN what
+        agent m did (the joint futures reweighted by how close their own sample of slot m came to it), "ess" [n, mno], and per horizon over
+        the same agents "predicted_given" [n_h] and "ess_mean" [n_h].  A model that captures interactions predicts the contacts of the others
+        better once it is told what agent m really did: predicted_given then lies closer to actual than predicted does."""
         torch = self.torch
         _check_weights(weights, "joint")
         h, d, hz, _, fut, _ = self._evaluation(Y, fut_windows, horizons)
         n = d.n_scenes
+        if condition:
+            sigma, t_cond = self._condition_args(d, condition_sigma, condition_horizon)
         counted = (fut[..., 0] != 0).permute(0, 2, 1)                          # [n, mno, T_pred]
         g = (fut[..., 1:] * self._scale(d)).permute(0, 2, 1, 3)
         plans = torch.where(counted[..., None], g, torch.full_like(g, float("nan"))).contiguous()
@@ -387,8 +454,16 @@ class ScoredSamples(object):
         predicted = torch.where(takes, res["risk"], torch.zeros_like(res["risk"])).to(torch.float64).sum((0, 1))
         actual = (takes & hit).sum((0, 1)).to(torch.float64)
         den = agents.clamp(min=1)
-        return {"risk": res["risk"].cpu().numpy(), "first": res["first"].cpu().numpy(), "takes_part": takes.cpu().numpy(),
-                "predicted": (predicted / den).cpu().numpy(), "actual": (actual / den).cpu().numpy(), "agents": agents.cpu().numpy().astype(np.int64)}
+        out = {"risk": res["risk"].cpu().numpy(), "first": res["first"].cpu().numpy(), "takes_part": takes.cpu().numpy(),
+               "predicted": (predicted / den).cpu().numpy(), "actual": (actual / den).cpu().numpy(), "agents": agents.cpu().numpy().astype(np.int64)}
+        if condition:
+            cres = self._plan_risk_cond(h, Y, fut, None, score if weights == "score" else None, plans, ego, hz, float(collision_radius), 1.0 / d.sx,
+                                        1.0 / d.sy, sigma, t_cond)
+            given = torch.where(takes, cres["risk"], torch.zeros_like(cres["risk"])).to(torch.float64).sum((0, 1))
+            ess = torch.where(takes, cres["ess"][..., None].expand_as(takes), torch.zeros_like(cres["risk"])).to(torch.float64).sum((0, 1))
+            out.update({"risk_given": cres["risk"].cpu().numpy(), "ess": cres["ess"].cpu().numpy(), "predicted_given": (given / den).cpu().numpy(),
+                        "ess_mean": (ess / den).cpu().numpy()})
+        return out
 
     @staticmethod
     def _modes_args(d, modes, seeds, nms_radius, iters, min_std, weights):

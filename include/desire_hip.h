@@ -541,6 +541,49 @@ int desire_plan_risk(desire_handle* h, const float* dev_Yhat, const float* dev_f
                      const int32_t* host_horizons, int32_t n_h, float radius, float unit_x, float unit_y,
                      int32_t* dev_first, float* dev_clear, float* dev_risk, float* dev_blame, void* stream);
 
+/* ---- the same, given that the ego drives the plan: desire_plan_risk weights the K joint futures by their prior weights W_k whatever the plan.
+ * When plan m replaces slot e, world k also holds the model's own prediction of slot e, and the other agents of world k reacted to THAT future.
+ * This call reweights the worlds of every plan by how well their ego sample agrees with the plan (importance reweighting of the joint samples
+ * with a Gaussian kernel of bandwidth sigma: no model change), and reports next to the conditioned risk how well the model's prediction of the
+ * ego supports the plan and how many worlds carry the answer.  Layouts, the counting rule c(a, t), g, host_horizons, radius and unit_x / unit_y
+ * are desire_plan_risk's exactly, and so is everything downstream of the weights.  All arithmetic is fp32, every operation rounded once (no fused
+ * multiply-add); no float atomics.
+ *   C1 compared    plan m HAS AN EGO SLOT when e = dev_ego[w, m] is in 0 .. mno-1 (a NULL dev_ego, a negative entry, an entry >= mno: none).  For such
+ *                  a plan frame t < t_cond is COMPARED iff c(e, t) holds and neither coordinate of P[m, t] is a NaN.  n_c = the number of compared
+ *                  frames: it depends on (plan, slot) only, never on k.
+ *   C2 distance    for every k < K: q_t = desire_plan_risk's step 2 between P[m, t] and row r_e of world k; S_k = the sum of q_t over the compared
+ *                  frames, in increasing t from 0.f; D_k = S_k / (float)n_c, a mean squared distance in squared units.  dev_dist [n_scenes, M, K]
+ *                  (may be NULL) = D_k as computed (a NaN or inf where the ego's rows are); 0.f for a plan without an ego slot or without a
+ *                  compared frame.
+ *   C3 logits      p_k = js_k (the bits of desire_plan_risk's step 6) when dev_score is non-NULL and every js_k of the window is finite, else 0.f.
+ *                  inv = 1.f / (2.f * sigma * sigma), computed once on the host in fp32, each operation rounded, and passed by value.
+ *                  l_k = p_k - D_k * inv: the product is rounded, then the difference.
+ *   C4 weights     the plan is CONDITIONED iff it has an ego slot, n_c >= 1 and every l_k is finite.  Then m = max_k l_k, e_k = expf(l_k - m),
+ *                  cw_k = e_k / sum_k e_k, the sum in increasing k from 0.f.  Otherwise cw_k = W_k, the bits desire_plan_risk would use.
+ *                  dev_cw [n_scenes, M, K] is REQUIRED: it is the weight table the risk is summed from, so the call allocates nothing and needs no
+ *                  scratch that grows with M.  dev_cond [n_scenes, M] int32 (may be NULL) = n_c for a conditioned plan, 0 otherwise.
+ *   C5 ess         dev_ess [n_scenes, M] (may be NULL) = 1.f / sum_k cw_k * cw_k, in increasing k from 0.f: the effective number of worlds, 1 .. K.
+ *   C6 support     dev_support [n_scenes, M] (may be NULL) = sum_k W_k * expf(-(D_k * inv)), in increasing k from 0.f; 1.f for a plan that is not
+ *                  conditioned.  The unnormalised Gaussian-kernel density of the plan under the model's prediction of the ego, in (0, 1].
+ *   C7 risk, blame dev_risk = desire_plan_risk's step 7 and dev_blame its step 8 with cw(m, k) in place of W_k, in the same order.  dev_first and
+ *                  dev_clear do not depend on weights: desire_plan_risk's bits.  The ego slot stays out of contact, clearance and blame.
+ *   C8 Step 9 of desire_plan_risk holds: a window's results depend on that window alone -- not on the grid, the batch, the chunks M is cut into or
+ *      DESIRE_FLAG_COMPACT_*.  Bitwise reproducible, stream-ordered, capturable, no host wait, no allocation.  A sigma whose square overflows
+ *      gives inv = 0 and therefore l_k = p_k and cw = W bit for bit wherever the D_k are finite.  Identical ego rows give cw = softmax(p).
+ * LDS plan: the weights take one workgroup per (window, chunk of PC plans), PC = as many plans as 1024 (plan, k) items hold, 64 at most, spread
+ * evenly over the chunks of M.  It stages the t_cond compared frames of the chunk's plans as float2 [PC][t_cond | 1] and, when the chunk's plans
+ * name ONE slot and there is room (8 (PC + K) (t_cond | 1) + 8 PC <= 61440 bytes), that slot's K rows next to them (6.4 KB at K 20, T_pred 40);
+ * otherwise a lane reads its world's row from dev_Yhat.  Beyond ~7600 frames of one plan the frames are walked in passes, the sums carried in
+ * dev_cw, with the bits of an unchunked walk.  The K distances and numerators of a plan are parked in dev_cw itself: nothing in the LDS grows
+ * with K.  The risk then runs desire_plan_risk's kernel and plan.  Every (mno, K, T_pred, M) that desire_plan_risk serves is served.
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing is launched or written: everything desire_plan_risk refuses; a NULL dev_cw; a sigma
+ * that is not finite or <= 0; t_cond outside 1 .. T_pred. */
+int desire_plan_risk_cond(desire_handle* h, const float* dev_Yhat, const float* dev_fut, const uint8_t* dev_present,
+                          const float* dev_score, const float* dev_plans, const int32_t* dev_ego, int32_t M,
+                          const int32_t* host_horizons, int32_t n_h, float radius, float unit_x, float unit_y, float sigma, int32_t t_cond,
+                          int32_t* dev_first, float* dev_clear, float* dev_risk, float* dev_blame,
+                          float* dev_cw, float* dev_dist, float* dev_ess, float* dev_support, int32_t* dev_cond, void* stream);
+
 /* ---- n modes with covariances per agent: what trackers, planners and the benchmark formats take -- a small mixture per agent: n modes, a
  * probability for each, a mean trajectory and a 2 x 2 covariance per frame -- fitted to the agent's K weighted samples by a weighted Lloyd
  * iteration from given seeds, and the likelihood of the ground truth under exactly that mixture.  Layouts are desire_select_diverse's: agent
