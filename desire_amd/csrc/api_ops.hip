@@ -237,6 +237,40 @@ int check_radius(float radius) {
     if (!std::isfinite(radius) || radius < 0.f) return fail(DESIRE_ERR_ARG, "radius must be finite and >= 0");
     return DESIRE_OK;
 }
+// exactly one of dev_fut / dev_present says what is counted
+int check_counted(const float* dev_fut, const uint8_t* dev_present) {
+    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
+    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    return DESIRE_OK;
+}
+// what desire_fit_modes and desire_fit_scene_modes check alike, in their order: the checks that need no handle come first, so a caller's
+// constants can be validated before a handle exists.  order_name is the call's name of dev_order, `fitted` what it fits; p (filled by the
+// caller from its arguments) gets the handle's sx, sy and, with dev_fut, the horizons
+int check_fit_modes_args(const desire_handle* h, const float* dev_Yhat, const int32_t* dev_order, const char* order_name, const char* fitted,
+                         const float* dev_fut, const int32_t* host_horizons, int32_t n_h, const ModesFitOut& o, ModesFitParams* p) {
+    const std::string n_modes = "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")";
+    if (p->n < 1 || p->n > DESIRE_MODES_MAX) return fail(DESIRE_ERR_ARG, n_modes);
+    if (p->t_end < 1) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    if (p->iters < 0 || p->iters > DESIRE_MODES_MAX_ITERS) return fail(DESIRE_ERR_ARG, "iters must be 0.." + std::to_string(DESIRE_MODES_MAX_ITERS));
+    if (int rc = check_units(p->ux, p->uy)) return rc;
+    if (!std::isfinite(p->var_floor) || p->var_floor < 0.f) return fail(DESIRE_ERR_ARG, "var_floor must be finite and >= 0");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!dev_order) return fail(DESIRE_ERR_ARG, std::string(order_name) + " is NULL");
+    if (!o.count) return fail(DESIRE_ERR_ARG, "dev_count is NULL");
+    if (!o.prob) return fail(DESIRE_ERR_ARG, "dev_prob is NULL");
+    if (!dev_fut && o.out) return fail(DESIRE_ERR_ARG, "dev_out needs dev_fut (the likelihood is that of the ground truth)");
+    if (!dev_fut && o.frame) return fail(DESIRE_ERR_ARG, "dev_frame needs dev_fut (the likelihood is that of the ground truth)");
+    if (dev_fut && !o.out) return fail(DESIRE_ERR_ARG, "dev_out is NULL (dev_fut asks for the likelihood)");
+    if (dev_fut && !host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
+    if (dev_fut && !std::isfinite(p->log_floor)) return fail(DESIRE_ERR_ARG, "log_floor must be finite");
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to fit " + std::string(fitted) + " to");
+    if (p->n > d.K) return fail(DESIRE_ERR_ARG, n_modes);
+    if (p->t_end > d.T_pred) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
+    p->sx = d.sx; p->sy = d.sy;
+    return dev_fut ? parse_horizons(host_horizons, n_h, d.T_pred, &p->hz) : DESIRE_OK;
+}
 }  // namespace
 
 // ---- ranking by IOC score (kernels_rank.hip): the order of every agent's K samples, the n_top best rows, the errors of the paper's protocol ----
@@ -340,8 +374,7 @@ extern "C" int desire_joint_metrics(desire_handle* h, const float* dev_Yhat, con
     if (!dev_cnt) return fail(DESIRE_ERR_ARG, "dev_cnt is NULL");
     if (!dev_jorder) return fail(DESIRE_ERR_ARG, "dev_jorder is NULL");
     if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
-    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
-    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    if (int rc = check_counted(dev_fut, dev_present)) return rc;
     if (!dev_fut && dev_jerr) return fail(DESIRE_ERR_ARG, "dev_jerr needs dev_fut (the errors are against the ground truth)");
     if (!dev_fut && dev_out) return fail(DESIRE_ERR_ARG, "dev_out needs dev_fut (the errors are against the ground truth)");
     const desire_dims& d = h->d;
@@ -403,8 +436,7 @@ extern "C" int desire_plan_risk(desire_handle* h, const float* dev_Yhat, const f
     if (!dev_plans) return fail(DESIRE_ERR_ARG, "dev_plans is NULL");
     if (!dev_risk) return fail(DESIRE_ERR_ARG, "dev_risk is NULL");
     if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
-    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
-    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    if (int rc = check_counted(dev_fut, dev_present)) return rc;
     if (M < 1) return fail(DESIRE_ERR_ARG, "M must be at least 1 (the candidate plans per window)");
     const desire_dims& d = h->d;
     if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read joint futures from");
@@ -436,8 +468,7 @@ extern "C" int desire_plan_risk_cond(desire_handle* h, const float* dev_Yhat, co
     if (!dev_risk) return fail(DESIRE_ERR_ARG, "dev_risk is NULL");
     if (!dev_cw) return fail(DESIRE_ERR_ARG, "dev_cw is NULL (the [n_scenes, M, K] weight table the risk is summed from)");
     if (!host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
-    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
-    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    if (int rc = check_counted(dev_fut, dev_present)) return rc;
     if (M < 1) return fail(DESIRE_ERR_ARG, "M must be at least 1 (the candidate plans per window)");
     if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(DESIRE_ERR_ARG, "sigma must be finite and > 0");
     const desire_dims& d = h->d;
@@ -471,28 +502,10 @@ extern "C" int desire_fit_modes(desire_handle* h, const float* dev_Yhat, const i
                                 int32_t n_modes, int32_t t_end, int32_t iters, float unit_x, float unit_y, float var_floor,
                                 const int32_t* host_horizons, int32_t n_h, float log_floor, int32_t* dev_label, int32_t* dev_count, float* dev_prob,
                                 float* dev_mean, float* dev_cov, int32_t* dev_passes, float* dev_out, float* dev_frame, void* stream) {
-    if (n_modes < 1 || n_modes > DESIRE_MODES_MAX) return fail(DESIRE_ERR_ARG, "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")");
-    if (t_end < 1) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
-    if (iters < 0 || iters > DESIRE_MODES_MAX_ITERS) return fail(DESIRE_ERR_ARG, "iters must be 0.." + std::to_string(DESIRE_MODES_MAX_ITERS));
-    if (int rc = check_units(unit_x, unit_y)) return rc;
-    if (!std::isfinite(var_floor) || var_floor < 0.f) return fail(DESIRE_ERR_ARG, "var_floor must be finite and >= 0");
-    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
-    if (!dev_order) return fail(DESIRE_ERR_ARG, "dev_order is NULL");
-    if (!dev_count) return fail(DESIRE_ERR_ARG, "dev_count is NULL");
-    if (!dev_prob) return fail(DESIRE_ERR_ARG, "dev_prob is NULL");
-    if (!dev_fut && dev_out) return fail(DESIRE_ERR_ARG, "dev_out needs dev_fut (the likelihood is that of the ground truth)");
-    if (!dev_fut && dev_frame) return fail(DESIRE_ERR_ARG, "dev_frame needs dev_fut (the likelihood is that of the ground truth)");
-    if (dev_fut && !dev_out) return fail(DESIRE_ERR_ARG, "dev_out is NULL (dev_fut asks for the likelihood)");
-    if (dev_fut && !host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
-    if (dev_fut && !std::isfinite(log_floor)) return fail(DESIRE_ERR_ARG, "log_floor must be finite");
-    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    const ModesFitOut o{dev_label, dev_count, dev_prob, dev_mean, dev_cov, dev_passes, dev_out, dev_frame};
+    ModesFitParams p{n_modes, t_end, iters, unit_x, unit_y, 0.f, 0.f, var_floor, log_floor, RankHz{}};
+    if (int rc = check_fit_modes_args(h, dev_Yhat, dev_order, "dev_order", "modes", dev_fut, host_horizons, n_h, o, &p)) return rc;
     const desire_dims& d = h->d;
-    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to fit modes to");
-    if (n_modes > d.K) return fail(DESIRE_ERR_ARG, "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")");
-    if (t_end > d.T_pred) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
-    RankHz hz{};
-    if (dev_fut)
-        if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
     int sc = 0, g = 0;
     if (!modes_geometry(d.mno, d.K, d.T_pred, n_modes, &sc, &g))
         return fail(DESIRE_ERR_ARG, "K samples and n_modes means of T_pred frames do not fit the mode kernel's LDS: " + std::to_string(EVAL_PAIR_BYTES) +
@@ -501,9 +514,7 @@ extern "C" int desire_fit_modes(desire_handle* h, const float* dev_Yhat, const i
                                         std::to_string(4 * ModesLds::MODE_WORDS) + " * n_modes + " + std::to_string(4 * ModesLds::SLOT_WORDS) +
                                         " must be <= " + std::to_string(EVAL_LDS_BYTES));
     if ((uint64_t)d.n_scenes * (uint64_t)((d.mno + sc - 1) / sc) >= (1ull << 31)) return fail(DESIRE_ERR_ARG, "n_scenes * slot chunks must be below 2^31");
-    launch_fit_modes(dev_Yhat, dev_order, dev_score, dev_fut, dev_label, dev_count, dev_prob, dev_mean, dev_cov, dev_passes, dev_out, dev_frame,
-                     d.n_scenes, d.mno, d.K, d.T_pred, n_modes, t_end, iters, hz, d.sx, d.sy, unit_x, unit_y, var_floor, log_floor,
-                     static_cast<hipStream_t>(stream));
+    launch_fit_modes(dev_Yhat, dev_order, dev_score, dev_fut, o, p, d.n_scenes, d.mno, d.K, d.T_pred, static_cast<hipStream_t>(stream));
     HIPCHK(hipGetLastError());
     return DESIRE_OK;
 }
@@ -515,28 +526,10 @@ extern "C" int desire_fit_scene_modes(desire_handle* h, const float* dev_Yhat, c
                                       float unit_y, float var_floor, const int32_t* host_horizons, int32_t n_h, float log_floor, int32_t* dev_label,
                                       int32_t* dev_count, float* dev_prob, float* dev_mean, float* dev_cov, int32_t* dev_passes, float* dev_out,
                                       float* dev_frame, void* stream) {
-    if (n_modes < 1 || n_modes > DESIRE_MODES_MAX) return fail(DESIRE_ERR_ARG, "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")");
-    if (t_end < 1) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
-    if (iters < 0 || iters > DESIRE_MODES_MAX_ITERS) return fail(DESIRE_ERR_ARG, "iters must be 0.." + std::to_string(DESIRE_MODES_MAX_ITERS));
-    if (int rc = check_units(unit_x, unit_y)) return rc;
-    if (!std::isfinite(var_floor) || var_floor < 0.f) return fail(DESIRE_ERR_ARG, "var_floor must be finite and >= 0");
-    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
-    if (!dev_worder) return fail(DESIRE_ERR_ARG, "dev_worder is NULL");
-    if (!dev_count) return fail(DESIRE_ERR_ARG, "dev_count is NULL");
-    if (!dev_prob) return fail(DESIRE_ERR_ARG, "dev_prob is NULL");
-    if (!dev_fut && dev_out) return fail(DESIRE_ERR_ARG, "dev_out needs dev_fut (the likelihood is that of the ground truth)");
-    if (!dev_fut && dev_frame) return fail(DESIRE_ERR_ARG, "dev_frame needs dev_fut (the likelihood is that of the ground truth)");
-    if (dev_fut && !dev_out) return fail(DESIRE_ERR_ARG, "dev_out is NULL (dev_fut asks for the likelihood)");
-    if (dev_fut && !host_horizons) return fail(DESIRE_ERR_ARG, "host_horizons is NULL");
-    if (dev_fut && !std::isfinite(log_floor)) return fail(DESIRE_ERR_ARG, "log_floor must be finite");
-    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    const ModesFitOut o{dev_label, dev_count, dev_prob, dev_mean, dev_cov, dev_passes, dev_out, dev_frame};
+    ModesFitParams p{n_modes, t_end, iters, unit_x, unit_y, 0.f, 0.f, var_floor, log_floor, RankHz{}};
+    if (int rc = check_fit_modes_args(h, dev_Yhat, dev_worder, "dev_worder", "scene modes", dev_fut, host_horizons, n_h, o, &p)) return rc;
     const desire_dims& d = h->d;
-    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to fit scene modes to");
-    if (n_modes > d.K) return fail(DESIRE_ERR_ARG, "n_modes must be 1..min(K, " + std::to_string(DESIRE_MODES_MAX) + ")");
-    if (t_end > d.T_pred) return fail(DESIRE_ERR_ARG, "t_end must be 1..T_pred");
-    RankHz hz{};
-    if (dev_fut)
-        if (int rc = parse_horizons(host_horizons, n_h, d.T_pred, &hz)) return rc;
     int sc = 0;
     if (!scene_modes_geometry(d.mno, d.K, d.T_pred, n_modes, &sc))
         return fail(DESIRE_ERR_ARG, "K worlds and n_modes means of one slot's T_pred frames do not fit the scene-mode kernel's LDS: " +
@@ -545,9 +538,8 @@ extern "C" int desire_fit_scene_modes(desire_handle* h, const float* dev_Yhat, c
                                         std::to_string(4 * SceneModesLds::K_WORDS) + " * K + " + std::to_string(4 * SceneModesLds::MODE_WORDS) +
                                         " * n_modes + 4 * n_modes * ceil(K / 32) + " + std::to_string(4 * SceneModesLds::T_WORDS) +
                                         " * T_pred + 4 * mno must be <= " + std::to_string(EVAL_LDS_BYTES));
-    launch_fit_scene_modes(dev_Yhat, dev_present, dev_worder, dev_wscore, dev_fut, dev_label, dev_count, dev_prob, dev_mean, dev_cov, dev_passes,
-                           dev_out, dev_frame, d.n_scenes, d.mno, d.K, d.T_pred, n_modes, t_end, iters, hz, d.sx, d.sy, unit_x, unit_y, var_floor,
-                           log_floor, h->scene_modes_chunk, static_cast<hipStream_t>(stream));
+    launch_fit_scene_modes(dev_Yhat, dev_present, dev_worder, dev_wscore, dev_fut, o, p, d.n_scenes, d.mno, d.K, d.T_pred, h->scene_modes_chunk,
+                           static_cast<hipStream_t>(stream));
     HIPCHK(hipGetLastError());
     return DESIRE_OK;
 }
@@ -564,8 +556,7 @@ extern "C" int desire_occupancy(desire_handle* h, const float* dev_Yhat, const f
     if (mode != DESIRE_OCC_AT && mode != DESIRE_OCC_UNTIL) return fail(DESIRE_ERR_ARG, "mode must be DESIRE_OCC_AT or DESIRE_OCC_UNTIL (0, 1)");
     if (Oh < 1 || Oh > DESIRE_OCC_MAX_SIDE) return fail(DESIRE_ERR_ARG, "Oh must be 1.." + std::to_string(DESIRE_OCC_MAX_SIDE));
     if (Ow < 1 || Ow > DESIRE_OCC_MAX_SIDE) return fail(DESIRE_ERR_ARG, "Ow must be 1.." + std::to_string(DESIRE_OCC_MAX_SIDE));
-    if (dev_fut && dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both given: exactly one of them says what is counted");
-    if (!dev_fut && !dev_present) return fail(DESIRE_ERR_ARG, "dev_fut and dev_present are both NULL: exactly one of them says what is counted");
+    if (int rc = check_counted(dev_fut, dev_present)) return rc;
     if (dev_hit && !dev_fut) return fail(DESIRE_ERR_ARG, "dev_hit needs dev_fut (the cell of the ground truth)");
     if (dev_hit && mode != DESIRE_OCC_AT) return fail(DESIRE_ERR_ARG, "dev_hit is defined in mode DESIRE_OCC_AT only");
     if (dev_viol && (!dev_mask || !dev_mask_of_scene)) return fail(DESIRE_ERR_ARG, "dev_viol needs dev_mask and dev_mask_of_scene");

@@ -285,20 +285,17 @@ void launch_select_worlds(const float* Y, const uint8_t* present, const float* w
                           int32_t* wlabel, int n_scenes, int mno, int K, int T, int metric, int reduce, int t_end, float radius, float ux, float uy,
                           hipStream_t s);
 
-// ---- n modes with covariances fitted to the K samples, and the mixture's likelihood (kernels_modes.hip) ----
-// score, fut, label, mean, cov and passes may be nullptr; out (required with fut) and frame only with fut; no scratch
-void launch_fit_modes(const float* Y, const int32_t* order, const float* score, const float* fut, int32_t* label, int32_t* count, float* prob,
-                      float* mean, float* cov, int32_t* passes, float* out, float* frame, int n_scenes, int mno, int K, int T, int n_modes,
-                      int t_end, int iters, const RankHz& hz, float sx, float sy, float ux, float uy, float var_floor, float log_floor,
-                      hipStream_t s);
-
-// ---- n scene modes with covariances fitted to a window's K joint futures, and the joint likelihood (kernels_scene_modes.hip) ----
-// present, wscore, fut, label, mean, cov and passes may be nullptr; out (required with fut) and frame only with fut; no scratch.  chunk > 0: at
-// most that many slots per chunk (the same bits)
-void launch_fit_scene_modes(const float* Y, const uint8_t* present, const int32_t* worder, const float* wscore, const float* fut, int32_t* label,
-                            int32_t* count, float* prob, float* mean, float* cov, int32_t* passes, float* out, float* frame, int n_scenes, int mno,
-                            int K, int T, int n_modes, int t_end, int iters, const RankHz& hz, float sx, float sy, float ux, float uy,
-                            float var_floor, float log_floor, int chunk, hipStream_t s);
+// ---- n modes with covariances fitted to the K samples, and the mixture's likelihood (kernels_modes.hip); the same for a window's K joint
+// futures (kernels_scene_modes.hip).  What the two calls share travels by value in both kernels' arguments; the steps are modes_fit.h's ----
+struct ModesFitParams { int n, t_end, iters; float ux, uy, sx, sy, var_floor, log_floor; RankHz hz; };      // hz is read with fut only
+// label, mean, cov and passes may be nullptr; out (required with fut) and frame only with fut
+struct ModesFitOut { int32_t* label; int32_t* count; float* prob; float* mean; float* cov; int32_t* passes; float* out; float* frame; };
+// score and fut may be nullptr; no scratch
+void launch_fit_modes(const float* Y, const int32_t* order, const float* score, const float* fut, const ModesFitOut& o, const ModesFitParams& p,
+                      int n_scenes, int mno, int K, int T, hipStream_t s);
+// present, wscore and fut may be nullptr; no scratch.  chunk > 0: at most that many slots per chunk (the same bits)
+void launch_fit_scene_modes(const float* Y, const uint8_t* present, const int32_t* worder, const float* wscore, const float* fut,
+                            const ModesFitOut& o, const ModesFitParams& p, int n_scenes, int mno, int K, int T, int chunk, hipStream_t s);
 
 // ---- candidate ego plans against the K joint futures (kernels_plan.hip) ----
 // exactly one of fut / present; plans [n_scenes, M, T, 2]; w [n_scenes, K] is scratch of the call (the handle's "joint_js": the joint scores, then

@@ -19,22 +19,21 @@
 // distinct bank pairs and the running mean's row is one address, a broadcast; in the update and the covariance the lanes of a wave walk
 // consecutive t of one row.  A workgroup takes up to 60 KB of LDS (two of them share a CU's 160 KB); the chunk is at most one agent per group, so
 // the assign has a lane for every sample.  No atomics, no host wait: capturable, bitwise reproducible, and a result depends on its agent's rows,
-// order, scores and targets only.  The LDS plan (ModesLds) and the slot chunk are eval_lds.h's.
+// order, scores and targets only.  The LDS plan (ModesLds) and the slot chunk are eval_lds.h's.  The arithmetic of the contract is modes_fit.h's,
+// shared with k_fit_scene_modes: the seed check, the weights, the row-to-mean distance, the nearest mode, the member sums of the update and of
+// the covariance, the Gaussian term, the mixture's value of a frame and the horizon emit.
 #include "eval_tile.h"
-
-#pragma clang fp contract(off)                 // the contract rounds every operation once (after the includes: eval_tile.h says why)
+#include "modes_fit.h"                         // (sets fp contract(off) from here on: the contract rounds every operation once)
 
 namespace {
 
 constexpr int FM_BATCH = 4;                    // 16-byte loads a lane has in flight while staging
-constexpr float FM_LOG_2PI = 1.8378770664093453f;
 
 struct ModesArgs {
     const float* Y; const int32_t* order; const float* score; const float* fut;
-    int32_t* label; int32_t* count; float* prob; float* mean; float* cov; int32_t* passes; float* out; float* frame;
-    int mno, K, T, n, t_end, iters, SC, n_sc, G, vec;
-    float sx, sy, ux, uy, var_floor, log_floor;
-    RankHz hz;
+    ModesFitOut o;
+    ModesFitParams p;
+    int mno, K, T, SC, n_sc, G, vec;
 };
 
 __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
@@ -42,7 +41,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
     __shared__ int hzs[8];
     EVAL_LDS_TIED(sizeof(float2) == EVAL_PAIR_BYTES && sizeof(int) == 4 && sizeof(float) == 4 && ModesLds::FRAME_WORDS == 2 &&
                   ModesLds::K_WORDS == 3 && ModesLds::MODE_WORDS == 2 && ModesLds::SLOT_WORDS == 4);
-    const int K = A.K, T = A.T, n = A.n, SC = A.SC;
+    const int K = A.K, T = A.T, n = A.p.n, SC = A.SC;
     const ModesLds L(T, SC, K, n);
     const int Tp = L.Tp;
     float2* Yl = fm_sm;                                                 // [SC, K, Tp]
@@ -64,8 +63,8 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
     const int sc = blockIdx.x % A.n_sc, scene = blockIdx.x / A.n_sc;
     const int slot0 = sc * SC, ns = min(SC, A.mno - slot0);
     const size_t a0 = (size_t)scene * A.mno + slot0;                    // first agent of the chunk
-    const float ux = A.ux, uy = A.uy;
-    if (A.fut) eval_stage_horizons(hzs, A.hz);
+    const float ux = A.p.ux, uy = A.p.uy;
+    if (A.fut) eval_stage_horizons(hzs, A.p.hz);
 
     // ---- stage: segment k = the chunk's rows of (window, k), contiguous in Y; the scores of the chunk (contiguous over the slots of one k)
     eval_stream<FM_BATCH>(A.Y, A.vec, K, ns * T, T,
@@ -78,24 +77,14 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
     __syncthreads();
     // ---- one lane per agent: the range check of its n seeds, and the weights (desire_kde_nll's step 1, eval_weight_stats) in place of the scores
     for (int sl = tid; sl < ns; sl += EVAL_THREADS) {
-        const int32_t* ord = A.order + (a0 + sl) * K;
-        int bad = 0;
-        for (int i = 0; i < n; ++i) {
-            const int c = ord[i];
-            bad |= (unsigned)c >= (unsigned)K;
-            for (int j = 0; j < i; ++j) bad |= ord[j] == c;
-            cntL[sl * n + i] = c;
-        }
+        const int bad = modes_seed_check(A.order + (a0 + sl) * K, n, K, [&](int i, int c, int) { cntL[sl * n + i] = c; });
         badL[sl] = bad;
         passL[sl] = 0;
         chgL[sl] = !bad;
         chgL[SC + sl] = 0;
         if (bad)
             for (int i = 0; i < n; ++i) { cntL[sl * n + i] = 0; WmL[sl * n + i] = 0.f; }
-        float* w = wL + sl * K;
-        const EvalWeightStats ws = eval_weight_stats(A.score != nullptr, K, [&](int k) { return w[k]; }, [&](int k, float e) { w[k] = e; });
-        const float u = 1.f / (float)K;
-        for (int k = 0; k < K; ++k) w[k] = ws.uniform ? u : w[k] / ws.sum;
+        modes_weights(A.score != nullptr, K, wL + sl * K);
     }
     __syncthreads();
     // ---- the seed means: the rows of the first n entries of the order (zeros, and labels -1, for a refused agent)
@@ -115,18 +104,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
             const float2* ma = ml + (size_t)g * n * Tp;
             for (int k = lg; k < K; k += A.G) {
                 const float2* y = Yl + ((size_t)g * K + k) * Tp;
-                int best = -1;
-                float bd = 0.f;
-                for (int i = 0; i < n; ++i) {
-                    const float2* m = ma + (size_t)i * Tp;
-                    float D = 0.f;
-#pragma unroll 4
-                    for (int t = 0; t < A.t_end; ++t) {
-                        const float a = (y[t].x - m[t].x) * ux, b = (y[t].y - m[t].y) * uy;
-                        D = D + (a * a + b * b);
-                    }
-                    if (D == D && (best < 0 || D < bd)) { best = i; bd = D; }      // strict: ties to the lower i; a NaN is never chosen
-                }
+                const int best = modes_nearest(n, [&](int i) { return modes_row_dist(y, ma + (size_t)i * Tp, A.p.t_end, ux, uy); });
                 const int old = labL[g * K + k];
                 prevL[g * K + k] = old;
                 labL[g * K + k] = best;
@@ -144,20 +122,10 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
         for (int it = tid; it < ns * n * T; it += EVAL_THREADS) {
             const int si = it / T, t = it - si * T, s = si / n, i = si - s * n;
             if (!chgL[(j & 1) * SC + s]) continue;
-            const float2* ys = Yl + (size_t)s * K * Tp + t;
-            float W = 0.f, mx = 0.f, my = 0.f;
-            int c = 0;
-            // branch-free, so that the LDS reads of several k are in flight at once: a sample of another mode adds 0.f, which leaves a sum that
-            // started at +0.f bit for bit as it is (it is never -0.f), and its row is selected away, not multiplied (it may hold a NaN)
-#pragma unroll 4
-            for (int k = 0; k < K; ++k) {
-                const bool in = labL[s * K + k] == i;
-                const float wk = wL[s * K + k];
-                const float2 y = ys[(size_t)k * Tp];
-                W = W + (in ? wk : 0.f); mx = mx + (in ? wk * y.x : 0.f); my = my + (in ? wk * y.y : 0.f); c += in;
-            }
-            if (W > 0.f) ml[(size_t)si * Tp + t] = make_float2(mx / W, my / W);      // without mass the mode keeps its mean
-            if (t == 0) { WmL[si] = W; cntL[si] = c; }
+            const ModesSum m = modes_member_sum<true>(Yl + (size_t)s * K * Tp + t, Tp, K, [&](int k) { return labL[s * K + k] == i; },
+                                                      [&](int k) { return wL[s * K + k]; });
+            if (m.W > 0.f) ml[(size_t)si * Tp + t] = make_float2(m.x / m.W, m.y / m.W);      // without mass the mode keeps its mean
+            if (t == 0) { WmL[si] = m.W; cntL[si] = m.c; }
         }
     };
 
@@ -167,7 +135,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
         update(j);
         if (tid < ns) chgL[((j + 1) & 1) * SC + tid] = 0;               // (last read before the barrier that ended iteration j - 1)
         __syncthreads();
-        if (j == A.iters) break;
+        if (j == A.p.iters) break;
         if (!__syncthreads_or(assign(j, j + 1))) break;                 // every agent's labels stood: their means are update(final labels) already
     }
 
@@ -175,38 +143,28 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
     for (int it = tid; it < ns * n * T; it += EVAL_THREADS) {
         const int si = it / T, t = it - si * T, s = si / n, i = si - s * n;
         const float W = WmL[si];
-        float cxx = 0.f, cyy = 0.f, cxy = 0.f;
-        if (W > 0.f) {
-            const float2 m = ml[(size_t)si * Tp + t];
-            const float2* ys = Yl + (size_t)s * K * Tp + t;
-#pragma unroll 4
-            for (int k = 0; k < K; ++k) {                               // branch-free as the update is
-                const bool in = labL[s * K + k] == i;
-                const float wk = wL[s * K + k];
-                const float2 y = ys[(size_t)k * Tp];
-                const float cx = (y.x - m.x) * ux, cy = (y.y - m.y) * uy;
-                cxx = cxx + (in ? wk * (cx * cx) : 0.f); cyy = cyy + (in ? wk * (cy * cy) : 0.f); cxy = cxy + (in ? wk * (cx * cy) : 0.f);
-            }
-            cxx = cxx / W + A.var_floor; cyy = cyy / W + A.var_floor; cxy = cxy / W;
-        }
+        ModesCov cv{0.f, 0.f, 0.f};
+        if (W > 0.f)
+            cv = modes_member_cov(Yl + (size_t)s * K * Tp + t, Tp, K, ml[(size_t)si * Tp + t], ux, uy, W, A.p.var_floor,
+                                  [&](int k) { return labL[s * K + k] == i; }, [&](int k) { return wL[s * K + k]; });
         float* c = covL + (size_t)it * 3;
-        c[0] = cxx; c[1] = cyy; c[2] = cxy;
+        c[0] = cv.xx; c[1] = cv.yy; c[2] = cv.xy;
     }
     __syncthreads();
 
     // ---- the outputs of the fit, coalesced
-    for (int i = tid; i < ns * n; i += EVAL_THREADS) { A.count[a0 * n + i] = cntL[i]; A.prob[a0 * n + i] = WmL[i]; }
-    if (A.label)
-        for (int i = tid; i < ns * K; i += EVAL_THREADS) A.label[a0 * K + i] = labL[i];
-    if (A.passes && tid < ns) A.passes[a0 + tid] = passL[tid];
-    if (A.cov)
-        for (int i = tid; i < ns * n * T * 3; i += EVAL_THREADS) A.cov[a0 * n * T * 3 + i] = covL[i];
-    if (A.mean) {
+    for (int i = tid; i < ns * n; i += EVAL_THREADS) { A.o.count[a0 * n + i] = cntL[i]; A.o.prob[a0 * n + i] = WmL[i]; }
+    if (A.o.label)
+        for (int i = tid; i < ns * K; i += EVAL_THREADS) A.o.label[a0 * K + i] = labL[i];
+    if (A.o.passes && tid < ns) A.o.passes[a0 + tid] = passL[tid];
+    if (A.o.cov)
+        for (int i = tid; i < ns * n * T * 3; i += EVAL_THREADS) A.o.cov[a0 * n * T * 3 + i] = covL[i];
+    if (A.o.mean) {
         const float* mf = reinterpret_cast<const float*>(ml);
         const int T2 = 2 * T;
         for (int i = tid; i < ns * n * T2; i += EVAL_THREADS) {
             const int si = i / T2;
-            A.mean[a0 * n * T2 + i] = mf[(size_t)si * Tp * 2 + (i - si * T2)];
+            A.o.mean[a0 * n * T2 + i] = mf[(size_t)si * Tp * 2 + (i - si * T2)];
         }
     }
     if (!A.fut) return;                                                 // (uniform)
@@ -218,59 +176,38 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
         const bool counted = f[0] != 0.f;
         float v = 0.f;
         if (counted) {
-            v = A.log_floor;
-            const float gx = f[1] * A.sx, gy = f[2] * A.sy;
-            auto mode = [&](int i, float& l) {
+            const float gx = f[1] * A.p.sx, gy = f[2] * A.p.sy;
+            v = modes_frame_value(n, A.p.log_floor, [&](int i, float& l) {
                 const int si = s * n + i;
                 const float P = WmL[si];
                 const float* c = covL + ((size_t)si * T + t) * 3;
                 const float cxx = c[0], cyy = c[1], cxy = c[2];
-                const float det = cxx * cyy - cxy * cxy;
-                if (!(P > 0.f) || !(det > DESIRE_KDE_MIN_DET_RATIO * cxx * cyy)) return false;
+                float det;
+                const bool usable = modes_cov_usable(cxx, cyy, cxy, det);
+                if (!(P > 0.f) || !usable) return false;
                 const float2 m = ml[(size_t)si * Tp + t];
-                const float dx = (m.x - gx) * ux, dy = (m.y - gy) * uy, c2 = 2.f * cxy;
-                l = logf(P) + (-0.5f * ((cyy * (dx * dx) - c2 * (dx * dy)) + cxx * (dy * dy))) / det - FM_LOG_2PI - 0.5f * logf(det);
+                l = modes_chain(logf(P), modes_gauss_term(cxx, cyy, cxy, det, m.x, m.y, gx, gy, ux, uy));
                 return true;
-            };
-            float M = -INFINITY, l = 0.f;
-            bool any = false;
-            for (int i = 0; i < n; ++i)
-                if (mode(i, l)) { M = fmaxf(M, l); any = true; }
-            if (any) {
-                float S = 0.f;
-                for (int i = 0; i < n; ++i)
-                    if (mode(i, l)) S = S + expf(l - M);
-                const float r = M + logf(S);
-                if (r > A.log_floor) v = r;
-            }
+            });
         }
         val[s * Tp + t] = v;
         cm[s * Tp + t] = counted ? 1.f : 0.f;
-        if (A.frame) A.frame[(a0 + s) * T + t] = v;
+        if (A.o.frame) A.o.frame[(a0 + s) * T + t] = v;
     }
     __syncthreads();
-    const int n_h = A.hz.n;
-    for (int s = tid; s < ns; s += EVAL_THREADS) {
-        float* o = A.out + (a0 + s) * n_h * 2;
-        eval_horizon_walk(cm + s * Tp, val + s * Tp, hzs, n_h, [&](int hi, float sum, float last, int np) {
-            o[2 * hi] = np ? -(sum / (float)np) : 0.f;
-            o[2 * hi + 1] = np ? -last : 0.f;
-        });
-    }
+    const int n_h = A.p.hz.n;
+    for (int s = tid; s < ns; s += EVAL_THREADS) modes_emit_nll(cm + s * Tp, val + s * Tp, hzs, n_h, A.o.out + (a0 + s) * n_h * 2);
 }
 
 }  // namespace
 
-void launch_fit_modes(const float* Y, const int32_t* order, const float* score, const float* fut, int32_t* label, int32_t* count, float* prob,
-                      float* mean, float* cov, int32_t* passes, float* out, float* frame, int n_scenes, int mno, int K, int T, int n_modes,
-                      int t_end, int iters, const RankHz& hz, float sx, float sy, float ux, float uy, float var_floor, float log_floor,
-                      hipStream_t s) {
+void launch_fit_modes(const float* Y, const int32_t* order, const float* score, const float* fut, const ModesFitOut& o, const ModesFitParams& p,
+                      int n_scenes, int mno, int K, int T, hipStream_t s) {
     int SC = 1, G = 1;
-    if (!modes_geometry(mno, K, T, n_modes, &SC, &G)) return;          // (refused by the caller before it gets here)
+    if (!modes_geometry(mno, K, T, p.n, &SC, &G)) return;              // (refused by the caller before it gets here)
     const int n_sc = eval_chunks(mno, SC);
-    const size_t lds = ModesLds(T, SC, K, n_modes).bytes();
+    const size_t lds = ModesLds(T, SC, K, p.n).bytes();
     const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    const ModesArgs a{Y, order, score, fut, label, count, prob, mean, cov, passes, out, frame, mno, K, T, n_modes, t_end, iters, SC, n_sc, G, vec,
-                      sx, sy, ux, uy, var_floor, log_floor, hz};
+    const ModesArgs a{Y, order, score, fut, o, p, mno, K, T, SC, n_sc, G, vec};
     hipLaunchKernelGGL(k_fit_modes, dim3((unsigned)((size_t)n_scenes * n_sc)), dim3(EVAL_THREADS), lds, s, a);
 }

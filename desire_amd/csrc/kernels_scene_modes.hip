@@ -22,15 +22,18 @@
 // LDS rows are float2 [t] at a stride of (T_pred | 1) pairs: the lanes of the distance phase, each on its own row at the same t, fall on distinct
 // bank pairs and a mean's row is a broadcast; in the update the lanes of a wave walk consecutive t of one row.  No atomics, no host wait:
 // capturable, bitwise reproducible, and a window's result depends on that window's taking-part rows, order row, scores and targets only.  The
-// LDS plan (SceneModesLds) and the slot chunk are eval_lds.h's.
+// LDS plan (SceneModesLds) and the slot chunk are eval_lds.h's.  The arithmetic of the contract is modes_fit.h's, shared with k_fit_modes: the
+// seed check, the weights, the row-to-mean distance, the member sums of the update and of the covariance, the Gaussian term and its chain step
+// and the horizon emit.  Three things are NOT taken from there, because this kernel sits at the SGPR limit (106, 75 of them spilled to lanes)
+// and with any of them it measured 0.7 - 1 % slower than the code below, which compiles to the instructions it had before the header existed
+// (DESIGN.md section 7l): the nearest mode of the assign and the mixture's value of a frame are written out (the same statements as
+// modes_nearest and modes_frame_value), and SceneModesArgs keeps its own field order, filled from ModesFitOut / ModesFitParams.
 #include "eval_tile.h"
-
-#pragma clang fp contract(off)                 // the contract rounds every operation once (after the includes: eval_tile.h says why)
+#include "modes_fit.h"                         // (sets fp contract(off) from here on: the contract rounds every operation once)
 
 namespace {
 
 constexpr int SM_BATCH = 4;                    // 16-byte loads a lane has in flight while staging
-constexpr float SM_LOG_2PI = 1.8378770664093453f;
 constexpr int SM_ABSENT = 0, SM_USABLE = 1, SM_UNUSABLE = 2;        // state of (slot, mode, t) in the likelihood
 
 struct SceneModesArgs {
@@ -95,18 +98,8 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_scene_modes(const SceneMod
     }
     __syncthreads();
     if (tid == 0) {
-        const int32_t* ord = A.worder + scene * K;
-        int bad = 0;
-        for (int i = 0; i < n; ++i) {
-            const int c = ord[i];
-            bad |= (unsigned)c >= (unsigned)K;
-            for (int j = 0; j < i; ++j) bad |= ord[j] == c;
-            seedL[i] = bad ? 0 : c;
-        }
-        badS = bad;
-        const EvalWeightStats st = eval_weight_stats(ws != nullptr, K, [&](int k) { return wL[k]; }, [&](int k, float e) { wL[k] = e; });
-        const float u = 1.f / (float)K;
-        for (int k = 0; k < K; ++k) wL[k] = st.uniform ? u : wL[k] / st.sum;
+        badS = modes_seed_check(A.worder + scene * K, n, K, [&](int i, int c, int bad) { seedL[i] = bad ? 0 : c; });
+        modes_weights(ws != nullptr, K, wL);
     }
     __syncthreads();
     const int np = npS;
@@ -115,7 +108,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_scene_modes(const SceneMod
     // one walk over the chunks.  !last: update, then D(k, i) of every world to the updated means.  last: update, covariance, the outputs of both
     // and the likelihood's chain.
     auto walk = [&](const bool last) {
-        const int Tm = last ? T : A.t_end;                              // the assignment looks at t < t_end only
+        const int Tm = last ? T : A.t_end;                            // the assignment looks at t < t_end only
         for (int c = tid; c < K * n; c += EVAL_THREADS) DL[c] = 0.f;
         for (int s0 = 0; s0 < np; s0 += SC) {
             const int ns = min(SC, np - s0);
@@ -131,71 +124,43 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_scene_modes(const SceneMod
                 const int si = it / Tm, t = it - si * Tm, s = si / n, i = si - s * n;
                 const float2* ys = Yl + (size_t)s * K * Tp + t;
                 const unsigned* mb = memL + i * KW;
+                const auto member = [&](int k) -> bool { return (mb[k >> 5] >> (k & 31)) & 1u; };
+                const auto weight = [&](int k) { return wL[k]; };
                 float2 m = ys[(size_t)seedL[i] * Tp];                   // a mode that never had mass: its seed's rows
                 if (hasL[i]) {
-                    float mx = 0.f, my = 0.f;
-                    // branch-free, so that the LDS reads of several k are in flight at once: a world of another mode adds 0.f, which leaves a sum
-                    // that started at +0.f bit for bit as it is, and its row is selected away, not multiplied (it may hold a NaN)
-#pragma unroll 4
-                    for (int k = 0; k < K; ++k) {
-                        const bool in = (mb[k >> 5] >> (k & 31)) & 1u;
-                        const float wk = wL[k];
-                        const float2 y = ys[(size_t)k * Tp];
-                        mx = mx + (in ? wk * y.x : 0.f); my = my + (in ? wk * y.y : 0.f);
-                    }
+                    const ModesSum sum = modes_member_sum<false>(ys, Tp, K, member, weight);
                     const float W = WdL[i];
-                    m = make_float2(mx / W, my / W);
+                    m = make_float2(sum.x / W, sum.y / W);
                 }
                 ml[(size_t)si * Tp + t] = m;
                 if (!last) continue;
                 // covariance about the final means: the members in increasing k (with mass the member set is the labels')
                 const float W = WmL[i];
-                float cxx = 0.f, cyy = 0.f, cxy = 0.f;
-                if (W > 0.f) {
-#pragma unroll 4
-                    for (int k = 0; k < K; ++k) {
-                        const bool in = (mb[k >> 5] >> (k & 31)) & 1u;
-                        const float wk = wL[k];
-                        const float2 y = ys[(size_t)k * Tp];
-                        const float cx = (y.x - m.x) * ux, cy = (y.y - m.y) * uy;
-                        cxx = cxx + (in ? wk * (cx * cx) : 0.f); cyy = cyy + (in ? wk * (cy * cy) : 0.f); cxy = cxy + (in ? wk * (cx * cy) : 0.f);
-                    }
-                    cxx = cxx / W + A.var_floor; cyy = cyy / W + A.var_floor; cxy = cxy / W;
-                }
+                ModesCov cv{0.f, 0.f, 0.f};
+                if (W > 0.f) cv = modes_member_cov(ys, Tp, K, m, ux, uy, W, A.var_floor, member, weight);
                 const int slot = slotL[s0 + s];
                 const size_t o = ((scene * n + i) * mno + slot) * T + t;
                 if (A.mean) { A.mean[2 * o] = m.x; A.mean[2 * o + 1] = m.y; }
-                if (A.cov) { A.cov[3 * o] = cxx; A.cov[3 * o + 1] = cyy; A.cov[3 * o + 2] = cxy; }
+                if (A.cov) { A.cov[3 * o] = cv.xx; A.cov[3 * o + 1] = cv.yy; A.cov[3 * o + 2] = cv.xy; }
                 if (!A.fut) continue;
                 const float* f = A.fut + ((scene * T + t) * mno + slot) * 3;
                 int st = SM_ABSENT;
-                float q = 0.f, hl = 0.f;
+                ModesTerm g{0.f, 0.f};
                 if (f[0] != 0.f) {
-                    const float det = cxx * cyy - cxy * cxy;
+                    float det;
                     st = SM_UNUSABLE;
-                    if (det > DESIRE_KDE_MIN_DET_RATIO * cxx * cyy) {
-                        const float gx = f[1] * A.sx, gy = f[2] * A.sy;
-                        const float dx = (m.x - gx) * ux, dy = (m.y - gy) * uy, c2 = 2.f * cxy;
-                        q = (-0.5f * ((cyy * (dx * dx) - c2 * (dx * dy)) + cxx * (dy * dy))) / det;
-                        hl = 0.5f * logf(det);
+                    if (modes_cov_usable(cv.xx, cv.yy, cv.xy, det)) {
+                        g = modes_gauss_term(cv.xx, cv.yy, cv.xy, det, m.x, m.y, f[1] * A.sx, f[2] * A.sy, ux, uy);
                         st = SM_USABLE;
                     }
                 }
-                tq[it] = q; th[it] = hl; ts[it] = st;
+                tq[it] = g.q; th[it] = g.hl; ts[it] = st;
             }
             __syncthreads();
             if (!last) {
                 for (int it = tid; it < K * n * ns; it += EVAL_THREADS) {
                     const int r = it / K, k = it - r * K, s = r / n, i = r - s * n;
-                    const float2* y = Yl + ((size_t)s * K + k) * Tp;
-                    const float2* m = ml + ((size_t)s * n + i) * Tp;
-                    float D = 0.f;
-#pragma unroll 4
-                    for (int t = 0; t < A.t_end; ++t) {
-                        const float a = (y[t].x - m[t].x) * ux, b = (y[t].y - m[t].y) * uy;
-                        D = D + (a * a + b * b);
-                    }
-                    dsL[(k * n + i) * DS + s] = D;
+                    dsL[(k * n + i) * DS + s] = modes_row_dist(Yl + ((size_t)s * K + k) * Tp, ml + ((size_t)s * n + i) * Tp, A.t_end, ux, uy);
                 }
                 __syncthreads();
                 for (int c = tid; c < K * n; c += EVAL_THREADS) {       // increasing slot: the chunks continue one sequence
@@ -210,7 +175,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_scene_modes(const SceneMod
                     int use = useL[it], c = 0;
                     for (int s = 0; s < ns; ++s) {
                         const int e = (s * n + i) * T + t, st = ts[e];
-                        if (st == SM_USABLE) Lv = ((Lv + tq[e]) - SM_LOG_2PI) - th[e];
+                        if (st == SM_USABLE) Lv = modes_chain(Lv, ModesTerm{tq[e], th[e]});
                         if (st == SM_UNUSABLE) use = 0;
                         c += st != SM_ABSENT;
                     }
@@ -229,7 +194,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_scene_modes(const SceneMod
             float bd = 0.f;
             for (int i = 0; i < n; ++i) {
                 const float D = DL[k * n + i];
-                if (D == D && (best < 0 || D < bd)) { best = i; bd = D; }      // strict: ties to the lower i; a NaN is never chosen
+                if (D == D && (best < 0 || D < bd)) { best = i; bd = D; }      // modes_nearest's rule, written out (the file header says why)
             }
             const int old = labL[k];
             prevL[k] = old;
@@ -302,7 +267,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_scene_modes(const SceneMod
         }
     if (!A.fut) return;                                                 // (uniform)
 
-    // ---- the mixture at the ground truth: a lane per t, the usable modes in increasing i; per agent counted at t
+    // ---- the mixture at the ground truth: a lane per t, the usable modes in increasing i; per agent counted at t (written out: see the header)
     for (int t = tid; t < T; t += EVAL_THREADS) {
         const int c = ctL[t];
         float v = 0.f;
@@ -325,28 +290,19 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_scene_modes(const SceneMod
         if (A.frame) A.frame[scene * T + t] = v;
     }
     __syncthreads();
-    if (tid == 0) {
-        const int n_h = A.hz.n;
-        float* o = A.out + scene * n_h * 2;
-        eval_horizon_walk(cm, val, hzs, n_h, [&](int hi, float sum, float last, int cnt) {
-            o[2 * hi] = cnt ? -(sum / (float)cnt) : 0.f;
-            o[2 * hi + 1] = cnt ? -last : 0.f;
-        });
-    }
+    if (tid == 0) modes_emit_nll(cm, val, hzs, A.hz.n, A.out + scene * A.hz.n * 2);
 }
 
 }  // namespace
 
-void launch_fit_scene_modes(const float* Y, const uint8_t* present, const int32_t* worder, const float* wscore, const float* fut, int32_t* label,
-                            int32_t* count, float* prob, float* mean, float* cov, int32_t* passes, float* out, float* frame, int n_scenes, int mno,
-                            int K, int T, int n_modes, int t_end, int iters, const RankHz& hz, float sx, float sy, float ux, float uy,
-                            float var_floor, float log_floor, int chunk, hipStream_t s) {
+void launch_fit_scene_modes(const float* Y, const uint8_t* present, const int32_t* worder, const float* wscore, const float* fut,
+                            const ModesFitOut& o, const ModesFitParams& p, int n_scenes, int mno, int K, int T, int chunk, hipStream_t s) {
     int SC = 1;
-    if (!scene_modes_geometry(mno, K, T, n_modes, &SC)) return;         // (refused by the caller before it gets here)
+    if (!scene_modes_geometry(mno, K, T, p.n, &SC)) return;            // (refused by the caller before it gets here)
     if (chunk > 0) SC = eval_min(SC, chunk);                            // a smaller chunk than the LDS holds: the same bits (the tests' lever)
-    const size_t lds = SceneModesLds(T, SC, K, n_modes, mno).bytes();
+    const size_t lds = SceneModesLds(T, SC, K, p.n, mno).bytes();
     const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    const SceneModesArgs a{Y, present, worder, wscore, fut, label, count, prob, mean, cov, passes, out, frame, mno, K, T, n_modes, t_end, iters, SC,
-                           vec, sx, sy, ux, uy, var_floor, log_floor, hz};
+    const SceneModesArgs a{Y, present, worder, wscore, fut, o.label, o.count, o.prob, o.mean, o.cov, o.passes, o.out, o.frame, mno, K, T, p.n,
+                           p.t_end, p.iters, SC, vec, p.sx, p.sy, p.ux, p.uy, p.var_floor, p.log_floor, p.hz};
     hipLaunchKernelGGL(k_fit_scene_modes, dim3((unsigned)n_scenes), dim3(EVAL_THREADS), lds, s, a);
 }

@@ -63,3 +63,39 @@ def walking_video():
         video[:, i, 2] = 150 + 100 * i + 2 * t
     video[30:, 4] = 0
     return video
+
+
+# ---- what the GPU tests of the two mode fits (test_gpu_modes.py, test_gpu_scene_modes.py) compare with
+def _t(torch, a):
+    return None if a is None else torch.as_tensor(np.array(a, order="C"), device="cuda")      # (a copy: the shared inputs are read-only)
+
+
+def _same_bits(a, b, keys, rows_a=slice(None), rows_b=slice(None)):
+    """a[key][rows_a] and b[key][rows_b] are equal bit for bit; a NaN may differ in its payload only."""
+    for key in keys:
+        x, y = np.asarray(a[key])[rows_a], np.asarray(b[key])[rows_b]
+        if x.dtype.kind == "f":
+            x, y = x.astype(np.float32), y.astype(np.float32)
+            nan = np.isnan(x)
+            np.testing.assert_array_equal(nan, np.isnan(y), err_msg=key)
+            np.testing.assert_array_equal(np.where(nan, 0, x).view(np.uint32), np.where(nan, 0, y).view(np.uint32), err_msg=key)
+        else:
+            np.testing.assert_array_equal(x, y, err_msg=key)
+
+
+def _within(got, want, bound, key):
+    """|got - want| <= bound wherever the float64 statement is finite, and a NaN exactly where it has one."""
+    fin = np.isfinite(want)
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(want), err_msg=key)
+    gap = np.abs(got.astype(np.float64) - want)[fin]
+    worst = float((gap / np.maximum(bound[fin], 1e-300)).max()) if gap.size else 0.0
+    return (float(gap.max()) if gap.size else 0.0), worst
+
+
+def _likelihood(got, f32, f64, tag):
+    basis = float(np.abs(f32["frame"].astype(np.float64) - f64["frame"]).max())
+    bar = max(4.0 * basis, 1e-5)
+    err = float(np.abs(got["frame"].astype(np.float64) - f64["frame"]).max())
+    print("%s: max |frame - f64| = %.3g, |f32 - f64| = %.3g, bar %.3g" % (tag, err, basis, bar))
+    assert err <= bar
+    np.testing.assert_allclose(got["out"], f64["out"], rtol=0, atol=bar)

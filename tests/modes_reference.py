@@ -68,14 +68,20 @@ def weights(s, K, dt):
     return (e / tot).astype(dt)
 
 
-def _assign(Yk, means, t_end, ux, uy, dt):
-    """labels [K] and the margin of this assign."""
-    K, n = Yk.shape[0], means.shape[0]
-    D = np.zeros((K, n), dt)
+def _dist(Yk, means, t_end, ux, uy, dt):
+    """D [K, n] of the rows Yk [K, T, 2] to the means [n, T, 2]: the sum over t < t_end in increasing t from 0."""
+    D = np.zeros((Yk.shape[0], means.shape[0]), dt)
     for t in range(t_end):
         a = (Yk[:, None, t, 0] - means[None, :, t, 0]) * ux
         b = (Yk[:, None, t, 1] - means[None, :, t, 1]) * uy
         D = D + (a * a + b * b)
+    return D
+
+
+def _nearest(D):
+    """labels [K] from the distances D [K, n] (strict <: ties to the lower mode; a NaN is never chosen; -1 without a choice) and their margin."""
+    K, n = D.shape
+    dt = D.dtype.type
     best = np.full(K, -1, np.int32)
     bd = np.zeros(K, dt)
     for i in range(n):
@@ -108,41 +114,66 @@ def _update(Yk, w, label, means, dt):
     return W, cnt
 
 
-def fit_agent(Yk, order, w, n, t_end, iters, ux, uy, var_floor, dt):
-    """Steps 2 - 7 for one agent: Yk [K, T, 2] and w [K] in dtype dt, order [K] int."""
-    K, T = Yk.shape[:2]
+def _cov(Yk, w, label, means, W, ux, uy, vf, dt):
+    """cov [n, ..., 3] about the final means [n, ..., 2] of the rows Yk [K, ..., 2]: a mode's members in increasing k; zeros without mass."""
+    cov = np.zeros(means.shape[:-1] + (3,), dt)
+    for i in range(means.shape[0]):
+        if not W[i] > 0:
+            continue
+        cxx = cyy = cxy = np.zeros(means.shape[1:-1], dt)
+        for k in np.nonzero(label == i)[0]:
+            cx, cy = (Yk[k, ..., 0] - means[i, ..., 0]) * ux, (Yk[k, ..., 1] - means[i, ..., 1]) * uy
+            cxx = cxx + w[k] * (cx * cx); cyy = cyy + w[k] * (cy * cy); cxy = cxy + w[k] * (cx * cy)
+        cov[i] = np.stack([cxx / W[i] + vf, cyy / W[i] + vf, cxy / W[i]], -1)
+    return cov
+
+
+def fit(Yk, order, w, n, t_end, iters, ux, uy, var_floor, dt, dist=_dist):
+    """The weighted Lloyd iteration and the covariances for one agent (steps 2 - 7) or one window: Yk [K, ..., T, 2] and w [K] in dtype dt, order
+    [K] int, dist(Yk, means, t_end, ux, uy, dt) the distances [K, n] of the assignment.  mean [n, ..., T, 2] and cov [n, ..., T, 3]."""
+    K = Yk.shape[0]
     seeds = [int(c) for c in order[:n]]
-    res = dict(label=np.full(K, -1, np.int32), count=np.zeros(n, np.int32), prob=np.zeros(n, dt), mean=np.zeros((n, T, 2), dt),
-               cov=np.zeros((n, T, 3), dt), passes=0, margin=np.inf, bad=True)
+    res = dict(label=np.full(K, -1, np.int32), count=np.zeros(n, np.int32), prob=np.zeros(n, dt), mean=np.zeros((n,) + Yk.shape[1:], dt),
+               cov=np.zeros((n,) + Yk.shape[1:-1] + (3,), dt), passes=0, margin=np.inf, bad=True)
     if any(c < 0 or c >= K for c in seeds) or len(set(seeds)) < n:
         return res
     ux, uy, vf = dt(np.float32(ux)), dt(np.float32(uy)), dt(np.float32(var_floor))
     with np.errstate(all="ignore"):
         means = Yk[seeds].copy()
-        label, margin = _assign(Yk, means, t_end, ux, uy, dt)
+        label, margin = _nearest(dist(Yk, means, t_end, ux, uy, dt))
         p = 0
         while True:
             W, cnt = _update(Yk, w, label, means, dt)
             if p == iters:
                 break
             p += 1
-            new, m = _assign(Yk, means, t_end, ux, uy, dt)
+            new, m = _nearest(dist(Yk, means, t_end, ux, uy, dt))
             margin = min(margin, m)
             same = np.array_equal(new, label)
             label = new
             if same:
                 break
-        cov = np.zeros((n, T, 3), dt)
-        for i in range(n):
-            if not W[i] > 0:
-                continue
-            cxx, cyy, cxy = np.zeros(T, dt), np.zeros(T, dt), np.zeros(T, dt)
-            for k in np.nonzero(label == i)[0]:
-                cx, cy = (Yk[k, :, 0] - means[i, :, 0]) * ux, (Yk[k, :, 1] - means[i, :, 1]) * uy
-                cxx = cxx + w[k] * (cx * cx); cyy = cyy + w[k] * (cy * cy); cxy = cxy + w[k] * (cx * cy)
-            cov[i] = np.stack([cxx / W[i] + vf, cyy / W[i] + vf, cxy / W[i]], -1)
+        cov = _cov(Yk, w, label, means, W, ux, uy, vf, dt)
     res.update(label=label, count=cnt, prob=W, mean=means, cov=cov, passes=p, margin=margin, bad=False)
     return res
+
+
+fit_agent = fit                                    # one agent: Yk [K, T, 2]
+
+
+def mixture(ls, oks, floor, dt, per=None):
+    """The frame values [T] of the mixture: the log-sum-exp over the usable modes (oks[i] [T]) of their ls[i] [T] in increasing i, divided by
+    `per` [T] where given; the floor where that is not above it or no mode is usable."""
+    M = np.full(ls[0].shape, -np.inf, dt)
+    for l, ok in zip(ls, oks):
+        M = np.where(ok, np.fmax(M, l), M)
+    S = np.zeros(ls[0].shape, dt)
+    for l, ok in zip(ls, oks):
+        S = np.where(ok, S + np.exp(l - M).astype(dt), S)
+    r = (M + np.log(S).astype(dt)).astype(dt)
+    if per is not None:
+        r = (r / per).astype(dt)
+    return np.where(np.any(oks, 0) & (r > floor), r, floor)
 
 
 def frame_values(res, f, ux, uy, log_floor, sx, sy, dt):
@@ -167,15 +198,7 @@ def frame_values(res, f, ux, uy, log_floor, sx, sy, dt):
             c2 = dt(2) * cxy
             l = np.log(P).astype(dt) + (dt(-0.5) * ((cyy * (dx * dx) - c2 * (dx * dy)) + cxx * (dy * dy))) / det - log2pi - dt(0.5) * np.log(det).astype(dt)
             ls.append(l.astype(dt)); oks.append(ok)
-        M = np.full(T, -np.inf, dt)
-        for l, ok in zip(ls, oks):
-            M = np.where(ok, np.fmax(M, l), M)
-        S = np.zeros(T, dt)
-        for l, ok in zip(ls, oks):
-            S = np.where(ok, S + np.exp(l - M).astype(dt), S)
-        r = (M + np.log(S).astype(dt)).astype(dt)
-        anyok = np.any(oks, 0)
-        v = np.where(anyok & (r > floor), r, floor)
+        v = mixture(ls, oks, floor, dt)
     return np.where(counted, v, dt(0)).astype(dt)
 
 

@@ -5,8 +5,8 @@ scene_modes_f32 is the contract as written, operation by operation in numpy fp32
 float64 on the same fp32 inputs.  World k of a window is sample k of every slot together; agent a = scene * mno + slot, row r_k = (scene * K +
 k) * mno + slot.  Both return a dict: label [n, K], count [n, n_modes], prob [n, n_modes], mean [n, n_modes, mno, T, 2], cov [n, n_modes, mno, T,
 3], passes [n], weights [n, K], margin [n] and, with `fut`, frame [n, T] and out [n, n_h, 2].  The weights are worlds_reference.world_weights,
-the update is modes_reference._update on whole worlds, and the likelihood's horizon reduction is kde_reference.kde_outputs on one pseudo-agent
-per window: the same statements as the per-agent calls'.
+the Lloyd loop with its nearest-mode rule, update and covariance is modes_reference.fit on whole worlds, the mixture modes_reference.mixture, and
+the likelihood's horizon reduction is kde_reference.kde_outputs on one pseudo-agent per window: the same statements as the per-agent calls'.
 
 margin [n]: modes_reference's, on the world distances D: over every executed assign and every world with a label, (D2 - D1) / D2 of its smallest
 and second smallest distance.  Labels are compared between precisions only on inputs whose float64 margin is above MARGIN; the generator redraws
@@ -19,7 +19,7 @@ import numpy as np
 from tests.helpers import small_dims
 from tests.joint_reference import _rank
 from tests.kde_reference import kde_outputs
-from tests.modes_reference import LOG_FLOOR, MARGIN, MIN_DET_RATIO, MIN_STD_PX, MODES_MAX, MODES_MAX_ITERS, U, _update, fit_bounds, var_floor_of  # noqa: F401
+from tests.modes_reference import LOG_FLOOR, MARGIN, MIN_DET_RATIO, MIN_STD_PX, MODES_MAX, MODES_MAX_ITERS, U, _dist, fit, fit_bounds, mixture, var_floor_of  # noqa: F401
 from tests.worlds_reference import planted_world_scores, world_weights
 
 # (n_scenes, mno, K, T_pred, n_modes)
@@ -61,69 +61,19 @@ def scene_modes_geometry(mno, K, T, n):
 
 
 # ---- the contract -----------------------------------------------------------------------------------------------------------------------------
-def _assign(Yw, means, t_end, ux, uy, dt):
-    """Steps 4 - 5 for one window: Yw [K, P, T, 2], means [n, P, T, 2] over the P taking-part slots -> labels [K] and the margin of this assign."""
-    K, P = Yw.shape[:2]
-    n = means.shape[0]
-    D = np.zeros((K, n), dt)
-    for s in range(P):                                                      # increasing slot from 0
-        ds = np.zeros((K, n), dt)
-        for t in range(t_end):                                              # increasing t from 0
-            a = (Yw[:, None, s, t, 0] - means[None, :, s, t, 0]) * ux
-            b = (Yw[:, None, s, t, 1] - means[None, :, s, t, 1]) * uy
-            ds = ds + (a * a + b * b)
-        D = D + ds
-    best = np.full(K, -1, np.int32)
-    bd = np.zeros(K, dt)
-    for i in range(n):
-        take = ~np.isnan(D[:, i]) & ((best < 0) | (D[:, i] < bd))
-        best[take] = i
-        bd[take] = D[take, i]
-    margin = np.inf
-    if n > 1:
-        S = np.sort(np.where(np.isnan(D), np.inf, D), 1)
-        two = np.isfinite(S[:, 1]) & (S[:, 1] > 0)
-        if two.any():
-            margin = float(((S[two, 1] - S[two, 0]) / S[two, 1]).min())
-    return best, margin
+def _world_dist(Yw, means, t_end, ux, uy, dt):
+    """Step 4 for one window: D [K, n] of the worlds Yw [K, P, T, 2] to the means [n, P, T, 2] -- per slot modes_reference's distance (increasing
+    t from 0), the slots added in increasing slot from 0."""
+    D = np.zeros((Yw.shape[0], means.shape[0]), dt)
+    for s in range(Yw.shape[1]):
+        D = D + _dist(Yw[:, s], means[:, s], t_end, ux, uy, dt)
+    return D
 
 
 def fit_window(Yw, order, w, n, t_end, iters, ux, uy, var_floor, dt):
-    """Steps 3 - 8 for one window: Yw [K, P, T, 2] and w [K] in dtype dt, order [K] int.  mean [n, P, T, 2] and cov [n, P, T, 3] over the
-    taking-part slots."""
-    K, P, T = Yw.shape[:3]
-    seeds = [int(c) for c in order[:n]]
-    res = dict(label=np.full(K, -1, np.int32), count=np.zeros(n, np.int32), prob=np.zeros(n, dt), mean=np.zeros((n, P, T, 2), dt),
-               cov=np.zeros((n, P, T, 3), dt), passes=0, margin=np.inf, bad=True)
-    if any(c < 0 or c >= K for c in seeds) or len(set(seeds)) < n:
-        return res
-    ux, uy, vf = dt(np.float32(ux)), dt(np.float32(uy)), dt(np.float32(var_floor))
-    with np.errstate(all="ignore"):
-        means = Yw[seeds].copy()
-        label, margin = _assign(Yw, means, t_end, ux, uy, dt)
-        p = 0
-        while True:
-            W, cnt = _update(Yw, w, label, means, dt)                       # modes_reference's, on whole worlds: every slot and every t
-            if p == iters:
-                break
-            p += 1
-            new, m = _assign(Yw, means, t_end, ux, uy, dt)
-            margin = min(margin, m)
-            same = np.array_equal(new, label)
-            label = new
-            if same:
-                break
-        cov = np.zeros((n, P, T, 3), dt)
-        for i in range(n):
-            if not W[i] > 0:
-                continue
-            cxx, cyy, cxy = np.zeros((P, T), dt), np.zeros((P, T), dt), np.zeros((P, T), dt)
-            for k in np.nonzero(label == i)[0]:
-                cx, cy = (Yw[k, ..., 0] - means[i, ..., 0]) * ux, (Yw[k, ..., 1] - means[i, ..., 1]) * uy
-                cxx = cxx + w[k] * (cx * cx); cyy = cyy + w[k] * (cy * cy); cxy = cxy + w[k] * (cx * cy)
-            cov[i] = np.stack([cxx / W[i] + vf, cyy / W[i] + vf, cxy / W[i]], -1)
-    res.update(label=label, count=cnt, prob=W, mean=means, cov=cov, passes=p, margin=margin, bad=False)
-    return res
+    """Steps 3 - 8 for one window: modes_reference.fit on whole worlds -- Yw [K, P, T, 2] and w [K] in dtype dt, order [K] int; the update and
+    the covariance run over every slot and every t.  mean [n, P, T, 2] and cov [n, P, T, 3] over the taking-part slots."""
+    return fit(Yw, order, w, n, t_end, iters, ux, uy, var_floor, dt, dist=_world_dist)
 
 
 def frame_values(res, f, ux, uy, log_floor, sx, sy, dt):
@@ -155,14 +105,7 @@ def frame_values(res, f, ux, uy, log_floor, sx, sy, dt):
                 l = np.where(counted[s] & good, step, l)
                 ok = ok & (~counted[s] | good)
             ls.append(l); oks.append(ok)
-        M = np.full(T, -np.inf, dt)
-        for l, ok in zip(ls, oks):
-            M = np.where(ok, np.fmax(M, l), M)
-        S = np.zeros(T, dt)
-        for l, ok in zip(ls, oks):
-            S = np.where(ok, S + np.exp(l - M).astype(dt), S)
-        r = ((M + np.log(S).astype(dt)).astype(dt) / np.maximum(ct, 1).astype(dt)).astype(dt)
-        v = np.where(np.any(oks, 0) & (r > floor), r, floor)
+        v = mixture(ls, oks, floor, dt, per=np.maximum(ct, 1).astype(dt))
     return np.where(ct > 0, v, dt(0)).astype(dt), ct
 
 

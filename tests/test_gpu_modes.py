@@ -8,14 +8,15 @@ arguments, and the calls through DESIREModel and the command line.
 
 Observed on an MI355X: see DESIGN.md section 7j."""
 import ctypes as C
+import functools
 import itertools
 
 import numpy as np
 import pytest
 
 from desire_amd.spec import FLAG_COMPACT_IOC, FLAG_COMPACT_ROWS, init_weights
-from tests.helpers import (EVAL_FLAGS as _FLAGS, PLAIN_KEYS as _PLAIN_KEYS, walking_video as _video,
-                           at_byte_offset, make_case, small_dims)
+from tests.helpers import (EVAL_FLAGS as _FLAGS, PLAIN_KEYS as _PLAIN_KEYS, walking_video as _video, _same_bits as _same_bits_of,
+                           _likelihood, _t, _within, at_byte_offset, make_case, small_dims)
 from tests.modes_reference import (LOG_FLOOR, MARGIN, SHAPES, fit_bounds, make_inputs, modes_f32, modes_f64, padded_mno, var_floor_of)
 
 pytestmark = pytest.mark.gpu
@@ -32,10 +33,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "gpu tests need an MI355X"
     return torch
-
-
-def _t(torch, a):
-    return None if a is None else torch.as_tensor(np.array(a, order="C"), device="cuda")      # (a copy: the shared inputs are read-only)
 
 
 def _dims(shape, **kw):
@@ -97,35 +94,7 @@ def _run(torch, h, c, scored, iters=ITERS, vf=None, fut=True, **kw):
                  _t(torch, c["fut"]) if fut else None, c["t_end"], iters, ux, uy, c["vf"] if vf is None else vf, c["hz"], **kw)
 
 
-def _same_bits(a, b, keys=ALL, rows=slice(None)):
-    """Equal bit for bit; a NaN may differ in its payload only."""
-    for key in keys:
-        x, y = np.asarray(a[key]), np.asarray(b[key])[rows]
-        if x.dtype.kind == "f":
-            x, y = x.astype(np.float32), y.astype(np.float32)
-            nan = np.isnan(x)
-            np.testing.assert_array_equal(nan, np.isnan(y), err_msg=key)
-            np.testing.assert_array_equal(np.where(nan, 0, x).view(np.uint32), np.where(nan, 0, y).view(np.uint32), err_msg=key)
-        else:
-            np.testing.assert_array_equal(x, y, err_msg=key)
-
-
-def _within(got, want, bound, key):
-    """|got - want| <= bound wherever the float64 statement is finite, and a NaN exactly where it has one."""
-    fin = np.isfinite(want)
-    np.testing.assert_array_equal(np.isnan(got), np.isnan(want), err_msg=key)
-    gap = np.abs(got.astype(np.float64) - want)[fin]
-    worst = float((gap / np.maximum(bound[fin], 1e-300)).max()) if gap.size else 0.0
-    return (float(gap.max()) if gap.size else 0.0), worst
-
-
-def _likelihood(got, f32, f64, tag):
-    basis = float(np.abs(f32["frame"].astype(np.float64) - f64["frame"]).max())
-    bar = max(4.0 * basis, 1e-5)
-    err = float(np.abs(got["frame"].astype(np.float64) - f64["frame"]).max())
-    print("%s: max |frame - f64| = %.3g, |f32 - f64| = %.3g, bar %.3g" % (tag, err, basis, bar))
-    assert err <= bar
-    np.testing.assert_allclose(got["out"], f64["out"], rtol=0, atol=bar)
+_same_bits = functools.partial(_same_bits_of, keys=ALL)             # this file's default: every output
 
 
 @pytest.mark.parametrize("unit", [0, 1], ids=["norm", "px"])

@@ -2,6 +2,7 @@
 scipy's Gaussian density, against the conditions their generator promises, the ABI of desire_fit_modes, and the mirror of the kernel's LDS
 geometry against desire_amd/csrc/eval_lds.h (tests/c_host/modes_lds_driver.cpp, compiled with g++: no ROCm header, no GPU)."""
 import itertools
+import json
 import os
 import re
 import shutil
@@ -75,6 +76,15 @@ def test_the_margin_holds_and_the_two_precisions_agree(shape, unit):
         live = np.array([k != "absent" for k in c["info"]["kinds"]])
         np.testing.assert_allclose(f64["prob"].sum(1)[live & (f64["label"] >= 0).all(1)], 1.0, rtol=1e-12)
         assert (f64["count"].sum(1) == (f64["label"] >= 0).sum(1)).all() and f64["passes"].max() <= ITERS
+
+
+@pytest.mark.parametrize("unit", [0, 1], ids=["norm", "px"])
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+def test_the_statements_reproduce_the_recorded_digests(shape, unit):
+    """Every array of modes_f32 and modes_f64 has the bytes it had when tests/golden/modes_reference_digests.json was recorded."""
+    from tests.golden.make_modes_reference_digests import PATH, digest, name
+    with open(PATH) as fh:
+        assert digest(case(shape, unit)) == json.load(fh)[name("modes", shape, unit)]
 
 
 def test_the_redraw_share_is_small_and_the_special_agents_behave():

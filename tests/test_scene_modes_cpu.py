@@ -3,6 +3,7 @@
 generator promises, the ABI of desire_fit_scene_modes, and the mirror of the kernel's LDS geometry against desire_amd/csrc/eval_lds.h
 (tests/c_host/scene_modes_lds_driver.cpp, compiled with g++: no ROCm header, no GPU)."""
 import itertools
+import json
 import os
 import re
 import shutil
@@ -74,6 +75,15 @@ def test_the_margin_holds_and_the_two_precisions_agree(shape, unit):
             if c["info"]["nan"] is not None:                               # the NaN world: label -1, its mass missing
                 w, k, _ = c["info"]["nan"]
                 assert f64["label"][w, k] == -1 and f64["prob"][w].sum() < 1 - 0.5 * f64["weights"][w, k]
+
+
+@pytest.mark.parametrize("unit", [0, 1], ids=["norm", "px"])
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
+def test_the_statements_reproduce_the_recorded_digests(shape, unit):
+    """Every array of scene_modes_f32 and scene_modes_f64 has the bytes it had when tests/golden/modes_reference_digests.json was recorded."""
+    from tests.golden.make_modes_reference_digests import PATH, digest, name
+    with open(PATH) as fh:
+        assert digest(case(shape, unit)) == json.load(fh)[name("scene_modes", shape, unit)]
 
 
 def test_the_redraw_caps_hold_and_the_iteration_is_exercised():
