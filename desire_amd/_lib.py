@@ -29,6 +29,7 @@ EXPORTS = [
     "desire_set_rng", "desire_set_rng_origin", "desire_rng_state", "desire_rng_fill", "desire_rollout_samples",
     "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy", "desire_plan_risk", "desire_fit_modes",
     "desire_select_worlds", "desire_fit_scene_modes", "desire_plan_risk_cond",
+    "desire_set_recon_scope", "desire_recon_weights_scene",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
@@ -37,6 +38,8 @@ DIST_FINAL, DIST_MEAN, DIST_MAX = 0, 1, 2                           # desire_sel
 WORLD_ALL, WORLD_MEAN = 0, 1                                        # desire_select_worlds reduces over the slots (DESIRE_WORLD_*)
 RECON_MEAN, RECON_MIN, RECON_SOFTMIN = 0, 1, 2                      # desire_set_recon_loss / desire_recon_weights modes (DESIRE_RECON_*)
 RECON_MODES = {"mean": RECON_MEAN, "min": RECON_MIN, "softmin": RECON_SOFTMIN}      # their names on the Python surface (args.recon_loss, --recon_loss)
+RECON_SCOPE_AGENT, RECON_SCOPE_SCENE = 0, 1                         # desire_set_recon_scope: per agent, or per window over its K worlds (DESIRE_RECON_SCOPE_*)
+RECON_SCOPES = {"agent": RECON_SCOPE_AGENT, "scene": RECON_SCOPE_SCENE}             # their names on the Python surface (args.recon_scope, --recon_scope)
 MODES_MAX, MODES_MAX_ITERS = 16, 32                                 # desire_fit_modes: the most modes and passes (DESIRE_MODES_MAX, _MAX_ITERS)
 KDE_LOG_FLOOR = -20.0                                               # desire_kde_nll: the clip of a frame's log-density (Trajectron++'s)
 
@@ -130,6 +133,8 @@ def load() -> C.CDLL:
     lib.desire_set_head_loss.argtypes = [vp, C.c_float]
     lib.desire_set_recon_loss.argtypes = [vp, i32, C.c_float]
     lib.desire_recon_weights.argtypes = [vp, f32p, f32p, i32, C.c_float, f32p, f32p, vp, f32p, vp]
+    lib.desire_set_recon_scope.argtypes = [vp, i32]
+    lib.desire_recon_weights_scene.argtypes = [vp, f32p, f32p, i32, C.c_float, f32p, f32p, vp, f32p, vp, f32p, vp]
     lib.desire_peer_export.argtypes = [vp, C.c_char_p, C.POINTER(C.c_size_t)]
     lib.desire_peer_open.argtypes = [vp, i32, i32, i32, C.c_char_p]
     lib.desire_ioc_peer_pass.argtypes = [vp, f32p, f32p, vp]
@@ -567,6 +572,21 @@ class Handle:
         "recon_e" / "recon_w" / "recon_win" / "recon_val").  Masking as in losses()."""
         _chk(self.lib.desire_recon_weights(self._h, fut_ptr or None, yhat_ptr or None, int(mode), C.c_float(float(tau)), e_ptr or None, w_ptr or None,
                                            winner_ptr or None, recon_ptr or None, stream or None))
+
+    def set_recon_scope(self, scope: int) -> None:
+        """The scope of that term: RECON_SCOPE_AGENT (default: every agent weighs its own K samples) or RECON_SCOPE_SCENE (a window's K joint
+        futures are weighed by their mean error over the window's counted agents: the best world, or a soft-min over the worlds, carries the
+        gradient of every agent of the window).  Ignored in RECON_MEAN."""
+        _chk(self.lib.desire_set_recon_scope(self._h, int(scope)))
+
+    def recon_weights_scene(self, fut_ptr: int, yhat_ptr: int, mode: int, tau: float = 0.0, e_ptr: int = 0, E_ptr: int = 0, count_ptr: int = 0,
+                            w_ptr: int = 0, winner_ptr: int = 0, recon_ptr: int = 0, stream: int = 0) -> None:
+        """recon_weights in the scene scope: e [A, K] as there, the world errors E [n_scenes, K] (the mean of e over the window's counted agents),
+        count [n_scenes] int32, and the window's weights w [A, K], winner [A] int32 and term recon [A] on every slot of the window; each output is
+        optional (0: kept in the workspace tensor "recon_e" / "recon_E" / "recon_cnt" / "recon_w" / "recon_win" / "recon_val")."""
+        _chk(self.lib.desire_recon_weights_scene(self._h, fut_ptr or None, yhat_ptr or None, int(mode), C.c_float(float(tau)), e_ptr or None,
+                                                 E_ptr or None, count_ptr or None, w_ptr or None, winner_ptr or None, recon_ptr or None,
+                                                 stream or None))
 
     def train_loss_async(self, fut_ptr: int, out8_ptr: int, stream: int = 0) -> None:
         """The loss terms of the last training-mode forward into a device buffer of 8 floats, no synchronisation (see loss_terms)."""

@@ -93,6 +93,46 @@ extern "C" int desire_recon_weights(desire_handle* h, const float* dev_fut, cons
     return DESIRE_OK;
 }
 
+// ---- the scene scope: the K worlds of a window weighed by their mean error over the window's counted agents ----
+int recon_scene_ws_setup(desire_ctx* h) {
+    if (int rc = recon_ws_setup(h)) return rc;
+    return ws_ensure(h, {{"recon_E", (size_t)h->d.n_scenes * h->d.K * sizeof(float)}, {"recon_cnt", (size_t)h->d.n_scenes * sizeof(int32_t)}});
+}
+
+void recon_weights_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s) {
+    const desire_dims& d = h->d;
+    if (h->recon_scope == DESIRE_RECON_SCOPE_SCENE)
+        launch_recon_weights_scene(W(h, "Y0"), fut, lmask, W(h, "nfut"), W(h, "recon_e"), W(h, "recon_E"), Wt<int32_t>(h, "recon_cnt"), W(h, "recon_w"),
+                                   Wt<int32_t>(h, "recon_win"), W(h, "recon_val"), d.n_scenes, d.mno, d.K, d.T_pred, h->recon_mode, h->recon_tau,
+                                   d.sx, d.sy, s);
+    else
+        launch_recon_weights(W(h, "Y0"), fut, lmask, W(h, "nfut"), W(h, "recon_e"), W(h, "recon_w"), Wt<int32_t>(h, "recon_win"), W(h, "recon_val"),
+                             d.n_scenes, d.mno, d.K, d.T_pred, h->recon_mode, h->recon_tau, d.sx, d.sy, s);
+}
+
+extern "C" int desire_recon_weights_scene(desire_handle* h, const float* dev_fut, const float* dev_Yhat, int32_t mode, float tau, float* dev_e,
+                                          float* dev_E, int32_t* dev_count, float* dev_w, int32_t* dev_winner, float* dev_recon, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_fut) return fail(DESIRE_ERR_ARG, "dev_fut is NULL");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (mode < DESIRE_RECON_MEAN || mode > DESIRE_RECON_SOFTMIN) return fail(DESIRE_ERR_ARG, "mode must be DESIRE_RECON_MEAN, _MIN or _SOFTMIN (0..2)");
+    if (mode == DESIRE_RECON_SOFTMIN && (!std::isfinite(tau) || !(tau > 0.f))) return fail(DESIRE_ERR_ARG, "tau must be finite and > 0 for DESIRE_RECON_SOFTMIN");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to take errors of");
+    int sc = 0, kc = 0;
+    if (!recon_geometry(d.mno, d.K, d.T_pred, &sc, &kc)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the reconstruction-weight kernel's LDS");
+    if (int rc = desire_ready(h)) return rc;
+    if (int rc = recon_scene_ws_setup(h)) return rc;    // (the first call allocates; later calls are capturable)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    launch_loss_mask(Wt<const uint8_t>(h, "valid"), dev_fut, Wt<uint8_t>(h, "lmask"), W(h, "nfut"), d.n_scenes, d.mno, d.T_pred, s);
+    launch_recon_weights_scene(dev_Yhat, dev_fut, Wt<const uint8_t>(h, "lmask"), W(h, "nfut"), dev_e ? dev_e : W(h, "recon_e"),
+                               dev_E ? dev_E : W(h, "recon_E"), dev_count ? dev_count : Wt<int32_t>(h, "recon_cnt"), dev_w ? dev_w : W(h, "recon_w"),
+                               dev_winner ? dev_winner : Wt<int32_t>(h, "recon_win"), dev_recon ? dev_recon : W(h, "recon_val"), d.n_scenes, d.mno,
+                               d.K, d.T_pred, mode, tau, d.sx, d.sy, s);
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
 extern "C" int desire_temporal_conv(desire_handle* h, const float* dev_past, float* dev_rho, void* stream) {
     if (int rc = desire_ready(h)) return rc;
     if (!dev_past || !dev_rho) return fail(DESIRE_ERR_ARG, "null argument");

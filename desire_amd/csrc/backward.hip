@@ -195,9 +195,9 @@ int loss_grads(const BwdPass& bp) {
     launch_count_valid(bp.valid, h->A, W(h, "nvalid"), s);
     if (h->recon_mode == DESIRE_RECON_MEAN) {
         launch_loss_grad_y(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred, d.sx, d.sy, s);
-    } else {          // best-of-many / soft-min (desire_set_recon_loss): the weights of the K samples on the full layout, then the weighted gradient
-        launch_recon_weights(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "recon_e"), W(h, "recon_w"), Wt<int32_t>(h, "recon_win"), W(h, "recon_val"),
-                             d.n_scenes, d.mno, d.K, d.T_pred, h->recon_mode, h->recon_tau, d.sx, d.sy, s);
+    } else {          // best-of-many / soft-min (desire_set_recon_loss): the weights of the K samples -- per agent, or in the scene scope the window's for
+                      // every one of its slots (desire_set_recon_scope) -- on the full layout, then the weighted gradient
+        recon_weights_enqueue(h, bp.fut, bp.valid, s);
         launch_loss_grad_y_w(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "recon_w"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred,
                              d.sx, d.sy, s);
     }

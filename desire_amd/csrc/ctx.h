@@ -62,6 +62,7 @@ struct desire_ctx {
     int* peer_err = nullptr;
     float head_loss_w = 0.f;                                 // desire_set_head_loss: weight of the Gaussian-head NLL term in the training loss
     int recon_mode = 0; float recon_tau = 0.f;               // desire_set_recon_loss: DESIRE_RECON_* of the training loss's reconstruction term, the soft-min temperature
+    int recon_scope = 0;                                     // desire_set_recon_scope: DESIRE_RECON_SCOPE_* (per agent, or per window over its K worlds)
     int* host_err = nullptr;                                 // mapped host word the bin-split IOC's bounded spins report into (checked by the next call)
     // present-row compaction (DESIRE_FLAG_COMPACT_ROWS, kernels_compact.hip): mapped host word the scan kernel reports the present-agent count
     // into, the event behind it, the count of the last desire_sample (-1: none yet)
@@ -162,4 +163,7 @@ void enc_weights(desire_ctx* h, const char* prefix, EncArgs& e);     // the fp32
 IocStepArgs ioc_step_args(desire_ctx* h, int t);               // what every launch of the step-wise IOC kernel shares (api_peer.hip)
 inline RngArgs rng_args(const desire_ctx* h) { return RngArgs{h->rng_state, 0u, 0u, 0u, h->rng_scene_base, h->rng_slot_base}; }      // the handle's generator
 int recon_ws_setup(desire_ctx* h);                             // "recon_e" / "recon_w" / "recon_win" / "recon_val" (api_ops.hip; idempotent)
+int recon_scene_ws_setup(desire_ctx* h);                       // those four and "recon_E" / "recon_cnt" of the scene scope (api_ops.hip; idempotent)
+// the reconstruction weights of the training step into the workspace tensors, in the handle's mode and scope (api_ops.hip; mode != MEAN)
+void recon_weights_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
 int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)

@@ -328,6 +328,11 @@ void launch_occupancy(const float* Y, const float* fut, const uint8_t* present, 
 // lmask / nfut: launch_loss_mask's; e, w [A, K], win [A], val [A] are all written (none may be nullptr); mode = DESIRE_RECON_*; no scratch
 void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
                           int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s);
+// the scene scope (desire_recon_weights_scene): the same e, then per window E [n_scenes, K] and cnt [n_scenes], and w, win, val of the window on
+// every one of its slots; two launches (the streaming pass without its per-agent tail, then one workgroup per window); none may be nullptr
+void launch_recon_weights_scene(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* E, int32_t* cnt, float* w,
+                                int32_t* win, float* val, int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy,
+                                hipStream_t s);
 
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);

@@ -13,6 +13,17 @@
 // The errors go through the e buffer itself (global memory, written and read by the same workgroup on either side of a barrier), so no LDS is
 // spent on K.  No atomics, no scratch, no host wait: capturable, bitwise reproducible, and a result
 // depends on its agent's rows and targets only.  The LDS plan (ReconLds), the slot chunk and the samples of a pass are eval_lds.h's.
+//
+// The scene scope (desire_set_recon_scope, desire_recon_weights_scene) weighs the K joint futures of a window -- its worlds -- instead of each
+// agent's K samples: the streaming pass runs in its e-only form (TAIL = false: no per-agent walk) and, a kernel boundary later -- a window's
+// reduction crosses its slot chunks --,
+//
+//   k_recon_scene   one workgroup = one window.  The lanes count the window's lmask slots; then lane k (striding over K) walks the window's
+//                  slots in increasing slot over e[(w * mno + s) * K + k] -- consecutive lanes, consecutive addresses -- and leaves the
+//                  world error E[w, k] in the E buffer itself, written and read by the same workgroup on either side of a barrier as e is
+//                  above.  One lane does the winner walk and exp / sum / divide in increasing k on E, with w's first row of the window as its
+//                  scratch and result; all lanes then copy that row, the winner and the term to the window's other slots with coalesced
+//                  stores.  K has no limit and no LDS grows with K; the static LDS is the count's 256 ints and two result words.
 #include "eval_tile.h"
 
 #pragma clang fp contract(off)                 // the contract rounds every operation once (after the includes: eval_tile.h says why)
@@ -21,6 +32,8 @@ namespace {
 
 constexpr int RW_BATCH = 4;                    // 16-byte loads a lane has in flight
 
+// TAIL: the per-agent walk at the end (false: e only -- w, win, val, mode and tau are not read)
+template <bool TAIL>
 __global__ __launch_bounds__(EVAL_THREADS) void k_recon_weights(const float* __restrict__ Y, const float* __restrict__ fut,
                                                               const uint8_t* __restrict__ lmask, const float* __restrict__ nfut, float* e,
                                                               float* w, int32_t* __restrict__ win, float* __restrict__ val, int n_scenes, int mno,
@@ -74,6 +87,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_recon_weights(const float* __r
             e[(a0 + s) * K + k0 + k] = ev;
         }
     }
+    if constexpr (!TAIL) return;
     __syncthreads();                                                    // every e of the chunk is written (and visible to this workgroup)
 
     // ---- one lane per agent: the walk for the minimum, then the weights and the term in increasing k
@@ -106,15 +120,102 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_recon_weights(const float* __r
     }
 }
 
+// ---- the scene scope: a window's K world errors, the walk over them, and the result on every slot of the window
+__global__ __launch_bounds__(EVAL_THREADS) void k_recon_scene(const uint8_t* __restrict__ lmask, const float* __restrict__ e, float* E,
+                                                            int32_t* __restrict__ cnt, float* w, int32_t* __restrict__ win,
+                                                            float* __restrict__ val, int mno, int K, int mode, float tau) {
+    __shared__ int red[EVAL_THREADS];
+    __shared__ int wn_s;
+    __shared__ float r_s;
+    const int tid = threadIdx.x, scene = blockIdx.x;
+    const size_t a0 = (size_t)scene * mno;                              // first agent of the window
+    float* Ew = E + (size_t)scene * K;
+    float* w0 = w + a0 * K;                                             // the window's first row of w: lane 0's scratch, then the result
+
+    // ---- 1. the counted slots
+    int c = 0;
+    for (int s = tid; s < mno; s += EVAL_THREADS) c += lmask[a0 + s] != 0;
+    red[tid] = c;
+    __syncthreads();
+    for (int o = EVAL_THREADS / 2; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    const int count = red[0];
+    if (tid == 0) cnt[scene] = count;
+
+    // ---- 2. one lane per world: the sum over the counted slots in increasing slot, over the count
+    for (int k = tid; k < K; k += EVAL_THREADS) {
+        const float* ek = e + a0 * K + k;
+        float sum = 0.f;
+#pragma unroll 4
+        for (int s = 0; s < mno; ++s) {
+            const float v = ek[(size_t)s * K];
+            if (lmask[a0 + s]) sum += v;
+        }
+        Ew[k] = count > 0 ? sum / (float)count : 0.f;
+    }
+    __syncthreads();                                                    // every E of the window is written (and visible to this workgroup)
+
+    // ---- 3. one lane: the walk for the minimum, then the weights and the term in increasing k (k_recon_weights' tail, on E)
+    if (tid == 0) {
+        int wn = 0;
+        float m = Ew[0];
+        for (int k = 1; k < K; ++k) {
+            const float v = Ew[k];
+            if (v < m || (m != m && v == v)) { m = v; wn = k; }        // strict: a tie stays with the lower k; a NaN gives way to any number
+        }
+        float r;
+        if (mode == DESIRE_RECON_MIN) {
+            for (int k = 0; k < K; ++k) w0[k] = k == wn ? 1.f : 0.f;
+            r = m;
+        } else if (mode == DESIRE_RECON_SOFTMIN) {
+            float S = 0.f;
+            for (int k = 0; k < K; ++k) { const float x = expf(-(Ew[k] - m) / tau); w0[k] = x; S += x; }
+            for (int k = 0; k < K; ++k) w0[k] = w0[k] / S;
+            r = m - tau * logf(S / (float)K);
+        } else {
+            float S = 0.f;
+            const float u = 1.f / (float)K;
+            for (int k = 0; k < K; ++k) { S += Ew[k]; w0[k] = u; }
+            r = S / (float)K;
+        }
+        wn_s = wn;
+        r_s = r;
+    }
+    __syncthreads();                                                    // the first row of w is final (and visible to this workgroup)
+
+    // ---- 4. every slot of the window gets the window's weights, winner and term (the first row of w holds them already)
+    const size_t nw = (size_t)mno * K;
+    for (size_t i = (size_t)K + tid; i < nw; i += EVAL_THREADS) w0[i] = w0[i % K];
+    const int wn = wn_s;
+    const float r = r_s;
+    for (int s = tid; s < mno; s += EVAL_THREADS) { win[a0 + s] = wn; val[a0 + s] = r; }
+}
+
 }  // namespace
 
-void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
-                          int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s) {
+// the streaming pass: with the per-agent tail (TAIL) or e only
+template <bool TAIL>
+static void launch_recon_pass(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
+                              int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s) {
     int SC = 1, KC = 1;
     if (!recon_geometry(mno, K, T, &SC, &KC)) return;                   // (refused by the caller before it gets here)
     const int n_sc = eval_chunks(mno, SC);
     const size_t lds = ReconLds(T, SC, KC).bytes();
     const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    hipLaunchKernelGGL(k_recon_weights, dim3((unsigned)((size_t)n_scenes * n_sc)), dim3(EVAL_THREADS), lds, s, Y, fut, lmask, nfut, e, w, win, val,
-                       n_scenes, mno, K, T, SC, n_sc, KC, vec, mode, tau, sx, sy);
+    hipLaunchKernelGGL(k_recon_weights<TAIL>, dim3((unsigned)((size_t)n_scenes * n_sc)), dim3(EVAL_THREADS), lds, s, Y, fut, lmask, nfut, e, w, win,
+                       val, n_scenes, mno, K, T, SC, n_sc, KC, vec, mode, tau, sx, sy);
+}
+
+void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
+                          int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s) {
+    launch_recon_pass<true>(Y, fut, lmask, nfut, e, w, win, val, n_scenes, mno, K, T, mode, tau, sx, sy, s);
+}
+
+void launch_recon_weights_scene(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* E, int32_t* cnt, float* w,
+                                int32_t* win, float* val, int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy,
+                                hipStream_t s) {
+    launch_recon_pass<false>(Y, fut, lmask, nfut, e, nullptr, nullptr, nullptr, n_scenes, mno, K, T, mode, tau, sx, sy, s);
+    hipLaunchKernelGGL(k_recon_scene, dim3((unsigned)n_scenes), dim3(EVAL_THREADS), 0, s, lmask, e, E, cnt, w, win, val, mno, K, mode, tau);
 }

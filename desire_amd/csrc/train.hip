@@ -151,6 +151,11 @@ __global__ void k_put_recon(const float* __restrict__ val, float* __restrict__ p
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     if (a < A) per_agent[(size_t)a * 4] = val[a];
 }
+// desire_set_recon_scope (SCENE): every slot of a window carries the window's term, so the agents that do not count are zeroed here
+__global__ void k_put_recon_counted(const float* __restrict__ val, const uint8_t* __restrict__ lmask, float* __restrict__ per_agent, int A) {
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a < A) per_agent[(size_t)a * 4] = lmask[a] ? val[a] : 0.f;
+}
 __global__ void k_sum_loss(const float* __restrict__ per_agent, const uint8_t* __restrict__ valid, int A, float* __restrict__ out) {
     __shared__ float red[4][256];
     float s[4] = {0.f, 0.f, 0.f, 0.f}; float nv = 0.f;
@@ -361,6 +366,19 @@ extern "C" int desire_set_recon_loss(desire_handle* h, int32_t mode, float tau) 
     return DESIRE_OK;
 }
 
+extern "C" int desire_set_recon_scope(desire_handle* h, int32_t scope) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null argument");
+    if (scope < DESIRE_RECON_SCOPE_AGENT || scope > DESIRE_RECON_SCOPE_SCENE) return fail(DESIRE_ERR_ARG, "scope must be DESIRE_RECON_SCOPE_AGENT or _SCENE (0..1)");
+    if (scope == DESIRE_RECON_SCOPE_SCENE) {
+        if (h->d.ref_compat) return fail(DESIRE_ERR_STATE, "ref_compat is forward-only");
+        int sc = 0, kc = 0;
+        if (!recon_geometry(h->d.mno, h->d.K, h->d.T_pred, &sc, &kc)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the reconstruction-weight kernel's LDS");
+        if (int rc = recon_scene_ws_setup(h)) return rc;    // here, whatever the mode is or becomes, so that no training step allocates
+    }
+    h->recon_scope = scope;
+    return DESIRE_OK;
+}
+
 extern "C" int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream) {
     if (!h || !name || !host_out) return fail(DESIRE_ERR_ARG, "null argument");
     if (!h->training) return fail(DESIRE_ERR_STATE, "not in training mode");
@@ -390,10 +408,12 @@ static int train_loss_enqueue(desire_handle* h, const float* dev_fut, hipStream_
     launch_loss_mask(Wt<const uint8_t>(h, "valid"), dev_fut, Wt<uint8_t>(h, "lmask"), W(h, "nfut"), d.n_scenes, d.mno, d.T_pred, s);
     hipLaunchKernelGGL(k_train_loss, dim3((h->A + 63) / 64), dim3(64), 0, s, W(h, "Y0"), W(h, "Y_ref"), dev_fut, W(h, "score_sv"),
                        W(h, "params"), valid, W(h, "nfut"), W(h, "loss_pa"), d.n_scenes, d.mno, d.K, d.T_pred, d.L, d.sx, d.sy);
-    if (h->recon_mode != DESIRE_RECON_MEAN) {          // slot 0 reports the term that is trained: the min / soft-min over the K samples (kernels_recon.hip)
-        launch_recon_weights(W(h, "Y0"), dev_fut, valid, W(h, "nfut"), W(h, "recon_e"), W(h, "recon_w"), Wt<int32_t>(h, "recon_win"), W(h, "recon_val"),
-                             d.n_scenes, d.mno, d.K, d.T_pred, h->recon_mode, h->recon_tau, d.sx, d.sy, s);
-        hipLaunchKernelGGL(k_put_recon, dim3((h->A + 255) / 256), dim3(256), 0, s, W(h, "recon_val"), W(h, "loss_pa"), h->A);
+    if (h->recon_mode != DESIRE_RECON_MEAN) {          // slot 0 reports the term that is trained: the min / soft-min over the K samples, or in the scene scope over the window's K worlds (kernels_recon.hip)
+        recon_weights_enqueue(h, dev_fut, valid, s);
+        if (h->recon_scope == DESIRE_RECON_SCOPE_SCENE)
+            hipLaunchKernelGGL(k_put_recon_counted, dim3((h->A + 255) / 256), dim3(256), 0, s, W(h, "recon_val"), valid, W(h, "loss_pa"), h->A);
+        else
+            hipLaunchKernelGGL(k_put_recon, dim3((h->A + 255) / 256), dim3(256), 0, s, W(h, "recon_val"), W(h, "loss_pa"), h->A);
     }
     hipLaunchKernelGGL(k_sum_loss, dim3(1), dim3(256), 0, s, W(h, "loss_pa"), valid, h->A, W(h, "loss_out"));
     HIPCHK(hipGetLastError());

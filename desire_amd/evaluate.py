@@ -55,8 +55,7 @@ def build_parser() -> argparse.ArgumentParser:
                    help="also report the K samples of a window as K JOINT futures of the scene (desire_joint_metrics): JADE / JFDE per horizon of the "
                         "joint sample with the best summed score and of the best among the top N, and the collision rate of the predicted joint futures "
                         "next to the ground truth's under the same rule, see --collision_radius")
-    p.add_argument("--collision_radius", type=float, default=None,
-                   help="--joint, --plan_risk: two agents closer than this many pixels in a frame touch (default: 0, nothing touches)")
+    # (--collision_radius comes with the training flags, where --report_joint reads it: here it serves --joint and --plan_risk)
     p.add_argument("--joint_select", type=str, default=None, choices=("nms",),
                    help="--joint: also report the best of the N most plausible MUTUALLY DISTINCT joint futures -- score-ordered non-maximum suppression "
                         "of the K joint samples of a window on the device (desire_select_worlds), see --joint_radius")

@@ -23,7 +23,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import RECON_MODES
+from ._lib import RECON_MODES, RECON_SCOPES
 from .scored import ScoredSamples, default_horizons, default_top  # noqa: F401  (the defaults are imported from here too)
 from .spec import Dims, init_weights, weight_shapes
 
@@ -397,15 +397,22 @@ class DESIREModel(ScoredSamples):
             self._head_given = True                   # the head is trained from now on: sample(mode="rollout") reads learned weights
 
     def _configure_recon_loss(self, h) -> None:
-        """Hook of the reconstruction term over the K samples (args.recon_loss = "mean" | "min" | "softmin", args.recon_tau)."""
+        """Hook of the reconstruction term over the K samples (args.recon_loss = "mean" | "min" | "softmin", args.recon_tau)
+        and of its scope (args.recon_scope = "agent" | "scene": per agent, or per window over its K joint futures; section 7n).  "scene" with
+        "mean" is accepted and changes nothing: the mean over the samples does not depend on the scope."""
         mode = str(getattr(self.args, "recon_loss", None) or "mean")
         if mode not in RECON_MODES:
             raise ValueError("args.recon_loss must be one of %s, got %r" % (", ".join(RECON_MODES), mode))
+        scope = str(getattr(self.args, "recon_scope", None) or "agent")
+        if scope not in RECON_SCOPES:
+            raise ValueError("args.recon_scope must be one of %s, got %r" % (", ".join(RECON_SCOPES), scope))
         if mode != "mean":
             tau = getattr(self.args, "recon_tau", None)
             if mode == "softmin" and tau is None:
                 raise ValueError("args.recon_loss = 'softmin' needs args.recon_tau > 0")
             h.set_recon_loss(RECON_MODES[mode], float(tau) if mode == "softmin" else 0.0)
+            if scope != "agent":
+                h.set_recon_scope(RECON_SCOPES[scope])
 
     def sync_weights(self) -> Dict[str, np.ndarray]:
         """Pull the trained weights back from the device; other handles (batch sizes / prior path) are rebuilt lazily."""

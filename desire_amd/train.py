@@ -25,7 +25,7 @@ from typing import Callable, List, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import RECON_MODES
+from ._lib import RECON_MODES, RECON_SCOPES
 
 
 def _noise(args, step: int, rank: int, world: int) -> dict:
@@ -98,6 +98,10 @@ def build_parser() -> argparse.ArgumentParser:
                         "terms keep their mean over K")
     p.add_argument("--recon_tau", type=float, default=None,
                    help="temperature of --recon_loss softmin in normalised units, > 0 (large: the mean, small: the min); required for softmin")
+    p.add_argument("--recon_scope", type=str, default="agent", choices=list(RECON_SCOPES),
+                   help="who picks among the K samples under --recon_loss min / softmin: agent (every agent its own best sample, default) or scene "
+                        "(sample k of every agent of a window is one joint future: the window's best joint future, or a soft-min over them, carries "
+                        "the gradient of all its agents -- the scene-level variety loss); ignored with --recon_loss mean")
     p.add_argument("--prefetch", type=int, default=2,
                    help="batches the loader thread keeps in flight (pinned staging -> copy stream -> device; desire_amd/prefetch.py); 0 = the "
                         "reference's serial loop: next_batch, copy, step, read the loss, every step (train.py:131-183)")
@@ -112,6 +116,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--report_nll", action="store_true",
                    help="after every epoch, on the same batch: KDE negative log-likelihood of the ground truth under the K prior samples over the "
                         "whole prediction (per pixel^2, log clipped at -20), with equal weights and with weights softmax(IOC score)")
+    p.add_argument("--report_joint", action="store_true",
+                   help="after every epoch, on the same batch: the K samples of a window as K joint futures -- JADE / JFDE per horizon in pixels of "
+                        "the best-scored joint future and of the best among the --eval_top best-scored, and the collision rate at --collision_radius")
+    p.add_argument("--collision_radius", type=float, default=None,
+                   help="--report_joint (and the evaluation's --joint, --plan_risk): two agents closer than this many pixels in a frame touch "
+                        "(default: 0, nothing touches)")
     p.add_argument("--eval_top", type=int, default=None, help="samples per agent the ranked report keeps (default: 10 %% of --num_samples, at least 1)")
     p.add_argument("--eval_horizons", type=str, default=None,
                    help="horizons of the ranked report in frames, comma separated and increasing, e.g. 3,6,9,12 (default: quarters of --pred_length)")
@@ -119,8 +129,12 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def check_recon_args(args) -> None:
-    """--recon_loss / --recon_tau: softmin needs a finite temperature > 0; a temperature without softmin is a mistake, not a default."""
+    """--recon_loss / --recon_tau: softmin needs a finite temperature > 0; a temperature without softmin is a mistake, not a default.
+    --recon_scope: agent or scene (scene with mean is accepted: the mean does not depend on the scope)."""
     mode = getattr(args, "recon_loss", "mean") or "mean"
+    scope = getattr(args, "recon_scope", "agent") or "agent"
+    if scope not in RECON_SCOPES:
+        raise ValueError("--recon_scope must be one of %s, got %r" % (", ".join(RECON_SCOPES), scope))
     tau = getattr(args, "recon_tau", None)
     if mode not in RECON_MODES:
         raise ValueError("--recon_loss must be one of %s, got %r" % (", ".join(RECON_MODES), mode))
@@ -139,6 +153,8 @@ def step_line(args, step: int, total: int, epoch: int, terms: dict, dt: float) -
     mode = getattr(args, "recon_loss", "mean") or "mean"
     if mode != "mean":
         tag = "softmin tau={:g}".format(float(args.recon_tau)) if mode == "softmin" else mode
+        if (getattr(args, "recon_scope", "agent") or "agent") == "scene":
+            tag = "scene " + tag
         line += ", recon[{}] = {:.5f}".format(tag, terms["recon"])
     return line
 
@@ -334,6 +350,30 @@ def _report_nll(args, model, past, fut, epoch, rank, log) -> None:
         log("epoch {} rank {}: KDE NLL px @h={}: uniform = {:.4f}, score-weighted = {:.4f} ({} agents)".format(epoch, rank, T, u, w, int(there.sum())))
 
 
+def _report_joint(args, model, past, fut, epoch, rank, log) -> None:
+    """--report_joint: the number the scene scope of the reconstruction loss is meant to move.  The batch, the prior samples (same seed) of
+    _report_ade; sample k of every agent of a window is one joint future, ranked by the summed IOC score on the device: JADE / JFDE per horizon in
+    pixels of the best-scored joint future and of the best among the top N, mean over the windows with an agent that takes part, and the share of
+    (joint future, agent) pairs that come within --collision_radius of another agent before each horizon."""
+    import torch
+    from .model import default_top
+    Y, score = (model.forward_device if torch.is_tensor(past) else model.forward)(past, None, seed=args.seed)
+    top = int(getattr(args, "eval_top", None) or default_top(int(Y.shape[1])))
+    hz = parse_horizons(getattr(args, "eval_horizons", None), int(Y.shape[3]))
+    radius = getattr(args, "collision_radius", None)
+    ev = model.evaluate_joint(Y, score, fut, top=top, horizons=hz, units="px", collision_radius=radius)
+    K = int(Y.shape[1])
+    cnt = ev["cnt"][:, :K].astype(np.float64)                          # [n, K, n_h, 2]: (touching, taking part) of the K joint futures
+    there = cnt[:, 0, -1, 1] > 0                                       # windows with an agent that takes part before the last horizon
+    if there.any():
+        e = np.nanmean(ev["out"][there].astype(np.float64), 0)         # [n_h, 4]
+        rate = cnt[there, :, :, 0].sum((0, 1)) / np.maximum(cnt[there, :, :, 1].sum((0, 1)), 1.0)
+        fmt = lambda v: "[" + ", ".join("%.3f" % x for x in v) + "]"
+        log("epoch {} rank {}: joint px @h={}: top-1 JADE/JFDE = {} / {}, best-of-top-{} = {} / {}, collision rate (r = {:g} px) = {} ({} windows)".format(
+            epoch, rank, "[" + ", ".join(str(h) for h in hz) + "]", fmt(e[:, 0]), fmt(e[:, 1]), top, fmt(e[:, 2]), fmt(e[:, 3]),
+            0.0 if radius is None else float(radius), "[" + ", ".join("%.4f" % x for x in rate) + "]", int(there.sum())))
+
+
 def _report(args, model, past, fut, epoch, rank, log) -> None:
     if getattr(args, "report_ade", False):
         _report_ade(args, model, past, fut, epoch, rank, log)
@@ -341,6 +381,8 @@ def _report(args, model, past, fut, epoch, rank, log) -> None:
         _report_ranked(args, model, past, fut, epoch, rank, log)
     if getattr(args, "report_nll", False):
         _report_nll(args, model, past, fut, epoch, rank, log)
+    if getattr(args, "report_joint", False):
+        _report_joint(args, model, past, fut, epoch, rank, log)
 
 
 def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred, losses) -> List[float]:
@@ -365,7 +407,8 @@ def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred,
 
     steps = 0
     last = None
-    reporting = getattr(args, "report_ade", False) or getattr(args, "report_ranked", False) or getattr(args, "report_nll", False)
+    reporting = getattr(args, "report_ade", False) or getattr(args, "report_ranked", False) or getattr(args, "report_nll", False) or \
+        getattr(args, "report_joint", False)
     try:
         for bt in feeder:
             start = time.time()

@@ -858,6 +858,43 @@ int desire_set_head_loss(desire_handle* h, float weight);
 int desire_set_recon_loss(desire_handle* h, int32_t mode, float tau);
 int desire_recon_weights(desire_handle* h, const float* dev_fut, const float* dev_Yhat, int32_t mode, float tau,
                          float* dev_e, float* dev_w, int32_t* dev_winner, float* dev_recon, void* stream);
+/* ---- the scope of that term: per agent (above), or per window over its K joint futures.  Sample k of every agent of a window is one joint
+ * future, a "world" (desire_joint_metrics, desire_select_worlds, desire_fit_scene_modes, desire_plan_risk*).  Per agent, every agent picks its own
+ * best k and no single world is pulled toward the observed scene; in scope SCENE the best WORLD of a window -- or a soft-min over its worlds --
+ * carries the reconstruction gradient of every agent of the window (the scene-level variety loss).  Layouts, lmask, nfut, g and the fp32 rule
+ * (every operation rounded once, no fused multiply-add, the device library's expf / logf) are desire_recon_weights'; window(a) = a / mno; a sum
+ * "in increasing X" starts from 0.f.
+ *   1 error       e[a, k]: step 1 of desire_recon_weights, the same bits on the same inputs.
+ *   2 world error count[w] = the number of slots of window w with lmask = 1 (int32).  E[w, k] = (the sum over the slots with lmask = 1, in
+ *                 increasing slot, of e[a, k]) / (float)count[w]; E[w, k] = 0.f where count[w] = 0.
+ *   3 winner      winner[w]: the walk of step 2 of desire_recon_weights on E[w, .] (strict, ties to the lower k, a NaN never beats a number).
+ *   4 weights     DESIRE_RECON_MEAN:    W[w, k] = 1.f / K;                  R[w] = (the sum of E[w, k] in increasing k) / K.
+ *                 DESIRE_RECON_MIN:     W[w, k] = k == winner ? 1.f : 0.f;  R[w] = E[w, winner].
+ *                 DESIRE_RECON_SOFTMIN: x_k = expf(-(E[w, k] - m) / tau), m = E[w, winner]; S = the sum of x_k in increasing k; W[w, k] = x_k / S;
+ *                                       R[w] = m - tau * logf(S / K).
+ * desire_recon_weights_scene is the stand-alone op: dev_e [A, K], dev_E [n_scenes, K], dev_count [n_scenes] int32; dev_w [A, K] with w[a, k] =
+ * W[window(a), k] on EVERY slot of the window (the gradient masks the slots that do not count itself), dev_winner [A] int32 = winner[window(a)]
+ * and dev_recon [A] = R[window(a)], on every slot too.  Each may be NULL (it then goes to the workspace tensor "recon_e" / "recon_E" /
+ * "recon_cnt" / "recon_w" / "recon_win" / "recon_val"), and what is written does not depend on which are.  It needs no training mode.  Two
+ * launches (the streaming pass of desire_recon_weights without its per-agent walk, then one workgroup per window), stream-ordered, no host wait,
+ * no atomics, no scratch: bitwise reproducible; the first call allocates the workspace tensors, later calls are capturable.  K has no limit;
+ * T_pred as for desire_recon_weights.  At mno = 1 w, winner and recon have the bits of desire_recon_weights.  DESIRE_ERR_ARG, and nothing is
+ * launched: a NULL handle / dev_fut / dev_Yhat, a mode outside 0 .. 2, in mode SOFTMIN a tau that is not finite or <= 0, a ref_compat handle,
+ * T_pred too long.
+ * desire_set_recon_scope chooses the scope of the TRAINING loss's term (default DESIRE_RECON_SCOPE_AGENT: everything above as it is).  In scope
+ * SCENE with mode MIN or SOFTMIN desire_backward runs steps 1 - 4 on the full layout where it ran desire_recon_weights' steps, the gradient is
+ * the formula above with this w, and slot 0 of desire_train_loss* is
+ *   L_recon = (sum over w of count[w] * R[w]) / (sum over w of count[w]),
+ * the mean of recon[a] over the counted agents; d L_recon / d e[a, k] = W[window(a), k] / nvalid for a counted agent.  In mode MEAN the scope is
+ * ignored (the mean over k of a mean over agents is the mean over both): the default's launches and bits.  KL, the IOC cross-entropy and the IOC
+ * regression term keep their mean over K.  SCENE allocates "recon_E" / "recon_cnt" (and the four above) when it is set, so that no step
+ * allocates.  A host value like the mode: it can be changed between steps, not inside a captured graph.  DESIRE_ERR_ARG: a NULL handle, a scope
+ * outside 0 .. 1, T_pred too long; DESIRE_ERR_STATE: SCENE on a ref_compat handle. */
+#define DESIRE_RECON_SCOPE_AGENT 0      /* default: per agent, as above */
+#define DESIRE_RECON_SCOPE_SCENE 1
+int desire_set_recon_scope(desire_handle* h, int32_t scope);
+int desire_recon_weights_scene(desire_handle* h, const float* dev_fut, const float* dev_Yhat, int32_t mode, float tau,
+                               float* dev_e, float* dev_E, int32_t* dev_count, float* dev_w, int32_t* dev_winner, float* dev_recon, void* stream);
 /* (dev_eps == NULL after desire_set_rng: the eps of the forward's draw is regenerated, see "device generator") */
 int desire_backward(desire_handle* h, const float* dev_past, const float* dev_fut, const float* dev_eps, void* stream);
 int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream);
