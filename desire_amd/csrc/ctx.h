@@ -162,8 +162,8 @@ inline bool scene_grad_on(const desire_ctx* h) { return h->scene_grad || h->img_
 void enc_weights(desire_ctx* h, const char* prefix, EncArgs& e);     // the fp32 GRU weights of the encoder "enc_x" / "enc_y" (api_forward.hip)
 IocStepArgs ioc_step_args(desire_ctx* h, int t);               // what every launch of the step-wise IOC kernel shares (api_peer.hip)
 inline RngArgs rng_args(const desire_ctx* h) { return RngArgs{h->rng_state, 0u, 0u, 0u, h->rng_scene_base, h->rng_slot_base}; }      // the handle's generator
-int recon_ws_setup(desire_ctx* h);                             // "recon_e" / "recon_w" / "recon_win" / "recon_val" (api_ops.hip; idempotent)
-int recon_scene_ws_setup(desire_ctx* h);                       // those four and "recon_E" / "recon_cnt" of the scene scope (api_ops.hip; idempotent)
-// the reconstruction weights of the training step into the workspace tensors, in the handle's mode and scope (api_ops.hip; mode != MEAN)
+int recon_ws_setup(desire_ctx* h);                             // "recon_e" / "recon_w" / "recon_win" / "recon_val" (api_eval.hip; idempotent)
+int recon_scene_ws_setup(desire_ctx* h);                       // those four and "recon_E" / "recon_cnt" of the scene scope (api_eval.hip; idempotent)
+// the reconstruction weights of the training step into the workspace tensors, in the handle's mode and scope (api_eval.hip; mode != MEAN)
 void recon_weights_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
 int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)

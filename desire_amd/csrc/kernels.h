@@ -212,14 +212,14 @@ void launch_hx_rows(float* out, const float* HxHy, int ldhx, int n_scenes, int K
 void launch_peer_publish(const uint8_t* valid, const float* p_last, const float* Y, const float* HxHy, int ldhx, uint8_t* o_valid,
                          float* o_plast, float* o_Y, float* o_H, int n_scenes, int K, int mno, int T, int H, hipStream_t s);
 void launch_ioc_finish(float* Y, const float* dY, const float* st_score, const float* b_score, float* score, int R, int T, hipStream_t s);
-struct ConvArgs;
+// bf16 forms of the conv stack, deconv1 and the mask fc (kernels_bf16.hip; weight pointers = bf16 packs)
 void launch_deconv2_bf16(const ConvArgs& a, hipStream_t s);
 void launch_conv2_bf16(const ConvArgs& a, hipStream_t s);
 void launch_conv3_bf16(const ConvArgs& a, hipStream_t s);
 void launch_deconv1_bf16(const GemmArgs& a, hipStream_t s);     // a.Bp = bf16 pack [L, 2048]
 void launch_mask_bf16(const MaskArgs& a, hipStream_t s);        // a.Wp = bf16 pack [1024, H]
 void launch_deconv3_bf16(const ConvArgs& a, hipStream_t s);
-void launch_deconv34_bf16(const ConvArgs& a, const float* sc4, const float* sh4, hipStream_t s);   // a.Wp = W3 pack, a.w_raw = W4 chain pack    // kernels_bf16.hip; weight pointers = bf16 packs
+void launch_deconv34_bf16(const ConvArgs& a, const float* sc4, const float* sh4, hipStream_t s);   // a.Wp = W3 pack, a.w_raw = W4 chain pack
 
 void launch_neighbor_bins(const float* pos, const uint8_t* valid, int32_t* bins, int n_groups, int mno,
                           float nb_w, float nb_h, int G, const float* bin_tab, hipStream_t s);
@@ -249,90 +249,96 @@ void launch_gaussian_sample(const float* p, const float* nrm, float* out, int n,
 void launch_ade_fde(const float* Y, const float* fut, float* out, int n_scenes, int mno, int K, int T, float sx, float sy,
                     hipStream_t s);
 
-// ---- ranking by IOC score (kernels_rank.hip) ----
+// ---- the evaluation ops over the sample tensor Y [R, T_pred, 2] (kernels_rank.hip .. kernels_recon.hip; api_eval.hip) ----
+// Every launcher takes named blocks, filled by field name as EncArgs / RollArgs are: what every op reads and the handle's shape (EvalIn), the scales
+// (EvalScale), one ...Out block with every pointer the op writes -- the call's outputs under their names in include/desire_hip.h without `dev_`,
+// then the call's scratch -- and one ...Params / ...In block where more than three scalars or inputs of the op's own remain (scratch that is only
+// read, filled by an earlier launch, is among them).  No output and no scratch pointer is positional.
+struct EvalIn {
+    const float* Y; const float* fut; const uint8_t* present; const float* score;   // a null field = the call's NULL argument; the world ops' wscore is score
+    int n_scenes, mno, K, T;                                                          // the handle's shape, T = T_pred
+};
+struct EvalScale { float sx, sy, ux, uy; };                // the handle's normalisation, the call's unit
 struct RankHz { int n; int h[8]; };                        // horizons in frames, strictly increasing, by value in the kernel arguments
-constexpr int RANK_MAX_K = 4096;                           // k_rank_select keeps an agent's K scores and its order in LDS
-void launch_rank_select(const float* score, const float* Y, int32_t* order, float* top_Y, float* top_score, int n_scenes, int mno, int K,
-                        int T, int n_top, hipStream_t s);
-// tab [R, hz.n, 2] and cnt [A, hz.n] are scratch of the call (the handle's "rank_tab" / "rank_cnt")
-void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order, float* tab, int32_t* cnt, float* out, int n_scenes, int mno,
-                          int K, int T, int n_top, const RankHz& hz, float sx, float sy, float ux, float uy, hipStream_t s);
 
-// the table alone, for a caller that reduces it itself (desire_joint_metrics)
-void launch_sample_errors(const float* Y, const float* fut, float* tab, int32_t* cnt, int n_scenes, int mno, int K, int T, const RankHz& hz,
-                          float sx, float sy, float ux, float uy, hipStream_t s);
+// ---- ranking by IOC score (kernels_rank.hip) ----
+constexpr int RANK_MAX_K = 4096;                           // k_rank_select keeps an agent's K scores and its order in LDS
+struct RankOut { int32_t* order; float* top_Y; float* top_score; };
+void launch_rank_select(const EvalIn& in, int n_top, const RankOut& o, hipStream_t s);
+// scratch: tab [R, hz.n, 2] and cnt [A, hz.n] (the handle's "rank_tab" / "rank_cnt")
+struct ErrOut { float* out; float* tab; int32_t* cnt; };
+void launch_ranked_errors(const EvalIn& in, const int32_t* order, int n_top, const RankHz& hz, const EvalScale& sc, const ErrOut& o, hipStream_t s);
+// the table alone, for a caller that reduces it itself (desire_joint_metrics): o.out is not written
+void launch_sample_errors(const EvalIn& in, const RankHz& hz, const EvalScale& sc, const ErrOut& o, hipStream_t s);
 
 // ---- KDE log-likelihood (kernels_kde.hip) ----
-// w [R] (the score layout) and st [A, 2] = (den, h2) are scratch of the call (the handle's "kde_w" / "kde_st"); score and frame may be nullptr
-void launch_kde_nll(const float* Y, const float* fut, const float* score, float* w, float* st, float* out, float* frame, int n_scenes, int mno,
-                    int K, int T, const RankHz& hz, float sx, float sy, float ux, float uy, float log_floor, hipStream_t s);
+// frame may be nullptr, as in.score; scratch: w [R] (the score layout) and st [A, 2] = (den, h2) (the handle's "kde_w" / "kde_st")
+struct KdeOut { float* out; float* frame; float* w; float* st; };
+void launch_kde_nll(const EvalIn& in, const RankHz& hz, const EvalScale& sc, float log_floor, const KdeOut& o, hipStream_t s);
+// step 1 of launch_kde_nll alone, for a caller that weighs the samples itself (desire_occupancy): o.w and o.st from in.score
+void launch_kde_weights(const EvalIn& in, const KdeOut& o, hipStream_t s);
 
 // ---- score-ordered non-maximum suppression (kernels_select.hip) ----
-// score, mass, top_Y and top_score may be nullptr; no scratch
-void launch_select_diverse(const float* Y, const int32_t* order, const float* score, int32_t* order_out, int32_t* count, float* mass, float* top_Y,
-                           float* top_score, int n_scenes, int mno, int K, int T, int metric, int t_end, int n_top, float radius, float ux,
-                           float uy, hipStream_t s);
+// in.score, mass, top_Y and top_score may be nullptr; no scratch
+struct SelectParams { const int32_t* order; int metric, t_end, n_top; float radius; };
+struct SelectOut { int32_t* order_out; int32_t* count; float* mass; float* top_Y; float* top_score; };
+void launch_select_diverse(const EvalIn& in, const SelectParams& p, const EvalScale& sc, const SelectOut& o, hipStream_t s);
 
 // ---- joint (scene-level) metrics of the K samples (kernels_joint.hip) ----
-// exactly one of fut / present; score, tab (the filled "rank_tab"; with it jerr), first and out may be nullptr; jscore and jorder never
-void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* tab, int32_t* first,
-                          int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
-                          const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
+// exactly one of in.fut / in.present; in.score, tab (the filled "rank_tab"; with it jerr), first and out may be nullptr; jscore and jorder never
+struct JointParams { const float* tab; int n_top; float radius; };
+struct JointOut { int32_t* first; int32_t* cnt; float* jerr; float* jscore; int32_t* jorder; float* out; };
+void launch_joint_metrics(const EvalIn& in, const JointParams& p, const RankHz& hz, const EvalScale& sc, const JointOut& o, hipStream_t s);
 
 // ---- score-ordered non-maximum suppression of a window's K joint futures (kernels_worlds.hip) ----
-// present, wscore, wmass and wlabel may be nullptr; no scratch
-void launch_select_worlds(const float* Y, const uint8_t* present, const float* wscore, int32_t* worder, int32_t* wcount, float* wmass,
-                          int32_t* wlabel, int n_scenes, int mno, int K, int T, int metric, int reduce, int t_end, float radius, float ux, float uy,
-                          hipStream_t s);
+// in.present, in.score (the call's wscore), wmass and wlabel may be nullptr; no scratch
+struct WorldsParams { int metric, reduce, t_end; float radius; };
+struct WorldsOut { int32_t* worder; int32_t* wcount; float* wmass; int32_t* wlabel; };
+void launch_select_worlds(const EvalIn& in, const WorldsParams& p, const EvalScale& sc, const WorldsOut& o, hipStream_t s);
 
 // ---- n modes with covariances fitted to the K samples, and the mixture's likelihood (kernels_modes.hip); the same for a window's K joint
 // futures (kernels_scene_modes.hip).  What the two calls share travels by value in both kernels' arguments; the steps are modes_fit.h's ----
 struct ModesFitParams { int n, t_end, iters; float ux, uy, sx, sy, var_floor, log_floor; RankHz hz; };      // hz is read with fut only
 // label, mean, cov and passes may be nullptr; out (required with fut) and frame only with fut
 struct ModesFitOut { int32_t* label; int32_t* count; float* prob; float* mean; float* cov; int32_t* passes; float* out; float* frame; };
-// score and fut may be nullptr; no scratch
-void launch_fit_modes(const float* Y, const int32_t* order, const float* score, const float* fut, const ModesFitOut& o, const ModesFitParams& p,
-                      int n_scenes, int mno, int K, int T, hipStream_t s);
-// present, wscore and fut may be nullptr; no scratch.  chunk > 0: at most that many slots per chunk (the same bits)
-void launch_fit_scene_modes(const float* Y, const uint8_t* present, const int32_t* worder, const float* wscore, const float* fut,
-                            const ModesFitOut& o, const ModesFitParams& p, int n_scenes, int mno, int K, int T, int chunk, hipStream_t s);
+// in.score and in.fut may be nullptr; no scratch
+void launch_fit_modes(const EvalIn& in, const int32_t* order, const ModesFitOut& o, const ModesFitParams& p, hipStream_t s);
+// in.present, in.score (the call's wscore) and in.fut may be nullptr; no scratch.  chunk > 0: at most that many slots per chunk (the same bits)
+void launch_fit_scene_modes(const EvalIn& in, const int32_t* worder, const ModesFitOut& o, const ModesFitParams& p, int chunk, hipStream_t s);
 
 // ---- candidate ego plans against the K joint futures (kernels_plan.hip) ----
-// exactly one of fut / present; plans [n_scenes, M, T, 2]; w [n_scenes, K] is scratch of the call (the handle's "joint_js": the joint scores, then
-// their weights); score, ego, first, clear and blame may be nullptr
-void launch_plan_risk(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* plans, const int32_t* ego,
-                      float* w, int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
-                      const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
+// exactly one of in.fut / in.present; plans [n_scenes, M, T, 2]; in.score, ego, first, clear and blame may be nullptr; scratch: w [n_scenes, K] (the
+// handle's "joint_js": the joint scores, then their weights)
+struct PlanIn { const float* plans; const int32_t* ego; int M; };
+struct PlanOut { int32_t* first; float* clear; float* risk; float* blame; float* w; };
+void launch_plan_risk(const EvalIn& in, const PlanIn& pl, const RankHz& hz, const EvalScale& sc, float radius, const PlanOut& o, hipStream_t s);
 // desire_plan_risk_cond's three steps.  launch_plan_prior: launch_plan_risk's weight kernel alone, which also keeps prior [n_scenes, K] = the
-// logits p_k (the joint scores where a window's are all finite, else 0.f; the handle's "joint_je").  launch_plan_cond_weights
-// (kernels_plan_cond.hip): cw [n_scenes, M, K] from w and prior; dist, ess, support and cond may be nullptr; inv = 1 / (2 sigma^2).
-// launch_plan_risk_per_plan: launch_plan_risk's walk reading plan m's weights from cw[(scene * M + m) * K + k]
-void launch_plan_prior(const float* fut, const uint8_t* present, const float* score, float* w, float* prior, int n_scenes, int mno, int K, int T,
-                       hipStream_t s);
-void launch_plan_cond_weights(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* w,
-                              const float* prior, float* cw, float* dist, float* ess, float* support, int32_t* cond, int n_scenes, int mno, int K,
-                              int T, int M, int t_cond, float ux, float uy, float inv, hipStream_t s);
-void launch_plan_risk_per_plan(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* cw,
-                               int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
-                               const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s);
+// logits p_k (the joint scores where a window's are all finite, else 0.f; the handle's "joint_je"); both are scratch of the call.
+// launch_plan_cond_weights (kernels_plan_cond.hip): cw [n_scenes, M, K] from the filled w and prior; dist, ess, support and cond may be nullptr;
+// inv = 1 / (2 sigma^2).  launch_plan_risk_per_plan: launch_plan_risk's walk reading plan m's weights from cw[(scene * M + m) * K + k]; o.w is not used
+struct PlanPriorOut { float* w; float* prior; };
+void launch_plan_prior(const EvalIn& in, const PlanPriorOut& o, hipStream_t s);
+struct PlanCondParams { const float* w; const float* prior; int t_cond; float inv; };
+struct PlanCondOut { float* cw; float* dist; float* ess; float* support; int32_t* cond; };
+void launch_plan_cond_weights(const EvalIn& in, const PlanIn& pl, const PlanCondParams& p, const EvalScale& sc, const PlanCondOut& o, hipStream_t s);
+void launch_plan_risk_per_plan(const EvalIn& in, const PlanIn& pl, const float* cw, const RankHz& hz, const EvalScale& sc, float radius, const PlanOut& o,
+                               hipStream_t s);
 
 // ---- predicted occupancy maps of the K weighted samples (kernels_occ.hip) ----
-// step 1 of launch_kde_nll alone: w [R] (the score layout) and st [A, 2], the handle's "kde_w" / "kde_st"; score may be nullptr (kernels_kde.hip)
-void launch_kde_weights(const float* score, float* w, float* st, int n_scenes, int mno, int K, hipStream_t s);
-// exactly one of fut / present; w = the filled "kde_w"; mask + mask_of_scene (with viol), expv, hit (fut and mode AT only), viol and off may be nullptr
-void launch_occupancy(const float* Y, const float* fut, const uint8_t* present, const float* w, const uint8_t* mask, const int32_t* mask_of_scene,
-                      float* occ, float* expv, float* hit, float* viol, float* off, int n_scenes, int mno, int K, int T, int Oh, int Ow, int mode,
-                      const RankHz& hz, float sx, float sy, hipStream_t s);
+// exactly one of in.fut / in.present; w = the filled "kde_w" (launch_kde_weights); mask + mask_of_scene (with viol), exp, hit (in.fut and mode AT
+// only), viol and off may be nullptr
+struct OccParams { const float* w; const uint8_t* mask; const int32_t* mask_of_scene; int Oh, Ow, mode; };
+struct OccOut { float* occ; float* exp; float* hit; float* viol; float* off; };
+void launch_occupancy(const EvalIn& in, const OccParams& p, const RankHz& hz, const EvalScale& sc, const OccOut& o, hipStream_t s);
 
 // ---- per-sample reconstruction errors and the best-of-many / soft-min weights (kernels_recon.hip) ----
-// lmask / nfut: launch_loss_mask's; e, w [A, K], win [A], val [A] are all written (none may be nullptr); mode = DESIRE_RECON_*; no scratch
-void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
-                          int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s);
-// the scene scope (desire_recon_weights_scene): the same e, then per window E [n_scenes, K] and cnt [n_scenes], and w, win, val of the window on
-// every one of its slots; two launches (the streaming pass without its per-agent tail, then one workgroup per window); none may be nullptr
-void launch_recon_weights_scene(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* E, int32_t* cnt, float* w,
-                                int32_t* win, float* val, int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy,
-                                hipStream_t s);
+// lmask / nfut: launch_loss_mask's; mode = DESIRE_RECON_*; no scratch.  Every field of the op's scope is written (none may be nullptr): e, w [A, K],
+// winner [A], recon [A]; in the scene scope (desire_recon_weights_scene) the same e, then per window E [n_scenes, K] and count [n_scenes], and w,
+// winner, recon of the window on every one of its slots -- two launches (the streaming pass without its per-agent tail, then one workgroup per window)
+struct ReconParams { const uint8_t* lmask; const float* nfut; int mode; float tau; };
+struct ReconOut { float* e; float* E; int32_t* count; float* w; int32_t* winner; float* recon; };     // E, count: the scene scope only
+void launch_recon_weights(const EvalIn& in, const ReconParams& p, const EvalScale& sc, const ReconOut& o, hipStream_t s);
+void launch_recon_weights_scene(const EvalIn& in, const ReconParams& p, const EvalScale& sc, const ReconOut& o, hipStream_t s);
 
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);

@@ -167,13 +167,11 @@ __global__ __launch_bounds__(64) void k_joint_pick(const float* __restrict__ js,
 
 }  // namespace
 
-void launch_joint_metrics(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* tab, int32_t* first,
-                          int32_t* cnt, float* jerr, float* jscore, int32_t* jorder, float* out, int n_scenes, int mno, int K, int T, int n_top,
-                          const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
-    const int TC = joint_chunk_frames(mno, T);
-    const size_t lds = JointLds(mno, TC).bytes();
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    hipLaunchKernelGGL(k_joint_unit, dim3((unsigned)((size_t)n_scenes * (K + 1))), dim3(EVAL_THREADS), lds, s, Y, fut, present, score, tab, first, cnt,
-                       jerr, jscore, mno, K, T, TC, vec, sx, sy, ux, uy, radius * radius, hz);
-    hipLaunchKernelGGL(k_joint_pick, dim3(n_scenes), dim3(64), 0, s, jscore, jerr, cnt, jorder, out, K, hz.n, n_top);
+void launch_joint_metrics(const EvalIn& in, const JointParams& p, const RankHz& hz, const EvalScale& sc, const JointOut& o, hipStream_t s) {
+    const int TC = joint_chunk_frames(in.mno, in.T);
+    const size_t lds = JointLds(in.mno, TC).bytes();
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0;
+    hipLaunchKernelGGL(k_joint_unit, dim3((unsigned)((size_t)in.n_scenes * (in.K + 1))), dim3(EVAL_THREADS), lds, s, in.Y, in.fut, in.present, in.score,
+                       p.tab, o.first, o.cnt, o.jerr, o.jscore, in.mno, in.K, in.T, TC, vec, sc.sx, sc.sy, sc.ux, sc.uy, p.radius * p.radius, hz);
+    hipLaunchKernelGGL(k_joint_pick, dim3(in.n_scenes), dim3(64), 0, s, o.jscore, o.jerr, o.cnt, o.jorder, o.out, in.K, hz.n, p.n_top);
 }

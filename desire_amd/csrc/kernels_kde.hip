@@ -158,24 +158,24 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_kde_nll(const float* __restric
 }  // namespace
 
 // step 1 alone, for a caller that weighs the samples itself (desire_occupancy): the same kernel into the same scratch
-void launch_kde_weights(const float* score, float* w, float* st, int n_scenes, int mno, int K, hipStream_t s) {
-    const int A = n_scenes * mno;
-    hipLaunchKernelGGL(k_kde_weights, dim3((A + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, s, score, w, st, A, mno, K);
+void launch_kde_weights(const EvalIn& in, const KdeOut& o, hipStream_t s) {
+    const int A = in.n_scenes * in.mno;
+    hipLaunchKernelGGL(k_kde_weights, dim3((A + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, s, in.score, o.w, o.st, A, in.mno, in.K);
 }
 
-void launch_kde_nll(const float* Y, const float* fut, const float* score, float* w, float* st, float* out, float* frame, int n_scenes, int mno,
-                    int K, int T, const RankHz& hz, float sx, float sy, float ux, float uy, float log_floor, hipStream_t s) {
+void launch_kde_nll(const EvalIn& in, const RankHz& hz, const EvalScale& sc, float log_floor, const KdeOut& o, hipStream_t s) {
     int SA = 1;
-    if (!kde_geometry(T, &SA)) return;                                // (refused by the caller before it gets here)
-    const int A = n_scenes * mno;
-    hipLaunchKernelGGL(k_kde_weights, dim3((A + EVAL_THREADS - 1) / EVAL_THREADS), dim3(EVAL_THREADS), 0, s, score, w, st, A, mno, K);
-    const size_t lds = KdeLds(T, SA).bytes();
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 7) == 0;
+    if (!kde_geometry(in.T, &SA)) return;                             // (refused by the caller before it gets here)
+    launch_kde_weights(in, o, s);
+    const int A = in.n_scenes * in.mno;
+    const size_t lds = KdeLds(in.T, SA).bytes();
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 7) == 0;
     const dim3 grid((A + SA - 1) / SA), block(EVAL_THREADS);
-    if (K <= 8)
-        hipLaunchKernelGGL(k_kde_nll<8>, grid, block, lds, s, Y, fut, w, st, out, frame, A, mno, K, T, SA, vec, sx, sy, ux, uy, log_floor, hz);
-    else if (K <= 24)
-        hipLaunchKernelGGL(k_kde_nll<24>, grid, block, lds, s, Y, fut, w, st, out, frame, A, mno, K, T, SA, vec, sx, sy, ux, uy, log_floor, hz);
-    else
-        hipLaunchKernelGGL(k_kde_nll<0>, grid, block, lds, s, Y, fut, w, st, out, frame, A, mno, K, T, SA, vec, sx, sy, ux, uy, log_floor, hz);
+#define KDE_LAUNCH(KK)                                                                                                                         \
+    hipLaunchKernelGGL(k_kde_nll<KK>, grid, block, lds, s, in.Y, in.fut, o.w, o.st, o.out, o.frame, A, in.mno, in.K, in.T, SA, vec, sc.sx, sc.sy, \
+                       sc.ux, sc.uy, log_floor, hz)
+    if (in.K <= 8) KDE_LAUNCH(8);
+    else if (in.K <= 24) KDE_LAUNCH(24);
+    else KDE_LAUNCH(0);
+#undef KDE_LAUNCH
 }

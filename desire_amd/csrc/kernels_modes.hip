@@ -201,13 +201,12 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_modes(const ModesArgs A) {
 
 }  // namespace
 
-void launch_fit_modes(const float* Y, const int32_t* order, const float* score, const float* fut, const ModesFitOut& o, const ModesFitParams& p,
-                      int n_scenes, int mno, int K, int T, hipStream_t s) {
+void launch_fit_modes(const EvalIn& in, const int32_t* order, const ModesFitOut& o, const ModesFitParams& p, hipStream_t s) {
     int SC = 1, G = 1;
-    if (!modes_geometry(mno, K, T, p.n, &SC, &G)) return;              // (refused by the caller before it gets here)
-    const int n_sc = eval_chunks(mno, SC);
-    const size_t lds = ModesLds(T, SC, K, p.n).bytes();
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    const ModesArgs a{Y, order, score, fut, o, p, mno, K, T, SC, n_sc, G, vec};
-    hipLaunchKernelGGL(k_fit_modes, dim3((unsigned)((size_t)n_scenes * n_sc)), dim3(EVAL_THREADS), lds, s, a);
+    if (!modes_geometry(in.mno, in.K, in.T, p.n, &SC, &G)) return;     // (refused by the caller before it gets here)
+    const int n_sc = eval_chunks(in.mno, SC);
+    const size_t lds = ModesLds(in.T, SC, in.K, p.n).bytes();
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0;
+    const ModesArgs a{in.Y, order, in.score, in.fut, o, p, in.mno, in.K, in.T, SC, n_sc, G, vec};
+    hipLaunchKernelGGL(k_fit_modes, dim3((unsigned)((size_t)in.n_scenes * n_sc)), dim3(EVAL_THREADS), lds, s, a);
 }

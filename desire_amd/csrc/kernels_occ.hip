@@ -169,15 +169,14 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_occupancy(const float* __restr
 
 }  // namespace
 
-void launch_occupancy(const float* Y, const float* fut, const uint8_t* present, const float* w, const uint8_t* mask, const int32_t* mask_of_scene,
-                      float* occ, float* expv, float* hit, float* viol, float* off, int n_scenes, int mno, int K, int T, int Oh, int Ow, int mode,
-                      const RankHz& hz, float sx, float sy, hipStream_t s) {
-    const int until = mode == DESIRE_OCC_UNTIL;
+void launch_occupancy(const EvalIn& in, const OccParams& p, const RankHz& hz, const EvalScale& sc, const OccOut& o, hipStream_t s) {
+    const int until = p.mode == DESIRE_OCC_UNTIL;
     int KC = 1, FC = 1, rows = 1;
-    if (!occupancy_geometry(K, until ? hz.h[hz.n - 1] : 1, Oh, Ow, until, &KC, &FC, &rows)) return;      // (refused by the caller before it gets here)
-    const int n_bands = eval_chunks(Oh, rows);
-    const size_t lds = OccLds(rows * Ow, KC * FC, until).bytes();
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    hipLaunchKernelGGL(k_occupancy, dim3((unsigned)((size_t)n_scenes * hz.n * n_bands)), dim3(EVAL_THREADS), lds, s, Y, fut, present, w, mask,
-                       mask_of_scene, occ, expv, hit, viol, off, mno, K, T, Oh, Ow, until, KC, FC, rows, n_bands, vec, sx, sy, hz);
+    if (!occupancy_geometry(in.K, until ? hz.h[hz.n - 1] : 1, p.Oh, p.Ow, until, &KC, &FC, &rows)) return;      // (refused by the caller before it gets here)
+    const int n_bands = eval_chunks(p.Oh, rows);
+    const size_t lds = OccLds(rows * p.Ow, KC * FC, until).bytes();
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0;
+    hipLaunchKernelGGL(k_occupancy, dim3((unsigned)((size_t)in.n_scenes * hz.n * n_bands)), dim3(EVAL_THREADS), lds, s, in.Y, in.fut, in.present, p.w,
+                       p.mask, p.mask_of_scene, o.occ, o.exp, o.hit, o.viol, o.off, in.mno, in.K, in.T, p.Oh, p.Ow, until, KC, FC, rows, n_bands, vec,
+                       sc.sx, sc.sy, hz);
 }

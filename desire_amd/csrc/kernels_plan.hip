@@ -237,33 +237,31 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_plan_risk(const float* __restr
 
 }  // namespace
 
+// w: the window's weights [n_scenes, K], or with PER_PLAN_W every plan's [n_scenes, M, K]
 template <bool PER_PLAN_W>
-static void plan_risk_launch(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* w,
-                             int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M, const RankHz& hz,
-                             float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
+static void plan_risk_launch(const EvalIn& in, const PlanIn& pl, const float* w, const RankHz& hz, const EvalScale& sc, float radius, const PlanOut& o,
+                             hipStream_t s) {
     int PC = 0, TC = 0;
-    plan_geometry(mno, T, M, &PC, &TC);
-    const size_t lds = PlanLds(mno, PC, TC).bytes();
-    const int vecY = (reinterpret_cast<uintptr_t>(Y) & 15) == 0, vecP = (reinterpret_cast<uintptr_t>(plans) & 15) == 0;
-    const size_t n_ch = (size_t)((M + PC - 1) / PC);
-    hipLaunchKernelGGL(k_plan_risk<PER_PLAN_W>, dim3((unsigned)((size_t)n_scenes * n_ch)), dim3(EVAL_THREADS), lds, s, Y, fut, present, plans, ego, w,
-                       first, clear, risk, blame, M, mno, K, T, PC, TC, vecY, vecP, sx, sy, ux, uy, radius * radius, hz);
+    plan_geometry(in.mno, in.T, pl.M, &PC, &TC);
+    const size_t lds = PlanLds(in.mno, PC, TC).bytes();
+    const int vecY = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0, vecP = (reinterpret_cast<uintptr_t>(pl.plans) & 15) == 0;
+    const size_t n_ch = (size_t)((pl.M + PC - 1) / PC);
+    hipLaunchKernelGGL(k_plan_risk<PER_PLAN_W>, dim3((unsigned)((size_t)in.n_scenes * n_ch)), dim3(EVAL_THREADS), lds, s, in.Y, in.fut, in.present,
+                       pl.plans, pl.ego, w, o.first, o.clear, o.risk, o.blame, pl.M, in.mno, in.K, in.T, PC, TC, vecY, vecP, sc.sx, sc.sy, sc.ux, sc.uy,
+                       radius * radius, hz);
 }
 
-void launch_plan_risk(const float* Y, const float* fut, const uint8_t* present, const float* score, const float* plans, const int32_t* ego,
-                      float* w, int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
-                      const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
-    hipLaunchKernelGGL(k_plan_weights<false>, dim3(n_scenes), dim3(EVAL_THREADS), 0, s, fut, present, score, w, static_cast<float*>(nullptr), mno, K, T);
-    plan_risk_launch<false>(Y, fut, present, plans, ego, w, first, clear, risk, blame, n_scenes, mno, K, T, M, hz, sx, sy, ux, uy, radius, s);
+void launch_plan_risk(const EvalIn& in, const PlanIn& pl, const RankHz& hz, const EvalScale& sc, float radius, const PlanOut& o, hipStream_t s) {
+    hipLaunchKernelGGL(k_plan_weights<false>, dim3(in.n_scenes), dim3(EVAL_THREADS), 0, s, in.fut, in.present, in.score, o.w,
+                       static_cast<float*>(nullptr), in.mno, in.K, in.T);
+    plan_risk_launch<false>(in, pl, o.w, hz, sc, radius, o, s);
 }
 
-void launch_plan_prior(const float* fut, const uint8_t* present, const float* score, float* w, float* prior, int n_scenes, int mno, int K, int T,
-                       hipStream_t s) {
-    hipLaunchKernelGGL(k_plan_weights<true>, dim3(n_scenes), dim3(EVAL_THREADS), 0, s, fut, present, score, w, prior, mno, K, T);
+void launch_plan_prior(const EvalIn& in, const PlanPriorOut& o, hipStream_t s) {
+    hipLaunchKernelGGL(k_plan_weights<true>, dim3(in.n_scenes), dim3(EVAL_THREADS), 0, s, in.fut, in.present, in.score, o.w, o.prior, in.mno, in.K, in.T);
 }
 
-void launch_plan_risk_per_plan(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* cw,
-                               int32_t* first, float* clear, float* risk, float* blame, int n_scenes, int mno, int K, int T, int M,
-                               const RankHz& hz, float sx, float sy, float ux, float uy, float radius, hipStream_t s) {
-    plan_risk_launch<true>(Y, fut, present, plans, ego, cw, first, clear, risk, blame, n_scenes, mno, K, T, M, hz, sx, sy, ux, uy, radius, s);
+void launch_plan_risk_per_plan(const EvalIn& in, const PlanIn& pl, const float* cw, const RankHz& hz, const EvalScale& sc, float radius, const PlanOut& o,
+                               hipStream_t s) {
+    plan_risk_launch<true>(in, pl, cw, hz, sc, radius, o, s);
 }

@@ -156,14 +156,13 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_plan_cond_weights(const float*
 
 }  // namespace
 
-void launch_plan_cond_weights(const float* Y, const float* fut, const uint8_t* present, const float* plans, const int32_t* ego, const float* w,
-                              const float* prior, float* cw, float* dist, float* ess, float* support, int32_t* cond, int n_scenes, int mno, int K,
-                              int T, int M, int t_cond, float ux, float uy, float inv, hipStream_t s) {
+void launch_plan_cond_weights(const EvalIn& in, const PlanIn& pl, const PlanCondParams& p, const EvalScale& sc, const PlanCondOut& o, hipStream_t s) {
     int PC = 0, TC = 0, rows = 0;
-    plan_cond_geometry(K, t_cond, M, &PC, &TC, &rows);
-    const size_t lds = PlanCondLds(K, PC, TC, rows).bytes();
-    const int vecY = (reinterpret_cast<uintptr_t>(Y) & 15) == 0, vecP = (reinterpret_cast<uintptr_t>(plans) & 15) == 0;
-    const size_t n_ch = (size_t)((M + PC - 1) / PC);
-    hipLaunchKernelGGL(k_plan_cond_weights, dim3((unsigned)((size_t)n_scenes * n_ch)), dim3(EVAL_THREADS), lds, s, Y, fut, present, plans, ego, w,
-                       prior, cw, dist, ess, support, cond, M, mno, K, T, t_cond, PC, TC, rows, vecY, vecP, ux, uy, inv);
+    plan_cond_geometry(in.K, p.t_cond, pl.M, &PC, &TC, &rows);
+    const size_t lds = PlanCondLds(in.K, PC, TC, rows).bytes();
+    const int vecY = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0, vecP = (reinterpret_cast<uintptr_t>(pl.plans) & 15) == 0;
+    const size_t n_ch = (size_t)((pl.M + PC - 1) / PC);
+    hipLaunchKernelGGL(k_plan_cond_weights, dim3((unsigned)((size_t)in.n_scenes * n_ch)), dim3(EVAL_THREADS), lds, s, in.Y, in.fut, in.present, pl.plans,
+                       pl.ego, p.w, p.prior, o.cw, o.dist, o.ess, o.support, o.cond, pl.M, in.mno, in.K, in.T, p.t_cond, PC, TC, rows, vecY, vecP, sc.ux,
+                       sc.uy, p.inv);
 }

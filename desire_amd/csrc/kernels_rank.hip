@@ -130,28 +130,26 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_ranked_pick(const float* __res
 
 }  // namespace
 
-void launch_rank_select(const float* score, const float* Y, int32_t* order, float* top_Y, float* top_score, int n_scenes, int mno, int K,
-                        int T, int n_top, hipStream_t s) {
-    hipLaunchKernelGGL(k_rank_select, dim3(n_scenes * mno), dim3(64), (size_t)K * 8, s, score, Y, order, top_Y, top_score, mno, K, T, n_top);
+void launch_rank_select(const EvalIn& in, int n_top, const RankOut& o, hipStream_t s) {
+    hipLaunchKernelGGL(k_rank_select, dim3(in.n_scenes * in.mno), dim3(64), (size_t)in.K * 8, s, in.score, in.Y, o.order, o.top_Y, o.top_score, in.mno,
+                       in.K, in.T, n_top);
 }
 
 // The table alone: tab [R, hz.n, 2] and cnt [A, hz.n] (desire_joint_metrics sums the same rows per (window, k)).
-void launch_sample_errors(const float* Y, const float* fut, float* tab, int32_t* cnt, int n_scenes, int mno, int K, int T, const RankHz& hz,
-                          float sx, float sy, float ux, float uy, hipStream_t s) {
+void launch_sample_errors(const EvalIn& in, const RankHz& hz, const EvalScale& sc, const ErrOut& o, hipStream_t s) {
     int SC = 1, KC = 1;
-    if (!sample_errors_geometry(mno, K, T, &SC, &KC)) return;         // (refused by the caller before it gets here)
-    const int n_sc = eval_chunks(mno, SC), n_kc = eval_chunks(K, KC);
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    hipLaunchKernelGGL(k_sample_errors, dim3((unsigned)((size_t)n_scenes * n_sc * n_kc)), dim3(EVAL_THREADS), ErrLds(T, SC, KC).bytes(), s, Y, fut,
-                       tab, cnt, mno, K, T, SC, KC, n_sc, n_kc, vec, sx, sy, ux, uy, hz);
+    if (!sample_errors_geometry(in.mno, in.K, in.T, &SC, &KC)) return;         // (refused by the caller before it gets here)
+    const int n_sc = eval_chunks(in.mno, SC), n_kc = eval_chunks(in.K, KC);
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0;
+    hipLaunchKernelGGL(k_sample_errors, dim3((unsigned)((size_t)in.n_scenes * n_sc * n_kc)), dim3(EVAL_THREADS), ErrLds(in.T, SC, KC).bytes(), s, in.Y,
+                       in.fut, o.tab, o.cnt, in.mno, in.K, in.T, SC, KC, n_sc, n_kc, vec, sc.sx, sc.sy, sc.ux, sc.uy, hz);
 }
 
-void launch_ranked_errors(const float* Y, const float* fut, const int32_t* order, float* tab, int32_t* cnt, float* out, int n_scenes, int mno,
-                          int K, int T, int n_top, const RankHz& hz, float sx, float sy, float ux, float uy, hipStream_t s) {
+void launch_ranked_errors(const EvalIn& in, const int32_t* order, int n_top, const RankHz& hz, const EvalScale& sc, const ErrOut& o, hipStream_t s) {
     int SC = 1, KC = 1;
-    if (!sample_errors_geometry(mno, K, T, &SC, &KC)) return;         // (refused by the caller before it gets here)
-    launch_sample_errors(Y, fut, tab, cnt, n_scenes, mno, K, T, hz, sx, sy, ux, uy, s);
-    const size_t n = (size_t)n_scenes * mno * hz.n;
-    hipLaunchKernelGGL(k_ranked_pick, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, s, tab, cnt, order, out,
-                       n_scenes * mno, mno, K, hz.n, n_top);
+    if (!sample_errors_geometry(in.mno, in.K, in.T, &SC, &KC)) return;         // (refused by the caller before it gets here)
+    launch_sample_errors(in, hz, sc, o, s);
+    const size_t n = (size_t)in.n_scenes * in.mno * hz.n;
+    hipLaunchKernelGGL(k_ranked_pick, dim3((unsigned)((n + EVAL_THREADS - 1) / EVAL_THREADS)), dim3(EVAL_THREADS), 0, s, o.tab, o.cnt, order, o.out,
+                       in.n_scenes * in.mno, in.mno, in.K, hz.n, n_top);
 }

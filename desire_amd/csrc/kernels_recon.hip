@@ -197,25 +197,23 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_recon_scene(const uint8_t* __r
 
 // the streaming pass: with the per-agent tail (TAIL) or e only
 template <bool TAIL>
-static void launch_recon_pass(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
-                              int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s) {
+static void launch_recon_pass(const EvalIn& in, const ReconParams& p, const EvalScale& sc, const ReconOut& o, hipStream_t s) {
     int SC = 1, KC = 1;
-    if (!recon_geometry(mno, K, T, &SC, &KC)) return;                   // (refused by the caller before it gets here)
-    const int n_sc = eval_chunks(mno, SC);
-    const size_t lds = ReconLds(T, SC, KC).bytes();
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    hipLaunchKernelGGL(k_recon_weights<TAIL>, dim3((unsigned)((size_t)n_scenes * n_sc)), dim3(EVAL_THREADS), lds, s, Y, fut, lmask, nfut, e, w, win,
-                       val, n_scenes, mno, K, T, SC, n_sc, KC, vec, mode, tau, sx, sy);
+    if (!recon_geometry(in.mno, in.K, in.T, &SC, &KC)) return;          // (refused by the caller before it gets here)
+    const int n_sc = eval_chunks(in.mno, SC);
+    const size_t lds = ReconLds(in.T, SC, KC).bytes();
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0;
+    hipLaunchKernelGGL(k_recon_weights<TAIL>, dim3((unsigned)((size_t)in.n_scenes * n_sc)), dim3(EVAL_THREADS), lds, s, in.Y, in.fut, p.lmask, p.nfut,
+                       o.e, TAIL ? o.w : nullptr, TAIL ? o.winner : nullptr, TAIL ? o.recon : nullptr, in.n_scenes, in.mno, in.K, in.T, SC, n_sc, KC,
+                       vec, p.mode, p.tau, sc.sx, sc.sy);
 }
 
-void launch_recon_weights(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* w, int32_t* win, float* val,
-                          int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy, hipStream_t s) {
-    launch_recon_pass<true>(Y, fut, lmask, nfut, e, w, win, val, n_scenes, mno, K, T, mode, tau, sx, sy, s);
+void launch_recon_weights(const EvalIn& in, const ReconParams& p, const EvalScale& sc, const ReconOut& o, hipStream_t s) {
+    launch_recon_pass<true>(in, p, sc, o, s);
 }
 
-void launch_recon_weights_scene(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, float* e, float* E, int32_t* cnt, float* w,
-                                int32_t* win, float* val, int n_scenes, int mno, int K, int T, int mode, float tau, float sx, float sy,
-                                hipStream_t s) {
-    launch_recon_pass<false>(Y, fut, lmask, nfut, e, nullptr, nullptr, nullptr, n_scenes, mno, K, T, mode, tau, sx, sy, s);
-    hipLaunchKernelGGL(k_recon_scene, dim3((unsigned)n_scenes), dim3(EVAL_THREADS), 0, s, lmask, e, E, cnt, w, win, val, mno, K, mode, tau);
+void launch_recon_weights_scene(const EvalIn& in, const ReconParams& p, const EvalScale& sc, const ReconOut& o, hipStream_t s) {
+    launch_recon_pass<false>(in, p, sc, o, s);
+    hipLaunchKernelGGL(k_recon_scene, dim3((unsigned)in.n_scenes), dim3(EVAL_THREADS), 0, s, p.lmask, o.e, o.E, o.count, o.w, o.winner, o.recon, in.mno,
+                       in.K, p.mode, p.tau);
 }

@@ -295,14 +295,13 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_fit_scene_modes(const SceneMod
 
 }  // namespace
 
-void launch_fit_scene_modes(const float* Y, const uint8_t* present, const int32_t* worder, const float* wscore, const float* fut,
-                            const ModesFitOut& o, const ModesFitParams& p, int n_scenes, int mno, int K, int T, int chunk, hipStream_t s) {
+void launch_fit_scene_modes(const EvalIn& in, const int32_t* worder, const ModesFitOut& o, const ModesFitParams& p, int chunk, hipStream_t s) {
     int SC = 1;
-    if (!scene_modes_geometry(mno, K, T, p.n, &SC)) return;            // (refused by the caller before it gets here)
+    if (!scene_modes_geometry(in.mno, in.K, in.T, p.n, &SC)) return;    // (refused by the caller before it gets here)
     if (chunk > 0) SC = eval_min(SC, chunk);                            // a smaller chunk than the LDS holds: the same bits (the tests' lever)
-    const size_t lds = SceneModesLds(T, SC, K, p.n, mno).bytes();
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    const SceneModesArgs a{Y, present, worder, wscore, fut, o.label, o.count, o.prob, o.mean, o.cov, o.passes, o.out, o.frame, mno, K, T, p.n,
-                           p.t_end, p.iters, SC, vec, p.sx, p.sy, p.ux, p.uy, p.var_floor, p.log_floor, p.hz};
-    hipLaunchKernelGGL(k_fit_scene_modes, dim3((unsigned)n_scenes), dim3(EVAL_THREADS), lds, s, a);
+    const size_t lds = SceneModesLds(in.T, SC, in.K, p.n, in.mno).bytes();
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0;
+    const SceneModesArgs a{in.Y, in.present, worder, in.score, in.fut, o.label, o.count, o.prob, o.mean, o.cov, o.passes, o.out, o.frame, in.mno, in.K,
+                           in.T, p.n, p.t_end, p.iters, SC, vec, p.sx, p.sy, p.ux, p.uy, p.var_floor, p.log_floor, p.hz};
+    hipLaunchKernelGGL(k_fit_scene_modes, dim3((unsigned)in.n_scenes), dim3(EVAL_THREADS), lds, s, a);
 }

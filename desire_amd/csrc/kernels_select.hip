@@ -216,20 +216,18 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_select_diverse(const float* __
 
 }  // namespace
 
-void launch_select_diverse(const float* Y, const int32_t* order, const float* score, int32_t* order_out, int32_t* count, float* mass, float* top_Y,
-                           float* top_score, int n_scenes, int mno, int K, int T, int metric, int t_end, int n_top, float radius, float ux,
-                           float uy, hipStream_t s) {
+void launch_select_diverse(const EvalIn& in, const SelectParams& p, const EvalScale& sc, const SelectOut& o, hipStream_t s) {
     int SC = 1, G = 1;
-    if (!select_geometry(mno, K, metric, t_end, &SC, &G)) return;       // (refused by the caller before it gets here)
-    const int n_sc = eval_chunks(mno, SC);
-    const size_t lds = SelLds(SelLds::staged(metric, t_end), SC, K).bytes();
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    const dim3 grid((unsigned)((size_t)n_scenes * n_sc)), block(EVAL_THREADS);
-#define SD_LAUNCH(M)                                                                                                                        \
-    hipLaunchKernelGGL(k_select_diverse<M>, grid, block, lds, s, Y, order, score, order_out, count, mass, top_Y, top_score, n_scenes, mno, K, T, \
-                       t_end, SC, n_sc, G, vec, n_top, radius, ux, uy)
-    if (metric == DESIRE_DIST_FINAL) SD_LAUNCH(DESIRE_DIST_FINAL);
-    else if (metric == DESIRE_DIST_MAX) SD_LAUNCH(DESIRE_DIST_MAX);
+    if (!select_geometry(in.mno, in.K, p.metric, p.t_end, &SC, &G)) return;       // (refused by the caller before it gets here)
+    const int n_sc = eval_chunks(in.mno, SC);
+    const size_t lds = SelLds(SelLds::staged(p.metric, p.t_end), SC, in.K).bytes();
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0;
+    const dim3 grid((unsigned)((size_t)in.n_scenes * n_sc)), block(EVAL_THREADS);
+#define SD_LAUNCH(M)                                                                                                                           \
+    hipLaunchKernelGGL(k_select_diverse<M>, grid, block, lds, s, in.Y, p.order, in.score, o.order_out, o.count, o.mass, o.top_Y, o.top_score,   \
+                       in.n_scenes, in.mno, in.K, in.T, p.t_end, SC, n_sc, G, vec, p.n_top, p.radius, sc.ux, sc.uy)
+    if (p.metric == DESIRE_DIST_FINAL) SD_LAUNCH(DESIRE_DIST_FINAL);
+    else if (p.metric == DESIRE_DIST_MAX) SD_LAUNCH(DESIRE_DIST_MAX);
     else SD_LAUNCH(DESIRE_DIST_MEAN);
 #undef SD_LAUNCH
 }

@@ -207,19 +207,17 @@ __global__ __launch_bounds__(EVAL_THREADS) void k_select_worlds(const float* __r
 
 }  // namespace
 
-void launch_select_worlds(const float* Y, const uint8_t* present, const float* wscore, int32_t* worder, int32_t* wcount, float* wmass,
-                          int32_t* wlabel, int n_scenes, int mno, int K, int T, int metric, int reduce, int t_end, float radius, float ux, float uy,
-                          hipStream_t s) {
+void launch_select_worlds(const EvalIn& in, const WorldsParams& p, const EvalScale& sc, const WorldsOut& o, hipStream_t s) {
     int SC = 1;
-    if (!worlds_geometry(mno, K, metric, t_end, &SC)) return;           // (refused by the caller before it gets here)
-    const size_t lds = WorldsLds(SelLds::staged(metric, t_end), SC, K, mno).bytes();
-    const int vec = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
-    const dim3 grid((unsigned)n_scenes), block(EVAL_THREADS);
-#define SW_LAUNCH(M)                                                                                                                          \
-    hipLaunchKernelGGL(k_select_worlds<M>, grid, block, lds, s, Y, present, wscore, worder, wcount, wmass, wlabel, mno, K, T, t_end, SC, vec, \
-                       reduce, radius, ux, uy)
-    if (metric == DESIRE_DIST_FINAL) SW_LAUNCH(DESIRE_DIST_FINAL);
-    else if (metric == DESIRE_DIST_MAX) SW_LAUNCH(DESIRE_DIST_MAX);
+    if (!worlds_geometry(in.mno, in.K, p.metric, p.t_end, &SC)) return;           // (refused by the caller before it gets here)
+    const size_t lds = WorldsLds(SelLds::staged(p.metric, p.t_end), SC, in.K, in.mno).bytes();
+    const int vec = (reinterpret_cast<uintptr_t>(in.Y) & 15) == 0;
+    const dim3 grid((unsigned)in.n_scenes), block(EVAL_THREADS);
+#define SW_LAUNCH(M)                                                                                                                            \
+    hipLaunchKernelGGL(k_select_worlds<M>, grid, block, lds, s, in.Y, in.present, in.score, o.worder, o.wcount, o.wmass, o.wlabel, in.mno, in.K, \
+                       in.T, p.t_end, SC, vec, p.reduce, p.radius, sc.ux, sc.uy)
+    if (p.metric == DESIRE_DIST_FINAL) SW_LAUNCH(DESIRE_DIST_FINAL);
+    else if (p.metric == DESIRE_DIST_MAX) SW_LAUNCH(DESIRE_DIST_MAX);
     else SW_LAUNCH(DESIRE_DIST_MEAN);
 #undef SW_LAUNCH
 }

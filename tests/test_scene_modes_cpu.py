@@ -43,7 +43,7 @@ def test_the_abi_is_declared_listed_and_exported():
     # the limit of the LDS plan is stated as the same formula in the header and in the message
     formula = "8 * (K + n_modes) * (T_pred | 1) + 20 * n_modes * T_pred + 12 * K * n_modes + 12 * K + 20 * n_modes + 4 * n_modes * ceil(K / 32) + 12 * T_pred + 4 * mno"
     assert formula in re.sub(r"\s*\n \*\s*", " ", text)
-    with open(os.path.join(ROOT, "desire_amd", "csrc", "api_ops.hip")) as fh:
+    with open(os.path.join(ROOT, "desire_amd", "csrc", "api_eval.hip")) as fh:
         assert "scene-mode kernel's LDS" in fh.read()
 
 
