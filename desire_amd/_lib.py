@@ -30,6 +30,7 @@ EXPORTS = [
     "desire_set_recon_loss", "desire_recon_weights", "desire_occupancy", "desire_plan_risk", "desire_fit_modes",
     "desire_select_worlds", "desire_fit_scene_modes", "desire_plan_risk_cond",
     "desire_set_recon_scope", "desire_recon_weights_scene",
+    "desire_set_collision_loss", "desire_collision_loss",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
@@ -135,6 +136,8 @@ def load() -> C.CDLL:
     lib.desire_recon_weights.argtypes = [vp, f32p, f32p, i32, C.c_float, f32p, f32p, vp, f32p, vp]
     lib.desire_set_recon_scope.argtypes = [vp, i32]
     lib.desire_recon_weights_scene.argtypes = [vp, f32p, f32p, i32, C.c_float, f32p, f32p, vp, f32p, vp, f32p, vp]
+    lib.desire_set_collision_loss.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
+    lib.desire_collision_loss.argtypes = [vp, f32p, f32p, C.c_float, C.c_float, C.c_float, f32p, vp, f32p, f32p, vp]
     lib.desire_peer_export.argtypes = [vp, C.c_char_p, C.POINTER(C.c_size_t)]
     lib.desire_peer_open.argtypes = [vp, i32, i32, i32, C.c_char_p]
     lib.desire_ioc_peer_pass.argtypes = [vp, f32p, f32p, vp]
@@ -587,6 +590,23 @@ class Handle:
         _chk(self.lib.desire_recon_weights_scene(self._h, fut_ptr or None, yhat_ptr or None, int(mode), C.c_float(float(tau)), e_ptr or None,
                                                  E_ptr or None, count_ptr or None, w_ptr or None, winner_ptr or None, recon_ptr or None,
                                                  stream or None))
+
+    def set_collision_loss(self, weight: float, radius: float = 0.0, unit_x: float = 1.0, unit_y: float = 1.0) -> None:
+        """The collision term of the training loss: weight (default 0: off, the step as it was) times the squared hinge (1 - dist / radius)^2 of
+        every pair of counted agents of one (window, k) and frame that are closer than radius, distances scaled by (unit_x, unit_y) as in
+        joint_metrics; the mean over K and over the counted agents.  The step leaves the term in the workspace tensor "col_term", the touching
+        (pair, frame)s per (window, k) in "col_touch"."""
+        _chk(self.lib.desire_set_collision_loss(self._h, C.c_float(float(weight)), C.c_float(float(radius)), C.c_float(float(unit_x)),
+                                                C.c_float(float(unit_y))))
+
+    def collision_loss(self, fut_ptr: int, yhat_ptr: int, radius: float, unit_x: float = 1.0, unit_y: float = 1.0, col_ptr: int = 0,
+                       touch_ptr: int = 0, dy_ptr: int = 0, term_ptr: int = 0, stream: int = 0) -> None:
+        """The collision penalty of yhat [R, T_pred, 2] read as K joint futures per window: col [A, K] per agent and sample, touch [n_scenes, K]
+        int32 (touching (pair, frame)s), dY [R, T_pred, 2] (the gradient of the term) and term [1]; each output is optional (0: kept in the
+        workspace tensor "col_val" / "col_touch" / "col_grad" / "col_term").  Masking as in losses()."""
+        _chk(self.lib.desire_collision_loss(self._h, fut_ptr or None, yhat_ptr or None, C.c_float(float(radius)), C.c_float(float(unit_x)),
+                                            C.c_float(float(unit_y)), col_ptr or None, touch_ptr or None, dy_ptr or None, term_ptr or None,
+                                            stream or None))
 
     def train_loss_async(self, fut_ptr: int, out8_ptr: int, stream: int = 0) -> None:
         """The loss terms of the last training-mode forward into a device buffer of 8 floats, no synchronisation (see loss_terms)."""

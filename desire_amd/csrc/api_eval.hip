@@ -464,3 +464,41 @@ extern "C" int desire_recon_weights_scene(desire_handle* h, const float* dev_fut
     ReconOut o{}; o.e = dev_e; o.E = dev_E; o.count = dev_count; o.w = dev_w; o.winner = dev_winner; o.recon = dev_recon;
     return recon_weights_call(h, true, dev_fut, dev_Yhat, mode, tau, o, stream);
 }
+
+// ---- the collision penalty of a window's K joint futures (kernels_collision.hip): the contract is stated in include/desire_hip.h.  The training
+// step (backward.hip: loss_grads) runs the same kernel in its accumulating form on "dY0". ----
+int collision_ws_setup(desire_ctx* h) {
+    const size_t f = sizeof(float);
+    return ws_ensure(h, {{"col_val", (size_t)h->A * h->d.K * f}, {"col_touch", (size_t)h->d.n_scenes * h->d.K * sizeof(int32_t)},
+                         {"col_grad", (size_t)h->R * h->d.T_pred * 2 * f}, {"col_term", f}, {"nvalid", 4 * f}});
+}
+int check_collision_args(float radius, float unit_x, float unit_y) {
+    if (int rc = check_radius(radius)) return rc;
+    return check_units(unit_x, unit_y);
+}
+void collision_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s) {
+    CollParams p{}; p.lmask = lmask; p.nfut = W(h, "nfut"); p.nvalid = W(h, "nvalid"); p.radius = h->col_radius; p.weight = h->col_w; p.accumulate = true;
+    CollOut o{}; o.col = W(h, "col_val"); o.touch = Wt<int32_t>(h, "col_touch"); o.dY = W(h, "dY0"); o.term = W(h, "col_term");
+    launch_collision_loss(eval_in(h, W(h, "Y0"), fut, nullptr, nullptr), p, eval_scale(h, h->col_ux, h->col_uy), o, s);
+}
+
+extern "C" int desire_collision_loss(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float radius, float unit_x, float unit_y,
+                                     float* dev_col, int32_t* dev_touch, float* dev_dY, float* dev_term, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_fut) return fail(DESIRE_ERR_ARG, "dev_fut is NULL");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (int rc = check_collision_args(radius, unit_x, unit_y)) return rc;
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read joint futures from");
+    if (int rc = desire_ready(h)) return rc;
+    if (int rc = collision_ws_setup(h)) return rc;          // (the first call allocates; later calls are capturable)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    launch_loss_mask(Wt<const uint8_t>(h, "valid"), dev_fut, Wt<uint8_t>(h, "lmask"), W(h, "nfut"), d.n_scenes, d.mno, d.T_pred, s);
+    launch_count_valid(Wt<const uint8_t>(h, "lmask"), h->A, W(h, "nvalid"), s);
+    CollParams p{}; p.lmask = Wt<const uint8_t>(h, "lmask"); p.nfut = W(h, "nfut"); p.nvalid = W(h, "nvalid"); p.radius = radius; p.weight = 1.f;
+    CollOut o{}; o.col = dev_col ? dev_col : W(h, "col_val"); o.touch = dev_touch ? dev_touch : Wt<int32_t>(h, "col_touch");
+    o.dY = dev_dY ? dev_dY : W(h, "col_grad"); o.term = dev_term ? dev_term : W(h, "col_term");
+    launch_collision_loss(eval_in(h, dev_Yhat, dev_fut, nullptr, nullptr), p, eval_scale(h, unit_x, unit_y), o, s);
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}

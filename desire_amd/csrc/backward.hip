@@ -201,6 +201,7 @@ int loss_grads(const BwdPass& bp) {
         launch_loss_grad_y_w(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "recon_w"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred,
                              d.sx, d.sy, s);
     }
+    if (h->col_w > 0.f) collision_enqueue(h, bp.fut, bp.valid, s);      // desire_set_collision_loss: dY0 += weight * d L_col / d Y0, on the full layout too
     if (bp.rows_compact) launch_gather_rows(W(h, "dY0"), W(h, "cp_dY0"), bp.amap, bp.n_present, d.K, d.mno, d.T_pred * 2, s);
     return DESIRE_OK;
 }

@@ -63,6 +63,7 @@ struct desire_ctx {
     float head_loss_w = 0.f;                                 // desire_set_head_loss: weight of the Gaussian-head NLL term in the training loss
     int recon_mode = 0; float recon_tau = 0.f;               // desire_set_recon_loss: DESIRE_RECON_* of the training loss's reconstruction term, the soft-min temperature
     int recon_scope = 0;                                     // desire_set_recon_scope: DESIRE_RECON_SCOPE_* (per agent, or per window over its K worlds)
+    float col_w = 0.f, col_radius = 0.f, col_ux = 1.f, col_uy = 1.f;      // desire_set_collision_loss: weight (0 = off), radius and unit of the training loss's collision term
     int* host_err = nullptr;                                 // mapped host word the bin-split IOC's bounded spins report into (checked by the next call)
     // present-row compaction (DESIRE_FLAG_COMPACT_ROWS, kernels_compact.hip): mapped host word the scan kernel reports the present-agent count
     // into, the event behind it, the count of the last desire_sample (-1: none yet)
@@ -166,4 +167,8 @@ int recon_ws_setup(desire_ctx* h);                             // "recon_e" / "r
 int recon_scene_ws_setup(desire_ctx* h);                       // those four and "recon_E" / "recon_cnt" of the scene scope (api_eval.hip; idempotent)
 // the reconstruction weights of the training step into the workspace tensors, in the handle's mode and scope (api_eval.hip; mode != MEAN)
 void recon_weights_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
+int collision_ws_setup(desire_ctx* h);                         // "col_val" / "col_touch" / "col_grad" / "col_term" and "nvalid" (api_eval.hip; idempotent)
+int check_collision_args(float radius, float unit_x, float unit_y);      // desire_collision_loss' checks of its scalars (api_eval.hip)
+// the collision term of the training step: dY0 = dY0 + col_w * G in place, col, touch and the term into the workspace tensors (api_eval.hip; col_w > 0)
+void collision_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
 int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)

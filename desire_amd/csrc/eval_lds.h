@@ -1,8 +1,8 @@
 // eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
-// _recon / _occ / _plan / _plan_cond / _modes / _worlds / _scene_modes.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// _recon / _occ / _plan / _plan_cond / _modes / _worlds / _scene_modes / _collision.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
 // that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
-// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp, occ_lds_driver.cpp, scene_modes_lds_driver.cpp and plan_cond_lds_driver.cpp compile it with g++
-// (tests/test_eval_lds.py, test_occ_lds.py, test_scene_modes_cpu.py, test_plan_cond_cpu.py).
+// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp, occ_lds_driver.cpp, scene_modes_lds_driver.cpp, plan_cond_lds_driver.cpp and coll_lds_driver.cpp compile it with g++
+// (tests/test_eval_lds.py, test_occ_lds.py, test_scene_modes_cpu.py, test_plan_cond_cpu.py, test_collision_cpu.py).
 #pragma once
 #include <stddef.h>
 
@@ -130,6 +130,35 @@ struct JointLds {
 inline int joint_chunk_frames(int mno, int T) {
     const size_t fixed = JointLds(mno, 0).bytes(), per = JointLds(mno, 1).bytes() - fixed, fit = ((size_t)EVAL_LDS_BYTES - fixed) / per;
     return (int)((size_t)T < fit ? (size_t)T : fit);
+}
+
+// ---- k_collision_unit: P float2 [TC][mp] (the unit's positions, JointLds' layout and frame stride), Gl float2 [mno][eval_odd(TC)] (the gradient of
+// the chunk's frames, parked slot-major so that it leaves in row order), then behind the pairs, in 32-bit words: Sl float [mno][eval_odd(TC)] (s(i, t),
+// walked by one lane per slot in increasing t), two [mno] floats (1 / nfut of a counted slot or 0, the running sum of s carried across the
+// chunks) and one int (the unit's touch count).  The odd row stride keeps the lanes of consecutive slots on distinct banks in both parks.
+struct CollLds {
+    enum { SLOT_WORDS = 2, UNIT_WORDS = 1 };
+    int mno, TC;
+    EVAL_HD constexpr CollLds(int mno_, int TC_) : mno(mno_), TC(TC_) {}
+    EVAL_HD constexpr int park_stride() const { return eval_odd(TC); }
+    EVAL_HD constexpr size_t pos() const { return (size_t)TC * JointLds::stride(mno); }     // float2 in front of the gradient park
+    EVAL_HD constexpr size_t grad() const { return (size_t)mno * park_stride(); }           // float2 in front of the words
+    EVAL_HD constexpr size_t s_words() const { return (size_t)mno * park_stride(); }        // word offsets behind the pairs: Sl at 0
+    EVAL_HD constexpr size_t slot_words(int r) const { return s_words() + (size_t)r * mno; }
+    EVAL_HD constexpr size_t unit_words() const { return slot_words(SLOT_WORDS); }
+    EVAL_HD constexpr size_t bytes() const { return (pos() + grad()) * EVAL_PAIR_BYTES + 4 * (unit_words() + UNIT_WORDS); }
+};
+// Frames per chunk: the whole horizon when the unit fits, else the largest number of frames that does.  A frame costs 8 stride + 12 mno bytes and
+// the odd park stride at most one more frame's worth of the parks: two frames of 256 slots are 15.4 KB with it, so every (mno, T_pred) a handle
+// can have is served (11 frames at 256 slots).
+inline int coll_chunk_frames(int mno, int T) {
+    auto fits = [&](int tc) { return CollLds(mno, tc).bytes() <= (size_t)EVAL_LDS_BYTES; };
+    if (fits(T)) return T;
+    int tc = (int)(((size_t)EVAL_LDS_BYTES - CollLds(mno, 0).bytes()) / ((size_t)EVAL_PAIR_BYTES * JointLds::stride(mno) + (size_t)12 * mno));
+    tc = eval_max(1, eval_min(tc, T));
+    while (tc > 1 && !fits(tc)) --tc;              // (the estimate counts the odd stride's extra column once: a step or two either way)
+    while (tc < T && fits(tc + 1)) ++tc;
+    return tc;
 }
 
 // ---- k_plan_risk: PL float2 [PC][eval_odd(TC)] (the frames of a pass of a chunk of PC candidate plans), P float2 [TC][mp] (the unit's positions,

@@ -340,6 +340,14 @@ struct ReconOut { float* e; float* E; int32_t* count; float* w; int32_t* winner;
 void launch_recon_weights(const EvalIn& in, const ReconParams& p, const EvalScale& sc, const ReconOut& o, hipStream_t s);
 void launch_recon_weights_scene(const EvalIn& in, const ReconParams& p, const EvalScale& sc, const ReconOut& o, hipStream_t s);
 
+// ---- the collision penalty of a window's K joint futures (kernels_collision.hip) ----
+// in.fut and in.Y; lmask / nfut: launch_loss_mask's, nvalid: launch_count_valid's; no scratch.  Every field of CollOut is written (none may be
+// nullptr): col [A, K], touch [n_scenes, K], term [1] and dY [R, T, 2] -- the gradient G of the term itself, or with `accumulate` (the training
+// step) dY = dY + weight * G in place.  Two launches: one workgroup per (window, k), then one workgroup for the term.
+struct CollParams { const uint8_t* lmask; const float* nfut; const float* nvalid; float radius, weight; bool accumulate; };
+struct CollOut { float* col; int32_t* touch; float* dY; float* term; };
+void launch_collision_loss(const EvalIn& in, const CollParams& p, const EvalScale& sc, const CollOut& o, hipStream_t s);
+
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);
 void launch_loss_grad_y(const float* Y, const float* fut, const uint8_t* lmask, const float* nfut, const float* nvalid, float* dY,

@@ -379,6 +379,16 @@ extern "C" int desire_set_recon_scope(desire_handle* h, int32_t scope) {
     return DESIRE_OK;
 }
 
+extern "C" int desire_set_collision_loss(desire_handle* h, float weight, float radius, float unit_x, float unit_y) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null argument");
+    if (!std::isfinite(weight) || weight < 0.f) return fail(DESIRE_ERR_ARG, "weight must be finite and >= 0");
+    if (int rc = check_collision_args(radius, unit_x, unit_y)) return rc;
+    if (h->d.ref_compat) return fail(DESIRE_ERR_STATE, "ref_compat is forward-only");
+    if (weight > 0.f) { if (int rc = collision_ws_setup(h)) return rc; }      // here, so that no training step allocates
+    h->col_w = weight; h->col_radius = radius; h->col_ux = unit_x; h->col_uy = unit_y;
+    return DESIRE_OK;
+}
+
 extern "C" int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream) {
     if (!h || !name || !host_out) return fail(DESIRE_ERR_ARG, "null argument");
     if (!h->training) return fail(DESIRE_ERR_STATE, "not in training mode");

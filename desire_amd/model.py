@@ -103,7 +103,10 @@ class PendingLoss(object):
     def get(self) -> Dict[str, float]:
         if self._terms is None:
             self._event.synchronize()
-            self._terms = _lib.Handle.loss_terms(self._host8.tolist())
+            v = self._host8.tolist()
+            self._terms = _lib.Handle.loss_terms(v)
+            if len(v) > 8:                                # the collision term of the step (args.collision_weight > 0), behind the eight
+                self._terms["col"] = float(v[8])
             self._dev8 = None
         return self._terms
 
@@ -365,6 +368,8 @@ class DESIREModel(ScoredSamples):
                 h.set_opt_state(pending)
             self._configure_head_loss(h)
             self._configure_recon_loss(h)
+            self._configure_collision_loss(h)
+        col_on = getattr(h, "_col_on", False)
         self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
         past, fut, eps_t = self._keep
         stream = torch.cuda.current_stream().cuda_stream
@@ -375,10 +380,14 @@ class DESIREModel(ScoredSamples):
             h.clip_grads(clip, stream=stream)
         if sync:
             terms = h.train_loss(fut.data_ptr(), stream)
+            if col_on:
+                terms["col"] = float(h.device_tensor("col_term")[0])
         else:
-            dev8 = torch.empty(8, device=self.device, dtype=torch.float32)
+            dev8 = torch.empty(9 if col_on else 8, device=self.device, dtype=torch.float32)
             h.train_loss_async(fut.data_ptr(), dev8.data_ptr(), stream)
-            host8 = torch.empty(8, dtype=torch.float32).pin_memory()
+            if col_on:                                # L_col of this step's backward, read one step late with the loss
+                dev8[8:9].copy_(h.device_tensor("col_term")[:1])
+            host8 = torch.empty(int(dev8.numel()), dtype=torch.float32).pin_memory()
             host8.copy_(dev8, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
@@ -413,6 +422,25 @@ class DESIREModel(ScoredSamples):
             h.set_recon_loss(RECON_MODES[mode], float(tau) if mode == "softmin" else 0.0)
             if scope != "agent":
                 h.set_recon_scope(RECON_SCOPES[scope])
+
+    def _configure_collision_loss(self, h) -> None:
+        """Hook of the collision term (args.collision_weight, default 0: off; args.collision_loss_radius in pixels, default args.collision_radius;
+        DESIGN.md section 7o): the squared hinge on the pairwise distances within each of the K joint futures, in pixels as joint_metrics reads
+        them.  The step's dict then carries "col", the term itself (the trained loss is loss + collision_weight * col)."""
+        weight = float(getattr(self.args, "collision_weight", 0.0) or 0.0)
+        if not (np.isfinite(weight) and weight >= 0.0):
+            raise ValueError("args.collision_weight must be finite and >= 0, got %r" % (weight,))
+        if weight == 0.0:
+            return
+        radius = getattr(self.args, "collision_loss_radius", None)
+        if radius is None:
+            radius = getattr(self.args, "collision_radius", None)
+        if radius is None or not (np.isfinite(float(radius)) and float(radius) > 0.0):
+            raise ValueError("args.collision_weight > 0 needs a radius > 0 in pixels (args.collision_loss_radius or args.collision_radius), got %r"
+                             % (radius,))
+        d = h.dims
+        h.set_collision_loss(weight, float(radius), 1.0 / d.sx, 1.0 / d.sy)
+        h._col_on = True
 
     def sync_weights(self) -> Dict[str, np.ndarray]:
         """Pull the trained weights back from the device; other handles (batch sizes / prior path) are rebuilt lazily."""

@@ -102,6 +102,12 @@ def build_parser() -> argparse.ArgumentParser:
                    help="who picks among the K samples under --recon_loss min / softmin: agent (every agent its own best sample, default) or scene "
                         "(sample k of every agent of a window is one joint future: the window's best joint future, or a soft-min over them, carries "
                         "the gradient of all its agents -- the scene-level variety loss); ignored with --recon_loss mean")
+    p.add_argument("--collision_weight", type=float, default=0.0,
+                   help="weight of the collision penalty in the training loss (default 0: off): per joint future -- sample k of every agent of a "
+                        "window -- and frame, (1 - dist / radius)^2 of every pair of agents closer than the radius, averaged over the K samples and "
+                        "the agents; the column --report_joint prints is the one it pushes down")
+    p.add_argument("--collision_loss_radius", type=float, default=None,
+                   help="radius of --collision_weight in pixels (default: --collision_radius)")
     p.add_argument("--prefetch", type=int, default=2,
                    help="batches the loader thread keeps in flight (pinned staging -> copy stream -> device; desire_amd/prefetch.py); 0 = the "
                         "reference's serial loop: next_batch, copy, step, read the loss, every step (train.py:131-183)")
@@ -145,6 +151,23 @@ def check_recon_args(args) -> None:
             raise ValueError("--recon_tau must be finite and > 0, got %r" % (tau,))
     elif tau is not None:
         raise ValueError("--recon_tau is the temperature of --recon_loss softmin (got --recon_loss %s)" % mode)
+    check_collision_args(args)
+
+
+def collision_loss_radius(args):
+    """The radius of the collision term in pixels: --collision_loss_radius, else --collision_radius, else None."""
+    r = getattr(args, "collision_loss_radius", None)
+    return getattr(args, "collision_radius", None) if r is None else r
+
+
+def check_collision_args(args) -> None:
+    """--collision_weight: finite and >= 0; > 0 needs a positive radius from --collision_loss_radius or --collision_radius."""
+    w = float(getattr(args, "collision_weight", 0.0) or 0.0)
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError("--collision_weight must be finite and >= 0, got %r" % (w,))
+    r = collision_loss_radius(args)
+    if w > 0.0 and (r is None or not (np.isfinite(float(r)) and float(r) > 0.0)):
+        raise ValueError("--collision_weight > 0 needs a radius > 0 in pixels: --collision_loss_radius or --collision_radius (got %r)" % (r,))
 
 
 def step_line(args, step: int, total: int, epoch: int, terms: dict, dt: float) -> str:
@@ -156,6 +179,9 @@ def step_line(args, step: int, total: int, epoch: int, terms: dict, dt: float) -
         if (getattr(args, "recon_scope", "agent") or "agent") == "scene":
             tag = "scene " + tag
         line += ", recon[{}] = {:.5f}".format(tag, terms["recon"])
+    w = float(getattr(args, "collision_weight", 0.0) or 0.0)
+    if w > 0.0:
+        line += ", col[r={:g} w={:g}] {:.5f}".format(float(collision_loss_radius(args)), w, terms.get("col", float("nan")))
     return line
 
 

@@ -895,6 +895,50 @@ int desire_recon_weights(desire_handle* h, const float* dev_fut, const float* de
 int desire_set_recon_scope(desire_handle* h, int32_t scope);
 int desire_recon_weights_scene(desire_handle* h, const float* dev_fut, const float* dev_Yhat, int32_t mode, float tau,
                                float* dev_e, float* dev_E, int32_t* dev_count, float* dev_w, int32_t* dev_winner, float* dev_recon, void* stream);
+/* ---- collision penalty on the K joint futures.  Every term above pulls samples toward the one observed future or does not see the other agents'
+ * samples at all; this one makes the worlds themselves collision-free: a squared hinge in the distance of every pair of counted agents of one
+ * (window, k) and frame.  Layouts are desire_joint_metrics': agent a = scene * mno + slot, row r_k = (scene * K + k) * mno + slot, window(a) = a /
+ * mno, dev_fut [n_scenes, T_pred, mno, 3]; lmask, nfut, nvalid (= max(the number of agents with lmask, 1) as a float) and the counted frames are
+ * desire_recon_weights' (the loss mask of desire_losses).  All arithmetic is fp32, every operation rounded once (no fused multiply-add), sqrtf and
+ * the divisions correctly rounded; no float atomics; a sum "in increasing X" starts from 0.f.
+ *   1 counted     cc(a, t) = lmask[a] && dev_fut[scene, t, slot, 0] != 0.
+ *   2 pair        for slots i != j of one (window, k) and a frame t with cc(i, t) && cc(j, t): a = (Y[r_i, t, 0] - Y[r_j, t, 0]) * unit_x; b =
+ *                 (Y[r_i, t, 1] - Y[r_j, t, 1]) * unit_y; q = a * a + b * b; r2 = radius * radius -- desire_joint_metrics' step 2, symmetric in i, j
+ *                 bit for bit.  The pair TOUCHES at t iff q < r2: strict, false for a NaN; radius 0: nothing touches.
+ *   3 penalty     for a touching pair dist = sqrtf(q); u = 1.f - dist / radius; phi = u * u; else phi = 0.  C1 at the radius, 1 at full overlap.
+ *   4 per agent   s(i, k, t) = the sum over j != i, in increasing j, of phi_ij(t) (a pair that does not touch adds nothing).  col[i, k] = (the sum
+ *                 over the counted frames of i, in increasing t, of s(i, k, t)) / nfut[i]; col[i, k] = 0.f where lmask[i] = 0.
+ *   5 count       touch[w, k] (int32) = the number of (unordered pair, frame) that touch: an integer path.
+ *   6 term        m[a] = (the sum of col[a, k] in increasing k) / (float)K.  S_l, l = 0 .. 255, = the sum of m[a] over the agents a = l, l + 256, ..
+ *                 in increasing a (col is 0.f where lmask = 0); the 256 sums meet in a binary tree, S_l = S_l + S_(l + st) for l < st, st = 128, 64,
+ *                 .., 1; L_col = S_0 / nvalid.  The mean over K, then the mean over the counted agents: the default reconstruction term's reduction.
+ *   7 gradient    of L_col at weight 1.  For a touching pair with dist > 0: c_ij = (inv[i] + inv[j]) * (u / (radius * dist)), inv[a] = 1.f /
+ *                 nfut[a]; X(i, t) = the sum over j != i in increasing j of c_ij * a, Y(i, t) the same with b (a pair at dist == 0 adds nothing:
+ *                 the rule nrm > 0 has in the reconstruction gradient).  scale = -2.f / (nvalid * (float)K).  G[r_i, t, 0] = (X * unit_x) * scale,
+ *                 G[r_i, t, 1] = (Y * unit_y) * scale; G = 0.f for frames and agents that are not counted.  This is d L_col / d Y[r_i, t, c] =
+ *                 the sum over j of (1 / nfut[i] + 1 / nfut[j]) / (nvalid * K) * d phi_ij / d Y[r_i, t, c].  Each (i, t) gathers its own sum.
+ * desire_collision_loss is the stand-alone op: dev_col [A, K], dev_touch [n_scenes, K] int32, dev_dY [R, T_pred, 2] = G, dev_term [1] = L_col; each
+ * may be NULL (it then goes to the workspace tensor "col_val" / "col_touch" / "col_grad" / "col_term"), and what is written does not depend on
+ * which are.  It needs no training mode (lmask comes from the handle's "valid", left by the last desire_encode / desire_forward, as in
+ * desire_recon_weights).  Stream-ordered, no host wait, no scratch: bitwise reproducible; the first call allocates the workspace tensors, later
+ * calls are capturable.  A window's col, touch and -- up to the common factor 1 / nvalid -- gradient depend on that window's rows and targets only.
+ * LDS plan: one workgroup owns one (window, k) and stages its positions as desire_joint_metrics does, next to the gradient and s of the staged
+ * frames parked slot-major (20 bytes per slot and frame in all); when the unit does not fit (256 slots x 40 frames) it walks the frames in chunks
+ * -- 11 at 256 slots -- carrying the per-slot sums across them, with the bits of an unchunked walk.  Every (mno, T_pred) of a handle is served.
+ * DESIRE_ERR_ARG with a desire_last_error text, and nothing is launched or written: a NULL handle / dev_fut / dev_Yhat; a radius that is negative
+ * or not finite; a unit that is not finite and > 0; a ref_compat handle.
+ * desire_set_collision_loss configures the term of the TRAINING loss (default weight 0, which leaves the launch sequence and every bit of every
+ * output as they were).  With weight > 0 desire_backward runs steps 1 - 7 on its own "Y0", on the full layout (after the reconstruction gradient,
+ * before the gather of DESIRE_FLAG_COMPACT_ROWS), and sets dY0 = dY0 + weight * G (the product rounded, then the sum); the trained loss is the
+ * one above plus weight * L_col.  The term keeps its mean over K whatever desire_set_recon_loss / desire_set_recon_scope say, as KL and the IOC
+ * terms do: every world should be collision-free, not only the winner.  The backward leaves col, touch and L_col of that step in "col_val",
+ * "col_touch" and "col_term" (desire_device_buffer); desire_train_loss / desire_train_loss_async keep their layouts and values.  weight > 0
+ * allocates the workspace tensors when it is set, so that no step allocates.  A host value like the recon mode: it can be changed between steps,
+ * not inside a captured graph.  DESIRE_ERR_ARG: a NULL handle, a weight that is negative or not finite, a bad radius or unit; DESIRE_ERR_STATE: a
+ * ref_compat handle. */
+int desire_set_collision_loss(desire_handle* h, float weight, float radius, float unit_x, float unit_y);
+int desire_collision_loss(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float radius, float unit_x, float unit_y,
+                          float* dev_col, int32_t* dev_touch, float* dev_dY, float* dev_term, void* stream);
 /* (dev_eps == NULL after desire_set_rng: the eps of the forward's draw is regenerated, see "device generator") */
 int desire_backward(desire_handle* h, const float* dev_past, const float* dev_fut, const float* dev_eps, void* stream);
 int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream);
