@@ -11,7 +11,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdesire_hip.so")
-SOURCES = ["api.hip", "api_pack.hip", "api_forward.hip", "api_peer.hip", "api_ops.hip", "api_eval.hip", "kernels_gemm.hip", "kernels_conv.hip", "kernels_rnn.hip", "kernels_aux.hip", "kernels_rank.hip", "kernels_kde.hip", "kernels_select.hip", "kernels_joint.hip", "kernels_worlds.hip", "kernels_plan.hip", "kernels_plan_cond.hip", "kernels_modes.hip", "kernels_scene_modes.hip", "kernels_occ.hip", "kernels_recon.hip", "kernels_collision.hip", "kernels_compact.hip", "kernels_bwd.hip", "kernels_bwd_x3.hip", "kernels_bwd_cl.hip", "kernels_bf16.hip", "kernels_bf16_cl.hip", "kernels_x3.hip", "kernels_x6.hip", "kernels_x6r2.hip", "kernels_scene.hip", "kernels_rng.hip", "kernels_rollout.hip", "train.hip", "backward.hip"]
+SOURCES = ["api.hip", "api_pack.hip", "api_forward.hip", "api_peer.hip", "api_ops.hip", "api_eval.hip", "kernels_gemm.hip", "kernels_conv.hip", "kernels_rnn.hip", "kernels_aux.hip", "kernels_rank.hip", "kernels_kde.hip", "kernels_select.hip", "kernels_joint.hip", "kernels_worlds.hip", "kernels_plan.hip", "kernels_plan_cond.hip", "kernels_modes.hip", "kernels_scene_modes.hip", "kernels_occ.hip", "kernels_recon.hip", "kernels_collision.hip", "kernels_offroad.hip", "kernels_compact.hip", "kernels_bwd.hip", "kernels_bwd_x3.hip", "kernels_bwd_cl.hip", "kernels_bf16.hip", "kernels_bf16_cl.hip", "kernels_x3.hip", "kernels_x6.hip", "kernels_x6r2.hip", "kernels_scene.hip", "kernels_rng.hip", "kernels_rollout.hip", "train.hip", "backward.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value", "-Wno-pass-failed"]
 FLAGS += os.environ.get("DESIRE_HIPCC_FLAGS", "").split()      # e.g. -DDESIRE_IOC_TIMING for the per-phase cycle counters (build_lib(force=True))
 # Per-file code-generation flags (part of source_hash).  -sink-insts-to-avoid-spills: MachineLICM sinks hoisted loop invariants (the

@@ -31,6 +31,7 @@ EXPORTS = [
     "desire_select_worlds", "desire_fit_scene_modes", "desire_plan_risk_cond",
     "desire_set_recon_scope", "desire_recon_weights_scene",
     "desire_set_collision_loss", "desire_collision_loss",
+    "desire_mask_distance", "desire_set_offroad_field", "desire_set_offroad_loss", "desire_offroad_loss",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
@@ -138,6 +139,10 @@ def load() -> C.CDLL:
     lib.desire_recon_weights_scene.argtypes = [vp, f32p, f32p, i32, C.c_float, f32p, f32p, vp, f32p, vp, f32p, vp]
     lib.desire_set_collision_loss.argtypes = [vp, C.c_float, C.c_float, C.c_float, C.c_float]
     lib.desire_collision_loss.argtypes = [vp, f32p, f32p, C.c_float, C.c_float, C.c_float, f32p, vp, f32p, f32p, vp]
+    lib.desire_mask_distance.argtypes = [vp, vp, i32, i32, i32, C.c_float, C.c_float, f32p, vp]
+    lib.desire_set_offroad_field.argtypes = [vp, f32p, i32, i32, i32, C.POINTER(i32)]
+    lib.desire_set_offroad_loss.argtypes = [vp, C.c_float, C.c_float]
+    lib.desire_offroad_loss.argtypes = [vp, f32p, f32p, C.c_float, f32p, vp, f32p, f32p, vp]
     lib.desire_peer_export.argtypes = [vp, C.c_char_p, C.POINTER(C.c_size_t)]
     lib.desire_peer_open.argtypes = [vp, i32, i32, i32, C.c_char_p]
     lib.desire_ioc_peer_pass.argtypes = [vp, f32p, f32p, vp]
@@ -607,6 +612,34 @@ class Handle:
         _chk(self.lib.desire_collision_loss(self._h, fut_ptr or None, yhat_ptr or None, C.c_float(float(radius)), C.c_float(float(unit_x)),
                                             C.c_float(float(unit_y)), col_ptr or None, touch_ptr or None, dy_ptr or None, term_ptr or None,
                                             stream or None))
+
+    def mask_distance(self, mask_ptr: int, n_masks: int, Mh: int, Mw: int, cell_x: float, cell_y: float, field_ptr: int, stream: int = 0) -> None:
+        """The exact distance field [n_masks, Mh, Mw] fp32 of the traversability masks [n_masks, Mh, Mw] uint8 (0 = not traversable): per cell the
+        distance from its centre to the nearest traversable centre, cells of (cell_x, cell_y); 0 on the road, 0 everywhere for a mask without road."""
+        _chk(self.lib.desire_mask_distance(self._h, mask_ptr or None, int(n_masks), int(Mh), int(Mw), C.c_float(float(cell_x)),
+                                           C.c_float(float(cell_y)), field_ptr or None, stream or None))
+
+    def set_offroad_field(self, field_ptr: int, n_fields: int, Mh: int, Mw: int, field_of_scene) -> None:
+        """Attach distance fields [n_fields, Mh, Mw] (referenced, not copied: keep the tensor alive) and the field of every window (a negative
+        entry: the window has none)."""
+        fos = np.ascontiguousarray(field_of_scene, dtype=np.int32)
+        if fos.shape != (self.dims.n_scenes,):
+            raise ValueError("field_of_scene must have n_scenes = %d entries, got shape %r" % (self.dims.n_scenes, fos.shape))
+        _chk(self.lib.desire_set_offroad_field(self._h, field_ptr or None, int(n_fields), int(Mh), int(Mw), fos.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def set_offroad_loss(self, weight: float, scale: float = 0.0) -> None:
+        """The off-road term of the training loss: weight (default 0: off, the step as it was) times the squared distance (d / scale)^2 of every
+        counted position of the K joint futures to the nearest traversable cell, read bilinearly off the attached field; the mean over K and over
+        the counted agents.  The step leaves the term in the workspace tensor "off_term", the off-road (slot, frame)s per (window, k) in "off_count"."""
+        _chk(self.lib.desire_set_offroad_loss(self._h, C.c_float(float(weight)), C.c_float(float(scale))))
+
+    def offroad_loss(self, fut_ptr: int, yhat_ptr: int, scale: float, off_ptr: int = 0, count_ptr: int = 0, dy_ptr: int = 0, term_ptr: int = 0,
+                     stream: int = 0) -> None:
+        """The off-road penalty of yhat [R, T_pred, 2] read as K joint futures per window: off [A, K] per agent and sample, count [n_scenes, K]
+        int32 (off-road (slot, frame)s), dY [R, T_pred, 2] (the gradient of the term) and term [1]; each output is optional (0: kept in the
+        workspace tensor "off_val" / "off_count" / "off_grad" / "off_term").  Masking as in losses()."""
+        _chk(self.lib.desire_offroad_loss(self._h, fut_ptr or None, yhat_ptr or None, C.c_float(float(scale)), off_ptr or None, count_ptr or None,
+                                          dy_ptr or None, term_ptr or None, stream or None))
 
     def train_loss_async(self, fut_ptr: int, out8_ptr: int, stream: int = 0) -> None:
         """The loss terms of the last training-mode forward into a device buffer of 8 floats, no synchronisation (see loss_terms)."""

@@ -502,3 +502,76 @@ extern "C" int desire_collision_loss(desire_handle* h, const float* dev_fut, con
     HIPCHK(hipGetLastError());
     return DESIRE_OK;
 }
+
+// ---- the off-road penalty of a window's K joint futures against the distance field of its scene mask (kernels_offroad.hip): the contracts are
+// stated in include/desire_hip.h.  The training step (backward.hip: loss_grads) runs the same kernel in its accumulating form on "dY0". ----
+extern "C" int desire_mask_distance(desire_handle* h, const uint8_t* dev_mask, int32_t n_masks, int32_t Mh, int32_t Mw, float cell_x, float cell_y,
+                                    float* dev_field, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_mask) return fail(DESIRE_ERR_ARG, "dev_mask is NULL");
+    if (!dev_field) return fail(DESIRE_ERR_ARG, "dev_field is NULL");
+    if (n_masks < 1 || n_masks > DESIRE_OFFROAD_MAX_MASKS) return fail(DESIRE_ERR_ARG, "n_masks must be 1.." + std::to_string(DESIRE_OFFROAD_MAX_MASKS));
+    if (Mh < 1 || Mh > DESIRE_OCC_MAX_SIDE) return fail(DESIRE_ERR_ARG, "Mh must be 1.." + std::to_string(DESIRE_OCC_MAX_SIDE));
+    if (Mw < 1 || Mw > DESIRE_OCC_MAX_SIDE) return fail(DESIRE_ERR_ARG, "Mw must be 1.." + std::to_string(DESIRE_OCC_MAX_SIDE));
+    if (!std::isfinite(cell_x) || !(cell_x > 0.f)) return fail(DESIRE_ERR_ARG, "cell_x must be finite and > 0");
+    if (!std::isfinite(cell_y) || !(cell_y > 0.f)) return fail(DESIRE_ERR_ARG, "cell_y must be finite and > 0");
+    if (h->d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] for a field to be read against");
+    launch_mask_distance(dev_mask, n_masks, Mh, Mw, cell_x, cell_y, dev_field, static_cast<hipStream_t>(stream));
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}
+
+extern "C" int desire_set_offroad_field(desire_handle* h, const float* dev_field, int32_t n_fields, int32_t Mh, int32_t Mw,
+                                        const int32_t* host_field_of_scene) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_field) return fail(DESIRE_ERR_ARG, "dev_field is NULL");
+    if (!host_field_of_scene) return fail(DESIRE_ERR_ARG, "host_field_of_scene is NULL");
+    if (n_fields < 1 || n_fields > DESIRE_OFFROAD_MAX_MASKS) return fail(DESIRE_ERR_ARG, "n_fields must be 1.." + std::to_string(DESIRE_OFFROAD_MAX_MASKS));
+    if (Mh < 1 || Mh > DESIRE_OCC_MAX_SIDE) return fail(DESIRE_ERR_ARG, "Mh must be 1.." + std::to_string(DESIRE_OCC_MAX_SIDE));
+    if (Mw < 1 || Mw > DESIRE_OCC_MAX_SIDE) return fail(DESIRE_ERR_ARG, "Mw must be 1.." + std::to_string(DESIRE_OCC_MAX_SIDE));
+    if (h->d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] for a field to be read against");
+    for (int i = 0; i < h->d.n_scenes; ++i)
+        if (host_field_of_scene[i] >= n_fields) return fail(DESIRE_ERR_ARG, "field_of_scene entry out of range (a negative entry: no field)");
+    if (int rc = ws_ensure(h, {{"off_fos", (size_t)h->d.n_scenes * sizeof(int32_t)}})) return rc;
+    HIPCHK(hipMemcpy(Wt<int32_t>(h, "off_fos"), host_field_of_scene, h->d.n_scenes * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->off_field = dev_field; h->off_n = n_fields; h->off_Mh = Mh; h->off_Mw = Mw;
+    return DESIRE_OK;
+}
+
+int offroad_ws_setup(desire_ctx* h) {
+    const size_t f = sizeof(float);
+    return ws_ensure(h, {{"off_val", (size_t)h->A * h->d.K * f}, {"off_count", (size_t)h->d.n_scenes * h->d.K * sizeof(int32_t)},
+                         {"off_grad", (size_t)h->R * h->d.T_pred * 2 * f}, {"off_term", f}, {"nvalid", 4 * f}});
+}
+namespace {
+OffParams offroad_params(desire_ctx* h, const uint8_t* lmask, float scale, float weight, bool accumulate) {
+    OffParams p{}; p.lmask = lmask; p.nfut = W(h, "nfut"); p.nvalid = W(h, "nvalid"); p.field = h->off_field;
+    p.field_of_scene = Wt<const int32_t>(h, "off_fos"); p.Mh = h->off_Mh; p.Mw = h->off_Mw; p.scale = scale; p.weight = weight; p.accumulate = accumulate;
+    return p;
+}
+}  // namespace
+void offroad_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s) {
+    OffOut o{}; o.off = W(h, "off_val"); o.count = Wt<int32_t>(h, "off_count"); o.dY = W(h, "dY0"); o.term = W(h, "off_term");
+    launch_offroad_loss(eval_in(h, W(h, "Y0"), fut, nullptr, nullptr), offroad_params(h, lmask, h->off_scale, h->off_w, true), o, s);
+}
+
+extern "C" int desire_offroad_loss(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float scale, float* dev_off, int32_t* dev_count,
+                                   float* dev_dY, float* dev_term, void* stream) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null handle");
+    if (!dev_fut) return fail(DESIRE_ERR_ARG, "dev_fut is NULL");
+    if (!dev_Yhat) return fail(DESIRE_ERR_ARG, "dev_Yhat is NULL");
+    if (!std::isfinite(scale) || !(scale > 0.f)) return fail(DESIRE_ERR_ARG, "scale must be finite and > 0");
+    const desire_dims& d = h->d;
+    if (d.ref_compat) return fail(DESIRE_ERR_ARG, "handle: ref_compat has no sample layout [R, T_pred, 2] to read joint futures from");
+    if (!h->off_field) return fail(DESIRE_ERR_STATE, "no distance field set (desire_set_offroad_field)");
+    if (int rc = desire_ready(h)) return rc;
+    if (int rc = offroad_ws_setup(h)) return rc;            // (the first call allocates; later calls are capturable)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    launch_loss_mask(Wt<const uint8_t>(h, "valid"), dev_fut, Wt<uint8_t>(h, "lmask"), W(h, "nfut"), d.n_scenes, d.mno, d.T_pred, s);
+    launch_count_valid(Wt<const uint8_t>(h, "lmask"), h->A, W(h, "nvalid"), s);
+    OffOut o{}; o.off = dev_off ? dev_off : W(h, "off_val"); o.count = dev_count ? dev_count : Wt<int32_t>(h, "off_count");
+    o.dY = dev_dY ? dev_dY : W(h, "off_grad"); o.term = dev_term ? dev_term : W(h, "off_term");
+    launch_offroad_loss(eval_in(h, dev_Yhat, dev_fut, nullptr, nullptr), offroad_params(h, Wt<const uint8_t>(h, "lmask"), scale, 1.f, false), o, s);
+    HIPCHK(hipGetLastError());
+    return DESIRE_OK;
+}

@@ -202,6 +202,7 @@ int loss_grads(const BwdPass& bp) {
                              d.sx, d.sy, s);
     }
     if (h->col_w > 0.f) collision_enqueue(h, bp.fut, bp.valid, s);      // desire_set_collision_loss: dY0 += weight * d L_col / d Y0, on the full layout too
+    if (h->off_w > 0.f) offroad_enqueue(h, bp.fut, bp.valid, s);        // desire_set_offroad_loss: dY0 += weight * d L_off / d Y0, after the collision term
     if (bp.rows_compact) launch_gather_rows(W(h, "dY0"), W(h, "cp_dY0"), bp.amap, bp.n_present, d.K, d.mno, d.T_pred * 2, s);
     return DESIRE_OK;
 }

@@ -64,6 +64,9 @@ struct desire_ctx {
     int recon_mode = 0; float recon_tau = 0.f;               // desire_set_recon_loss: DESIRE_RECON_* of the training loss's reconstruction term, the soft-min temperature
     int recon_scope = 0;                                     // desire_set_recon_scope: DESIRE_RECON_SCOPE_* (per agent, or per window over its K worlds)
     float col_w = 0.f, col_radius = 0.f, col_ux = 1.f, col_uy = 1.f;      // desire_set_collision_loss: weight (0 = off), radius and unit of the training loss's collision term
+    // desire_set_offroad_field / desire_set_offroad_loss: the caller's distance fields (referenced, not copied; nullptr: none set) with their shape,
+    // the weight (0 = off) and the scale of the training loss's off-road term; the window -> field map is the workspace's "off_fos"
+    const float* off_field = nullptr; int off_n = 0, off_Mh = 0, off_Mw = 0; float off_w = 0.f, off_scale = 0.f;
     int* host_err = nullptr;                                 // mapped host word the bin-split IOC's bounded spins report into (checked by the next call)
     // present-row compaction (DESIRE_FLAG_COMPACT_ROWS, kernels_compact.hip): mapped host word the scan kernel reports the present-agent count
     // into, the event behind it, the count of the last desire_sample (-1: none yet)
@@ -171,4 +174,7 @@ int collision_ws_setup(desire_ctx* h);                         // "col_val" / "c
 int check_collision_args(float radius, float unit_x, float unit_y);      // desire_collision_loss' checks of its scalars (api_eval.hip)
 // the collision term of the training step: dY0 = dY0 + col_w * G in place, col, touch and the term into the workspace tensors (api_eval.hip; col_w > 0)
 void collision_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
+int offroad_ws_setup(desire_ctx* h);                           // "off_val" / "off_count" / "off_grad" / "off_term" and "nvalid" (api_eval.hip; idempotent)
+// the off-road term of the training step: dY0 = dY0 + off_w * G in place, off, count and the term into the workspace tensors (api_eval.hip; off_w > 0)
+void offroad_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
 int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)

@@ -1,8 +1,8 @@
 // eval_lds.h -- the dynamic-LDS plans of the evaluation kernels over the sample tensor Y [R, T_pred, 2] (kernels_rank / _kde / _select / _joint /
-// _recon / _occ / _plan / _plan_cond / _modes / _worlds / _scene_modes / _collision.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
+// _recon / _occ / _plan / _plan_cond / _modes / _worlds / _scene_modes / _collision / _offroad.hip): the one budget, the one workgroup size, and per kernel a plan (its regions in order, with their offsets and bytes()) and the geometry
 // that picks the plan's parameters.  The geometry, the launcher's LDS argument and the kernel's carve-up all go through the plan.
-// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp, occ_lds_driver.cpp, scene_modes_lds_driver.cpp, plan_cond_lds_driver.cpp and coll_lds_driver.cpp compile it with g++
-// (tests/test_eval_lds.py, test_occ_lds.py, test_scene_modes_cpu.py, test_plan_cond_cpu.py, test_collision_cpu.py).
+// Plain C++ without HIP headers: tests/c_host/eval_lds_driver.cpp, occ_lds_driver.cpp, scene_modes_lds_driver.cpp, plan_cond_lds_driver.cpp, coll_lds_driver.cpp and offroad_lds_driver.cpp compile it with g++
+// (tests/test_eval_lds.py, test_occ_lds.py, test_scene_modes_cpu.py, test_plan_cond_cpu.py, test_collision_cpu.py, test_offroad_cpu.py).
 #pragma once
 #include <stddef.h>
 
@@ -159,6 +159,23 @@ inline int coll_chunk_frames(int mno, int T) {
     while (tc > 1 && !fits(tc)) --tc;              // (the estimate counts the odd stride's extra column once: a step or two either way)
     while (tc < T && fits(tc + 1)) ++tc;
     return tc;
+}
+
+// ---- k_offroad_unit: CollLds' regions in CollLds' order -- P float2 [TC][mp], Gl float2 [mno][eval_odd(TC)], then in words Sl [mno][eval_odd(TC)]
+// (phi(i, t)), two [mno] floats (1 / nfut of a counted slot or 0, the running sum of phi) and one int (the unit's off-road count) -- and behind them
+// F float [cells]: the window's distance field, cells = Mh * Mw when it is staged, 0 when the kernel gathers the taps from global memory.
+struct OffLds {
+    CollLds c;
+    int cells;
+    EVAL_HD constexpr OffLds(int mno_, int TC_, int cells_) : c(mno_, TC_), cells(cells_) {}
+    EVAL_HD constexpr size_t field_words() const { return c.unit_words() + CollLds::UNIT_WORDS; }      // word offset of F behind the pairs
+    EVAL_HD constexpr size_t bytes() const { return c.bytes() + (size_t)4 * cells; }
+};
+// The frames per chunk are CollLds' (a field never makes a unit walk more chunks); the field is staged when it fits behind that plan -- 64 x 64
+// cells next to 32 slots x 40 frames do (42.9 KB), next to 256 slots x 11 frames they do not -- and is read from global memory otherwise.
+inline void offroad_geometry(int mno, int T, int Mh, int Mw, int* TC, int* staged) {
+    *TC = coll_chunk_frames(mno, T);
+    *staged = OffLds(mno, *TC, Mh * Mw).bytes() <= (size_t)EVAL_LDS_BYTES ? 1 : 0;
 }
 
 // ---- k_plan_risk: PL float2 [PC][eval_odd(TC)] (the frames of a pass of a chunk of PC candidate plans), P float2 [TC][mp] (the unit's positions,

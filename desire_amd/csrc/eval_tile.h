@@ -3,7 +3,7 @@
 // The sinks and everything that is arithmetic on positions stay in the kernels.
 //
 // RULE: no floating-point multiply that feeds an add in this header.  kernels_rank.hip is compiled with the compiler's default contraction,
-// the other four files set `#pragma clang fp contract(off)` AFTER their includes, so this header is compiled under the default in every
+// the other files (kernels_offroad.hip among them) set `#pragma clang fp contract(off)` AFTER their includes, so this header is compiled under the default in every
 // file: a product-sum here could be fused in all of them.  What is here is integer index work, comparisons, expf(a - b), plain sums and one
 // division; every product-sum (the distance, the density, the moments) belongs in the including file, behind its pragma.
 #pragma once
@@ -20,6 +20,7 @@
 //   k_joint_unit      sg: the slot when the unit is walked in frame chunks (one segment per slot, EVAL_ONE_ROW), 0 for the whole unit
 //   k_recon_weights   sg: the sample of the pass
 //   k_occupancy       sg: the sample of the chunk (one segment per sample: a run of one row's frames, EVAL_ONE_ROW)
+//   k_collision_unit, k_offroad_unit   k_joint_unit's: sg, the slot of a frame chunk's segment, 0 for the whole unit
 // An item is (segment, quad): a quad is two pairs at an even pair index of the buffer, and seg_len / 2 + 1 quads cover a segment at either
 // parity of its first index.  A lane issues the BATCH 16-byte loads of its items before it consumes any; a quad that straddles its segment's
 // ends, and every quad of a buffer off 16-byte alignment (vec == 0), takes 8-byte loads of the pairs that are inside.  With one segment its

@@ -347,6 +347,21 @@ void launch_recon_weights_scene(const EvalIn& in, const ReconParams& p, const Ev
 struct CollParams { const uint8_t* lmask; const float* nfut; const float* nvalid; float radius, weight; bool accumulate; };
 struct CollOut { float* col; int32_t* touch; float* dY; float* term; };
 void launch_collision_loss(const EvalIn& in, const CollParams& p, const EvalScale& sc, const CollOut& o, hipStream_t s);
+// its second launch alone (the contract's step 6: val [A, K] -> term [1]), for a term of the same reduction (kernels_offroad.hip)
+void launch_collision_term(const float* val, const float* nvalid, float* term, int A, int K, hipStream_t s);
+
+// ---- the off-road penalty of the K joint futures against the distance field of the scene mask (kernels_offroad.hip) ----
+// launch_mask_distance: field [n_masks, Mh, Mw] from mask [n_masks, Mh, Mw]; no scratch (pass 1 parks its integer column distances in `field`).
+void launch_mask_distance(const uint8_t* mask, int n_masks, int Mh, int Mw, float cell_x, float cell_y, float* field, hipStream_t s);
+// launch_offroad_loss: in.fut and in.Y; lmask / nfut / nvalid as above; field [n_fields, Mh, Mw] and field_of_scene [n_scenes] (device words, a
+// negative entry: no field) are the handle's.  Every field of OffOut is written (none may be nullptr): off [A, K], count [n_scenes, K], term [1]
+// and dY [R, T, 2] -- G, or with `accumulate` dY = dY + weight * G in place.  Two launches, the second launch_collision_term.
+struct OffParams {
+    const uint8_t* lmask; const float* nfut; const float* nvalid; const float* field; const int32_t* field_of_scene; int Mh, Mw;
+    float scale, weight; bool accumulate;
+};
+struct OffOut { float* off; int32_t* count; float* dY; float* term; };
+void launch_offroad_loss(const EvalIn& in, const OffParams& p, const OffOut& o, hipStream_t s);
 
 // ---- backward (kernels_bwd.hip) ----
 void launch_count_valid(const uint8_t* valid, int A, float* out, hipStream_t s);

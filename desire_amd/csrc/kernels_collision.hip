@@ -208,5 +208,9 @@ void launch_collision_loss(const EvalIn& in, const CollParams& p, const EvalScal
     auto* kern = p.accumulate ? k_collision_unit<true> : k_collision_unit<false>;
     hipLaunchKernelGGL(kern, grid, dim3(EVAL_THREADS), lds, s, in.Y, in.fut, p.lmask, p.nfut, p.nvalid, o.col, o.touch, o.dY, in.mno, in.K, in.T, TC, vec,
                        vec_out, sc.ux, sc.uy, p.radius, p.weight);
-    hipLaunchKernelGGL(k_collision_term, dim3(1), dim3(256), 0, s, o.col, p.nvalid, o.term, in.n_scenes * in.mno, in.K);
+    launch_collision_term(o.col, p.nvalid, o.term, in.n_scenes * in.mno, in.K, s);
+}
+
+void launch_collision_term(const float* val, const float* nvalid, float* term, int A, int K, hipStream_t s) {
+    hipLaunchKernelGGL(k_collision_term, dim3(1), dim3(256), 0, s, val, nvalid, term, A, K);
 }

@@ -389,6 +389,19 @@ extern "C" int desire_set_collision_loss(desire_handle* h, float weight, float r
     return DESIRE_OK;
 }
 
+extern "C" int desire_set_offroad_loss(desire_handle* h, float weight, float scale) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null argument");
+    if (!std::isfinite(weight) || weight < 0.f) return fail(DESIRE_ERR_ARG, "weight must be finite and >= 0");
+    if (weight > 0.f && (!std::isfinite(scale) || !(scale > 0.f))) return fail(DESIRE_ERR_ARG, "scale must be finite and > 0");
+    if (h->d.ref_compat) return fail(DESIRE_ERR_STATE, "ref_compat is forward-only");
+    if (weight > 0.f) {
+        if (!h->off_field) return fail(DESIRE_ERR_STATE, "no distance field set (desire_set_offroad_field)");
+        if (int rc = offroad_ws_setup(h)) return rc;       // here, so that no training step allocates
+    }
+    h->off_w = weight; h->off_scale = scale;
+    return DESIRE_OK;
+}
+
 extern "C" int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream) {
     if (!h || !name || !host_out) return fail(DESIRE_ERR_ARG, "null argument");
     if (!h->training) return fail(DESIRE_ERR_STATE, "not in training mode");

@@ -86,6 +86,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--occupancy_mode", type=str, default="at", choices=("at", "until"),
                    help="--occupancy: the maps at the frame of the horizon (at) or swept over every frame before it (until); the mass on the ground "
                         "truth's cell is always the frame's")
+    p.add_argument("--offroad", type=str, default=None, metavar="MASKFILE",
+                   help="also report how far the K joint futures leave the road (desire_offroad_loss): MASKFILE is the .npz of train.py's "
+                        "--scene_masks (one [Mh, Mw] uint8 traversability mask per video, keyed by the video directory relative to --data_dir); the "
+                        "share of predicted positions on a cell off the road per joint future, the same of the ground truth, and the mean penalty "
+                        "at --offroad_scale pixels (the training flag; default here: one cell of the mask, the wider side)")
     p.add_argument("--modes", type=int, default=0, metavar="N",
                    help="also report the mixture of N modes per agent that predict_modes hands out (desire_fit_modes): per horizon its negative "
                         "log-likelihood of the ground truth (mean over the frames and final frame; density per unit^2 of --units, log clipped at -20) and "
@@ -351,6 +356,41 @@ class _Occupancy:
                               "expected_in_frame": [float(self.exp[i] / max(r.windows, 1)) for i in range(nh)]}}
 
 
+class _Offroad:
+    """--offroad MASKFILE: the off-road rate of the K joint futures and of the ground truth against each video's traversability mask, and the mean
+    penalty (the training term of --offroad_weight, window by window, weighted by the window's counted frames)."""
+
+    def __init__(self, args, hz, run):
+        self.path = getattr(args, "offroad", None)
+        self.on = bool(self.path)
+        self.scale, self.run, self.args = getattr(args, "offroad_scale", None), run, args
+        if self.on and self.scale is not None and not (np.isfinite(float(self.scale)) and float(self.scale) > 0.0):
+            raise ValueError("--offroad_scale must be finite and > 0 (pixels), got %r" % (self.scale,))
+        self.masks, self.frames, self.count, self.gt, self.best, self.pen, self.gt_pen, self.batches = None, 0, 0, 0, 0.0, 0.0, 0.0, 0
+
+    def update(self, model, Y, score, fut, masks):
+        if self.masks is None:
+            from .train import load_scene_masks, scene_image_keys
+            self.masks, self.of_video = load_scene_masks(self.path, scene_image_keys(masks.loader, self.args.data_dir))
+            if self.scale is None:
+                d = model._handle(len(fut), False).dims
+                self.scale = max((1.0 / d.sx) / self.masks.shape[2], (1.0 / d.sy) / self.masks.shape[1])
+        r = model.evaluate_offroad(Y, score, fut, self.masks, self.of_video[np.asarray(masks.video, np.int64)], float(self.scale))
+        self.frames += int(r["frames"].sum())
+        self.count += int(r["count"].sum())
+        self.gt += int(r["gt_count"].sum())
+        self.best += float(r["count"].min(1).sum())
+        w = int(r["frames"].sum())
+        self.pen, self.gt_pen, self.batches = self.pen + r["penalty"] * w, self.gt_pen + r["gt_penalty"] * w, self.batches + w
+
+    def result(self) -> dict:
+        f = max(self.frames, 1)
+        return {"offroad": {"masks": self.path, "scale_px": float(self.scale) if self.scale is not None else None, "frames": int(self.frames),
+                            "rate_mean_of_K": float(self.count / (f * self.run.K)), "rate_best_of_K": float(self.best / f),
+                            "rate_ground_truth": float(self.gt / f), "penalty": float(self.pen / max(self.batches, 1)),
+                            "penalty_ground_truth": float(self.gt_pen / max(self.batches, 1))}}
+
+
 class _Modes:
     """--modes N: the mixture of N modes per agent -- its likelihood of the ground truth, the errors of the most probable and of the best mode's
     mean, and the Lloyd passes per agent present at the last observed frame."""
@@ -452,14 +492,15 @@ def evaluate(args, data_loader=None, model=None) -> dict:
     hz = parse_horizons(args.eval_horizons, t_pred)
     run = _Run(args, hz, generator, K, int(args.eval_top or default_top(K)), t_pred)
     # every block reads its flags here -- a bad one is refused before a window is touched --, the enabled ones report in this order
-    blocks = [run] + [b for b in [B(args, hz, run) for B in (_Ranked, _Select, _KdeNll, _Joint, _PlanRisk, _Occupancy, _Modes, _JointModes)] if b.on]
+    blocks = [run] + [b for b in [B(args, hz, run) for B in (_Ranked, _Select, _KdeNll, _Joint, _PlanRisk, _Occupancy, _Offroad, _Modes, _JointModes)] if b.on]
     mno = dims_from_args(args, 1, False).mno                             # the model's slot axis: max_num_obj padded up
-    for xs, _ in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
+    for xs, ds in iter_batches(data_loader, int(args.batch_size), int(args.max_windows or 0)):
         past, fut = split_windows(xs, t_obs)
         # --device_rng: a window's noise is a function of its running index, so the result does not depend on --batch_size
         gen = {} if generator == "cvae" else {"generator": generator}
         model.predict(past, top=run.top, seed=args.seed, device_rng=bool(getattr(args, "device_rng", False)), window_base=run.windows, **gen)
         masks = _masks(past, fut, hz, mno)
+        masks.video, masks.loader = ds, data_loader                      # (--offroad: the video of every window picks its mask)
         for b in blocks:
             b.update(model, model.final_output, model.final_states, fut, masks)
     res = {}

@@ -94,8 +94,8 @@ class PendingLoss(object):
     """Loss terms of a training step that has been ENQUEUED, not waited for.  get() blocks on the step's event (at most once) and returns
     the same dict train_step(sync=True) returns."""
 
-    def __init__(self, host8, event, dev8):
-        self._host8, self._event, self._dev8, self._terms = host8, event, dev8, None
+    def __init__(self, host8, event, dev8, extra=("col",)):
+        self._host8, self._event, self._dev8, self._terms, self._extra = host8, event, dev8, None, tuple(extra)
 
     def done(self) -> bool:
         return self._terms is not None or self._event.query()
@@ -105,8 +105,8 @@ class PendingLoss(object):
             self._event.synchronize()
             v = self._host8.tolist()
             self._terms = _lib.Handle.loss_terms(v)
-            if len(v) > 8:                                # the collision term of the step (args.collision_weight > 0), behind the eight
-                self._terms["col"] = float(v[8])
+            for i, name in enumerate(self._extra[: max(len(v) - 8, 0)]):      # the step's collision / off-road terms (weight > 0), behind the eight
+                self._terms[name] = float(v[8 + i])
             self._dev8 = None
         return self._terms
 
@@ -135,6 +135,9 @@ class DESIREModel(ScoredSamples):
         self._grids = None
         self._grid_of_scene = None
         self._images = None                  # set_scene_images: the library runs (and trains) the scene CNN
+        self._masks = None                   # set_scene_masks: the traversability masks, their distance field (built on first use) and mapping
+        self._mask_field = None
+        self._mask_of_scene = None
         # reference attribute names (model/model.py:62-75)
         self.input_data = None
         self.target_data = None
@@ -201,6 +204,45 @@ class DESIREModel(ScoredSamples):
         self._images = img
         self._grids = None
         self._grid_of_scene = np.asarray(grid_of_scene, np.int32)
+
+    def set_scene_masks(self, masks, mask_of_scene: Sequence[int]) -> None:
+        """masks [n_masks, Mh, Mw] uint8 over the normalised frame (0 = not traversable, desire_occupancy's meaning): the off-road term of the
+        training loss (args.offroad_weight) reads their exact distance field, built on the device in pixels -- cells of (1 / sx) / Mw by (1 / sy) /
+        Mh -- by the first step that uses it and kept alive here.  mask_of_scene[i] = mask index of window i, negative: the window has none
+        (replaced per batch by the mask_of_scene= argument of train_step)."""
+        torch = self.torch
+        m = masks if torch.is_tensor(masks) else torch.as_tensor(np.ascontiguousarray(masks, np.uint8))
+        m = m.to(device=self.device, dtype=torch.uint8).contiguous()
+        if m.dim() != 3:
+            raise ValueError("scene masks must be [n_masks, Mh, Mw] uint8, got %s" % (tuple(m.shape),))
+        self._masks = m
+        self._mask_field = None
+        self._mask_of_scene = np.asarray(mask_of_scene, np.int32)
+
+    def _attach_masks(self, h, n: int, mask_of_scene=None) -> None:
+        """Gives handle h the distance field of the scene masks with this batch's mapping (the stored one resized to n windows when none is given);
+        nothing without set_scene_masks."""
+        if self._masks is None:
+            if mask_of_scene is not None:
+                raise ValueError("mask_of_scene needs set_scene_masks")
+            return
+        nm, Mh, Mw = (int(v) for v in self._masks.shape)
+        if self._mask_field is None:
+            d = h.dims
+            field = self.torch.empty((nm, Mh, Mw), device=self.device, dtype=self.torch.float32)
+            h.mask_distance(self._masks.data_ptr(), nm, Mh, Mw, (1.0 / d.sx) / Mw, (1.0 / d.sy) / Mh, field.data_ptr(),
+                            self.torch.cuda.current_stream().cuda_stream)
+            self._mask_field = field
+        if mask_of_scene is not None:
+            mos = np.ascontiguousarray(mask_of_scene, np.int32).reshape(-1)
+            if mos.size != n:
+                raise ValueError("mask_of_scene has %d entries for %d windows" % (mos.size, n))
+        else:
+            mos = self._mask_of_scene if len(self._mask_of_scene) == n else np.resize(self._mask_of_scene, n)
+        src = (self._mask_field.data_ptr(), mos.tobytes())
+        if getattr(h, "_mask_src", None) != src:
+            h.set_offroad_field(self._mask_field.data_ptr(), nm, Mh, Mw, mos)
+            h._mask_src = src
 
     def _attach_scene(self, h, n: int, grid_of_scene=None) -> None:
         """Gives handle h this batch's scene input -- the images (the handle runs the CNN) or the grids -- with the batch's grid_of_scene when
@@ -333,7 +375,8 @@ class DESIREModel(ScoredSamples):
 
     # ---- training (train.py:140-181 runs only `cost`; the Adam op of model/model.py:386-403 is never applied) ----
     def train_step(self, x_batch: Sequence[np.ndarray], y_batch: Sequence[np.ndarray], eps: Optional[np.ndarray] = None,
-                   seed: int = 0, group=None, sync: bool = True, grid_of_scene=None, device_rng: bool = False, window_base: int = 0):
+                   seed: int = 0, group=None, sync: bool = True, grid_of_scene=None, device_rng: bool = False, window_base: int = 0,
+                   mask_of_scene=None):
         """One optimiser step on a batch of loader windows: forward (posterior path), backward, gradient mean over
         the data-parallel ranks (RCCL all-reduce of ONE flat buffer when torch.distributed is initialised),
         clip_by_global_norm(args.grad_clip), Adam(args.learning_rate).  Returns the loss terms of DESIGN.md section 8
@@ -341,12 +384,12 @@ class DESIREModel(ScoredSamples):
         whose .get() returns them later (see train_step_device)."""
         d = self._handle(len(x_batch), True).dims
         out = self.train_step_device(self._pad_windows(x_batch, d.mno), self._pad_windows(y_batch, d.mno), eps, seed, group, sync,
-                                     grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
+                                     grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base, mask_of_scene=mask_of_scene)
         self.input_data, self.target_data = x_batch, y_batch
         return out
 
     def train_step_device(self, past, fut, eps=None, seed: int = 0, group=None, sync: bool = True, grid_of_scene=None, device_rng: bool = False,
-                          window_base: int = 0):
+                          window_base: int = 0, mask_of_scene=None):
         """train_step on windows already in HBM (forward_device's layout).  device_rng=True: the step holds no eps tensor -- the forward draws
         it and the backward regenerates the same draw.  sync=False: nothing waits for the GPU -- the loss terms
         go to a device buffer (desire_train_loss_async), a pinned copy is enqueued, and the returned PendingLoss reads them when asked,
@@ -360,6 +403,7 @@ class DESIREModel(ScoredSamples):
             raise ValueError("train_step was called with %d windows after training with %d: the Adam moments live in the handle "
                              "of one batch size (keep the batch size fixed, as DataLoader.next_batch does)"
                              % (int(past.shape[0]), prev.dims.n_scenes))
+        self._attach_masks(h, int(past.shape[0]), mask_of_scene)
         if not getattr(h, "_training_on", False):
             h.set_training(True)
             h._training_on = True
@@ -369,7 +413,9 @@ class DESIREModel(ScoredSamples):
             self._configure_head_loss(h)
             self._configure_recon_loss(h)
             self._configure_collision_loss(h)
-        col_on = getattr(h, "_col_on", False)
+            self._configure_offroad_loss(h)
+        col_on, off_on = getattr(h, "_col_on", False), getattr(h, "_off_on", False)
+        extra = [(name, ws) for name, ws, on in (("col", "col_term", col_on), ("off", "off_term", off_on)) if on]
         self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
         past, fut, eps_t = self._keep
         stream = torch.cuda.current_stream().cuda_stream
@@ -380,18 +426,18 @@ class DESIREModel(ScoredSamples):
             h.clip_grads(clip, stream=stream)
         if sync:
             terms = h.train_loss(fut.data_ptr(), stream)
-            if col_on:
-                terms["col"] = float(h.device_tensor("col_term")[0])
+            for name, ws in extra:
+                terms[name] = float(h.device_tensor(ws)[0])
         else:
-            dev8 = torch.empty(9 if col_on else 8, device=self.device, dtype=torch.float32)
+            dev8 = torch.empty(8 + len(extra), device=self.device, dtype=torch.float32)
             h.train_loss_async(fut.data_ptr(), dev8.data_ptr(), stream)
-            if col_on:                                # L_col of this step's backward, read one step late with the loss
-                dev8[8:9].copy_(h.device_tensor("col_term")[:1])
+            for i, (_, ws) in enumerate(extra):       # L_col / L_off of this step's backward, read one step late with the loss
+                dev8[8 + i:9 + i].copy_(h.device_tensor(ws)[:1])
             host8 = torch.empty(int(dev8.numel()), dtype=torch.float32).pin_memory()
             host8.copy_(dev8, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
-            terms = PendingLoss(host8, ev, dev8)
+            terms = PendingLoss(host8, ev, dev8, [name for name, _ in extra])
         h.adam_step(self.learning_rate, stream=stream)
         self._trained = h
         self._version = getattr(self, "_version", 0) + 1
@@ -441,6 +487,23 @@ class DESIREModel(ScoredSamples):
         d = h.dims
         h.set_collision_loss(weight, float(radius), 1.0 / d.sx, 1.0 / d.sy)
         h._col_on = True
+
+    def _configure_offroad_loss(self, h) -> None:
+        """Hook of the off-road term (args.offroad_weight, default 0: off; args.offroad_scale in pixels): the squared
+        distance, over the scale, of every position of the K joint futures to the nearest traversable cell of the window's scene mask
+        (set_scene_masks).  The step's dict then carries "off", the term itself (the trained loss is loss + offroad_weight * off)."""
+        weight = float(getattr(self.args, "offroad_weight", 0.0) or 0.0)
+        if not (np.isfinite(weight) and weight >= 0.0):
+            raise ValueError("args.offroad_weight must be finite and >= 0, got %r" % (weight,))
+        if weight == 0.0:
+            return
+        scale = getattr(self.args, "offroad_scale", None)
+        if scale is None or not (np.isfinite(float(scale)) and float(scale) > 0.0):
+            raise ValueError("args.offroad_weight > 0 needs args.offroad_scale > 0 in pixels, got %r" % (scale,))
+        if self._masks is None:
+            raise ValueError("args.offroad_weight > 0 needs scene masks (set_scene_masks)")
+        h.set_offroad_loss(weight, float(scale))
+        h._off_on = True
 
     def sync_weights(self) -> Dict[str, np.ndarray]:
         """Pull the trained weights back from the device; other handles (batch sizes / prior path) are rebuilt lazily."""

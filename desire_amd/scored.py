@@ -759,6 +759,51 @@ class ScoredSamples(object):
         res = self._occupancy(h, Y, fut, None, score if weights == "score" else None, args, mode == "at")
         return {k: v.cpu().numpy() for k, v in res.items()}
 
+    def evaluate_offroad(self, Y, score, fut_windows, mask, mask_of_window=None, scale: float = 1.0) -> dict:
+        """The off-road read-out of samples Y [n, K, mno, T_pred, 2] read as K joint futures per window, against traversability masks [n_masks, Mh,
+        Mw] (or [Mh, Mw]; nonzero: traversable; mask_of_window [n]: its mask per window, negative: none; default mask 0 for every window):
+        desire_offroad_loss on the masks' distance field in pixels, the quantities the training term (args.offroad_weight) pushes down.  Returns
+        numpy values: "count" [n, K] = the counted (slot, frame)s of world k on a cell off the road, "frames" [n] = the counted (slot, frame)s of
+        the window, "rate" [n, K] = count / frames (0 where there are none), "penalty" = the term L_off at `scale` pixels, and the same of the
+        ground truth by the same rule -- the op run on the futures laid out as K identical worlds --: "gt_count" [n], "gt_rate" [n],
+        "gt_penalty".  `score` is not read (every world counts alike); `fut_windows` as in evaluate_ranked."""
+        torch = self.torch
+        h, d, _, _, fut, stream = self._evaluation(Y, fut_windows)
+        if not (np.isfinite(float(scale)) and float(scale) > 0.0):
+            raise ValueError("scale must be finite and > 0 (pixels), got %r" % (scale,))
+        mask = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+        if mask.dim() == 2:
+            mask = mask[None]
+        if mask.dim() != 3:
+            raise ValueError("mask must be [n_masks, Mh, Mw] (or [Mh, Mw]), got %s" % (tuple(mask.shape),))
+        nm, Mh, Mw = (int(v) for v in mask.shape)
+        mow = np.zeros(d.n_scenes, np.int32) if mask_of_window is None else np.asarray(mask_of_window, np.int64).reshape(-1).astype(np.int32)
+        if mow.size != d.n_scenes or (mow >= nm).any():
+            raise ValueError("mask_of_window must hold one index below n_masks (negative: no mask) per window")
+        field = torch.empty((nm, Mh, Mw), device=self.device, dtype=torch.float32)
+        h.mask_distance(mask.data_ptr(), nm, Mh, Mw, (1.0 / d.sx) / Mw, (1.0 / d.sy) / Mh, field.data_ptr(), stream)
+        h.set_offroad_field(field.data_ptr(), nm, Mh, Mw, mow)
+        h._mask_src = None                                     # (a training step on this handle attaches its own field again)
+        gt = (fut[..., 1:].to(torch.float32) * self._scale(d)).permute(0, 2, 1, 3)                      # [n, mno, T_pred, 2], normalised
+        worlds = {"": Y.reshape(d.R, d.T_pred, 2).contiguous(),
+                  "gt_": gt[:, None].expand(d.n_scenes, d.K, d.mno, d.T_pred, 2).reshape(d.R, d.T_pred, 2).contiguous()}
+        res = {}
+        for tag, rows in worlds.items():
+            count = torch.empty((d.n_scenes, d.K), device=self.device, dtype=torch.int32)
+            term = torch.empty((1,), device=self.device, dtype=torch.float32)
+            h.offroad_loss(fut.data_ptr(), rows.data_ptr(), float(scale), 0, count.data_ptr(), 0, term.data_ptr(), stream)
+            res[tag + "count"], res[tag + "penalty"] = count.cpu().numpy(), float(term[0])
+        lmask = h.device_tensor("lmask", "|u1")[: d.A].reshape(d.n_scenes, d.mno) != 0
+        seen = (fut[..., 0] != 0).sum(1)                                                                # [n, mno] counted frames per slot
+        frames = (seen * lmask * torch.as_tensor(mow >= 0, device=self.device)[:, None]).sum(1).cpu().numpy().astype(np.int64)
+        res["frames"] = frames
+        res["rate"] = res["count"] / np.maximum(frames, 1)[:, None]
+        res["gt_count"] = res["gt_count"][:, 0]
+        res["gt_rate"] = res["gt_count"] / np.maximum(frames, 1)
+        torch.cuda.synchronize()                               # `field` is referenced by the handle until the next set_offroad_field: keep it
+        self._eval_field = field
+        return res
+
     def evaluate_nll(self, Y, score, fut_windows, horizons=None, units="px", weighted: bool = False, log_floor: float = _lib.KDE_LOG_FLOOR,
                      return_frames: bool = False):
         """[A, n_h, 2] = per horizon (mean, final) KDE negative log-likelihood of the ground truth under the agent's K samples: at every counted

@@ -108,6 +108,14 @@ def build_parser() -> argparse.ArgumentParser:
                         "the agents; the column --report_joint prints is the one it pushes down")
     p.add_argument("--collision_loss_radius", type=float, default=None,
                    help="radius of --collision_weight in pixels (default: --collision_radius)")
+    p.add_argument("--offroad_weight", type=float, default=0.0,
+                   help="weight of the off-road penalty in the training loss (default 0: off): per joint future and frame, (d / scale)^2 with d the "
+                        "distance in pixels from the predicted position to the nearest traversable cell of the video's mask (--scene_masks), "
+                        "averaged over the K samples and the agents; needs --offroad_scale and --scene_masks")
+    p.add_argument("--offroad_scale", type=float, default=None, help="scale of --offroad_weight in pixels: a position this far off the road costs 1")
+    p.add_argument("--scene_masks", type=str, default=None,
+                   help=".npz with one [Mh, Mw] uint8 traversability mask per video over the whole frame (0 = not traversable), keyed like "
+                        "--scene_images by the video directory relative to --data_dir; every mask has the same shape")
     p.add_argument("--prefetch", type=int, default=2,
                    help="batches the loader thread keeps in flight (pinned staging -> copy stream -> device; desire_amd/prefetch.py); 0 = the "
                         "reference's serial loop: next_batch, copy, step, read the loss, every step (train.py:131-183)")
@@ -152,6 +160,21 @@ def check_recon_args(args) -> None:
     elif tau is not None:
         raise ValueError("--recon_tau is the temperature of --recon_loss softmin (got --recon_loss %s)" % mode)
     check_collision_args(args)
+    check_offroad_args(args)
+
+
+def check_offroad_args(args) -> None:
+    """--offroad_weight: finite and >= 0; > 0 needs --offroad_scale finite and > 0 and --scene_masks."""
+    w = float(getattr(args, "offroad_weight", 0.0) or 0.0)
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError("--offroad_weight must be finite and >= 0, got %r" % (w,))
+    if w == 0.0:
+        return
+    s = getattr(args, "offroad_scale", None)
+    if s is None or not (np.isfinite(float(s)) and float(s) > 0.0):
+        raise ValueError("--offroad_weight > 0 needs --offroad_scale finite and > 0 in pixels (got %r)" % (s,))
+    if not getattr(args, "scene_masks", None):
+        raise ValueError("--offroad_weight > 0 needs --scene_masks: the masks its distance field is built from")
 
 
 def collision_loss_radius(args):
@@ -182,6 +205,9 @@ def step_line(args, step: int, total: int, epoch: int, terms: dict, dt: float) -
     w = float(getattr(args, "collision_weight", 0.0) or 0.0)
     if w > 0.0:
         line += ", col[r={:g} w={:g}] {:.5f}".format(float(collision_loss_radius(args)), w, terms.get("col", float("nan")))
+    w = float(getattr(args, "offroad_weight", 0.0) or 0.0)
+    if w > 0.0:
+        line += ", off[s={:g} w={:g}] {:.5f}".format(float(args.offroad_scale), w, terms.get("off", float("nan")))
     return line
 
 
@@ -199,6 +225,11 @@ def parse_horizons(text, t_pred: int) -> List[int]:
 def _gos(grid_of_video, dval):
     """grid_of_scene of a batch: the scene image of each window's video index (None without --scene_images)."""
     return None if grid_of_video is None else grid_of_video[np.asarray(dval, np.int64)]
+
+
+def _mos(mask_of_video, dval) -> dict:
+    """The mask_of_scene= keyword of a batch: the mask of each window's video index (no keyword at all without --scene_masks)."""
+    return {} if mask_of_video is None else {"mask_of_scene": mask_of_video[np.asarray(dval, np.int64)]}
 
 
 def lr_at_epoch(args, epoch: int) -> float:
@@ -242,6 +273,25 @@ def load_scene_images(path: str, video_keys: Sequence[str], Gh: int, Gw: int) ->
     return images, np.array([keys.index(k) for k in video_keys], np.int32)
 
 
+def load_scene_masks(path: str, video_keys: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
+    """--scene_masks: (masks [n_masks, Mh, Mw] uint8, mask of every video index).  n_masks = the entries of the file (sorted by key); a video
+    without an entry, an entry that is not two-dimensional or of another shape than the first, or a side beyond 1024 raises ValueError."""
+    with np.load(path) as z:
+        keys = sorted(z.files)
+        arrays = {k: np.asarray(z[k]) for k in keys}
+    missing = [k for k in video_keys if k not in arrays]
+    if missing:
+        raise ValueError("--scene_masks %s has no mask for the video(s) %s (keys: %s)" % (path, ", ".join(missing), ", ".join(keys)))
+    want = tuple(arrays[keys[0]].shape)
+    if len(want) != 2 or not all(1 <= s <= 1024 for s in want):
+        raise ValueError("--scene_masks %s: a mask must be [Mh, Mw] with sides 1..1024, got %s %s" % (path, keys[0], want))
+    bad = ["%s %s" % (k, tuple(a.shape)) for k, a in arrays.items() if tuple(a.shape) != want]
+    if bad:
+        raise ValueError("--scene_masks %s: every mask must be %s, got %s" % (path, want, ", ".join(bad)))
+    masks = np.stack([(arrays[k] != 0).astype(np.uint8) for k in keys])
+    return masks, np.array([keys.index(k) for k in video_keys], np.int32)
+
+
 def train(args, data_loader=None, model=None, log: Callable[[str], None] = print) -> List[float]:
     """Runs the loop; returns the per-step losses.  `data_loader` / `model` may be injected (tests)."""
     from .data_loader import DataLoader
@@ -274,11 +324,17 @@ def train(args, data_loader=None, model=None, log: Callable[[str], None] = print
         G = int(getattr(args, "scene_grid", 64))
         images, grid_of_video = load_scene_images(args.scene_images, scene_image_keys(data_loader, args.data_dir), G, G)
         args.n_grids = int(images.shape[0])
+    mask_of_video = None
+    if getattr(args, "scene_masks", None):
+        masks, mask_of_video = load_scene_masks(args.scene_masks, scene_image_keys(data_loader, args.data_dir))
     if model is None:
         model = DESIREModel(args, seed=args.seed)
     if grid_of_video is not None:
         model.set_scene_images(images, np.zeros(1, np.int32))
         model._grid_of_video = grid_of_video
+    if mask_of_video is not None:
+        model.set_scene_masks(masks, np.zeros(1, np.int32))
+        model._mask_of_video = mask_of_video
     losses: List[float] = []
     # the overlapped schedule needs the fast loader's next_batch_into; a reference-shaped loader (utils/data_loader.py's API: next_batch only) gets
     # the reference's serial loop instead of an AttributeError from the feeder thread
@@ -292,7 +348,8 @@ def train(args, data_loader=None, model=None, log: Callable[[str], None] = print
             start = time.time()
             xval, _, dval = data_loader.next_batch()
             past, fut = split_windows(shard_batch(xval, rank, world), t_obs)
-            terms = model.train_step(past, fut, **_noise(args, steps, rank, world), grid_of_scene=_gos(grid_of_video, shard_batch(dval, rank, world)))
+            terms = model.train_step(past, fut, **_noise(args, steps, rank, world), grid_of_scene=_gos(grid_of_video, shard_batch(dval, rank, world)),
+                                     **_mos(mask_of_video, shard_batch(dval, rank, world)))
             losses.append(terms["loss"])
             steps += 1
             if rank == 0:
@@ -443,7 +500,8 @@ def _train_overlapped(args, data_loader, model, log, rank, world, t_obs, t_pred,
                 _report(args, model, last[0], last[1], last[2], rank, log)
             bt.wait()
             pl = model.train_step_device(bt.past, bt.fut, **_noise(args, steps, rank, world), sync=False,
-                                         grid_of_scene=_gos(getattr(model, "_grid_of_video", None), bt.d))
+                                         grid_of_scene=_gos(getattr(model, "_grid_of_video", None), bt.d),
+                                         **_mos(getattr(model, "_mask_of_video", None), bt.d))
             if reporting:                                 # the epoch's last batch is evaluated after the feeder has moved on: keep a copy
                 last = (bt.past.clone(), bt.fut.clone(), bt.epoch)
             bt.release()

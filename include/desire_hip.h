@@ -939,6 +939,72 @@ int desire_recon_weights_scene(desire_handle* h, const float* dev_fut, const flo
 int desire_set_collision_loss(desire_handle* h, float weight, float radius, float unit_x, float unit_y);
 int desire_collision_loss(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float radius, float unit_x, float unit_y,
                           float* dev_col, int32_t* dev_touch, float* dev_dY, float* dev_term, void* stream);
+/* ---- off-road penalty on the K joint futures.  desire_occupancy reports `violation`, the sample mass on cells a traversability mask forbids; this
+ * term pushes it down: the squared distance, read off the distance field of the mask, of every counted position to the nearest traversable cell.
+ * All arithmetic is fp32, every operation rounded once (no fused multiply-add), sqrtf and the divisions correctly rounded; no float atomics; a sum
+ * "in increasing X" starts from 0.f.
+ * desire_mask_distance: the exact distance field of a binary mask.  dev_mask [n_masks, Mh, Mw] uint8 with desire_occupancy's meaning (byte 0 = not
+ * traversable), dev_field [n_masks, Mh, Mw] fp32.  For the cell (y, x): q = the min over the traversable cells (y', x') of the same mask of a * a +
+ * b * b with a = (float)(x - x') * cell_x and b = (float)(y - y') * cell_y (two rounded products, one rounded sum); field = sqrtf(q): the distance
+ * from the cell's centre to the nearest traversable centre in the caller's unit, 0.f on a traversable cell.  A mask with NO traversable cell gives
+ * 0.f everywhere: no constraint, not an infinite one.  A min does not depend on the order of its operands; the device takes it in two passes (per
+ * column the nearest traversable row, then per cell the min over the columns: the rounded expression is monotone in |y - y'|), with the bits of
+ * the statement.  Mh, Mw: 1 .. DESIRE_OCC_MAX_SIDE; n_masks: 1 .. DESIRE_OFFROAD_MAX_MASKS.  Stream-ordered and capturable: it waits for nothing
+ * and allocates nothing (dev_field itself holds the first pass's integers until the second overwrites them).  Not on the step path: a field is
+ * built once per set of scenes.  DESIRE_ERR_ARG with a desire_last_error text, nothing launched: a NULL handle / dev_mask / dev_field; n_masks, Mh
+ * or Mw out of range; a cell size that is not finite and > 0; a ref_compat handle.
+ * desire_set_offroad_field attaches fields to the handle as desire_set_scene_grids attaches grids: dev_field [n_fields, Mh, Mw] is referenced, not
+ * copied (it must outlive its use); host_field_of_scene [n_scenes] maps each window to a field and is copied to device words the handle owns: every
+ * entry must be < n_fields, a NEGATIVE entry means the window has no field (it costs, counts and pushes nothing).  It may be called between steps
+ * with the same field and another mapping.  The map goes up as desire_set_scene_grids' does, by a synchronous hipMemcpy from the caller's pageable
+ * array: the host waits for the device's earlier work on the null stream, so a caller that changes the mapping every step gives up running ahead
+ * of the device, and on a non-blocking stream the caller orders the copy against a step that still reads the map; not inside a captured graph.  DESIRE_ERR_ARG: a NULL argument, n_fields or a side
+ * out of range, an entry >= n_fields, a ref_compat handle.
+ * The penalty.  Layouts, lmask, nfut, nvalid and the counted frames cc(a, t) are desire_collision_loss': agent a = scene * mno + slot, row r_k =
+ * (scene * K + k) * mno + slot.  D = the field of the agent's window, fMw = (float)Mw, fMh = (float)Mh.  Per counted (a, k, t) with (x, y) = Y[r_k,
+ * t, 0 .. 1] in the normalised frame:
+ *   1 lookup      xm = x * fMw; u = xm - 0.5f; uc = min(max(u, 0.f), (float)(Mw - 1)); x0 = (int)floorf(uc); x1 = min(x0 + 1, Mw - 1); fx = uc -
+ *                 floorf(uc); likewise ym, v, vc, y0, y1, fy with Mh: cell centres sit on integers, and the lookup is clamped to them.  If x or y
+ *                 is a NaN the item costs nothing, pushes nothing and counts nothing.
+ *   2 distance    D00 = D[y0, x0], D01 = D[y0, x1], D10 = D[y1, x0], D11 = D[y1, x1]; h0 = D01 - D00; h1 = D11 - D10; top = D00 + fx * h0; bot =
+ *                 D10 + fx * h1; vd = bot - top; d = top + fy * vd.
+ *   3 penalty     e = d / scale; phi = e * e (scale in the field's unit).  0 on the road; continuous with a continuous gradient across the road's
+ *                 edge (d -> 0), so a sample that crosses it between two steps changes neither by a jump; off the road the slope jumps at cell
+ *                 lines, as any bilinear lookup's does.
+ *   4 per agent   off[a, k] = (the sum over the counted frames of a, in increasing t, of phi) / nfut[a]; 0.f where lmask[a] = 0 or the window
+ *                 has no field.
+ *   5 count       count[w, k] (int32) = the number of counted (slot, frame)s of window w whose cell by desire_occupancy's step 3 -- floorf(xm),
+ *                 floorf(ym), no clamp -- is IN FRAME and has D > 0.f there: the rule dev_viol applies to the mask, read off the field.  An
+ *                 integer path.
+ *   6 term        L_off = desire_collision_loss' step 6 on off: the mean over K, the 256 strided sums in increasing a, the binary tree, / nvalid.
+ *   7 gradient    of L_off at weight 1.  sx = (h0 + fy * (h1 - h0)) * fMw, and sx = 0.f unless 0.f <= u <= (float)(Mw - 1) (the clamped lookup
+ *                 does not move with x); sy = vd * fMh, 0.f unless 0.f <= v <= (float)(Mh - 1).  m = (2.f * e) / scale; coef = (1.f / nfut[a]) /
+ *                 (nvalid * (float)K).  G[r_k, t, 0] = (m * sx) * coef; G[r_k, t, 1] = (m * sy) * coef; G = 0.f for whatever is not counted.
+ *                 Every (row, t) owns its element: nothing scatters.
+ * desire_offroad_loss is the stand-alone op on the fields set by desire_set_offroad_field: dev_off [A, K], dev_count [n_scenes, K] int32, dev_dY [R,
+ * T_pred, 2] = G, dev_term [1] = L_off; each may be NULL (it then goes to the workspace tensor "off_val" / "off_count" / "off_grad" / "off_term"),
+ * and what is written does not depend on which are.  It needs no training mode (lmask comes from the handle's "valid", as in
+ * desire_collision_loss).  Stream-ordered, no host wait, no scratch: bitwise reproducible; the first call allocates the workspace tensors, later
+ * calls are capturable.  LDS plan: desire_collision_loss' (one workgroup per (window, k), frame chunks with the bits of an unchunked walk), with
+ * the window's field behind it when it fits (64 x 64 cells next to 32 slots x 40 frames do); else the four taps are read from global memory: the
+ * same bits.  DESIRE_ERR_ARG, nothing launched or written: a NULL handle / dev_fut / dev_Yhat; a scale that is not finite and > 0; a ref_compat
+ * handle.  DESIRE_ERR_STATE: no field set.
+ * desire_set_offroad_loss configures the term of the TRAINING loss (default weight 0, which leaves the launch sequence and every bit of every
+ * output as they were; the scale is then not read).  With weight > 0 desire_backward runs steps 1 - 7 on its own "Y0", on the full layout, after
+ * the collision term and before the gather of DESIRE_FLAG_COMPACT_ROWS, and sets dY0 = dY0 + weight * G (the product rounded, then the sum); the
+ * trained loss is the one above plus weight * L_off.  The term keeps its mean over K whatever desire_set_recon_loss / desire_set_recon_scope say.
+ * The backward leaves off, count and L_off of that step in "off_val", "off_count" and "off_term"; desire_train_loss / desire_train_loss_async keep
+ * their layouts and values.  weight > 0 needs a field to be set (DESIRE_ERR_STATE otherwise) and allocates the workspace tensors when it is set,
+ * so that no step allocates.  A host value: it can be changed between steps, not inside a captured graph.  DESIRE_ERR_ARG: a NULL handle, a weight
+ * that is negative or not finite, with weight > 0 a scale that is not finite and > 0; DESIRE_ERR_STATE: a ref_compat handle, no field. */
+#define DESIRE_OFFROAD_MAX_MASKS 65535
+int desire_mask_distance(desire_handle* h, const uint8_t* dev_mask, int32_t n_masks, int32_t Mh, int32_t Mw, float cell_x, float cell_y,
+                         float* dev_field, void* stream);
+int desire_set_offroad_field(desire_handle* h, const float* dev_field, int32_t n_fields, int32_t Mh, int32_t Mw,
+                             const int32_t* host_field_of_scene);
+int desire_set_offroad_loss(desire_handle* h, float weight, float scale);
+int desire_offroad_loss(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float scale, float* dev_off, int32_t* dev_count,
+                        float* dev_dY, float* dev_term, void* stream);
 /* (dev_eps == NULL after desire_set_rng: the eps of the forward's draw is regenerated, see "device generator") */
 int desire_backward(desire_handle* h, const float* dev_past, const float* dev_fut, const float* dev_eps, void* stream);
 int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream);
