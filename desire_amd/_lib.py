@@ -32,6 +32,7 @@ EXPORTS = [
     "desire_set_recon_scope", "desire_recon_weights_scene",
     "desire_set_collision_loss", "desire_collision_loss",
     "desire_mask_distance", "desire_set_offroad_field", "desire_set_offroad_loss", "desire_offroad_loss",
+    "desire_set_refined_loss",
 ]
 OCC_AT, OCC_UNTIL = 0, 1                                            # desire_occupancy modes (DESIRE_OCC_*)
 OCC_MODES = {"at": OCC_AT, "until": OCC_UNTIL}                      # their names on the Python surface (mode=, --occupancy_mode)
@@ -143,6 +144,7 @@ def load() -> C.CDLL:
     lib.desire_set_offroad_field.argtypes = [vp, f32p, i32, i32, i32, C.POINTER(i32)]
     lib.desire_set_offroad_loss.argtypes = [vp, C.c_float, C.c_float]
     lib.desire_offroad_loss.argtypes = [vp, f32p, f32p, C.c_float, f32p, vp, f32p, f32p, vp]
+    lib.desire_set_refined_loss.argtypes = [vp, i32, C.c_float, C.c_float]
     lib.desire_peer_export.argtypes = [vp, C.c_char_p, C.POINTER(C.c_size_t)]
     lib.desire_peer_open.argtypes = [vp, i32, i32, i32, C.c_char_p]
     lib.desire_ioc_peer_pass.argtypes = [vp, f32p, f32p, vp]
@@ -640,6 +642,13 @@ class Handle:
         workspace tensor "off_val" / "off_count" / "off_grad" / "off_term").  Masking as in losses()."""
         _chk(self.lib.desire_offroad_loss(self._h, fut_ptr or None, yhat_ptr or None, C.c_float(float(scale)), off_ptr or None, count_ptr or None,
                                           dy_ptr or None, term_ptr or None, stream or None))
+
+    def set_refined_loss(self, recon: int = 0, collision_weight: float = 0.0, offroad_weight: float = 0.0) -> None:
+        """The recon mode, the collision term and the off-road term on the REFINED trajectories (default (0, 0, 0): the step as it was).  recon = 1:
+        the IOC regression term follows set_recon_loss / set_recon_scope, with weights from the refined errors; the weights add weight * L_col(Y) and
+        weight * L_off(Y) with the radius / units of set_collision_loss and the field / scale of the off-road setters (whose own weights may be 0).
+        The step leaves the terms in the workspace tensors "rcol_term" / "roff_term", the counts in "rcol_touch" / "roff_count"."""
+        _chk(self.lib.desire_set_refined_loss(self._h, int(recon), C.c_float(float(collision_weight)), C.c_float(float(offroad_weight))))
 
     def train_loss_async(self, fut_ptr: int, out8_ptr: int, stream: int = 0) -> None:
         """The loss terms of the last training-mode forward into a device buffer of 8 floats, no synchronisation (see loss_terms)."""

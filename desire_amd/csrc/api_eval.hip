@@ -415,14 +415,15 @@ int recon_scene_ws_setup(desire_ctx* h) {
 
 namespace {
 // the launch of either scope: every output the caller did not give (o: its pointers, null = not wanted) goes to the workspace tensor of its name
+// (tg: the names of those tensors; the stand-alone ops keep the Y0 side's)
 void recon_weights_launch(desire_ctx* h, bool scene, const float* Y, const float* fut, const uint8_t* lmask, int mode, float tau, ReconOut o,
-                          hipStream_t s) {
-    if (!o.e) o.e = W(h, "recon_e");
-    if (!o.w) o.w = W(h, "recon_w");
-    if (!o.winner) o.winner = Wt<int32_t>(h, "recon_win");
-    if (!o.recon) o.recon = W(h, "recon_val");
-    if (scene && !o.E) o.E = W(h, "recon_E");
-    if (scene && !o.count) o.count = Wt<int32_t>(h, "recon_cnt");
+                          hipStream_t s, const ReconTarget& tg = RECON_Y0) {
+    if (!o.e) o.e = W(h, tg.e);
+    if (!o.w) o.w = W(h, tg.w);
+    if (!o.winner) o.winner = Wt<int32_t>(h, tg.win);
+    if (!o.recon) o.recon = W(h, tg.val);
+    if (scene && !o.E) o.E = W(h, tg.E);
+    if (scene && !o.count) o.count = Wt<int32_t>(h, tg.cnt);
     ReconParams p{}; p.lmask = lmask; p.nfut = W(h, "nfut"); p.mode = mode; p.tau = tau;
     (scene ? launch_recon_weights_scene : launch_recon_weights)(eval_in(h, Y, fut, nullptr, nullptr), p, eval_scale(h), o, s);
 }
@@ -448,9 +449,21 @@ int recon_weights_call(desire_handle* h, bool scene, const float* dev_fut, const
 }
 }  // namespace
 
-// the training step's: the handle's mode and scope over its own "Y0", everything into the workspace
-void recon_weights_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s) {
-    recon_weights_launch(h, h->recon_scope == DESIRE_RECON_SCOPE_SCENE, W(h, "Y0"), fut, lmask, h->recon_mode, h->recon_tau, ReconOut{}, s);
+// the training step's: the handle's mode and scope over the target's samples ("Y0", or the refined "Y_ref"), everything into the target's tensors
+void recon_weights_enqueue(desire_ctx* h, const ReconTarget& tg, const float* fut, const uint8_t* lmask, hipStream_t s) {
+    recon_weights_launch(h, h->recon_scope == DESIRE_RECON_SCOPE_SCENE, W(h, tg.Y), fut, lmask, h->recon_mode, h->recon_tau, ReconOut{}, s, tg);
+}
+
+// the refined side's tensors (desire_set_refined_loss).  No gradient tensor of its own: the terms add to "dYr", and the stand-alone ops keep theirs.
+int refined_ws_setup(desire_ctx* h, bool recon, bool collision, bool offroad) {
+    const size_t f = sizeof(float), A = h->A, K = h->d.K, n = h->d.n_scenes;
+    if (recon) {          // both scopes: the scope is read at the time of the step and may change after the setter
+        if (int rc = ws_ensure(h, {{"rrecon_e", (size_t)h->R * f}, {"rrecon_w", (size_t)h->R * f}, {"rrecon_win", A * sizeof(int32_t)}, {"rrecon_val", A * f},
+                                   {"rrecon_E", n * K * f}, {"rrecon_cnt", n * sizeof(int32_t)}})) return rc;
+    }
+    if (collision) { if (int rc = ws_ensure(h, {{"rcol_val", A * K * f}, {"rcol_touch", n * K * sizeof(int32_t)}, {"rcol_term", f}, {"nvalid", 4 * f}})) return rc; }
+    if (offroad) { if (int rc = ws_ensure(h, {{"roff_val", A * K * f}, {"roff_count", n * K * sizeof(int32_t)}, {"roff_term", f}, {"nvalid", 4 * f}})) return rc; }
+    return DESIRE_OK;
 }
 
 extern "C" int desire_recon_weights(desire_handle* h, const float* dev_fut, const float* dev_Yhat, int32_t mode, float tau, float* dev_e,
@@ -476,10 +489,10 @@ int check_collision_args(float radius, float unit_x, float unit_y) {
     if (int rc = check_radius(radius)) return rc;
     return check_units(unit_x, unit_y);
 }
-void collision_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s) {
-    CollParams p{}; p.lmask = lmask; p.nfut = W(h, "nfut"); p.nvalid = W(h, "nvalid"); p.radius = h->col_radius; p.weight = h->col_w; p.accumulate = true;
-    CollOut o{}; o.col = W(h, "col_val"); o.touch = Wt<int32_t>(h, "col_touch"); o.dY = W(h, "dY0"); o.term = W(h, "col_term");
-    launch_collision_loss(eval_in(h, W(h, "Y0"), fut, nullptr, nullptr), p, eval_scale(h, h->col_ux, h->col_uy), o, s);
+void collision_enqueue(desire_ctx* h, const TermTarget& tg, const float* fut, const uint8_t* lmask, hipStream_t s) {
+    CollParams p{}; p.lmask = lmask; p.nfut = W(h, "nfut"); p.nvalid = W(h, "nvalid"); p.radius = h->col_radius; p.weight = tg.weight; p.accumulate = true;
+    CollOut o{}; o.col = W(h, tg.val); o.touch = Wt<int32_t>(h, tg.count); o.dY = W(h, tg.dY); o.term = W(h, tg.term);
+    launch_collision_loss(eval_in(h, W(h, tg.Y), fut, nullptr, nullptr), p, eval_scale(h, h->col_ux, h->col_uy), o, s);
 }
 
 extern "C" int desire_collision_loss(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float radius, float unit_x, float unit_y,
@@ -504,7 +517,7 @@ extern "C" int desire_collision_loss(desire_handle* h, const float* dev_fut, con
 }
 
 // ---- the off-road penalty of a window's K joint futures against the distance field of its scene mask (kernels_offroad.hip): the contracts are
-// stated in include/desire_hip.h.  The training step (backward.hip: loss_grads) runs the same kernel in its accumulating form on "dY0". ----
+// stated in include/desire_hip.h.  The training step (backward.hip: loss_grads, ioc_bwd) runs the same kernel in its accumulating form on "dY0" / "dYr". ----
 extern "C" int desire_mask_distance(desire_handle* h, const uint8_t* dev_mask, int32_t n_masks, int32_t Mh, int32_t Mw, float cell_x, float cell_y,
                                     float* dev_field, void* stream) {
     if (!h) return fail(DESIRE_ERR_ARG, "null handle");
@@ -550,9 +563,9 @@ OffParams offroad_params(desire_ctx* h, const uint8_t* lmask, float scale, float
     return p;
 }
 }  // namespace
-void offroad_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s) {
-    OffOut o{}; o.off = W(h, "off_val"); o.count = Wt<int32_t>(h, "off_count"); o.dY = W(h, "dY0"); o.term = W(h, "off_term");
-    launch_offroad_loss(eval_in(h, W(h, "Y0"), fut, nullptr, nullptr), offroad_params(h, lmask, h->off_scale, h->off_w, true), o, s);
+void offroad_enqueue(desire_ctx* h, const TermTarget& tg, const float* fut, const uint8_t* lmask, hipStream_t s) {
+    OffOut o{}; o.off = W(h, tg.val); o.count = Wt<int32_t>(h, tg.count); o.dY = W(h, tg.dY); o.term = W(h, tg.term);
+    launch_offroad_loss(eval_in(h, W(h, tg.Y), fut, nullptr, nullptr), offroad_params(h, lmask, h->off_scale, tg.weight, true), o, s);
 }
 
 extern "C" int desire_offroad_loss(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float scale, float* dev_off, int32_t* dev_count,

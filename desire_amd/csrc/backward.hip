@@ -197,12 +197,12 @@ int loss_grads(const BwdPass& bp) {
         launch_loss_grad_y(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred, d.sx, d.sy, s);
     } else {          // best-of-many / soft-min (desire_set_recon_loss): the weights of the K samples -- per agent, or in the scene scope the window's for
                       // every one of its slots (desire_set_recon_scope) -- on the full layout, then the weighted gradient
-        recon_weights_enqueue(h, bp.fut, bp.valid, s);
+        recon_weights_enqueue(h, RECON_Y0, bp.fut, bp.valid, s);
         launch_loss_grad_y_w(W(h, "Y0"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "recon_w"), W(h, "dY0"), d.n_scenes, d.mno, d.K, d.T_pred,
                              d.sx, d.sy, s);
     }
-    if (h->col_w > 0.f) collision_enqueue(h, bp.fut, bp.valid, s);      // desire_set_collision_loss: dY0 += weight * d L_col / d Y0, on the full layout too
-    if (h->off_w > 0.f) offroad_enqueue(h, bp.fut, bp.valid, s);        // desire_set_offroad_loss: dY0 += weight * d L_off / d Y0, after the collision term
+    if (h->col_w > 0.f) collision_enqueue(h, col_target_y0(h), bp.fut, bp.valid, s);      // desire_set_collision_loss: dY0 += weight * d L_col / d Y0, on the full layout too
+    if (h->off_w > 0.f) offroad_enqueue(h, off_target_y0(h), bp.fut, bp.valid, s);        // desire_set_offroad_loss: dY0 += weight * d L_off / d Y0, after the collision term
     if (bp.rows_compact) launch_gather_rows(W(h, "dY0"), W(h, "cp_dY0"), bp.amap, bp.n_present, d.K, d.mno, d.T_pred * 2, s);
     return DESIRE_OK;
 }
@@ -336,7 +336,16 @@ int ioc_bwd(const BwdPass& bp) {
     const int H = d.H, T = d.T_pred;
     if (bp.rows_compact) launch_fill_f32(W(h, "dHx_rows"), (size_t)h->R * H, 0.f, s);      // the IOC module accumulates into it; the decoder no longer initialises it
     Timer t(h, s, "bwd_ioc");
-    launch_loss_grad_y(W(h, "Y_ref"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "dYr"), d.n_scenes, d.mno, d.K, T, d.sx, d.sy, s);
+    // d loss / d Y of the refined trajectories, on the full layout (before the class gather; every pass reads it).  desire_set_refined_loss: the
+    // regression term takes the recon mode's weights from the refined errors; then dYr += weight * G of the collision and of the off-road term
+    if (h->ref_recon && h->recon_mode != DESIRE_RECON_MEAN) {
+        recon_weights_enqueue(h, RECON_REFINED, bp.fut, bp.valid, s);
+        launch_loss_grad_y_w(W(h, "Y_ref"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "rrecon_w"), W(h, "dYr"), d.n_scenes, d.mno, d.K, T,
+                             d.sx, d.sy, s);
+    } else
+        launch_loss_grad_y(W(h, "Y_ref"), bp.fut, bp.valid, W(h, "nfut"), W(h, "nvalid"), W(h, "dYr"), d.n_scenes, d.mno, d.K, T, d.sx, d.sy, s);
+    if (h->rcol_w > 0.f) collision_enqueue(h, col_target_refined(h), bp.fut, bp.valid, s);
+    if (h->roff_w > 0.f) offroad_enqueue(h, off_target_refined(h), bp.fut, bp.valid, s);
     launch_score_grad(W(h, "Y0"), bp.fut, W(h, "score_sv"), bp.valid, W(h, "nvalid"), W(h, "dscore"), W(h, "dscoreT"), d.n_scenes,
                       d.mno, d.K, T, d.sx, d.sy, s);
     std::vector<IocView> views;
@@ -597,6 +606,7 @@ extern "C" int desire_backward(desire_handle* h, const float* dev_past, const fl
     if (!h->training) return fail(DESIRE_ERR_STATE, "desire_set_training(h, 1) and a training-mode desire_forward come first");
     if (!dev_past || !dev_fut || (!dev_eps && !h->rng_state)) return fail(DESIRE_ERR_ARG, "null argument");      // (dev_eps == NULL: legal after desire_set_rng)
     if (scene_grad_on(h) && !h->ws.find("sg_wcat")) return fail(DESIRE_ERR_STATE, "scene-gradient buffers missing");
+    if (h->roff_w > 0.f && !(h->off_scale > 0.f)) return fail(DESIRE_ERR_STATE, "desire_set_refined_loss: the off-road scale was reset to a value that is not > 0");
     if (int rc = backward_alloc(h)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const BwdPass bp = make_pass(h, dev_past, dev_fut, dev_eps, s);

@@ -67,6 +67,9 @@ struct desire_ctx {
     // desire_set_offroad_field / desire_set_offroad_loss: the caller's distance fields (referenced, not copied; nullptr: none set) with their shape,
     // the weight (0 = off) and the scale of the training loss's off-road term; the window -> field map is the workspace's "off_fos"
     const float* off_field = nullptr; int off_n = 0, off_Mh = 0, off_Mw = 0; float off_w = 0.f, off_scale = 0.f;
+    // desire_set_refined_loss: the same three terms on the refined trajectories "Y_ref" -- the regression term follows the recon mode and scope (0: the
+    // plain mean), the weights of the collision and the off-road term there (0 = off; radius, units, field and scale are the ones above)
+    int ref_recon = 0; float rcol_w = 0.f, roff_w = 0.f;
     int* host_err = nullptr;                                 // mapped host word the bin-split IOC's bounded spins report into (checked by the next call)
     // present-row compaction (DESIRE_FLAG_COMPACT_ROWS, kernels_compact.hip): mapped host word the scan kernel reports the present-agent count
     // into, the event behind it, the count of the last desire_sample (-1: none yet)
@@ -168,13 +171,26 @@ IocStepArgs ioc_step_args(desire_ctx* h, int t);               // what every lau
 inline RngArgs rng_args(const desire_ctx* h) { return RngArgs{h->rng_state, 0u, 0u, 0u, h->rng_scene_base, h->rng_slot_base}; }      // the handle's generator
 int recon_ws_setup(desire_ctx* h);                             // "recon_e" / "recon_w" / "recon_win" / "recon_val" (api_eval.hip; idempotent)
 int recon_scene_ws_setup(desire_ctx* h);                       // those four and "recon_E" / "recon_cnt" of the scene scope (api_eval.hip; idempotent)
-// the reconstruction weights of the training step into the workspace tensors, in the handle's mode and scope (api_eval.hip; mode != MEAN)
-void recon_weights_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
+// Where a term of the training step reads and writes, by workspace tensor name: the sample tensor, the gradient it adds to, its outputs.  Two targets
+// each: the decoder's samples "Y0" with "dY0" (backward.hip: loss_grads) and the refined trajectories "Y_ref" with "dYr" (ioc_bwd), whose outputs are
+// tensors of their own (r*) so that neither side overwrites what the other left.
+struct ReconTarget { const char *Y, *e, *w, *win, *val, *E, *cnt; };
+struct TermTarget { const char *Y, *dY, *val, *count, *term; float weight; };
+constexpr ReconTarget RECON_Y0{"Y0", "recon_e", "recon_w", "recon_win", "recon_val", "recon_E", "recon_cnt"};
+constexpr ReconTarget RECON_REFINED{"Y_ref", "rrecon_e", "rrecon_w", "rrecon_win", "rrecon_val", "rrecon_E", "rrecon_cnt"};
+inline TermTarget col_target_y0(const desire_ctx* h) { return TermTarget{"Y0", "dY0", "col_val", "col_touch", "col_term", h->col_w}; }
+inline TermTarget col_target_refined(const desire_ctx* h) { return TermTarget{"Y_ref", "dYr", "rcol_val", "rcol_touch", "rcol_term", h->rcol_w}; }
+inline TermTarget off_target_y0(const desire_ctx* h) { return TermTarget{"Y0", "dY0", "off_val", "off_count", "off_term", h->off_w}; }
+inline TermTarget off_target_refined(const desire_ctx* h) { return TermTarget{"Y_ref", "dYr", "roff_val", "roff_count", "roff_term", h->roff_w}; }
+// the reconstruction weights of the training step into the target's workspace tensors, in the handle's mode and scope (api_eval.hip; mode != MEAN)
+void recon_weights_enqueue(desire_ctx* h, const ReconTarget& tg, const float* fut, const uint8_t* lmask, hipStream_t s);
 int collision_ws_setup(desire_ctx* h);                         // "col_val" / "col_touch" / "col_grad" / "col_term" and "nvalid" (api_eval.hip; idempotent)
 int check_collision_args(float radius, float unit_x, float unit_y);      // desire_collision_loss' checks of its scalars (api_eval.hip)
-// the collision term of the training step: dY0 = dY0 + col_w * G in place, col, touch and the term into the workspace tensors (api_eval.hip; col_w > 0)
-void collision_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
+// the collision term of the training step: dY = dY + weight * G in place, col, touch and the term into the target's tensors (api_eval.hip; weight > 0)
+void collision_enqueue(desire_ctx* h, const TermTarget& tg, const float* fut, const uint8_t* lmask, hipStream_t s);
 int offroad_ws_setup(desire_ctx* h);                           // "off_val" / "off_count" / "off_grad" / "off_term" and "nvalid" (api_eval.hip; idempotent)
-// the off-road term of the training step: dY0 = dY0 + off_w * G in place, off, count and the term into the workspace tensors (api_eval.hip; off_w > 0)
-void offroad_enqueue(desire_ctx* h, const float* fut, const uint8_t* lmask, hipStream_t s);
+// the off-road term of the training step: dY = dY + weight * G in place, off, count and the term into the target's tensors (api_eval.hip; weight > 0)
+void offroad_enqueue(desire_ctx* h, const TermTarget& tg, const float* fut, const uint8_t* lmask, hipStream_t s);
+// the refined side's workspace (desire_set_refined_loss): the six "rrecon_*" with recon, "rcol_*" / "roff_*" with their weights (api_eval.hip; idempotent)
+int refined_ws_setup(desire_ctx* h, bool recon, bool collision, bool offroad);
 int scene_images_run(desire_ctx* h, hipStream_t s);            // the scene CNN over the attached images into "scene_img_grid" (api_ops.hip)

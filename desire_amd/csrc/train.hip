@@ -402,6 +402,26 @@ extern "C" int desire_set_offroad_loss(desire_handle* h, float weight, float sca
     return DESIRE_OK;
 }
 
+extern "C" int desire_set_refined_loss(desire_handle* h, int32_t recon, float collision_weight, float offroad_weight) {
+    if (!h) return fail(DESIRE_ERR_ARG, "null argument");
+    if (recon != 0 && recon != 1) return fail(DESIRE_ERR_ARG, "recon must be 0 or 1");
+    if (!std::isfinite(collision_weight) || collision_weight < 0.f) return fail(DESIRE_ERR_ARG, "collision_weight must be finite and >= 0");
+    if (!std::isfinite(offroad_weight) || offroad_weight < 0.f) return fail(DESIRE_ERR_ARG, "offroad_weight must be finite and >= 0");
+    if (h->d.ref_compat) return fail(DESIRE_ERR_STATE, "ref_compat is forward-only");
+    if (collision_weight > 0.f && !(std::isfinite(h->col_radius) && h->col_radius > 0.f))
+        return fail(DESIRE_ERR_STATE, "collision_weight > 0: no radius > 0 set (desire_set_collision_loss; its own weight may be 0)");
+    if (offroad_weight > 0.f && !h->off_field) return fail(DESIRE_ERR_STATE, "offroad_weight > 0: no distance field set (desire_set_offroad_field)");
+    if (offroad_weight > 0.f && !(std::isfinite(h->off_scale) && h->off_scale > 0.f))
+        return fail(DESIRE_ERR_STATE, "offroad_weight > 0: no scale > 0 set (desire_set_offroad_loss; its own weight may be 0)");
+    if (recon) {
+        int sc = 0, kc = 0;
+        if (!recon_geometry(h->d.mno, h->d.K, h->d.T_pred, &sc, &kc)) return fail(DESIRE_ERR_ARG, "T_pred is too long for the reconstruction-weight kernel's LDS");
+    }
+    if (int rc = refined_ws_setup(h, recon != 0, collision_weight > 0.f, offroad_weight > 0.f)) return rc;      // here, so that no training step allocates
+    h->ref_recon = recon; h->rcol_w = collision_weight; h->roff_w = offroad_weight;
+    return DESIRE_OK;
+}
+
 extern "C" int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream) {
     if (!h || !name || !host_out) return fail(DESIRE_ERR_ARG, "null argument");
     if (!h->training) return fail(DESIRE_ERR_STATE, "not in training mode");
@@ -432,11 +452,18 @@ static int train_loss_enqueue(desire_handle* h, const float* dev_fut, hipStream_
     hipLaunchKernelGGL(k_train_loss, dim3((h->A + 63) / 64), dim3(64), 0, s, W(h, "Y0"), W(h, "Y_ref"), dev_fut, W(h, "score_sv"),
                        W(h, "params"), valid, W(h, "nfut"), W(h, "loss_pa"), d.n_scenes, d.mno, d.K, d.T_pred, d.L, d.sx, d.sy);
     if (h->recon_mode != DESIRE_RECON_MEAN) {          // slot 0 reports the term that is trained: the min / soft-min over the K samples, or in the scene scope over the window's K worlds (kernels_recon.hip)
-        recon_weights_enqueue(h, dev_fut, valid, s);
+        recon_weights_enqueue(h, RECON_Y0, dev_fut, valid, s);
         if (h->recon_scope == DESIRE_RECON_SCOPE_SCENE)
             hipLaunchKernelGGL(k_put_recon_counted, dim3((h->A + 255) / 256), dim3(256), 0, s, W(h, "recon_val"), valid, W(h, "loss_pa"), h->A);
         else
             hipLaunchKernelGGL(k_put_recon, dim3((h->A + 255) / 256), dim3(256), 0, s, W(h, "recon_val"), W(h, "loss_pa"), h->A);
+        if (h->ref_recon) {          // desire_set_refined_loss: slot 3 by the same rule, the term of the refined errors (per_agent + 3: the same stride, slot 3)
+            recon_weights_enqueue(h, RECON_REFINED, dev_fut, valid, s);
+            if (h->recon_scope == DESIRE_RECON_SCOPE_SCENE)
+                hipLaunchKernelGGL(k_put_recon_counted, dim3((h->A + 255) / 256), dim3(256), 0, s, W(h, "rrecon_val"), valid, W(h, "loss_pa") + 3, h->A);
+            else
+                hipLaunchKernelGGL(k_put_recon, dim3((h->A + 255) / 256), dim3(256), 0, s, W(h, "rrecon_val"), W(h, "loss_pa") + 3, h->A);
+        }
     }
     hipLaunchKernelGGL(k_sum_loss, dim3(1), dim3(256), 0, s, W(h, "loss_pa"), valid, h->A, W(h, "loss_out"));
     HIPCHK(hipGetLastError());

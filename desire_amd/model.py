@@ -414,8 +414,11 @@ class DESIREModel(ScoredSamples):
             self._configure_recon_loss(h)
             self._configure_collision_loss(h)
             self._configure_offroad_loss(h)
+            self._configure_refined_loss(h)
         col_on, off_on = getattr(h, "_col_on", False), getattr(h, "_off_on", False)
-        extra = [(name, ws) for name, ws, on in (("col", "col_term", col_on), ("off", "off_term", off_on)) if on]
+        rcol_on, roff_on = getattr(h, "_rcol_on", False), getattr(h, "_roff_on", False)
+        extra = [(name, ws) for name, ws, on in (("col", "col_term", col_on), ("off", "off_term", off_on), ("rcol", "rcol_term", rcol_on),
+                                                 ("roff", "roff_term", roff_on)) if on]
         self.forward_device(past, fut, eps, seed, grid_of_scene=grid_of_scene, device_rng=device_rng, window_base=window_base)
         past, fut, eps_t = self._keep
         stream = torch.cuda.current_stream().cuda_stream
@@ -504,6 +507,41 @@ class DESIREModel(ScoredSamples):
             raise ValueError("args.offroad_weight > 0 needs scene masks (set_scene_masks)")
         h.set_offroad_loss(weight, float(scale))
         h._off_on = True
+
+    def _configure_refined_loss(self, h) -> None:
+        """Hook of the terms on the REFINED trajectories: args.refine_recon (bool: the IOC regression term follows
+        args.recon_loss / recon_tau / recon_scope, with weights from the refined errors), args.refine_collision_weight and
+        args.refine_offroad_weight (default 0: off).  Radius, scale and masks are the Y0 terms' own arguments; where their weights are 0 the radius
+        and the scale are set here.  The step's dict then carries "rcol" / "roff", the terms themselves on the step's refined Y."""
+        recon = getattr(self.args, "refine_recon", False)
+        if not isinstance(recon, (bool, int, np.bool_, type(None))) or int(recon or 0) not in (0, 1):
+            raise ValueError("args.refine_recon must be a bool, got %r" % (recon,))
+        rcw = float(getattr(self.args, "refine_collision_weight", 0.0) or 0.0)
+        if not (np.isfinite(rcw) and rcw >= 0.0):
+            raise ValueError("args.refine_collision_weight must be finite and >= 0, got %r" % (rcw,))
+        row = float(getattr(self.args, "refine_offroad_weight", 0.0) or 0.0)
+        if not (np.isfinite(row) and row >= 0.0):
+            raise ValueError("args.refine_offroad_weight must be finite and >= 0, got %r" % (row,))
+        if not recon and rcw == 0.0 and row == 0.0:
+            return
+        if rcw > 0.0 and not getattr(h, "_col_on", False):
+            radius = getattr(self.args, "collision_loss_radius", None)
+            if radius is None:
+                radius = getattr(self.args, "collision_radius", None)
+            if radius is None or not (np.isfinite(float(radius)) and float(radius) > 0.0):
+                raise ValueError("args.refine_collision_weight > 0 needs a radius > 0 in pixels (args.collision_loss_radius or "
+                                 "args.collision_radius), got %r" % (radius,))
+            d = h.dims
+            h.set_collision_loss(0.0, float(radius), 1.0 / d.sx, 1.0 / d.sy)
+        if row > 0.0 and not getattr(h, "_off_on", False):
+            scale = getattr(self.args, "offroad_scale", None)
+            if scale is None or not (np.isfinite(float(scale)) and float(scale) > 0.0):
+                raise ValueError("args.refine_offroad_weight > 0 needs args.offroad_scale > 0 in pixels, got %r" % (scale,))
+            if self._masks is None:
+                raise ValueError("args.refine_offroad_weight > 0 needs scene masks (set_scene_masks)")
+            h.set_offroad_loss(0.0, float(scale))
+        h.set_refined_loss(1 if recon else 0, rcw, row)
+        h._rcol_on, h._roff_on = rcw > 0.0, row > 0.0
 
     def sync_weights(self) -> Dict[str, np.ndarray]:
         """Pull the trained weights back from the device; other handles (batch sizes / prior path) are rebuilt lazily."""

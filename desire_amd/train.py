@@ -113,6 +113,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "distance in pixels from the predicted position to the nearest traversable cell of the video's mask (--scene_masks), "
                         "averaged over the K samples and the agents; needs --offroad_scale and --scene_masks")
     p.add_argument("--offroad_scale", type=float, default=None, help="scale of --offroad_weight in pixels: a position this far off the road costs 1")
+    p.add_argument("--refine_recon", action="store_true",
+                   help="the regression term of the refined trajectories follows --recon_loss / --recon_tau / --recon_scope, with weights from the "
+                        "refined errors (default: the plain mean over the K samples, which pulls every refined sample to the observed future); "
+                        "changes nothing with --recon_loss mean")
+    p.add_argument("--refine_collision_weight", type=float, default=0.0,
+                   help="weight of the collision penalty on the REFINED trajectories, the ones the reports read (default 0: off); the radius is "
+                        "--collision_loss_radius / --collision_radius, and --collision_weight may stay 0")
+    p.add_argument("--refine_offroad_weight", type=float, default=0.0,
+                   help="weight of the off-road penalty on the REFINED trajectories (default 0: off); needs --offroad_scale and --scene_masks, and "
+                        "--offroad_weight may stay 0")
     p.add_argument("--scene_masks", type=str, default=None,
                    help=".npz with one [Mh, Mw] uint8 traversability mask per video over the whole frame (0 = not traversable), keyed like "
                         "--scene_images by the video directory relative to --data_dir; every mask has the same shape")
@@ -161,6 +171,29 @@ def check_recon_args(args) -> None:
         raise ValueError("--recon_tau is the temperature of --recon_loss softmin (got --recon_loss %s)" % mode)
     check_collision_args(args)
     check_offroad_args(args)
+    check_refined_args(args)
+
+
+def check_refined_args(args) -> None:
+    """--refine_collision_weight / --refine_offroad_weight: finite and >= 0; > 0 needs what the Y0 term of the same kind needs (a positive radius; a
+    positive --offroad_scale and --scene_masks).  --refine_recon is a switch."""
+    w = float(getattr(args, "refine_collision_weight", 0.0) or 0.0)
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError("--refine_collision_weight must be finite and >= 0, got %r" % (w,))
+    r = collision_loss_radius(args)
+    if w > 0.0 and (r is None or not (np.isfinite(float(r)) and float(r) > 0.0)):
+        raise ValueError("--refine_collision_weight > 0 needs a radius > 0 in pixels: --collision_loss_radius or --collision_radius (got %r)" % (r,))
+    w = float(getattr(args, "refine_offroad_weight", 0.0) or 0.0)
+    if not (np.isfinite(w) and w >= 0.0):
+        raise ValueError("--refine_offroad_weight must be finite and >= 0, got %r" % (w,))
+    if w > 0.0:
+        s = getattr(args, "offroad_scale", None)
+        if s is None or not (np.isfinite(float(s)) and float(s) > 0.0):
+            raise ValueError("--refine_offroad_weight > 0 needs --offroad_scale finite and > 0 in pixels (got %r)" % (s,))
+        if not getattr(args, "scene_masks", None):
+            raise ValueError("--refine_offroad_weight > 0 needs --scene_masks: the masks its distance field is built from")
+    if getattr(args, "refine_recon", False) not in (False, True, 0, 1, None):
+        raise ValueError("--refine_recon is a switch (got %r)" % (getattr(args, "refine_recon"),))
 
 
 def check_offroad_args(args) -> None:
@@ -208,6 +241,12 @@ def step_line(args, step: int, total: int, epoch: int, terms: dict, dt: float) -
     w = float(getattr(args, "offroad_weight", 0.0) or 0.0)
     if w > 0.0:
         line += ", off[s={:g} w={:g}] {:.5f}".format(float(args.offroad_scale), w, terms.get("off", float("nan")))
+    w = float(getattr(args, "refine_collision_weight", 0.0) or 0.0)
+    if w > 0.0:
+        line += ", rcol[w={:g}] {:.5f}".format(w, terms.get("rcol", float("nan")))
+    w = float(getattr(args, "refine_offroad_weight", 0.0) or 0.0)
+    if w > 0.0:
+        line += ", roff[w={:g}] {:.5f}".format(w, terms.get("roff", float("nan")))
     return line
 
 

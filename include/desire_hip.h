@@ -1005,6 +1005,33 @@ int desire_set_offroad_field(desire_handle* h, const float* dev_field, int32_t n
 int desire_set_offroad_loss(desire_handle* h, float weight, float scale);
 int desire_offroad_loss(desire_handle* h, const float* dev_fut, const float* dev_Yhat, float scale, float* dev_off, int32_t* dev_count,
                         float* dev_dY, float* dev_term, void* stream);
+/* ---- the same three terms on the REFINED trajectories.  The model's output is Y = Y0 + the sum over the IOC passes of dY_p ("Y_ref" of a training
+ * step); the four settings above act on the decoder's samples Y0, and the one term that trains the refinement, the IOC regression term, is the plain
+ * mean over K of ||Y - g||.  desire_set_refined_loss(recon, collision_weight, offroad_weight) -- default (0, 0, 0): the step as it is, its launches
+ * and every bit -- moves them onto Y.  The IOC trajectories stay detached from Y0: what is added here reaches ioc/ * and, through Hx, the encoders
+ * (and the scene CNN when images are attached), nothing else.  d loss / d Y enters the IOC backward at one point, "dYr" on the full layout, before
+ * the gather of the slot classes and shared by every refinement pass; the terms are applied there in this order:
+ *   recon = 1             the regression term follows desire_set_recon_loss / desire_set_recon_scope as they stand AT THE STEP: the weights are
+ *                         desire_recon_weights' (scope SCENE: desire_recon_weights_scene's) on the refined errors e1[a, k] -- the error of Y against
+ *                         the future with the loss mask and the counted frames of slot 0 -- and the gradient is the weighted formula of
+ *                         desire_set_recon_loss with Y for Y0.  Slot 3 (regression) of desire_train_loss* then reports the term that is trained, by
+ *                         slot 0's rule: the mean over the counted agents of the min / soft-min of e1, in scope SCENE of the window's term.  In mode
+ *                         MEAN the flag is accepted and changes neither launches nor bits.  Weights and winners stay in "rrecon_e" / "rrecon_w" /
+ *                         "rrecon_win" / "rrecon_val" (scope SCENE: also "rrecon_E" / "rrecon_cnt").
+ *   collision_weight > 0  dYr = dYr + collision_weight * G (the product rounded, then the sum), G = step 7 of desire_collision_loss on Y with the
+ *                         radius and units the handle holds from desire_set_collision_loss, whose own weight may be 0: that is how the refinement
+ *                         alone is penalised.  col, touch and L_col(Y) of the step: "rcol_val" / "rcol_touch" / "rcol_term".
+ *   offroad_weight > 0    the same with desire_offroad_loss' G on the fields of desire_set_offroad_field and the scale of desire_set_offroad_loss
+ *                         (its weight may be 0): "roff_val" / "roff_count" / "roff_term".
+ * Both penalties keep their mean over K whatever the recon mode says, as their Y0 twins do.  The trained loss is
+ *   L_sgm + mean_counted(ce + reg') + cw * L_col(Y0) + ow * L_off(Y0) + collision_weight * L_col(Y) + offroad_weight * L_off(Y)   [+ head term]
+ * with reg' the plain mean, or with recon = 1 and a mode other than MEAN the min / soft-min term of e1.  The layouts of desire_train_loss* do not
+ * change.  Under DESIRE_FLAG_COMPACT_* the padded rows of Y hold anything; the kernels read uncounted slots through the loss mask only.  Workspace
+ * is allocated here, never in a step; with everything off nothing is allocated.  Host values: they can be changed between steps, not inside a
+ * captured graph.  Refusals, in this order, each leaving the handle's settings as they were: DESIRE_ERR_ARG: a NULL handle; recon not 0 or 1; a
+ * weight that is negative or not finite.  DESIRE_ERR_STATE: a ref_compat handle; collision_weight > 0 with no radius > 0 set; offroad_weight > 0
+ * with no field set, or with a scale that is not finite and > 0.  (recon = 1 with T_pred too long for desire_recon_weights: DESIRE_ERR_ARG.) */
+int desire_set_refined_loss(desire_handle* h, int32_t recon, float collision_weight, float offroad_weight);
 /* (dev_eps == NULL after desire_set_rng: the eps of the forward's draw is regenerated, see "device generator") */
 int desire_backward(desire_handle* h, const float* dev_past, const float* dev_fut, const float* dev_eps, void* stream);
 int desire_get_grad(desire_handle* h, const char* name, float* host_out, size_t n, void* stream);
